@@ -25,12 +25,19 @@ N = 1: workload = BASELINE configs[1] (4 GiB, 16-byte pattern).  N > 1: weak
 scaling, each rank holds one 4 GiB shard (+ 15 halo bytes) of an N x 4 GiB
 corpus -- at N = 8 this is configs[3] (32 GiB).
 
-Rank 0 prints ONE JSON line (contract in the task description) with two extra
-objects: `roofline` (scan kernel vs the HBM read roofline, duration from HIP
-events on that kernel's own dispatch, on its launch stream) and, at N = 1,
-`cpu_baseline` (the reference's serial CPU Boyer-Moore -- oracle/_ref when it
-is present, else the C restatement -- timed on this host over the same text,
-which doubles as the full-size bit-exactness check of the GPU match list).
+Rank 0 prints ONE JSON line (contract in the task description) with an extra
+object `roofline` (scan kernel vs the HBM read roofline, duration from HIP
+events on that kernel's own dispatch, on its launch stream).  A plain run does
+only what that line needs: set-up, warm-up, the --steps timed steps, the line.
+--full adds what is measured or checked beside it: at N = 1 `cpu_baseline` (the
+reference's serial CPU Boyer-Moore -- oracle/_ref when it is present, else the C
+restatement -- timed on this host over the same text, which doubles as the
+full-size bit-exactness check of the GPU match list) and `pcie_inclusive_GBps`;
+at N > 1 every rank's CPU check of its shard; for ed64k / sa2m the CPU baseline
+and its parity flag.  --no-cpu-baseline leaves the CPU legs out of --full.
+--dump-outputs DIR writes what the last timed step computed (the match offsets,
+the distance, the suffix array) as DIR/<name>.npy in float64; the inputs are
+seeded, so two builds can be compared output for output.
 Before the --warmup steps the device's clocks are ramped up with 40 untimed
 searches (--ramp-up; the first ~10 launches after the set-up's idle time run
 5-10 % slower); the line reports it as config.ramp_up_searches.
@@ -69,7 +76,12 @@ def parse_args(argv=None):
                     "--variant), or the path of another build; default: the product library")
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE",
                     help="measurement only, with --library exp: a switch of bmx_exp_set_knob (e.g. sa_flags=4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU baseline and full-text "
+                         "bit-exactness against it, PCIe-inclusive rate (N = 1), every rank's CPU check of its shard (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline and its checks out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0)
     ap.add_argument("--overlap-scans", action="store_true",
                     help="let the scan kernels of consecutive searches share the GPU (a CU holds one workgroup, so search "
@@ -224,6 +236,13 @@ def cpu_baseline(h_text: np.ndarray, pat: bytes, gpu_list: np.ndarray, budget_s:
     }, ok
 
 
+def dump_outputs(dirpath: str, arrays: dict) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (match offsets < 2^53 are exact)."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}.npy"), np.asarray(a).astype(np.float64).reshape(-1))
+
+
 def bench_edit_distance(args, dev, local_rank):
     """Config 5: Levenshtein distance of two 64k-character ACGT strings on one GPU.  A step is
     one distance computation with both strings resident; cell updates per second."""
@@ -243,6 +262,8 @@ def bench_edit_distance(args, dev, local_rank):
         kern_ms.append(ctx.last_edit_distance_ms())
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"distance": [int(d)]})
     line = {"metric": "edit-distance cell updates, 64k x 64k chars, 1x MI355X (BASELINE config 5)",
             "value": round(n * n * args.steps / elapsed / 1e9, 2), "unit": "GCUPS", "n_gpus": 1, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
@@ -256,7 +277,7 @@ def bench_edit_distance(args, dev, local_rank):
             "roofline": {"bound": "valu-int32", "achieved": round(n * n / (float(np.mean(kern_ms)) * 1e-3) / 1e9, 1),
                          "peak": 19661.0, "unit": "GCUPS",
                          "frac": round(n * n / (float(np.mean(kern_ms)) * 1e-3) / 1e9 / 19661.0, 4), "traffic": None}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle  # reported baseline + checker only
 
         t0 = time.perf_counter()
@@ -281,8 +302,8 @@ def bench_suffix_array(args, dev, local_rank):
     x = np.tile(para, n // para.size + 1)[:n].copy()
     ctx = make_context(args, local_rank)
     dx = torch.from_numpy(x).to(dev)
-    steps = min(args.steps, 50)
-    for _ in range(min(args.warmup, 3)):
+    steps = args.steps
+    for _ in range(args.warmup):
         sa = ctx.suffix_array_device(dx)
     torch.cuda.synchronize()
     dev_ms = []
@@ -292,14 +313,16 @@ def bench_suffix_array(args, dev, local_rank):
         dev_ms.append(ctx.last_suffix_array_ms())
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"suffix_array": sa.cpu().numpy()})
     line = {"metric": "suffix-array construction, 2 MiB repeated-paragraph text, 1x MI355X", "value":
             round(n * steps / elapsed / 1e6, 1), "unit": "Mchar/s", "n_gpus": 1, "steps": steps,
-            "warmup": min(args.warmup, 3), "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "config": {"workload": "sa2m", "chars": n, "period": int(para.size), "rounds": ctx.last_suffix_array_rounds(),
                        "rounds_in_lds": ctx.last_suffix_array_lds_rounds(),
                        "device_ms": round(float(np.mean(dev_ms)), 3)}, "roofline": None}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle  # reported baseline + checker only
 
         chk = oracle.reference() or oracle.port()
@@ -474,6 +497,8 @@ def main():
         step(i)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # the match list the last timed step handed its caller (global offsets at N > 1)
+        dump_outputs(args.dump_outputs, {"matches": last["lane"]["result"].cpu().numpy()})
     if multi:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -547,7 +572,8 @@ def main():
     if args.overlap_scans:  # launches share the GPU: one launch's duration is not the kernel's
         line["roofline"]["note"] = "scans overlap: kernel_ms is the span of a launch that shares the GPU with its neighbours; not comparable"
 
-    if world > 1 and not args.no_cpu_baseline:
+    cpu_legs = args.full and not args.no_cpu_baseline
+    if world > 1 and cpu_legs:
         # Every rank checks ITS shard of the merged global list against the reference's serial CPU scan of the shard's
         # own bytes (copied to the host once, here, outside the timed region; one pass of one core per rank, the ranks
         # side by side): the slice [start, start + n_own) of the list every rank ends a step with must be exactly what
@@ -565,7 +591,7 @@ def main():
         line["parity"]["bit_exact_vs_cpu_baseline_every_shard"] = bool(int(flag.item()) == 1)
         line["parity"]["shards_checked"] = world
         line["cpu_baseline"] = cb
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and cpu_legs:
         h_text = d_text.cpu().numpy()
         cb, exact = cpu_baseline(h_text, pat, result, args.cpu_budget_s)
         line["cpu_baseline"] = cb

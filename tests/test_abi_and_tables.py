@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from golden import reference_runs
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
 
 
@@ -57,16 +58,13 @@ def test_build_tables_matches_oracle_random(built, port):
 
 
 def test_build_tables_matches_reference_build(built, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(100)
-    for _ in range(2000):
-        alpha = int(rng.integers(1, 4))
-        m = int(rng.integers(1, 100))
-        pat = (rng.integers(0, alpha, m) + 97).astype(np.uint8).tobytes()
+    """Against the reference build when it is present, and against its recorded answers (tests/golden/reference_runs.py)."""
+    for pat, want in zip(reference_runs.table_patterns(), reference_runs.load("tables"), strict=True):
         b1, g1 = host.build_tables(pat)
-        b2, g2 = reference.tables(pat)
-        assert np.array_equal(b1, b2) and np.array_equal(g1[1:], g2[1:]), pat
+        if reference is not None:
+            b2, g2 = reference.tables(pat)
+            assert np.array_equal(b1, b2) and np.array_equal(g1[1:], g2[1:]), pat
+        assert reference_runs.digest(b1, g1[1:]) == want, pat
 
 
 def test_build_tables_long_patterns(built, port):

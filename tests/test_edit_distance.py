@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_file_bytes, load_golden
+from golden import reference_runs
 
 
 def _case_strings(case):
@@ -31,15 +32,12 @@ def test_survey_known_answers(port):
 
 
 def test_oracle_equals_reference_build_random(port, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(42)
-    for _ in range(200):
-        la, lb = int(rng.integers(0, 700)), int(rng.integers(0, 700))
-        al = int(rng.integers(1, 6))
-        x = (rng.integers(0, al, la) + 97).astype(np.uint8)
-        y = (rng.integers(0, al, lb) + 97).astype(np.uint8)
-        assert port.edit_distance(x, y) == reference.edit_distance(x, y)
+    """Against the reference build when it is present, and against its recorded answers (tests/golden/reference_runs.py)."""
+    for (x, y), want in zip(reference_runs.edit_distance_pairs(), reference_runs.load("edit_distance"), strict=True):
+        d = port.edit_distance(x, y)
+        if reference is not None:
+            assert d == reference.edit_distance(x, y)
+        assert d == want
 
 
 def test_oracle_metric_properties(port):

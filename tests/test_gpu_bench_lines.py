@@ -37,3 +37,22 @@ def test_config3_line(ctx, workload, alphabet, m):
     assert abs(roof["achieved"] - (4 << 30) / (roof["kernel_ms"] * 1e-3) / 1e9) < 2.0
     assert roof["kernel_ms"] <= line["ms_per_step"] * 1.05  # the kernel cannot take longer than the step around it
     print(json.dumps(line))
+
+
+def test_dump_outputs_holds_the_last_steps_match_list(ctx, tmp_path):
+    """--dump-outputs DIR: the match offsets of the last timed step as DIR/matches.npy (float64), the same from run to
+    run; --steps sets the number of timed steps."""
+    import numpy as np
+
+    from parallel_implementation_of_string_matching_algorithms_opencl_amd import corpus
+
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        line = _line("--gib-per-gpu", "0.25", "--steps", "7", "--dump-outputs", str(d))
+        assert line["steps"] == 7 and line["ms_per_step"] > 0
+        outs.append(np.load(d / "matches.npy"))
+    spec = corpus.scaled(corpus.CONFIGS["cfg2_4GiB_m16"], 1 << 28)
+    assert outs[0].dtype == np.float64 and outs[0].size == line["config"]["matches"]
+    assert np.array_equal(outs[0], spec.planted_offsets().astype(np.float64))
+    assert np.array_equal(outs[0], outs[1])

@@ -203,7 +203,7 @@ def test_bench_multi_rank_path_rehearsal(ctx):
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--gib-per-gpu", "0.25", "--rehearse-on-one-gpu"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--gib-per-gpu", "0.25", "--rehearse-on-one-gpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -228,7 +228,7 @@ def test_bench_plain_launch_starts_its_own_ranks(ctx):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--gib-per-gpu", "0.25", "--rehearse-on-one-gpu"]
+           "--gib-per-gpu", "0.25", "--rehearse-on-one-gpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -240,7 +240,7 @@ def test_bench_plain_launch_starts_its_own_ranks(ctx):
     assert line["config"]["text_bytes_total"] == 2 * line["config"]["text_bytes_per_gpu"]
     # four ranks (with this process: five on the card; a GPU box admits six), each checking its own shard on the CPU
     r4 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1",
-                         "--gib-per-gpu", "0.0625", "--rehearse-on-one-gpu"], capture_output=True, text=True, timeout=600,
+                         "--gib-per-gpu", "0.0625", "--rehearse-on-one-gpu", "--full"], capture_output=True, text=True, timeout=600,
                         cwd=ROOT, env=env)
     assert r4.returncode == 0, r4.stderr[-2000:]
     l4 = json.loads([l for l in r4.stdout.splitlines() if l.startswith("{")][-1])

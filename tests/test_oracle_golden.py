@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import as_u64, golden_file_bytes, load_golden
+from golden import reference_runs
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import corpus
 
 
@@ -101,30 +102,26 @@ def test_ranges_match_golden(port):
 
 
 def test_port_equals_reference_build_random(port, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    rng = np.random.default_rng(123)
-    for _ in range(3000):
-        alpha = int(rng.integers(1, 5))
-        m = int(rng.integers(1, 13))
-        n = int(rng.integers(1, 201))
-        text = (rng.integers(0, alpha, n) + 97).astype(np.uint8)
-        pat = (rng.integers(0, alpha, m) + 97).astype(np.uint8).tobytes()
-        hp, hr = port.search(text, pat), reference.search(text, pat)
-        assert np.array_equal(hp, hr)
+    """Against the reference build when it is present, and against its recorded answers (tests/golden/reference_runs.py)."""
+    for (text, pat), want in zip(reference_runs.search_cases(), reference_runs.load("search"), strict=True):
+        hp = port.search(text, pat)
         assert np.array_equal(hp, port.naive(text, pat))
         bp, gp = port.tables(pat)
-        br, gr = reference.tables(pat)
-        assert np.array_equal(bp, br) and np.array_equal(gp[1:], gr[1:])
+        if reference is not None:
+            hr = reference.search(text, pat)
+            assert np.array_equal(hp, hr)
+            br, gr = reference.tables(pat)
+            assert np.array_equal(bp, br) and np.array_equal(gp[1:], gr[1:])
+        assert reference_runs.digest(hp) + " " + reference_runs.digest(bp, gp[1:]) == want
 
 
 def test_port_equals_reference_build_on_configs(port, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    for name in ("cfg2_4GiB_m16", "cfg3_4GiB_m64_acgt"):
-        spec = corpus.scaled(corpus.CONFIGS[name], 5 * (1 << 20) + 3)
-        text = spec.host_text()
-        assert np.array_equal(port.search(text, spec.pattern()), reference.search(text, spec.pattern()))
+    cases = reference_runs.config_cases(5 * (1 << 20) + 3)
+    for (text, pat), want in zip(cases, reference_runs.load("search_configs_5MiB"), strict=True):
+        got = port.search(text, pat)
+        if reference is not None:
+            assert np.array_equal(got, reference.search(text, pat))
+        assert reference_runs.digest(got) == want
 
 
 def test_edge_cases(port):

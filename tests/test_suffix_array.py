@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_file_bytes, load_golden
+from golden import reference_runs
 
 
 def sha(a):
@@ -33,13 +34,12 @@ def test_oracle_matches_reference_golden(port):
 
 
 def test_oracle_equals_reference_build_random(port, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(21)
-    for _ in range(200):
-        n = int(rng.integers(1, 500))
-        x = (rng.integers(0, int(rng.integers(1, 27)), n) + 97).astype(np.uint8)
-        assert np.array_equal(port.suffix_array(x), reference.suffix_array(x))
+    """Against the reference build when it is present, and against its recorded answers (tests/golden/reference_runs.py)."""
+    for x, want in zip(reference_runs.suffix_array_texts(), reference_runs.load("suffix_array"), strict=True):
+        sa = port.suffix_array(x)
+        if reference is not None:
+            assert np.array_equal(sa, reference.suffix_array(x))
+        assert reference_runs.digest(sa) == want
 
 
 def test_oracle_is_the_ordinary_suffix_array_on_lowercase(port):

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/r03_final
 mkdir -p "$OUT"
 cd "$R"
 : > "$OUT/bench_lines.jsonl"
-b() { timeout -k 10 400 python3 bench.py "$@" >> "$OUT/bench_lines.jsonl" 2>> "$OUT/bench.err"; rc=$?; echo "bench $* rc $rc"; [ $rc -ge 124 ] && exit 1; return 0; }
+b() { timeout -k 10 400 python3 bench.py --full "$@" >> "$OUT/bench_lines.jsonl" 2>> "$OUT/bench.err"; rc=$?; echo "bench $* rc $rc"; [ $rc -ge 124 ] && exit 1; return 0; }
 b
 b --steps 20 --warmup 5
 b --steps 20 --warmup 5 --ramp-up 0

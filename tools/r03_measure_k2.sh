@@ -10,7 +10,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$OUT/tests.log" 2>&1; r
 tail -4 "$OUT/tests.log"
 if [ $rc -ge 124 ]; then echo "tests killed"; exit 1; fi
 timeout -k 10 300 python3 tools/ed_sweep.py > "$OUT/ed_sweep.jsonl" 2> "$OUT/ed_sweep.err" || exit 1
-B="python3 bench.py"
+B="python3 bench.py --full"
 timeout -k 10 200 $B --steps 200 --warmup 20 > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err" &&
 timeout -k 10 200 $B --steps 20 --warmup 5 > "$OUT/bench_cfg2_driver_flags.json" 2>> "$OUT/bench.err" &&
 timeout -k 10 200 $B --steps 20 --warmup 5 --ramp-up 0 > "$OUT/bench_cfg2_no_ramp_up.json" 2>> "$OUT/bench.err" &&

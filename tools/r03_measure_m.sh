@@ -14,6 +14,6 @@ timeout -k 10 300 python3 tools/short_patterns.py --gib 4 --ms 1,2,3 --variants 
 timeout -k 10 300 python3 tools/multi_pattern.py --gib 4 --m 16 --kind 0 > "$OUT/multi_pattern_p95_m16.jsonl" 2> "$OUT/multi.err" &&
 timeout -k 10 300 python3 tools/multi_pattern.py --gib 4 --m 6 --kind 0 > "$OUT/multi_pattern_p95_m6.jsonl" 2>> "$OUT/multi.err" &&
 timeout -k 10 300 python3 tools/multi_pattern.py --gib 4 --m 64 --kind 1 > "$OUT/multi_pattern_acgt_m64.jsonl" 2>> "$OUT/multi.err" &&
-timeout -k 10 200 python3 bench.py --workload ed64k --steps 30 --warmup 3 > "$OUT/bench_ed64k.json" 2> "$OUT/bench.err" &&
+timeout -k 10 200 python3 bench.py --full --workload ed64k --steps 30 --warmup 3 > "$OUT/bench_ed64k.json" 2> "$OUT/bench.err" &&
 timeout -k 10 200 python3 tools/dense_results.py --gib 1 --kind 0 --ms 1,2,3 > "$OUT/dense_p95.jsonl" 2>> "$OUT/dense.err" &&
 echo done

@@ -12,4 +12,4 @@ timeout -k 10 400 python3 tools/ed_soak.py > "$OUT/ed_soak.txt" 2>&1; rc=$?; ech
 if [ $rc -ge 124 ]; then exit 1; fi
 timeout -k 10 300 python3 tools/ed_sweep.py --n 65536 > "$OUT/ed_sweep.jsonl" 2> "$OUT/ed_sweep.err"; echo "sweep rc $?"; head -3 "$OUT/ed_sweep.jsonl"
 timeout -k 10 300 python3 tools/ed_step_experiments.py > "$OUT/ed_step_experiments.jsonl" 2> "$OUT/ed_step.err"; echo "step x rc $?"
-timeout -k 10 300 python3 bench.py --workload ed64k --steps 50 --warmup 5 > "$OUT/bench_ed64k.jsonl" 2> "$OUT/bench_ed.err"; echo "bench rc $?"; cat "$OUT/bench_ed64k.jsonl"
+timeout -k 10 300 python3 bench.py --full --workload ed64k --steps 50 --warmup 5 > "$OUT/bench_ed64k.jsonl" 2> "$OUT/bench_ed.err"; echo "bench rc $?"; cat "$OUT/bench_ed64k.jsonl"
