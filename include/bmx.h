@@ -157,6 +157,8 @@ int bmx_search_ranges(bmx_ctx *ctx, const char *text, uint64_t n, const char *pa
  * (n_own == n - m + 1 or more means "all of it").
  * `stream` is a hipStream_t used as is (NULL = the null stream).  On return the
  * offsets are sorted ascending in d_match_positions and *n_matches is valid.
+ * capacity 0 counts only; like any capacity below the total it returns
+ * BMX_ERR_CAPACITY when there are matches.
  * The host waits by polling a pinned status word that the ordering kernel writes
  * after the list is complete (system-scope release), not by synchronising the
  * stream: work the caller enqueues on `stream` afterwards is ordered as usual. */

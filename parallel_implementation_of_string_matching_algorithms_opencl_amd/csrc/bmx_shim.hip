@@ -898,7 +898,7 @@ int bmx_search_device_finish(bmx_ctx *ctx, uint64_t *d_match_positions, uint64_t
             if (rc != BMX_OK) return rc;
         }
     }
-    return total > capacity && capacity > 0 ? BMX_ERR_CAPACITY : BMX_OK;
+    return total > capacity ? BMX_ERR_CAPACITY : BMX_OK; // (count-only calls too: capacity 0 holds none of a non-empty list)
 }
 
 int bmx_search_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
@@ -1630,6 +1630,7 @@ int bmx_search_ranges(bmx_ctx *ctx_in, const char *text, uint64_t n, const char 
         uint64_t total = 0;
         rc = bmx_search_device(ctx, (const char *)d_text + s, len, len, (uint64_t)s, pat, m, good, bad, nullptr,
                                0, &total, nullptr);
+        if (rc == BMX_ERR_CAPACITY) rc = BMX_OK; // (a count-only call: the total is all it asks for)
         ans[r] = (int32_t)total;
     }
     if (d_text) (void)hipFree(d_text);
