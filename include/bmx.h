@@ -26,6 +26,8 @@
  *   bmx_suffix_array      SuffixArrays/SuffixArrays/SuffixArrays.cpp:101-154, :417-470 + kernel.cl (third program)
  *   bmx_search_device     the same scan on a text already resident in HBM (the reference re-uploads
  *                         per iteration, BoyreMoore.cpp:246; its timer also starts after the upload, :258)
+ *   bmx_search_approx     no counterpart: matches within k edits, the recurrence of kernal.cl:5-56 in Myers'
+ *                         bit-parallel form with kernel1.cl:24's one report per hit (section below)
  *
  * Semantics (bit-exact with the reference kernel run as one work-item over
  * [0, n-1]): match_positions receives, in ascending order, every
@@ -298,6 +300,41 @@ float bmx_last_edit_distance_ms(bmx_ctx *ctx);
  * diagonals from both corners; +16 = one launch per tile diagonal from the top-left corner only.
  * Every schedule returns the same distance. */
 int bmx_set_ed_variant(bmx_ctx *ctx, int variant);
+
+/* ---- approximate search: matches within k edits (Sellers' k-differences problem) ---------- */
+
+/* The question that joins the scan and the edit distance above: where does pat occur in the text with at most k
+ * substitutions, insertions or deletions?  The reference has no such program; its closest relatives are the
+ * edit-distance recurrence of EditDistance-1/EditDistance-1/kernal.cl:5-56 (here Myers' bit-parallel form of it, one
+ * 32- or 64-bit word per lane) and the one report per hit of BoyreMoore/x64/Debug/kernel1.cl:24.  A caller that
+ * would otherwise run bmx_edit_distance over every substring of the text, or an agrep-style filter on the host, calls
+ * this instead.
+ *
+ * Semantics: for the view d_text[0..n) and pat[0..m), every END index j with min over s of ED(pat, text[s..j]) <= k
+ * (Levenshtein distance, unit costs; 0 <= s <= j + 1), ascending, each with that minimum (0..k) in d_dist.  Every
+ * qualifying j is reported, so one match with k errors usually shows as a short run of adjacent ends.  With k = 0 the
+ * ends are exactly bmx_search_device's starts + m - 1.  Any byte values; 1 <= m <= BMX_MAX_APPROX_PATTERN,
+ * 0 <= k < m, n < 2^40, any alignment of d_text.
+ * Shards: only ends j in [lead, n) are reported, each as base_offset + j; alignments may start anywhere in the view,
+ * before lead included.  An alignment of cost <= k spans at most m + k bytes, so a shard passes a view that begins
+ * m + k - 1 bytes (clipped at 0) before its first end, with lead = that amount: the shards' lists then concatenate to
+ * the whole text's list.
+ * Capacity: d_ends (and d_dist, which may be NULL) have room for `capacity` entries; the stored entries are the LOWEST
+ * `capacity` ends, ascending; *n_matches is the true total, and a total above capacity returns BMX_ERR_CAPACITY
+ * (capacity 0 counts only).  Argument errors (m or k out of range, lead > n, NULL pointers where a capacity needs
+ * them) return BMX_ERR_ARG before any HIP call.  A workgroup that waits longer than its bound (~1 s) for its
+ * predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly ordered.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream. */
+#define BMX_MAX_APPROX_PATTERN 64
+int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                             const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist /* may be NULL */,
+                             uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_approx_device, download).  ctx may be NULL (a context on
+ * device 0 is created and destroyed inside); ends / dist as above (dist may be NULL). */
+int bmx_search_approx(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *pat, int32_t m,
+                      int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the approximate-search kernel) of the last call on ctx; < 0 if none. */
+float bmx_last_approx_ms(bmx_ctx *ctx);
 
 /* ---- suffix array: the reference's third program -------------------- */
 

@@ -19,6 +19,10 @@
 //                             of the runs and the distance, :358-383)
 //   bmx_cli --suffix-array F [--iters N] [--max-print K]   its third (SuffixArrays.cpp: text from
 //                             input.txt, :181; array printed, :155-161; mean time, :514)
+//   bmx_cli --approx K [--text F] [--pattern F] [--iters N] [--positions] [--max-print K]
+//                             approximate search (no counterpart in the reference): every end of a match
+//                             with at most K edits, on the resident text; prints the hit count, the first
+//                             and last ends with their distances and the mean time
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -80,7 +84,7 @@ std::vector<int32_t> split_like_reference(const std::string &text, int P)
 int main(int argc, char **argv)
 {
     std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path;
-    int iters = 10, device = 0, ranges = 0, gpus = 0;
+    int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
     bool positions = false;
     uint64_t max_print = 32;
     for (int i = 1; i < argc; ++i) {
@@ -100,6 +104,7 @@ int main(int argc, char **argv)
         else if (a == "--ranges") ranges = atoi(need("--ranges"));
         else if (a == "--max-print") max_print = strtoull(need("--max-print"), nullptr, 10);
         else if (a == "--positions") positions = true;
+        else if (a == "--approx") approx_k = atoi(need("--approx"));
         else if (a == "--edit-distance") {
             ed_a = need("--edit-distance");
             ed_b = need("--edit-distance");
@@ -177,6 +182,62 @@ int main(int argc, char **argv)
     const int32_t m = (int32_t)pat.size();
     printf("text %s: %llu bytes, pattern %s: %d bytes\n", text_path.c_str(), (unsigned long long)n,
            pat_path.c_str(), m);
+
+    if (approx_k >= 0) {
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        void *d_text = nullptr;
+        uint64_t *d_ends = nullptr;
+        uint8_t *d_dist = nullptr;
+        const uint64_t cap = n ? n : 1; // at most one hit per end
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap * sizeof(uint64_t), (void **)&d_ends);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap, (void **)&d_dist);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "device setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        double total = 0.0, kernel_ms = 0.0;
+        uint64_t hits = 0;
+        for (int it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_search_approx_device(ctx, d_text, n, 0, 0, pat.data(), m, approx_k, d_ends, d_dist, cap, &hits, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_search_approx_device failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_approx_ms(ctx);
+        }
+        // the list itself through the host-buffer entry point (text, pattern, k) -> (ends, distances)
+        std::vector<uint64_t> ends(hits ? hits : 1);
+        std::vector<uint8_t> dist(hits ? hits : 1);
+        uint64_t got = 0;
+        rc = bmx_search_approx(ctx, text.data(), n, pat.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
+        if (rc != BMX_OK || got != hits) {
+            fprintf(stderr, "bmx_search_approx failed: %d (%s), %llu hits against %llu\n", rc, bmx_last_error(),
+                    (unsigned long long)got, (unsigned long long)hits);
+            return 1;
+        }
+        printf("approximate matches (k = %d): %llu\n", approx_k, (unsigned long long)hits);
+        if (hits) {
+            printf("first end: %llu (distance %d)\n", (unsigned long long)ends[0], dist[0]);
+            printf("last end: %llu (distance %d)\n", (unsigned long long)ends[hits - 1], dist[hits - 1]);
+        }
+        if (positions) {
+            for (uint64_t i = 0; i < hits && i < max_print; ++i)
+                printf("End at : %llu (distance %d)\n", (unsigned long long)ends[i], dist[i]);
+            if (hits > max_print) printf("... %llu more\n", (unsigned long long)(hits - max_print));
+        }
+        if (iters > 0)
+            printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        bmx_device_free(ctx, d_dist);
+        bmx_device_free(ctx, d_ends);
+        bmx_device_free(ctx, d_text);
+        bmx_ctx_destroy(ctx);
+        return 0;
+    }
 
     int32_t bad[BMX_BAD_TABLE_SIZE];
     std::vector<int32_t> good(m > 0 ? m : 1);

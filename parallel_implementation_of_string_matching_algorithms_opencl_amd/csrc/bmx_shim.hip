@@ -44,6 +44,12 @@ int bmx_internal_radix_sort(uint64_t *d_keys, uint64_t n, unsigned end_bit, void
 // bmx_sa.hip
 int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, float *ms_out,
                               int *rounds_out, void **ws, size_t *ws_bytes, uint32_t **pinned, int flags, char *err, size_t errlen);
+// bmx_approx.hip
+int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                        const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
+                        uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_approx_free(void *state);
+float bmx_internal_approx_ms(const void *state);
 
 namespace {
 
@@ -202,6 +208,7 @@ struct bmx_ctx {
     size_t sa_ws_bytes = 0;
     uint32_t *sa_pinned = nullptr; // pinned host block the queued LDS rounds report into (allocated on first use, freed with the context)
     int sa_last_rounds = 0, sa_last_lds_rounds = 0;
+    void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     int blocks_per_cu = 0; // 0 = as many as LDS and the 32-wave limit admit
     unsigned long long *d_count = nullptr; // live match counter; re-armed by order_kernel
     uint32_t *d_tile_count = nullptr;      // matches per tile of the last scan (dense results: input of the fill pass)
@@ -545,6 +552,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     if (ctx->ed_ws) (void)hipFree(ctx->ed_ws);
     if (ctx->sa_ws) (void)hipFree(ctx->sa_ws);
     if (ctx->sa_pinned) (void)hipHostFree(ctx->sa_pinned);
+    bmx_internal_approx_free(ctx->approx);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
     for (int i = 0; i < bmx_ctx::EV_RING; ++i) {
         if (ctx->ev0[i]) (void)hipEventDestroy(ctx->ev0[i]);
@@ -1517,6 +1525,67 @@ int bmx_suffix_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_
 float bmx_last_suffix_array_ms(bmx_ctx *ctx) { return ctx ? ctx->sa_last_ms : -1.0f; }
 int bmx_last_suffix_array_rounds(bmx_ctx *ctx) { return ctx ? ctx->sa_last_rounds : 0; }
 int bmx_last_suffix_array_lds_rounds(bmx_ctx *ctx) { return ctx ? ctx->sa_last_lds_rounds : 0; }
+
+// ---- approximate search (bmx_approx.hip) -------------------------------------------------------
+namespace {
+// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
+bool approx_args_ok(uint64_t n, uint64_t lead, const char *pat, int32_t m, int32_t k, const void *ends, uint64_t capacity)
+{
+    return pat && m >= 1 && m <= BMX_MAX_APPROX_PATTERN && k >= 0 && k < m && lead <= n && n < (1ull << 40) &&
+           (capacity == 0 || ends);
+}
+} // namespace
+
+int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                             const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
+                             uint64_t *n_matches, void *stream_v)
+{
+    if (!approx_args_ok(n, lead, pat, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, pat, m, k, d_ends, d_dist, capacity,
+                               n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_search_approx(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t *ends,
+                      uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!approx_args_ok(n, 0, pat, m, k, ends, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        int rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    void *d_text = nullptr;
+    uint64_t *d_ends = nullptr;
+    uint8_t *d_dist = nullptr;
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    int rc = bmx_text_upload(ctx, text, n, &d_text);
+    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
+    if (rc == BMX_OK && dev_cap && dist) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
+    if (rc == BMX_OK) rc = bmx_search_approx_device(ctx, d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr);
+    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
+        const uint64_t stored = std::min(total, dev_cap);
+        hipError_t e = hipSuccess;
+        if (stored) e = hipMemcpy(ends, d_ends, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (stored && dist && e == hipSuccess) e = hipMemcpy(dist, d_dist, stored, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_err("download of approximate matches: %s", hipGetErrorString(e));
+            rc = BMX_ERR_HIP;
+        }
+        if (n_matches) *n_matches = total;
+        if (rc == BMX_OK && total > capacity) rc = BMX_ERR_CAPACITY;
+    }
+    if (d_dist) (void)hipFree(d_dist);
+    if (d_ends) (void)hipFree(d_ends);
+    if (d_text) (void)hipFree(d_text);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+
+float bmx_last_approx_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_approx_ms(ctx->approx) : -1.0f; }
 
 int bmx_device_alloc(bmx_ctx *ctx, uint64_t bytes, void **d_ptr_out)
 {

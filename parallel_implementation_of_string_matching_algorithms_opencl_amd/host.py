@@ -32,6 +32,7 @@ EXP_LIB_PATH = os.path.join(_HERE, "lib", "libbmx_exp.so")
 
 MAX_PATTERN = 512
 MAX_MULTI = 8
+MAX_APPROX_PATTERN = 64
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -96,6 +97,11 @@ SYMBOLS = [
                                            C.c_void_p]),
     ("bmx_last_edit_distance_ms", C.c_float, [C.c_void_p]),
     ("bmx_set_ed_variant", C.c_int, [C.c_void_p, C.c_int]),
+    ("bmx_search_approx_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_approx", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_approx_ms", C.c_float, [C.c_void_p]),
     ("bmx_suffix_array", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _i32p]),
     ("bmx_suffix_array_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("bmx_last_suffix_array_ms", C.c_float, [C.c_void_p]),
@@ -464,6 +470,56 @@ class Context:
     def set_ed_variant(self, v: int):
         self._chk(self._L.bmx_set_ed_variant(self._h, v), "bmx_set_ed_variant")
 
+    # -- approximate search: ends of matches within k edits ---------------------------
+    def search_approx_device(self, d_text, pattern, k: int, *, n: Optional[int] = None, lead: int = 0, base_offset: int = 0,
+                             out=None, dist_out=None, capacity: Optional[int] = None):
+        """Every end j in [lead, n) of the view ``d_text[0:n)`` with min over s of ED(pattern, text[s..j]) <= k, ascending,
+        reported as base_offset + j (bmx_search_approx_device).  ``out``: int64/uint64 CUDA tensor, ``dist_out``: uint8
+        CUDA tensor (both allocated if None).  Returns (ends view, distances view, true total); the views hold the lowest
+        min(total, capacity) ends.  A capacity below the total is not an error here (the total says so)."""
+        import torch
+
+        pat = _pat_bytes(pattern)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            cap = capacity if capacity is not None else 1 << 16
+            out = torch.empty(max(cap, 1), dtype=torch.int64, device=d_text.device)
+        if dist_out is None:
+            dist_out = torch.empty(max(out.numel(), 1), dtype=torch.uint8, device=d_text.device)
+        cap = min(out.numel(), dist_out.numel()) if capacity is None else min(capacity, out.numel(), dist_out.numel())
+        stream = C.c_void_p(torch.cuda.current_stream(d_text.device).cuda_stream)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_approx_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset, pat, len(pat),
+                                              int(k), C.c_void_p(out.data_ptr()), C.c_void_p(dist_out.data_ptr()), cap,
+                                              C.byref(total), stream)
+        self._chk(rc, "bmx_search_approx_device", allow=(ERR_CAPACITY,))
+        got = min(int(total.value), cap)
+        return out[:got], dist_out[:got], int(total.value)
+
+    def search_approx(self, text, pattern, k: int, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_approx): (ends uint64, distances uint8), ascending.  With ``capacity`` given and too
+        small, raises BmxError(ERR_CAPACITY); without it the list is always complete."""
+        pat = _pat_bytes(pattern)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            ends = np.empty(max(cap, 1), dtype=np.uint64)
+            dist = np.empty(max(cap, 1), dtype=np.uint8)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_approx(self._h, tptr, n, pat, len(pat), int(k), C.c_void_p(ends.ctypes.data),
+                                           C.c_void_p(dist.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_approx")
+            del keep
+            t = int(total.value)
+            return ends[:t].copy(), dist[:t].copy()
+
+    def last_approx_ms(self) -> float:
+        return float(self._L.bmx_last_approx_ms(self._h))
+
     # -- suffix array (the reference's third program) -----------------------------
     def suffix_array(self, text) -> np.ndarray:
         """int32 suffix array in the reference's order (SuffixArrays.cpp:101-154)."""
@@ -637,6 +693,11 @@ def default_context() -> Context:
 def search(text, pattern) -> np.ndarray:
     """(text, pattern) -> match_positions, the north-star entry point."""
     return default_context().search(text, pattern)
+
+
+def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(text, pattern, k) -> (ends, distances): every end of a match with at most k edits (bmx_search_approx)."""
+    return default_context().search_approx(text, pattern, k)
 
 
 def search_multi(text, pattern, devices: Union[int, Sequence[int]], capacity: Optional[int] = None) -> np.ndarray:
