@@ -336,6 +336,44 @@ int bmx_search_approx(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint6
 /* Device time (ms, HIP events around the approximate-search kernel) of the last call on ctx; < 0 if none. */
 float bmx_last_approx_ms(bmx_ctx *ctx);
 
+/* ---- dictionary search: many patterns in one pass ------------------------------------------ */
+
+/* What `grep -F -f words.txt` asks: every occurrence of every pattern of a word list, a block list or a set of primers,
+ * in ONE pass over a resident text (bmx_search_device_multi takes at most BMX_MAX_MULTI patterns and walks each with its
+ * own tables).  The reference has no such program; its one report per hit is BoyreMoore/x64/Debug/kernel1.cl:24.
+ *
+ * A dictionary is built once on the host (LDS filter bitmaps, an exact-prefix table, the patterns packed in one blob),
+ * uploaded to ctx's device and reused across searches and texts.  1 <= K <= BMX_MAX_DICT patterns, 1 <= ms[i] <=
+ * BMX_MAX_PATTERN; a pattern byte >= 0x80 returns BMX_ERR_DOMAIN (as bmx_build_tables does).
+ * Semantics: every pair (p, i) with text[p .. p + ms[i]) == pats[i], ordered by p, then by i, positions in d_pos and
+ * pattern indices in d_pid (which may be NULL).  Overlapping matches count, every pattern matching at one p counts, and
+ * identical patterns under different indices are each reported.  Restricted to one i the positions are those of
+ * bmx_search_device(pats[i]).  Text bytes may have any value; n < 2^40, any alignment of d_text.
+ * Shards: only windows that start in [0, n_own) and fit in n are reported, each as base_offset + p (n_own >= n: all);
+ * a shard passes a halo of max(ms) - 1 bytes and the shards' lists concatenate to the whole text's list.
+ * Capacity: the stored pairs are the LOWEST `capacity` pairs in the order above; *n_matches is the true total, and a
+ * larger total returns BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers, K or m out of
+ * range, a dictionary of another context) return BMX_ERR_ARG / BMX_ERR_DOMAIN before any HIP call, with ctx = NULL
+ * too.  A workgroup that waits longer than its bound (~1 s) for its predecessors' counts makes the call return
+ * BMX_ERR_HIP: a list is never returned partly ordered.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream. */
+#define BMX_MAX_DICT 65536
+typedef struct bmx_dict bmx_dict;
+int bmx_dict_create(bmx_ctx *ctx, const char *const *pats, const int32_t *ms, int32_t K, bmx_dict **out);
+void bmx_dict_destroy(bmx_dict *d);
+int bmx_dict_search_device(bmx_ctx *ctx, const bmx_dict *d, const void *d_text, uint64_t n, uint64_t n_own,
+                           uint64_t base_offset, uint64_t *d_pos, uint32_t *d_pid /* may be NULL */, uint64_t capacity,
+                           uint64_t *n_matches, void *stream);
+/* Host buffers in and out (upload, bmx_dict_create, bmx_dict_search_device, download, bmx_dict_destroy).  ctx may be
+ * NULL (a context on device 0 is created and destroyed inside); pid may be NULL. */
+int bmx_dict_search(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *const *pats,
+                    const int32_t *ms, int32_t K, uint64_t *pos, uint32_t *pid, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the dictionary kernel) of the last dictionary search on ctx; < 0 if none. */
+float bmx_last_dict_ms(bmx_ctx *ctx);
+/* Text positions of the last dictionary search on ctx that passed the LDS filters and were looked up in the
+ * exact-prefix table (the filters' false positives plus the matching positions); < 0 if none. */
+int64_t bmx_last_dict_candidates(bmx_ctx *ctx);
+
 /* ---- suffix array: the reference's third program -------------------- */
 
 /* sa[j] = start of the j-th suffix of text[0..n), n < 2^31, in the order the reference's

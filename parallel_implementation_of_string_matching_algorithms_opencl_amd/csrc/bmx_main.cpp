@@ -23,6 +23,11 @@
 //                             approximate search (no counterpart in the reference): every end of a match
 //                             with at most K edits, on the resident text; prints the hit count, the first
 //                             and last ends with their distances and the mean time
+//   bmx_cli --dict F [--text F] [--iters N] [--positions] [--max-print K]
+//                             dictionary search (no counterpart in the reference): every occurrence of every
+//                             pattern of F, one per line as `grep -F -f` reads it (empty lines skipped), in
+//                             one pass; prints the pair count, the first and last (position, pattern) pairs
+//                             and the mean time
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -83,7 +88,7 @@ std::vector<int32_t> split_like_reference(const std::string &text, int P)
 
 int main(int argc, char **argv)
 {
-    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path;
+    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
     bool positions = false;
     uint64_t max_print = 32;
@@ -105,6 +110,7 @@ int main(int argc, char **argv)
         else if (a == "--max-print") max_print = strtoull(need("--max-print"), nullptr, 10);
         else if (a == "--positions") positions = true;
         else if (a == "--approx") approx_k = atoi(need("--approx"));
+        else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--edit-distance") {
             ed_a = need("--edit-distance");
             ed_b = need("--edit-distance");
@@ -174,14 +180,94 @@ int main(int argc, char **argv)
         fprintf(stderr, "cannot read text file %s\n", text_path.c_str());
         return 1;
     }
-    if (!read_file(pat_path, pat)) {
+    if (dict_path.empty() && !read_file(pat_path, pat)) { // (a dictionary search reads its own list)
         fprintf(stderr, "cannot read pattern file %s\n", pat_path.c_str());
         return 1;
     }
     const uint64_t n = text.size();
     const int32_t m = (int32_t)pat.size();
-    printf("text %s: %llu bytes, pattern %s: %d bytes\n", text_path.c_str(), (unsigned long long)n,
-           pat_path.c_str(), m);
+    if (dict_path.empty())
+        printf("text %s: %llu bytes, pattern %s: %d bytes\n", text_path.c_str(), (unsigned long long)n,
+               pat_path.c_str(), m);
+    else
+        printf("text %s: %llu bytes\n", text_path.c_str(), (unsigned long long)n);
+
+    if (!dict_path.empty()) {
+        std::string words;
+        if (!read_file(dict_path, words)) {
+            fprintf(stderr, "File Not Found!\n");
+            return 1;
+        }
+        std::vector<std::string> list;
+        for (size_t at = 0; at < words.size();) {
+            size_t nl = words.find('\n', at);
+            if (nl == std::string::npos) nl = words.size();
+            std::string w = words.substr(at, nl - at);
+            if (!w.empty() && w.back() == '\r') w.pop_back();
+            if (!w.empty()) list.push_back(w);
+            at = nl + 1;
+        }
+        std::vector<const char *> pats;
+        std::vector<int32_t> ms;
+        for (const auto &w : list) pats.push_back(w.data()), ms.push_back((int32_t)w.size());
+        const int32_t K = (int32_t)list.size();
+        printf("dictionary %s: %d patterns\n", dict_path.c_str(), K);
+        bmx_ctx *ctx = nullptr;
+        bmx_dict *dict = nullptr;
+        void *d_text = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        if (rc == BMX_OK) rc = bmx_dict_create(ctx, pats.data(), ms.data(), K, &dict);
+        if (rc == BMX_OK && n) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "device setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        double total = 0.0, kernel_ms = 0.0;
+        uint64_t hits = 0;
+        for (int it = 0; it < iters; ++it) { // count only: the timed calls store nothing
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_dict_search_device(ctx, dict, d_text, n, n, 0, nullptr, nullptr, 0, &hits, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) {
+                fprintf(stderr, "bmx_dict_search_device failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_dict_ms(ctx);
+        }
+        // the list itself through the host-buffer entry point (text, patterns) -> (positions, pattern indices)
+        uint64_t got = 0;
+        rc = bmx_dict_search(ctx, text.data(), n, pats.data(), ms.data(), K, nullptr, nullptr, 0, &got);
+        if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) {
+            fprintf(stderr, "bmx_dict_search failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        std::vector<uint64_t> pos(got ? got : 1);
+        std::vector<uint32_t> pid(got ? got : 1);
+        uint64_t got2 = 0;
+        rc = bmx_dict_search(ctx, text.data(), n, pats.data(), ms.data(), K, pos.data(), pid.data(), got, &got2);
+        if (rc != BMX_OK || got2 != got || (iters > 0 && got != hits)) {
+            fprintf(stderr, "bmx_dict_search failed: %d (%s), %llu pairs against %llu\n", rc, bmx_last_error(),
+                    (unsigned long long)got2, (unsigned long long)got);
+            return 1;
+        }
+        printf("dictionary matches: %llu\n", (unsigned long long)got);
+        if (got) {
+            printf("first match: %llu (pattern %u)\n", (unsigned long long)pos[0], pid[0]);
+            printf("last match: %llu (pattern %u)\n", (unsigned long long)pos[got - 1], pid[got - 1]);
+        }
+        if (positions) {
+            for (uint64_t i = 0; i < got && i < max_print; ++i)
+                printf("Match at : %llu (pattern %u)\n", (unsigned long long)pos[i], pid[i]);
+            if (got > max_print) printf("... %llu more\n", (unsigned long long)(got - max_print));
+        }
+        if (iters > 0)
+            printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        if (d_text) bmx_device_free(ctx, d_text);
+        bmx_dict_destroy(dict);
+        bmx_ctx_destroy(ctx);
+        return 0;
+    }
 
     if (approx_k >= 0) {
         bmx_ctx *ctx = nullptr;

@@ -50,6 +50,17 @@ int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n
                         uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_approx_free(void *state);
 float bmx_internal_approx_ms(const void *state);
+// bmx_dict.hip
+int bmx_internal_dict_create(const void *owner, int device, const char *const *pats, const int32_t *ms, int32_t K,
+                             bmx_dict **out, char *err, size_t errlen);
+void bmx_internal_dict_destroy(bmx_dict *d);
+const void *bmx_internal_dict_owner(const bmx_dict *d);
+int bmx_internal_dict_search(void **state, int num_cu, const bmx_dict *d, const void *d_text, uint64_t n, uint64_t n_own,
+                             uint64_t base_offset, uint64_t *d_pos, uint32_t *d_pid, uint64_t capacity,
+                             uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_dict_state_free(void *state);
+float bmx_internal_dict_ms(const void *state);
+int64_t bmx_internal_dict_candidates(const void *state);
 
 namespace {
 
@@ -209,6 +220,7 @@ struct bmx_ctx {
     uint32_t *sa_pinned = nullptr; // pinned host block the queued LDS rounds report into (allocated on first use, freed with the context)
     int sa_last_rounds = 0, sa_last_lds_rounds = 0;
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
+    void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
     int blocks_per_cu = 0; // 0 = as many as LDS and the 32-wave limit admit
     unsigned long long *d_count = nullptr; // live match counter; re-armed by order_kernel
     uint32_t *d_tile_count = nullptr;      // matches per tile of the last scan (dense results: input of the fill pass)
@@ -553,6 +565,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     if (ctx->sa_ws) (void)hipFree(ctx->sa_ws);
     if (ctx->sa_pinned) (void)hipHostFree(ctx->sa_pinned);
     bmx_internal_approx_free(ctx->approx);
+    bmx_internal_dict_state_free(ctx->dict);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
     for (int i = 0; i < bmx_ctx::EV_RING; ++i) {
         if (ctx->ev0[i]) (void)hipEventDestroy(ctx->ev0[i]);
@@ -1586,6 +1599,91 @@ int bmx_search_approx(bmx_ctx *ctx_in, const char *text, uint64_t n, const char 
 }
 
 float bmx_last_approx_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_approx_ms(ctx->approx) : -1.0f; }
+
+// ---- dictionary search (bmx_dict.hip) ----------------------------------------------------------
+namespace {
+// the patterns, before any HIP call: BMX_ERR_ARG for NULL arrays or a count or length out of range, BMX_ERR_DOMAIN for a
+// byte >= 0x80 (as bmx_build_tables)
+int dict_patterns_ok(const char *const *pats, const int32_t *ms, int32_t K)
+{
+    if (!pats || !ms || K < 1 || K > BMX_MAX_DICT) return BMX_ERR_ARG;
+    for (int32_t i = 0; i < K; ++i)
+        if (!pats[i] || ms[i] < 1 || ms[i] > BMX_MAX_PATTERN) return BMX_ERR_ARG;
+    for (int32_t i = 0; i < K; ++i)
+        for (int32_t j = 0; j < ms[i]; ++j)
+            if ((uint8_t)pats[i][j] >= 0x80) return BMX_ERR_DOMAIN;
+    return BMX_OK;
+}
+} // namespace
+
+int bmx_dict_create(bmx_ctx *ctx, const char *const *pats, const int32_t *ms, int32_t K, bmx_dict **out)
+{
+    const int rc = dict_patterns_ok(pats, ms, K);
+    if (rc != BMX_OK) return rc;
+    if (!ctx || !out) return BMX_ERR_ARG;
+    *out = nullptr;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_dict_create(ctx, ctx->device, pats, ms, K, out, g_err, sizeof g_err);
+}
+
+void bmx_dict_destroy(bmx_dict *d) { bmx_internal_dict_destroy(d); }
+
+int bmx_dict_search_device(bmx_ctx *ctx, const bmx_dict *d, const void *d_text, uint64_t n, uint64_t n_own,
+                           uint64_t base_offset, uint64_t *d_pos, uint32_t *d_pid, uint64_t capacity, uint64_t *n_matches,
+                           void *stream_v)
+{
+    if (!ctx || !d || bmx_internal_dict_owner(d) != ctx || (n > 0 && !d_text) || n >= (1ull << 40) ||
+        (capacity > 0 && !d_pos))
+        return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_dict_search(&ctx->dict, ctx->num_cu, d, d_text, n, n_own, base_offset, d_pos, d_pid, capacity,
+                                    n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_dict_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *const *pats, const int32_t *ms, int32_t K,
+                    uint64_t *pos, uint32_t *pid, uint64_t capacity, uint64_t *n_matches)
+{
+    int rc = dict_patterns_ok(pats, ms, K);
+    if (rc != BMX_OK) return rc;
+    if ((n > 0 && !text) || n >= (1ull << 40) || (capacity > 0 && !pos)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    bmx_dict *d = nullptr;
+    void *d_text = nullptr;
+    uint64_t *d_pos = nullptr;
+    uint32_t *d_pid = nullptr;
+    uint64_t total = 0;
+    rc = bmx_dict_create(ctx, pats, ms, K, &d);
+    if (rc == BMX_OK && n) rc = bmx_text_upload(ctx, text, n, &d_text);
+    if (rc == BMX_OK && capacity) rc = bmx_device_alloc(ctx, capacity * sizeof(uint64_t), (void **)&d_pos);
+    if (rc == BMX_OK && capacity && pid) rc = bmx_device_alloc(ctx, capacity * sizeof(uint32_t), (void **)&d_pid);
+    if (rc == BMX_OK) rc = bmx_dict_search_device(ctx, d, d_text, n, n, 0, d_pos, d_pid, capacity, &total, nullptr);
+    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
+        const uint64_t stored = std::min(total, capacity);
+        hipError_t e = hipSuccess;
+        if (stored) e = hipMemcpy(pos, d_pos, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (stored && pid && e == hipSuccess) e = hipMemcpy(pid, d_pid, stored * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_err("download of dictionary matches: %s", hipGetErrorString(e));
+            rc = BMX_ERR_HIP;
+        }
+        if (n_matches) *n_matches = total;
+    }
+    if (d_pid) (void)hipFree(d_pid);
+    if (d_pos) (void)hipFree(d_pos);
+    if (d_text) (void)hipFree(d_text);
+    bmx_dict_destroy(d);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+
+float bmx_last_dict_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_dict_ms(ctx->dict) : -1.0f; }
+
+int64_t bmx_last_dict_candidates(bmx_ctx *ctx) { return ctx ? bmx_internal_dict_candidates(ctx->dict) : -1; }
 
 int bmx_device_alloc(bmx_ctx *ctx, uint64_t bytes, void **d_ptr_out)
 {

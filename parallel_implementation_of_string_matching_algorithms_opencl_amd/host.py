@@ -33,6 +33,7 @@ EXP_LIB_PATH = os.path.join(_HERE, "lib", "libbmx_exp.so")
 MAX_PATTERN = 512
 MAX_MULTI = 8
 MAX_APPROX_PATTERN = 64
+MAX_DICT = 65536
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -102,6 +103,14 @@ SYMBOLS = [
     ("bmx_search_approx", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_last_approx_ms", C.c_float, [C.c_void_p]),
+    ("bmx_dict_create", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), _i32p, C.c_int32, C.POINTER(C.c_void_p)]),
+    ("bmx_dict_destroy", None, [C.c_void_p]),
+    ("bmx_dict_search_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_dict_search", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), _i32p, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_dict_ms", C.c_float, [C.c_void_p]),
+    ("bmx_last_dict_candidates", C.c_int64, [C.c_void_p]),
     ("bmx_suffix_array", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _i32p]),
     ("bmx_suffix_array_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("bmx_last_suffix_array_ms", C.c_float, [C.c_void_p]),
@@ -520,6 +529,38 @@ class Context:
     def last_approx_ms(self) -> float:
         return float(self._L.bmx_last_approx_ms(self._h))
 
+    # -- dictionary search: many patterns in one pass ----------------------------------
+    def dictionary(self, patterns) -> "Dictionary":
+        """Build a dictionary of ``patterns`` (str / bytes each) on this context's device (bmx_dict_create)."""
+        return Dictionary(self, patterns)
+
+    def search_dict(self, text, patterns, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_dict_search): (positions uint64, pattern indices uint32), ordered by position, then index.
+        With ``capacity`` given and too small, raises BmxError(ERR_CAPACITY); without it the list is always complete."""
+        arr, ms, K, keep_p = _dict_arrays(patterns)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            pos = np.empty(max(cap, 1), dtype=np.uint64)
+            pid = np.empty(max(cap, 1), dtype=np.uint32)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_dict_search(self._h, tptr, n, arr, ms, K, C.c_void_p(pos.ctypes.data),
+                                         C.c_void_p(pid.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_dict_search")
+            del keep, keep_p
+            t = int(total.value)
+            return pos[:t].copy(), pid[:t].copy()
+
+    def last_dict_ms(self) -> float:
+        return float(self._L.bmx_last_dict_ms(self._h))
+
+    def last_dict_candidates(self) -> int:
+        """Positions of the last dictionary search that passed the LDS filters (false positives + matching positions)."""
+        return int(self._L.bmx_last_dict_candidates(self._h))
+
     # -- suffix array (the reference's third program) -----------------------------
     def suffix_array(self, text) -> np.ndarray:
         """int32 suffix array in the reference's order (SuffixArrays.cpp:101-154)."""
@@ -565,6 +606,91 @@ class Context:
         stream = C.c_void_p(torch.cuda.current_stream(d_dst.device).cuda_stream)
         self._chk(self._L.bmx_plant_device(self._h, C.c_void_p(d_dst.data_ptr()), start, length, pat, len(pat),
                                       off.ctypes.data_as(_u64p), off.size, stream), "bmx_plant_device")
+
+
+def _dict_arrays(patterns):
+    pats = [_pat_bytes(p) for p in patterns]
+    K = len(pats)
+    arr = (C.c_char_p * max(K, 1))(*pats)
+    ms = (C.c_int32 * max(K, 1))(*[len(p) for p in pats])
+    return arr, ms, K, pats
+
+
+class Dictionary:
+    """A dictionary of up to MAX_DICT patterns resident on one context's device (bmx_dict_create): its filter bitmaps,
+    exact-prefix table and pattern blob are built once and reused across searches and texts."""
+
+    def __init__(self, ctx: "Context", patterns):
+        self._ctx = ctx
+        self._L = ctx._L
+        arr, ms, K, pats = _dict_arrays(patterns)
+        self.patterns = pats
+        self.max_m = max((len(p) for p in pats), default=0)
+        self._h = C.c_void_p()
+        ctx._chk(self._L.bmx_dict_create(ctx._h, arr, ms, K, C.byref(self._h)), "bmx_dict_create")
+
+    def __len__(self):
+        return len(self.patterns)
+
+    def close(self):
+        if self._h:
+            self._L.bmx_dict_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def search_device(self, d_text, n: Optional[int] = None, n_own: Optional[int] = None, base_offset: int = 0, out=None,
+                      pid_out=None, capacity: Optional[int] = None):
+        """Every (p, i) with d_text[p:p + len(pattern i)] == pattern i, p in [0, n_own), ordered by p then i, reported as
+        base_offset + p (bmx_dict_search_device).  ``out``: int64/uint64 CUDA tensor, ``pid_out``: int32/uint32 CUDA
+        tensor (both allocated if None; pass ``pid_out=False`` for no ids).  Returns (positions view, ids view or None,
+        true total); the views hold the lowest min(total, capacity) pairs.  A capacity below the total is not an error
+        here (the total says so)."""
+        import torch
+
+        if n is None:
+            n = d_text.numel()
+        if n_own is None:
+            n_own = n
+        if out is None:
+            cap = capacity if capacity is not None else 1 << 16
+            out = torch.empty(max(cap, 1), dtype=torch.int64, device=d_text.device)
+        if pid_out is None:
+            pid_out = torch.empty(max(out.numel(), 1), dtype=torch.int32, device=d_text.device)
+        room = out.numel() if pid_out is False else min(out.numel(), pid_out.numel())
+        cap = room if capacity is None else min(capacity, room)
+        stream = C.c_void_p(torch.cuda.current_stream(d_text.device).cuda_stream)
+        total = C.c_uint64(0)
+        pid_ptr = None if pid_out is False else C.c_void_p(pid_out.data_ptr())
+        rc = self._L.bmx_dict_search_device(self._ctx._h, self._h, C.c_void_p(d_text.data_ptr()), n, n_own, base_offset,
+                                            C.c_void_p(out.data_ptr()), pid_ptr, cap, C.byref(total), stream)
+        self._ctx._chk(rc, "bmx_dict_search_device", allow=(ERR_CAPACITY,))
+        got = min(int(total.value), cap)
+        return out[:got], (None if pid_out is False else pid_out[:got]), int(total.value)
+
+    def search(self, text) -> Tuple[np.ndarray, np.ndarray]:
+        """Host text in, (positions uint64, pattern indices uint32) out, through this resident dictionary."""
+        import torch
+
+        arr = np.frombuffer(text.encode("latin-1") if isinstance(text, str) else bytes(text), np.uint8) \
+            if isinstance(text, (str, bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+        d_text = torch.from_numpy(arr.copy()).to(f"cuda:{self._ctx.device}")
+        cap = max(1, min(arr.size, 1 << 20))
+        while True:
+            pos, pid, total = self.search_device(d_text, capacity=cap)
+            if total <= cap:
+                return pos.cpu().numpy().astype(np.uint64), pid.cpu().numpy().astype(np.uint32)
+            cap = total
 
 
 class PreparedSearch:
@@ -698,6 +824,12 @@ def search(text, pattern) -> np.ndarray:
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
     """(text, pattern, k) -> (ends, distances): every end of a match with at most k edits (bmx_search_approx)."""
     return default_context().search_approx(text, pattern, k)
+
+
+def search_dict(text, patterns) -> Tuple[np.ndarray, np.ndarray]:
+    """(text, patterns) -> (positions, pattern indices): every occurrence of every pattern, ordered by position, then
+    index (bmx_dict_search)."""
+    return default_context().search_dict(text, patterns)
 
 
 def search_multi(text, pattern, devices: Union[int, Sequence[int]], capacity: Optional[int] = None) -> np.ndarray:
