@@ -123,6 +123,8 @@ class Port(_Checker):
         L.bmo_splitmix64.restype = C.c_uint64
         L.edo_edit_distance.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.edo_edit_distance.restype = C.c_int64
+        L.edo_edit_distance_within.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.edo_edit_distance_within.restype = C.c_int64
         L.sao_suffix_array.argtypes = [C.c_void_p, C.c_int32, _i32p]
         L.sao_suffix_array.restype = C.c_int
         self.lib = L
@@ -161,6 +163,16 @@ class Port(_Checker):
         if d < 0:
             raise MemoryError("edo_edit_distance")
         return d
+
+    def edit_distance_within(self, a, b, t: int) -> Optional[int]:
+        """The distance if it is <= t, None ("more than t") otherwise: the two-row recurrence on the diagonal band
+        -t <= c - r <= t + (la - lb) only (Ukkonen's cut-off), about max(la, lb) * (2 t + |la - lb|) cells."""
+        pa, la, ka = _text_ptr(a)
+        pb, lb, kb = _text_ptr(b)
+        d = int(self.lib.edo_edit_distance_within(pa, la, pb, lb, int(t)))
+        if d == -1:
+            raise MemoryError("edo_edit_distance_within")
+        return None if d < 0 else d
 
     def suffix_array(self, text) -> np.ndarray:
         """Suffix array by prefix doubling (restatement of the reference's buildSuffixArray)."""

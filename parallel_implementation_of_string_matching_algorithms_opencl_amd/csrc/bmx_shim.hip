@@ -1366,8 +1366,10 @@ int bmx_edit_distance_device(bmx_ctx *ctx, const void *d_a, uint64_t la, const v
     if (v.band && !(ctx->ed_variant & ED_FLAGS)) {
         // The distance is symmetric and the pipeline is not: a row costs a step of every band, a column only its
         // share of one more band's lag (0.5 vs lag / (128 C) = 0.23 steps per character).  So the longer string
-        // provides the columns; and with the default variant the band width is the one the step model likes best
-        // (step ~ 25 + 3 C instructions, lb/2 + bands * lag / 2 of them: C = 6 at 64k x 64k, C = 3 at 8k x 128k).
+        // provides the columns; and with the default variant the band is the one the step model likes best
+        // (lb/2 + bands * lag / 2 steps of step_cost instructions).  Among the value bands alone that was C = 6 at
+        // 64k x 64k and C = 3 at 8k x 128k; with the table as it stands schedule 13 has the least step cost, the least
+        // step cost x lag and the fewest bands, so it is the pick at every shape (tests/test_gpu_ed_shapes.py).
         if (lb > la) {
             std::swap(d_a, d_b);
             std::swap(la, lb);

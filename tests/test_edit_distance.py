@@ -51,6 +51,46 @@ def test_oracle_metric_properties(port):
         assert port.edit_distance(x, x) == 0
 
 
+def test_thresholded_oracle_agrees_with_the_full_oracle(port):
+    """oracle.Port.edit_distance_within (the diagonal band -t <= c - r <= t + (la - lb), Ukkonen's cut-off) against the full
+    two-row oracle: unrelated and related pairs up to 2,000 characters, either string the longer one, t below, at and above
+    the distance.  It must say "more than t" (None) exactly when the distance is more than t."""
+    rng = np.random.default_rng(41)
+    pairs = []
+    for it in range(240):
+        la = int(rng.choice([1, 2, 3, 17, 64, 65, 300, 999, 2000])) if it % 3 else int(rng.integers(1, 2001))
+        al = int(rng.integers(1, 5))
+        x = (rng.integers(0, al, la) + 97).astype(np.uint8)
+        kind = it % 4
+        if kind == 0:  # unrelated, any two lengths
+            y = (rng.integers(0, al, int(rng.integers(1, 2001))) + 97).astype(np.uint8)
+        else:  # related: substitutions, deletions, inserted runs; kind 3 also cuts a piece out of the copy
+            y = x.copy()
+            y[rng.integers(0, la, int(rng.integers(0, la // 8 + 2)))] = ord("z")
+            y = np.delete(y, rng.integers(0, y.size, int(rng.integers(0, la // 10 + 1))))
+            for _ in range(int(rng.integers(0, 4))):
+                at = int(rng.integers(0, y.size + 1))
+                y = np.concatenate([y[:at], np.full(int(rng.integers(1, 40)), ord("y"), dtype=np.uint8), y[at:]])
+            if kind == 3 and y.size > 4:
+                lo = int(rng.integers(0, y.size // 2))
+                y = y[lo:lo + int(rng.integers(1, y.size - lo + 1))]
+            if y.size == 0:
+                y = x[:1].copy()
+        pairs.append((x, y))
+    pairs += [(np.frombuffer(b"kitten", np.uint8), np.frombuffer(b"sitting", np.uint8)),
+              (np.full(500, 97, np.uint8), np.full(500, 97, np.uint8)), (np.full(300, 97, np.uint8), np.full(200, 98, np.uint8))]
+    n_within = n_more = 0
+    for it, (x, y) in enumerate(pairs):
+        d = port.edit_distance(x, y)
+        for t in sorted({0, d // 2, max(d - 1, 0), d, d + 1, 2 * d + 3} | ({5000} if it % 8 == 0 else set())):  # (t = 5000: the whole table)
+            for a, b in ((x, y), (y, x)):
+                got = port.edit_distance_within(a, b, t)
+                assert got == (d if d <= t else None), (x.size, y.size, d, t, got)
+            n_within += d <= t
+            n_more += d > t
+    assert n_within > 500 and n_more > 300  # (both answers are exercised)
+
+
 # ------------------------------------------------------------------ GPU
 @pytest.mark.gpu
 def test_gpu_golden(ctx):

@@ -9,6 +9,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import sa_checks
 from conftest import golden_file_bytes, load_golden
 from golden import reference_runs
 
@@ -49,6 +50,74 @@ def test_oracle_is_the_ordinary_suffix_array_on_lowercase(port):
         b = x.tobytes()
         want = sorted(range(len(b)), key=lambda i: b[i:])
         assert port.suffix_array(x).tolist() == want
+
+
+def _periodic(rng, n, p, primitive=True):
+    if primitive:
+        para = (rng.integers(0, 26, p) + 97).astype(np.uint8)
+    else:  # a paragraph that is itself a repetition: the text's primitive period divides p
+        q = [d for d in range(1, p + 1) if p % d == 0][int(rng.integers(0, sum(p % d == 0 for d in range(1, p + 1))))]
+        para = np.tile((rng.integers(0, 3, q) + 97).astype(np.uint8), p // q)
+    return np.tile(para, n // p + 1)[:n].copy()
+
+
+def test_periodic_order_rule_is_the_ordinary_suffix_order():
+    """tests/sa_checks.py: on x = tile(paragraph of p letters)[:n], comparing the first 2 p bytes (0-padded) and then "shorter
+    first" is the ordinary suffix order: 300 random cases, p 1..11, n 1..119, non-primitive paragraphs included."""
+    rng = np.random.default_rng(61)
+    for it in range(300):
+        p, n = int(rng.integers(1, 12)), int(rng.integers(1, 120))
+        x = _periodic(rng, n, p, primitive=bool(it % 3))
+        b = x.tobytes()
+        want = sorted(range(n), key=lambda i: b[i:])
+        assert sa_checks.periodic_suffix_array(x, p).tolist() == want, (p, n, b)
+        assert sa_checks.periodic_is_sorted(x, p, np.array(want)) and sa_checks.is_sorted(x, np.array(want))
+
+
+def test_order_checks_accept_the_oracle_and_reject_its_neighbours(port):
+    """The chunked checks (permutation + adjacent pairs ascending) accept the oracle's array, and reject it after any one
+    adjacent swap, after swapping two entries of one residue class, and with an entry doubled.  Periodic texts up to
+    50,000 characters (the rule's lexsort equals the oracle there), chunks smaller than the array so that pairs straddle them.
+    The check to the suffixes' ends (is_sorted) is quadratic on a periodic text: it runs on the short ones and on random text."""
+    rng = np.random.default_rng(62)
+    for n, p, primitive in ((50_000, 61, True), (50_021, 8, True), (30_000, 12, False), (4_099, 509, True), (1_000, 1, True)):
+        x = _periodic(rng, n, p, primitive)
+        want = port.suffix_array(x)
+        where = np.empty(n, dtype=np.int64)  # where[i] = position of suffix i in the array
+        where[want] = np.arange(n)
+        assert np.array_equal(sa_checks.periodic_suffix_array(x, p), want), (n, p)
+        assert sa_checks.is_permutation(want, n)
+        for chunk in (sa_checks.CHUNK, 4_001):
+            assert sa_checks.periodic_is_sorted(x, p, want, chunk), (n, p, chunk)
+        if n <= 5_000:
+            assert sa_checks.is_sorted(x, want, 4_001)
+        for j in [0, n - 2, min(4_000, n - 2), min(4_001, n - 2)] + rng.integers(0, n - 1, 8).tolist():  # also across a chunk's end
+            bad = want.copy()
+            bad[j], bad[j + 1] = bad[j + 1], bad[j]
+            assert sa_checks.is_permutation(bad, n)
+            assert not sa_checks.periodic_is_sorted(x, p, bad, 4_001), (n, p, j)
+            if n <= 5_000:
+                assert not sa_checks.is_sorted(x, bad, 4_001), (n, p, j)
+        for _ in range(6):  # two entries of one residue class: equal on 2 p bytes unless one of them is near the end
+            i = int(rng.integers(0, max(1, n - p)))
+            k = i + p * int(rng.integers(1, max(2, (n - i) // p)))
+            if k >= n:
+                continue
+            bad = want.copy()
+            bad[where[i]], bad[where[k]] = k, i
+            assert sa_checks.is_permutation(bad, n) and not sa_checks.periodic_is_sorted(x, p, bad), (n, p, i, k)
+        bad = want.copy()
+        bad[n // 2] = bad[n // 2 - 1]
+        assert not sa_checks.is_permutation(bad, n)
+    # random text: the plain check against the oracle's array and its neighbours
+    for al in (26, 2):
+        x = (rng.integers(0, al, 40_000) + 97).astype(np.uint8)
+        want = port.suffix_array(x)
+        assert sa_checks.is_permutation(want, x.size) and sa_checks.is_sorted(x, want, 4096)
+        for j in rng.integers(0, x.size - 1, 10).tolist():
+            bad = want.copy()
+            bad[j], bad[j + 1] = bad[j + 1], bad[j]
+            assert not sa_checks.is_sorted(x, bad, 4096)
 
 
 # ------------------------------------------------------------------ GPU
