@@ -290,7 +290,8 @@ __global__ __launch_bounds__(DICT_BLOCK) void dict_kernel(const DictArgs a)
     __shared__ uint32_t bm[DICT_BM_WORDS];
     __shared__ uint64_t stage[DICT_STAGE];
     __shared__ uint32_t wave_sums[DICT_BLOCK / 64];
-    __shared__ uint32_t stage_n, cand_n;
+    __shared__ unsigned long long stage_n; // the tile's pairs: 64 bits (2^18 starts x 2^16 duplicates of one pattern is 2^34)
+    __shared__ uint32_t cand_n;
     __shared__ uint64_t sh_tile, sh_prefix;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t i = tid; i < DICT_BM_WORDS; i += DICT_BLOCK) bm[i] = a.bitmaps[i];
@@ -314,8 +315,8 @@ __global__ __launch_bounds__(DICT_BLOCK) void dict_kernel(const DictArgs a)
         // first walk: park every pair
         {
             auto park = [&](uint64_t p, uint32_t id) {
-                const uint32_t slot = atomicAdd(&stage_n, 1u);
-                if (a.out != nullptr && slot < (uint32_t)DICT_STAGE) stage[slot] = ((p - tile0) << 16) | id;
+                const unsigned long long slot = atomicAdd(&stage_n, 1ull);
+                if (a.out != nullptr && slot < (unsigned long long)DICT_STAGE) stage[slot] = ((p - tile0) << 16) | id;
             };
             uint4 v0, v1;
             uint32_t x0, x1;
@@ -384,9 +385,10 @@ __global__ __launch_bounds__(DICT_BLOCK) void dict_kernel(const DictArgs a)
         }
         __syncthreads();
         const uint64_t prefix = sh_prefix;
-        const uint32_t parked = stage_n;
-        if (a.out != nullptr && prefix < a.cap && parked > 0) { // (a tile that starts at or past the capacity stores nothing)
-            if (parked <= (uint32_t)DICT_STAGE) {
+        const uint64_t tile_pairs = stage_n;
+        if (a.out != nullptr && prefix < a.cap && tile_pairs > 0) { // (a tile that starts at or past the capacity stores nothing)
+            if (tile_pairs <= (uint64_t)DICT_STAGE) {
+                const uint32_t parked = (uint32_t)tile_pairs;
                 // slot = prefix + rank of the key among the parked ones (keys are distinct: one per (p, id))
                 for (uint32_t j = tid; j < parked; j += DICT_BLOCK) {
                     const uint64_t e = stage[j];
