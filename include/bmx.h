@@ -210,7 +210,9 @@ int bmx_stream_wait_last_scan(bmx_ctx *ctx, void *stream);
  * (no host round trip): lets a rank publish [count | offsets...] as one fixed-size
  * slot of an all-gather.  If the list is not ordered yet at that point (dense or
  * clustered matches: _finish will sort it) the published count has bit 62 set, i.e.
- * it is larger than any slot, and every rank falls back to the exact exchange. */
+ * it is larger than any slot, and every rank falls back to the exact exchange.
+ * With bmx_set_order_overlap on, `stream` is first made to wait for the context's ordering kernel (the count and the list
+ * are that kernel's): the copy and whatever the caller enqueues on `stream` behind it see both. */
 int bmx_count_to_device(bmx_ctx *ctx, uint64_t *d_dst, void *stream);
 
 /* After an all-gather of `world` slots of `slot_stride` uint64 each, laid out

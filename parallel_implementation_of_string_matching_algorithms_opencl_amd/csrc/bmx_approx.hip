@@ -81,9 +81,13 @@ int bmx_internal_approx(void **state_v, int num_cu, const void *d_text, uint64_t
 {
     if (!*state_v) *state_v = new ApproxState();
     ApproxState *st = static_cast<ApproxState *>(*state_v);
+    if (n_matches) *n_matches = 0;
+    st->last_ms = 0.0f;
+    if (lead >= n) return BMX_OK; // no end to report (before anything is put on `stream`: what is cleared below is cleared
+                                  // in front of the kernel that reads it, on the same stream)
     if (!st->d_ticket) {
         AHIP(hipMalloc(&st->d_ticket, sizeof(unsigned long long)));
-        AHIP(hipMemset(st->d_ticket, 0, sizeof(unsigned long long)));
+        AHIP(hipMemsetAsync(st->d_ticket, 0, sizeof(unsigned long long), stream));
         st->ticket_base = 0;
     }
     if (!st->h_status) {
@@ -100,10 +104,6 @@ int bmx_internal_approx(void **state_v, int num_cu, const void *d_text, uint64_t
         AHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, bmx::APPROX_BLOCK, 0));
         bpc = std::max(1, std::min(bpc, 8));
     }
-
-    if (n_matches) *n_matches = 0;
-    st->last_ms = 0.0f;
-    if (lead >= n) return BMX_OK; // no end to report
 
     const uint64_t resident = (uint64_t)num_cu * (uint64_t)bpc * bmx::APPROX_BLOCK;
     const uint32_t ps = bmx_internal_approx_piece_shift(n, m, k, resident);
@@ -133,12 +133,12 @@ int bmx_internal_approx(void **state_v, int num_cu, const void *d_text, uint64_t
         st->status_cap = 0;
         const uint64_t cap = std::max<uint64_t>(a.n_tiles, 1024);
         AHIP(hipMalloc(&st->d_status, cap * sizeof(uint64_t)));
-        AHIP(hipMemset(st->d_status, 0, cap * sizeof(uint64_t))); // tag 0 is never a call's
+        AHIP(hipMemsetAsync(st->d_status, 0, cap * sizeof(uint64_t), stream)); // tag 0 is never a call's
         st->status_cap = cap;
     }
     ++st->seq;
     if ((st->seq & bmx::APPROX_TAG_MASK) == 0) { // the tag wraps: old words could carry this call's tag
-        AHIP(hipMemset(st->d_status, 0, st->status_cap * sizeof(uint64_t)));
+        AHIP(hipMemsetAsync(st->d_status, 0, st->status_cap * sizeof(uint64_t), stream));
         ++st->seq;
     }
     a.status = st->d_status;

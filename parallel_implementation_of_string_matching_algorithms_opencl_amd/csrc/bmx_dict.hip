@@ -197,8 +197,9 @@ float bmx_internal_dict_ms(const void *state_v)
 int64_t bmx_internal_dict_candidates(const void *state_v)
 {
     const DictState *st = static_cast<const DictState *>(state_v);
-    if (!st || !st->d_cand) return -1;
-    if (!st->launched) return 0;
+    if (!st) return -1;
+    if (!st->launched) return 0; // (a search of nothing: no kernel, and on a new context no counter yet)
+    if (!st->d_cand) return -1;
     unsigned long long v = 0;
     if (hipMemcpy(&v, st->d_cand, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (int64_t)v;
@@ -211,9 +212,15 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
     const char *where = "bmx_dict_search_device";
     if (!*state_v) *state_v = new DictState();
     DictState *st = static_cast<DictState *>(*state_v);
+    if (n_matches) *n_matches = 0;
+    st->last_ms = 0.0f;
+    st->launched = false;
+    const uint64_t own = std::min(n_own, n);
+    if (own == 0) return BMX_OK; // no start to report (before anything is put on `stream`: what is cleared below is cleared
+                                 // in front of the kernel that reads it, on the same stream)
     if (!st->d_ticket) {
         DHIP(hipMalloc(&st->d_ticket, sizeof(unsigned long long)));
-        DHIP(hipMemset(st->d_ticket, 0, sizeof(unsigned long long)));
+        DHIP(hipMemsetAsync(st->d_ticket, 0, sizeof(unsigned long long), stream));
         st->ticket_base = 0;
     }
     if (!st->d_cand) DHIP(hipMalloc(&st->d_cand, sizeof(unsigned long long)));
@@ -228,12 +235,6 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
         DHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&st->blocks_per_cu, bmx::dict_kernel, bmx::DICT_BLOCK, 0));
         st->blocks_per_cu = std::max(1, std::min(st->blocks_per_cu, 4));
     }
-
-    if (n_matches) *n_matches = 0;
-    st->last_ms = 0.0f;
-    st->launched = false;
-    const uint64_t own = std::min(n_own, n);
-    if (own == 0) return BMX_OK; // no start to report
 
     const uint64_t addr = reinterpret_cast<uint64_t>(d_text);
     bmx::DictArgs a;
@@ -269,12 +270,12 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
         st->status_cap = 0;
         const uint64_t cap = std::max<uint64_t>(a.n_tiles, 1024);
         DHIP(hipMalloc(&st->d_status, cap * sizeof(uint64_t)));
-        DHIP(hipMemset(st->d_status, 0, cap * sizeof(uint64_t))); // tag 0 is never a call's
+        DHIP(hipMemsetAsync(st->d_status, 0, cap * sizeof(uint64_t), stream)); // tag 0 is never a call's
         st->status_cap = cap;
     }
     ++st->seq;
     if ((st->seq & bmx::DICT_TAG_MASK) == 0) { // the tag wraps: old words could carry this call's tag
-        DHIP(hipMemset(st->d_status, 0, st->status_cap * sizeof(uint64_t)));
+        DHIP(hipMemsetAsync(st->d_status, 0, st->status_cap * sizeof(uint64_t), stream));
         ++st->seq;
     }
     a.status = st->d_status;

@@ -1135,6 +1135,9 @@ int bmx_count_to_device(bmx_ctx *ctx, uint64_t *d_dst, void *stream_v)
 {
     if (!ctx || !d_dst) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
+    // bmx_set_order_overlap: the count (and the list) come from the ordering kernel on the context's own stream, which `stream`
+    // is not ordered behind -- the copy, and with it the exchange the caller puts behind it, wait for that kernel
+    if (ctx->order_forked) HIPCHK(hipStreamWaitEvent((hipStream_t)stream_v, ctx->ev_order, 0));
     HIPCHK(hipMemcpyAsync(d_dst, ctx->d_status + 2, sizeof(uint64_t), hipMemcpyDeviceToDevice, (hipStream_t)stream_v));
     return BMX_OK;
 }
