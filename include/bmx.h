@@ -23,6 +23,7 @@
  *                         launch of BoyreMoore.cpp:264-286: same seven arguments, same per-range
  *                         counts in ans[]
  *   bmx_edit_distance     EditDistance-1/EditDistance-1/EditDistance-1.cpp:278-345 + kernal.cl:5-56 (second program)
+ *   bmx_edit_distance_batch  EditDistance-1.cpp:278-345 looped by the caller: a column of string pairs in one call
  *   bmx_suffix_array      SuffixArrays/SuffixArrays/SuffixArrays.cpp:101-154, :417-470 + kernel.cl (third program)
  *   bmx_search_device     the same scan on a text already resident in HBM (the reference re-uploads
  *                         per iteration, BoyreMoore.cpp:246; its timer also starts after the upload, :258)
@@ -302,6 +303,50 @@ float bmx_last_edit_distance_ms(bmx_ctx *ctx);
  * diagonals from both corners; +16 = one launch per tile diagonal from the top-left corner only.
  * Every schedule returns the same distance. */
 int bmx_set_ed_variant(bmx_ctx *ctx, int variant);
+
+/* ---- batched edit distance: many string pairs in one call ------------------------------------ */
+
+/* A column of pairs instead of one pair per call: a fuzzy join of two string columns, a query word against a word list,
+ * reads against candidate loci, the hits of bmx_search_approx or bmx_dict_search post-filtered.  The reference sets
+ * everything up again for each run (EditDistance-1/EditDistance-1/EditDistance-1.cpp:278-345); here one launch takes
+ * every pair, one pair per lane, with Myers' bit-parallel recurrence in its global form (csrc/bmx_ed_batch_kernel.h).
+ *
+ * Layout: two string columns in the Arrow layout.  Each side is a byte blob plus count + 1 non-decreasing uint64
+ * offsets; string i of side b is d_b[d_b_off[i] .. d_b_off[i+1]), side a the same.  a_count is count (pairwise: a[i]
+ * against b[i]) or 1 (the single query a[0] against every b[i]; d_a_off then has two entries).  Any byte values, any
+ * alignment, empty strings allowed (the distance is then the other string's length; the blob of an all-empty side may be
+ * NULL with 0 bytes); every string has fewer than 2^31 bytes, the blobs are 64-bit sized.
+ * Result: d_dist[i] = the unit-cost Levenshtein distance of pair i, the value bmx_edit_distance returns.  With limit !=
+ * BMX_ED_NO_LIMIT it is min(distance, limit + 1) ("within limit or not"), and a pair whose lengths differ by more than
+ * limit is answered without touching its bytes.
+ * Which path a pair takes: a pair whose SHORTER string has at most BMX_ED_BATCH_WORD bytes and whose longer one has at
+ * most BMX_ED_BATCH_LONG runs in the batch kernel, and so does every pair of a one-against-many call whose query has 1 ..
+ * BMX_ED_BATCH_WORD bytes, whatever the candidate's length.  Every other pair is listed by the kernel and answered by
+ * bmx_edit_distance_device, pair by pair on the same stream: the same answer with no speed-up (one launch and one host
+ * wait per such pair).  bmx_last_ed_batch_fallbacks says how many there were.
+ * Such a pair is a bmx_edit_distance_device call on ctx like any other: after a batch call that had some,
+ * bmx_last_edit_distance_ms reports the last of them.  A batch call without any leaves that value alone.
+ * Errors: NULL pointers where count > 0 and a_count not in {1, count} return BMX_ERR_ARG before any HIP call, with ctx =
+ * NULL too; count == 0 returns BMX_OK and launches nothing.  The host entry checks the offsets on the host (monotone, the
+ * last one at most the blob size, strings below 2^31 bytes), also before any HIP call.  The device entry checks them in
+ * the kernel: a lane that finds off[i+1] < off[i], an end past a_bytes / b_bytes or a length of 2^31 or more reads no
+ * string byte and raises a status word; the call then returns BMX_ERR_ARG and d_dist is unspecified.
+ * All device work goes on `stream` (NULL = the null stream); the call returns after synchronising that stream. */
+#define BMX_ED_BATCH_WORD 64            /* a pair whose SHORTER string has at most this many bytes runs in the batch kernel */
+#define BMX_ED_BATCH_LONG 65536         /* ... unless its longer string has more bytes than this (one lane walks it) */
+#define BMX_ED_NO_LIMIT 0xFFFFFFFFu
+int bmx_edit_distance_batch_device(bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
+                                   const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
+                                   uint32_t *d_dist, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_edit_distance_batch_device on the null stream, download).  ctx may be
+ * NULL (a context on device 0 is created and destroyed inside). */
+int bmx_edit_distance_batch(bmx_ctx *ctx /* NULL: device 0 */, const void *a, uint64_t a_bytes, const uint64_t *a_off,
+                            uint64_t a_count, const void *b, uint64_t b_bytes, const uint64_t *b_off, uint64_t count,
+                            uint32_t limit, uint32_t *dist);
+/* Device time (ms, HIP events around the batch kernel) of the last batch call on ctx; < 0 if none. */
+float bmx_last_ed_batch_ms(bmx_ctx *ctx);
+/* Pairs of the last batch call on ctx that took the pair-by-pair path; < 0 if none. */
+int64_t bmx_last_ed_batch_fallbacks(bmx_ctx *ctx);
 
 /* ---- approximate search: matches within k edits (Sellers' k-differences problem) ---------- */
 

@@ -28,6 +28,10 @@
 //                             pattern of F, one per line as `grep -F -f` reads it (empty lines skipped), in
 //                             one pass; prints the pair count, the first and last (position, pattern) pairs
 //                             and the mean time
+//   bmx_cli --edit-distance-batch FILE_A FILE_B [--limit T] [--iters N]
+//                             batched edit distance (EditDistance-1.cpp:278-345 looped by the caller): the files
+//                             paired line by line, a one-line FILE_A against every line of FILE_B; one distance per
+//                             line on stdout (min(d, T + 1) with --limit), the mean time on stderr
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -84,11 +88,27 @@ std::vector<int32_t> split_like_reference(const std::string &text, int P)
     return se;
 }
 
+// Lines of a file as one blob plus offsets (the Arrow layout of bmx_edit_distance_batch); the newlines are dropped and a
+// last line needs none.
+void split_lines(const std::string &text, std::string &blob, std::vector<uint64_t> &off)
+{
+    off.assign(1, 0);
+    size_t pos = 0;
+    while (pos < text.size()) {
+        size_t nl = text.find('\n', pos);
+        if (nl == std::string::npos) nl = text.size();
+        blob.append(text, pos, nl - pos);
+        off.push_back(blob.size());
+        pos = nl + 1;
+    }
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
-    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path;
+    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b;
+    uint32_t limit = BMX_ED_NO_LIMIT;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
     bool positions = false;
     uint64_t max_print = 32;
@@ -111,7 +131,11 @@ int main(int argc, char **argv)
         else if (a == "--positions") positions = true;
         else if (a == "--approx") approx_k = atoi(need("--approx"));
         else if (a == "--dict") dict_path = need("--dict");
-        else if (a == "--edit-distance") {
+        else if (a == "--limit") limit = (uint32_t)strtoul(need("--limit"), nullptr, 10);
+        else if (a == "--edit-distance-batch") {
+            edb_a = need("--edit-distance-batch");
+            edb_b = need("--edit-distance-batch");
+        } else if (a == "--edit-distance") {
             ed_a = need("--edit-distance");
             ed_b = need("--edit-distance");
         } else if (a == "--suffix-array") sa_path = need("--suffix-array");
@@ -119,6 +143,49 @@ int main(int argc, char **argv)
             fprintf(stderr, "unknown option %s\n", a.c_str());
             return 2;
         }
+    }
+
+    if (!edb_a.empty()) {
+        std::string x, y, ablob, bblob;
+        std::vector<uint64_t> aoff, boff;
+        if (!read_file(edb_a, x) || !read_file(edb_b, y)) {
+            fprintf(stderr, "File Not Found!\n");
+            return 1;
+        }
+        split_lines(x, ablob, aoff);
+        split_lines(y, bblob, boff);
+        const uint64_t a_count = aoff.size() - 1, count = boff.size() - 1;
+        if (a_count != 1 && a_count != count) {
+            fprintf(stderr, "%llu lines against %llu: FILE_A needs one line or as many as FILE_B\n", (unsigned long long)a_count,
+                    (unsigned long long)count);
+            return 1;
+        }
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "bmx_ctx_create failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        std::vector<uint32_t> dist(count ? count : 1);
+        double total = 0.0, kernel_ms = 0.0;
+        if (iters < 1) iters = 1;
+        for (int it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_edit_distance_batch(ctx, ablob.data(), ablob.size(), aoff.data(), a_count, bblob.data(), bblob.size(),
+                                         boff.data(), count, limit, dist.data());
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_edit_distance_batch failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += count ? bmx_last_ed_batch_ms(ctx) : 0.0;
+        }
+        for (uint64_t i = 0; i < count; ++i) printf("%u\n", dist[i]);
+        fprintf(stderr, "Average time = %.6f s  (kernel %.3f ms, %llu pairs, %lld pair by pair)\n", total / iters, kernel_ms / iters,
+                (unsigned long long)count, count ? (long long)bmx_last_ed_batch_fallbacks(ctx) : 0ll);
+        bmx_ctx_destroy(ctx);
+        return 0;
     }
 
     if (!ed_a.empty() || !sa_path.empty()) {

@@ -50,6 +50,13 @@ int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n
                         uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_approx_free(void *state);
 float bmx_internal_approx_ms(const void *state);
+// bmx_ed_batch.hip
+int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
+                          const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
+                          uint32_t *d_dist, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_ed_batch_free(void *state);
+float bmx_internal_ed_batch_ms(const void *state);
+int64_t bmx_internal_ed_batch_fallbacks(const void *state);
 // bmx_dict.hip
 int bmx_internal_dict_create(const void *owner, int device, const char *const *pats, const int32_t *ms, int32_t K,
                              bmx_dict **out, char *err, size_t errlen);
@@ -220,6 +227,7 @@ struct bmx_ctx {
     uint32_t *sa_pinned = nullptr; // pinned host block the queued LDS rounds report into (allocated on first use, freed with the context)
     int sa_last_rounds = 0, sa_last_lds_rounds = 0;
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
+    void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
     void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
     int blocks_per_cu = 0; // 0 = as many as LDS and the 32-wave limit admit
     unsigned long long *d_count = nullptr; // live match counter; re-armed by order_kernel
@@ -565,6 +573,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     if (ctx->sa_ws) (void)hipFree(ctx->sa_ws);
     if (ctx->sa_pinned) (void)hipHostFree(ctx->sa_pinned);
     bmx_internal_approx_free(ctx->approx);
+    bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_dict_state_free(ctx->dict);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
     for (int i = 0; i < bmx_ctx::EV_RING; ++i) {
@@ -1494,6 +1503,74 @@ int bmx_edit_distance(bmx_ctx *ctx_in, const char *a, uint64_t la, const char *b
     if (!ctx_in) bmx_ctx_destroy(ctx);
     return rc;
 }
+
+// ---- batched edit distance (bmx_ed_batch.hip) --------------------------------------------------
+namespace {
+// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
+bool ed_batch_args_ok(const void *a, uint64_t a_bytes, const uint64_t *a_off, uint64_t a_count, const void *b, uint64_t b_bytes,
+                      const uint64_t *b_off, uint64_t count, const uint32_t *dist)
+{
+    if (count == 0) return true;
+    return (a_count == 1 || a_count == count) && a_off && b_off && dist && (a || a_bytes == 0) && (b || b_bytes == 0);
+}
+// the host entry's offsets: monotone, the last one inside the blob, every string below 2^31 bytes
+bool ed_batch_offsets_ok(const uint64_t *off, uint64_t strings, uint64_t bytes)
+{
+    for (uint64_t i = 0; i < strings; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ull << 31)) return false;
+    return off[strings] <= bytes;
+}
+} // namespace
+
+int bmx_edit_distance_batch_device(bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
+                                   const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
+                                   uint32_t *d_dist, void *stream_v)
+{
+    if (!ed_batch_args_ok(d_a, a_bytes, d_a_off, a_count, d_b, b_bytes, d_b_off, count, d_dist)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_ed_batch(&ctx->ed_batch, ctx, d_a, a_bytes, d_a_off, a_count, d_b, b_bytes, d_b_off, count, limit, d_dist,
+                                 (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_edit_distance_batch(bmx_ctx *ctx_in, const void *a, uint64_t a_bytes, const uint64_t *a_off, uint64_t a_count,
+                            const void *b, uint64_t b_bytes, const uint64_t *b_off, uint64_t count, uint32_t limit, uint32_t *dist)
+{
+    if (!ed_batch_args_ok(a, a_bytes, a_off, a_count, b, b_bytes, b_off, count, dist)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ed_batch_offsets_ok(a_off, a_count, a_bytes) || !ed_batch_offsets_ok(b_off, count, b_bytes)) return BMX_ERR_ARG;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        int rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    void *d_a = nullptr, *d_b = nullptr, *d_a_off = nullptr, *d_b_off = nullptr, *d_dist = nullptr;
+    int rc = BMX_OK;
+    if (a_bytes) rc = bmx_text_upload(ctx, (const char *)a, a_bytes, &d_a);
+    if (rc == BMX_OK && b_bytes) rc = bmx_text_upload(ctx, (const char *)b, b_bytes, &d_b);
+    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)a_off, (a_count + 1) * sizeof(uint64_t), &d_a_off);
+    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)b_off, (count + 1) * sizeof(uint64_t), &d_b_off);
+    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, count * sizeof(uint32_t), &d_dist);
+    if (rc == BMX_OK)
+        rc = bmx_edit_distance_batch_device(ctx, d_a, a_bytes, (const uint64_t *)d_a_off, a_count, d_b, b_bytes,
+                                            (const uint64_t *)d_b_off, count, limit, (uint32_t *)d_dist, nullptr);
+    if (rc == BMX_OK) {
+        hipError_t e = hipMemcpy(dist, d_dist, count * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_err("download of the distances: %s", hipGetErrorString(e));
+            rc = BMX_ERR_HIP;
+        }
+    }
+    for (void *p : {d_a, d_b, d_a_off, d_b_off, d_dist})
+        if (p) (void)hipFree(p);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+
+float bmx_last_ed_batch_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_ed_batch_ms(ctx->ed_batch) : -1.0f; }
+
+int64_t bmx_last_ed_batch_fallbacks(bmx_ctx *ctx) { return ctx ? bmx_internal_ed_batch_fallbacks(ctx->ed_batch) : -1; }
 
 // ---- suffix array -------------------------------------------------------
 int bmx_suffix_array_device(bmx_ctx *ctx, const void *d_text, uint64_t n, int32_t *d_sa, void *stream_v)

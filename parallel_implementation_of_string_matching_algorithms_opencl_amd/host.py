@@ -34,6 +34,9 @@ MAX_PATTERN = 512
 MAX_MULTI = 8
 MAX_APPROX_PATTERN = 64
 MAX_DICT = 65536
+ED_BATCH_WORD = 64
+ED_BATCH_LONG = 65536
+ED_NO_LIMIT = 0xFFFFFFFF
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -98,6 +101,12 @@ SYMBOLS = [
                                            C.c_void_p]),
     ("bmx_last_edit_distance_ms", C.c_float, [C.c_void_p]),
     ("bmx_set_ed_variant", C.c_int, [C.c_void_p, C.c_int]),
+    ("bmx_edit_distance_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                 C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_edit_distance_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("bmx_last_ed_batch_ms", C.c_float, [C.c_void_p]),
+    ("bmx_last_ed_batch_fallbacks", C.c_int64, [C.c_void_p]),
     ("bmx_search_approx_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
     ("bmx_search_approx", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p,
@@ -204,6 +213,18 @@ def _host_text(text) -> Tuple[C.c_void_p, int, object]:
         return C.cast(C.c_char_p(b), C.c_void_p), len(b), b
     arr = np.ascontiguousarray(text, dtype=np.uint8)
     return C.c_void_p(arr.ctypes.data), arr.size, arr
+
+
+def pack_strings(strings) -> Tuple[np.ndarray, np.ndarray]:
+    """A string column in the Arrow layout of bmx_edit_distance_batch: (blob uint8, offsets uint64 of len + 1 entries).
+    ``strings``: a sequence of bytes / str, or a (blob, offsets) pair, which is passed through."""
+    if isinstance(strings, tuple) and len(strings) == 2 and isinstance(strings[1], np.ndarray):
+        return np.ascontiguousarray(strings[0], dtype=np.uint8).reshape(-1), np.ascontiguousarray(strings[1], dtype=np.uint64)
+    items = [_pat_bytes(x) for x in strings]
+    off = np.zeros(len(items) + 1, dtype=np.uint64)
+    if items:
+        off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
+    return np.frombuffer(b"".join(items), dtype=np.uint8), off
 
 
 def build_tables(pattern) -> Tuple[np.ndarray, np.ndarray]:
@@ -478,6 +499,55 @@ class Context:
 
     def set_ed_variant(self, v: int):
         self._chk(self._L.bmx_set_ed_variant(self._h, v), "bmx_set_ed_variant")
+
+    # -- batched edit distance: many string pairs in one call ---------------------------
+    def edit_distance_batch(self, a, b, limit: Optional[int] = None) -> np.ndarray:
+        """Levenshtein distances of a column of pairs, host buffers (bmx_edit_distance_batch): uint32, one per string of
+        ``b``.  ``a`` and ``b``: sequences of bytes / str, or (blob, offsets) numpy pairs; a single bytes / str ``a`` is
+        measured against every string of ``b``.  With ``limit`` the values are min(distance, limit + 1)."""
+        ablob, aoff = pack_strings([a] if isinstance(a, (bytes, bytearray, str)) else a)
+        bblob, boff = pack_strings(b)
+        count = boff.size - 1
+        dist = np.empty(max(count, 1), dtype=np.uint32)
+        rc = self._L.bmx_edit_distance_batch(self._h, C.c_void_p(ablob.ctypes.data), ablob.size, C.c_void_p(aoff.ctypes.data),
+                                             aoff.size - 1, C.c_void_p(bblob.ctypes.data), bblob.size,
+                                             C.c_void_p(boff.ctypes.data), count, ED_NO_LIMIT if limit is None else int(limit),
+                                             C.c_void_p(dist.ctypes.data))
+        self._chk(rc, "bmx_edit_distance_batch")
+        return dist[:count]
+
+    def edit_distance_batch_device(self, d_a, d_a_off, d_b, d_b_off, count: int, *, a_count: Optional[int] = None,
+                                   limit: Optional[int] = None, out=None):
+        """The same on CUDA tensors (bmx_edit_distance_batch_device): ``d_a`` / ``d_b`` uint8 blobs, ``d_a_off`` / ``d_b_off``
+        int64 or uint64 offsets (count + 1 entries; two for ``d_a_off`` with a_count = 1), ``out`` an int32 / uint32 tensor
+        of at least ``count`` entries (allocated if None).  Runs on torch's current stream and returns after synchronising
+        it; the result is the first ``count`` entries of ``out``."""
+        import torch
+
+        if a_count is None:
+            a_count = count
+        if out is None:
+            out = torch.empty(max(count, 1), dtype=torch.int32, device=d_b_off.device)
+        if out.numel() < count or out.element_size() != 4 or d_a_off.element_size() != 8 or d_b_off.element_size() != 8:
+            raise ValueError("out: 4-byte entries, at least count of them; offsets: 8-byte entries")
+        if d_a_off.numel() < a_count + 1 or d_b_off.numel() < count + 1:
+            raise ValueError("offset tensors need one entry more than strings")
+        if d_a.element_size() != 1 or d_b.element_size() != 1:
+            raise ValueError("blobs: 1-byte entries (uint8)")
+        stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+        rc = self._L.bmx_edit_distance_batch_device(self._h, C.c_void_p(d_a.data_ptr()), d_a.numel(),
+                                                    C.c_void_p(d_a_off.data_ptr()), a_count, C.c_void_p(d_b.data_ptr()),
+                                                    d_b.numel(), C.c_void_p(d_b_off.data_ptr()), count,
+                                                    ED_NO_LIMIT if limit is None else int(limit), C.c_void_p(out.data_ptr()),
+                                                    stream)
+        self._chk(rc, "bmx_edit_distance_batch_device")
+        return out[:count]
+
+    def last_ed_batch_ms(self) -> float:
+        return float(self._L.bmx_last_ed_batch_ms(self._h))
+
+    def last_ed_batch_fallbacks(self) -> int:
+        return int(self._L.bmx_last_ed_batch_fallbacks(self._h))
 
     # -- approximate search: ends of matches within k edits ---------------------------
     def search_approx_device(self, d_text, pattern, k: int, *, n: Optional[int] = None, lead: int = 0, base_offset: int = 0,
@@ -824,6 +894,11 @@ def search(text, pattern) -> np.ndarray:
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
     """(text, pattern, k) -> (ends, distances): every end of a match with at most k edits (bmx_search_approx)."""
     return default_context().search_approx(text, pattern, k)
+
+
+def edit_distance_batch(a, b, limit: Optional[int] = None) -> np.ndarray:
+    """(a, b) -> uint32 distances, pair by pair, or one ``a`` against every string of ``b`` (bmx_edit_distance_batch)."""
+    return default_context().edit_distance_batch(a, b, limit)
 
 
 def search_dict(text, patterns) -> Tuple[np.ndarray, np.ndarray]:
