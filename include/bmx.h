@@ -29,6 +29,8 @@
  *                         per iteration, BoyreMoore.cpp:246; its timer also starts after the upload, :258)
  *   bmx_search_approx     no counterpart: matches within k edits, the recurrence of kernal.cl:5-56 in Myers'
  *                         bit-parallel form with kernel1.cl:24's one report per hit (section below)
+ *   bmx_search_classes    no counterpart in the reference: a pattern position is a set of byte values (wildcards,
+ *                         sets, case folding, IUPAC codes), matched by Shift-And (section below)
  *
  * Semantics (bit-exact with the reference kernel run as one work-item over
  * [0, n-1]): match_positions receives, in ascending order, every
@@ -382,6 +384,60 @@ int bmx_search_approx(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint6
                       int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
 /* Device time (ms, HIP events around the approximate-search kernel) of the last call on ctx; < 0 if none. */
 float bmx_last_approx_ms(bmx_ctx *ctx);
+
+/* ---- class-pattern search: wildcards, sets, case folding, IUPAC codes ---------------------- */
+
+/* A fixed-length pattern whose every position is a SET of byte values: what `grep -i`, a `.` or `[0-9]` position and a
+ * degenerate primer such as GTGYCAGCMGCCGCGGTAA ask for.  The reference has no such program.  The matcher is Shift-And
+ * (Baeza-Yates and Gonnet), one 32- or 64-bit word per lane, with the approximate search's ordered output
+ * (csrc/bmx_classes_kernel.h).
+ *
+ * A pattern is m classes of BMX_CLASS_BYTES bytes each: byte value b belongs to class i iff bit (b & 7) of
+ * classes[i * BMX_CLASS_BYTES + (b >> 3)] is set.  An empty class is legal and matches nothing.
+ * Semantics: every start p with p < n_own, p + m <= n and text[p + i] in class i for all i in [0, m), ascending, each
+ * reported as base_offset + p; overlapping matches count; n_own >= n means all of the view.  These are
+ * bmx_search_device's conventions: a shard passes m - 1 halo bytes and the shards' lists concatenate to the whole text's
+ * list, and with every class a singleton the list is exactly bmx_search_device's for that string.  Any byte values in
+ * text and classes; 1 <= m <= BMX_MAX_CLASS_PATTERN, n < 2^40, any alignment of d_text.
+ * Capacity: the stored entries are the LOWEST `capacity` starts; *n_matches is the true total, and a larger total returns
+ * BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers where needed, m out of range, n too large)
+ * return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer than its bound (~1 s) for
+ * its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly ordered.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream. */
+#define BMX_MAX_CLASS_PATTERN 64
+#define BMX_CLASS_BYTES 32 /* one class: a 256-bit set; byte value b belongs iff bit (b & 7) of byte (b >> 3) is set */
+#define BMX_CLASS_ICASE 1u
+#define BMX_CLASS_IUPAC 2u
+/* Pure host code, no GPU (like bmx_build_tables): one element of expr is one class, *m the number of elements.
+ *   .        every byte value
+ *   [...]    a set: x-y is an inclusive range (x <= y), a leading ^ negates, ] directly after [ or [^ is a literal
+ *            (so is a - that does not stand between two items)
+ *   \xHH     the byte with that two-digit hexadecimal value; \ before any other byte: that byte as a literal (both
+ *            inside sets too)
+ *   any byte other than . [ \ is itself.  No repetition, alternation or anchors.
+ * BMX_CLASS_ICASE: every ASCII letter in a class brings its other case (applied before a set's negation).
+ * BMX_CLASS_IUPAC: outside brackets and escapes the upper-case letters R Y S W K M B D H V N stand for their nucleotide
+ * sets over ACGT (N = ACGT, R = AG, Y = CT, ...); A C G T stay literal; with both flags the lower-case bases belong too.
+ * BMX_ERR_ARG: NULL arguments, an unterminated set, a reversed range, a dangling \, bad hex, zero elements or more than
+ * BMX_MAX_CLASS_PATTERN; *m and classes are then untouched.  classes has room for BMX_MAX_CLASS_PATTERN classes. */
+int bmx_compile_classes(const char *expr, uint64_t expr_len, uint32_t flags,
+                        uint8_t *classes /* BMX_MAX_CLASS_PATTERN * BMX_CLASS_BYTES */, int32_t *m);
+int bmx_search_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                              const uint8_t *classes, int32_t m, uint64_t *d_match_positions, uint64_t capacity,
+                              uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_classes_device, download). */
+int bmx_search_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                       uint64_t *match_positions, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the class-search kernel) of the last call on ctx; < 0 if none. */
+float bmx_last_classes_ms(bmx_ctx *ctx);
+/* bmx_search_approx_device with "text[j] == pat[i]" replaced by "text[j] in class i": the same ends, distances, lead
+ * contract, domain (m <= BMX_MAX_APPROX_PATTERN, 0 <= k < m), errors and kernel; bmx_last_approx_ms times it. */
+int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                     const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
+                                     uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out, as bmx_search_approx (ctx may be NULL; dist may be NULL). */
+int bmx_search_approx_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                              int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
 
 /* ---- dictionary search: many patterns in one pass ------------------------------------------ */
 

@@ -76,8 +76,8 @@ float bmx_internal_approx_ms(const void *state_v)
 }
 
 int bmx_internal_approx(void **state_v, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
-                        const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
-                        uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen)
+                        const char *pat, const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
+                        uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen)
 {
     if (!*state_v) *state_v = new ApproxState();
     ApproxState *st = static_cast<ApproxState *>(*state_v);
@@ -125,7 +125,13 @@ int bmx_internal_approx(void **state_v, int num_cu, const void *d_text, uint64_t
     a.k = (uint32_t)k;
     a.warm = (uint32_t)(m + k - 1);
     a.p_shift = ps;
-    for (int32_t i = 0; i < m; ++i) a.peq[(uint8_t)pat[i]] |= 1ull << i;
+    if (pat) { // a string: position i holds one byte value
+        for (int32_t i = 0; i < m; ++i) a.peq[(uint8_t)pat[i]] |= 1ull << i;
+    } else { // classes (bmx_search_approx_classes_device): bit i = "the byte belongs to class i"
+        for (int32_t i = 0; i < m; ++i)
+            for (uint32_t c = 0; c < 256; ++c)
+                if ((classes[(size_t)i * BMX_CLASS_BYTES + (c >> 3)] >> (c & 7)) & 1u) a.peq[c] |= 1ull << i;
+    }
 
     if (a.n_tiles > st->status_cap) {
         if (st->d_status) (void)hipFree(st->d_status);

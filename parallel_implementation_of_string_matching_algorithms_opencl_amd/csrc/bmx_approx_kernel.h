@@ -67,6 +67,46 @@ __device__ __forceinline__ void approx_store_status(uint64_t *p, uint64_t v)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The look-back of one tile, for kernels that share this design (bmx_classes_kernel.h; approx_kernel below keeps its own
+// copy: its code object is recorded).  Lane 0 of the workgroup that holds tile t publishes the tile's aggregate, finds
+// the exclusive prefix over the status words of tiles t - 1 .. 0 and publishes the inclusive one; the last tile writes the
+// total and the call's sequence number to pinned memory.  Tiles t - 1 .. 0 were handed out before this one, so each is
+// owned by a running workgroup and publishes.  The bound (~1 s) only keeps a wave from spinning for ever: a waiter that
+// reaches it raises the give-up word (the host returns BMX_ERR_HIP, never this list) and goes on.  Returns the prefix.
+__device__ __forceinline__ uint64_t approx_lookback(const ApproxArgs &a, uint64_t t, uint64_t agg)
+{
+    const uint64_t tagbits = a.tag << APPROX_TAG_SHIFT;
+    uint64_t prefix = 0;
+    if (t == 0) {
+        approx_store_status(&a.status[0], tagbits | (APPROX_KIND_PREFIX << 40) | agg);
+    } else {
+        approx_store_status(&a.status[t], tagbits | (APPROX_KIND_AGG << 40) | agg);
+        uint64_t i = t - 1;
+        uint32_t spins = 0;
+        for (;;) {
+            const uint64_t w = approx_load_status(&a.status[i]);
+            const uint64_t kind = (w >> 40) & 3u;
+            if ((w >> APPROX_TAG_SHIFT) != a.tag || kind == 0) {
+                if (++spins > (1u << 24)) {
+                    __hip_atomic_store(&a.host_status[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(2);
+                continue;
+            }
+            prefix += w & APPROX_VALUE_MASK;
+            if (kind == APPROX_KIND_PREFIX || i == 0) break;
+            --i;
+        }
+        approx_store_status(&a.status[t], tagbits | (APPROX_KIND_PREFIX << 40) | ((prefix + agg) & APPROX_VALUE_MASK));
+    }
+    if (t == a.n_tiles - 1) {
+        __hip_atomic_store(&a.host_status[0], prefix + agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&a.host_status[2], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return prefix;
+}
+
 // Column state of Myers' recurrence for one lane.
 template <typename W>
 struct MyersState {

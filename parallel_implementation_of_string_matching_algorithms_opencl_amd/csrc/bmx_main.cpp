@@ -23,6 +23,12 @@
 //                             approximate search (no counterpart in the reference): every end of a match
 //                             with at most K edits, on the resident text; prints the hit count, the first
 //                             and last ends with their distances and the mean time
+//   bmx_cli --classes EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K]
+//                             class-pattern search (no counterpart in the reference): EXPR is a fixed-length
+//                             expression of bytes, `.`, `[...]` sets and `\xHH` escapes (bmx_compile_classes);
+//                             --icase folds the case of ASCII letters, --iupac reads R Y S W K M B D H V N as
+//                             nucleotide sets; prints the hit count, the first and last starts and the mean time.
+//                             With --approx K: the ends within K edits of the class pattern, printed as --approx does
 //   bmx_cli --dict F [--text F] [--iters N] [--positions] [--max-print K]
 //                             dictionary search (no counterpart in the reference): every occurrence of every
 //                             pattern of F, one per line as `grep -F -f` reads it (empty lines skipped), in
@@ -107,8 +113,9 @@ void split_lines(const std::string &text, std::string &blob, std::vector<uint64_
 
 int main(int argc, char **argv)
 {
-    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b;
-    uint32_t limit = BMX_ED_NO_LIMIT;
+    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr;
+    uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
+    bool have_classes = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
     bool positions = false;
     uint64_t max_print = 32;
@@ -131,6 +138,9 @@ int main(int argc, char **argv)
         else if (a == "--positions") positions = true;
         else if (a == "--approx") approx_k = atoi(need("--approx"));
         else if (a == "--dict") dict_path = need("--dict");
+        else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
+        else if (a == "--icase") class_flags |= BMX_CLASS_ICASE;
+        else if (a == "--iupac") class_flags |= BMX_CLASS_IUPAC;
         else if (a == "--limit") limit = (uint32_t)strtoul(need("--limit"), nullptr, 10);
         else if (a == "--edit-distance-batch") {
             edb_a = need("--edit-distance-batch");
@@ -247,13 +257,21 @@ int main(int argc, char **argv)
         fprintf(stderr, "cannot read text file %s\n", text_path.c_str());
         return 1;
     }
-    if (dict_path.empty() && !read_file(pat_path, pat)) { // (a dictionary search reads its own list)
+    if (dict_path.empty() && !have_classes && !read_file(pat_path, pat)) { // (a dictionary search reads its own list, a class search its expression)
         fprintf(stderr, "cannot read pattern file %s\n", pat_path.c_str());
         return 1;
     }
     const uint64_t n = text.size();
-    const int32_t m = (int32_t)pat.size();
-    if (dict_path.empty())
+    int32_t m = (int32_t)pat.size();
+    std::vector<uint8_t> classes(BMX_MAX_CLASS_PATTERN * BMX_CLASS_BYTES);
+    if (have_classes && bmx_compile_classes(class_expr.data(), class_expr.size(), class_flags, classes.data(), &m) != BMX_OK) {
+        fprintf(stderr, "bad class expression %s\n", class_expr.c_str());
+        return 1;
+    }
+    if (have_classes)
+        printf("text %s: %llu bytes, class expression %s: %d positions\n", text_path.c_str(), (unsigned long long)n,
+               class_expr.c_str(), m);
+    else if (dict_path.empty())
         printf("text %s: %llu bytes, pattern %s: %d bytes\n", text_path.c_str(), (unsigned long long)n,
                pat_path.c_str(), m);
     else
@@ -336,6 +354,57 @@ int main(int argc, char **argv)
         return 0;
     }
 
+    if (have_classes && approx_k < 0) {
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        void *d_text = nullptr;
+        uint64_t *d_starts = nullptr;
+        const uint64_t cap = n ? n : 1; // at most one hit per start
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap * sizeof(uint64_t), (void **)&d_starts);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "device setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        double total = 0.0, kernel_ms = 0.0;
+        uint64_t hits = 0;
+        for (int it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_search_classes_device(ctx, d_text, n, n, 0, classes.data(), m, d_starts, cap, &hits, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_search_classes_device failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_classes_ms(ctx);
+        }
+        // the list itself through the host-buffer entry point (text, classes) -> starts
+        std::vector<uint64_t> starts(hits ? hits : 1);
+        uint64_t got = 0;
+        rc = bmx_search_classes(ctx, text.data(), n, classes.data(), m, starts.data(), hits, &got);
+        if (rc != BMX_OK || got != hits) {
+            fprintf(stderr, "bmx_search_classes failed: %d (%s), %llu hits against %llu\n", rc, bmx_last_error(),
+                    (unsigned long long)got, (unsigned long long)hits);
+            return 1;
+        }
+        printf("class matches: %llu\n", (unsigned long long)got);
+        if (got) {
+            printf("first start: %llu\n", (unsigned long long)starts[0]);
+            printf("last start: %llu\n", (unsigned long long)starts[got - 1]);
+        }
+        if (positions) {
+            for (uint64_t i = 0; i < got && i < max_print; ++i) printf("Start at : %llu\n", (unsigned long long)starts[i]);
+            if (got > max_print) printf("... %llu more\n", (unsigned long long)(got - max_print));
+        }
+        if (iters > 0)
+            printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        bmx_device_free(ctx, d_starts);
+        bmx_device_free(ctx, d_text);
+        bmx_ctx_destroy(ctx);
+        return 0;
+    }
+
     if (approx_k >= 0) {
         bmx_ctx *ctx = nullptr;
         int rc = bmx_ctx_create(device, &ctx);
@@ -354,7 +423,10 @@ int main(int argc, char **argv)
         uint64_t hits = 0;
         for (int it = 0; it < iters; ++it) {
             auto t0 = std::chrono::steady_clock::now();
-            rc = bmx_search_approx_device(ctx, d_text, n, 0, 0, pat.data(), m, approx_k, d_ends, d_dist, cap, &hits, nullptr);
+            rc = have_classes ? bmx_search_approx_classes_device(ctx, d_text, n, 0, 0, classes.data(), m, approx_k, d_ends, d_dist,
+                                                                 cap, &hits, nullptr)
+                              : bmx_search_approx_device(ctx, d_text, n, 0, 0, pat.data(), m, approx_k, d_ends, d_dist, cap, &hits,
+                                                         nullptr);
             auto t1 = std::chrono::steady_clock::now();
             if (rc != BMX_OK) {
                 fprintf(stderr, "bmx_search_approx_device failed: %d (%s)\n", rc, bmx_last_error());
@@ -367,7 +439,10 @@ int main(int argc, char **argv)
         std::vector<uint64_t> ends(hits ? hits : 1);
         std::vector<uint8_t> dist(hits ? hits : 1);
         uint64_t got = 0;
-        rc = bmx_search_approx(ctx, text.data(), n, pat.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
+        if (have_classes)
+            rc = bmx_search_approx_classes(ctx, text.data(), n, classes.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
+        else
+            rc = bmx_search_approx(ctx, text.data(), n, pat.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
         if (rc != BMX_OK || got != hits) {
             fprintf(stderr, "bmx_search_approx failed: %d (%s), %llu hits against %llu\n", rc, bmx_last_error(),
                     (unsigned long long)got, (unsigned long long)hits);

@@ -46,10 +46,16 @@ int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, 
                               int *rounds_out, void **ws, size_t *ws_bytes, uint32_t **pinned, int flags, char *err, size_t errlen);
 // bmx_approx.hip
 int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
-                        const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
-                        uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+                        const char *pat, const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
+                        uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_approx_free(void *state);
 float bmx_internal_approx_ms(const void *state);
+// bmx_classes.hip
+int bmx_internal_classes(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                         const uint8_t *classes, int32_t m, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
+                         hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_classes_free(void *state);
+float bmx_internal_classes_ms(const void *state);
 // bmx_ed_batch.hip
 int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
                           const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
@@ -226,6 +232,7 @@ struct bmx_ctx {
     size_t sa_ws_bytes = 0;
     uint32_t *sa_pinned = nullptr; // pinned host block the queued LDS rounds report into (allocated on first use, freed with the context)
     int sa_last_rounds = 0, sa_last_lds_rounds = 0;
+    void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
     void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
@@ -573,6 +580,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     if (ctx->sa_ws) (void)hipFree(ctx->sa_ws);
     if (ctx->sa_pinned) (void)hipHostFree(ctx->sa_pinned);
     bmx_internal_approx_free(ctx->approx);
+    bmx_internal_classes_free(ctx->classes);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_dict_state_free(ctx->dict);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
@@ -1637,14 +1645,27 @@ int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint6
 {
     if (!approx_args_ok(n, lead, pat, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
-    return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, pat, m, k, d_ends, d_dist, capacity,
-                               n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+    return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, pat, nullptr, m, k, d_ends, d_dist,
+                               capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
-int bmx_search_approx(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t *ends,
-                      uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+// the same with a class per pattern position: only the kernel's Peq table is built differently
+int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                     const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
+                                     uint64_t capacity, uint64_t *n_matches, void *stream_v)
 {
-    if (!approx_args_ok(n, 0, pat, m, k, ends, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (!approx_args_ok(n, lead, (const char *)classes, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, nullptr, classes, m, k, d_ends, d_dist,
+                               capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+namespace {
+// host buffers in, host buffers out, for a string (classes == NULL) or for classes (pat == NULL)
+int search_approx_host(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes, int32_t m, int32_t k,
+                       uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!approx_args_ok(n, 0, pat ? pat : (const char *)classes, m, k, ends, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
     if (n_matches) *n_matches = 0;
     if (n == 0) return BMX_OK;
     bmx_ctx *ctx = ctx_in;
@@ -1660,7 +1681,9 @@ int bmx_search_approx(bmx_ctx *ctx_in, const char *text, uint64_t n, const char 
     int rc = bmx_text_upload(ctx, text, n, &d_text);
     if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
     if (rc == BMX_OK && dev_cap && dist) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
-    if (rc == BMX_OK) rc = bmx_search_approx_device(ctx, d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr);
+    if (rc == BMX_OK)
+        rc = pat ? bmx_search_approx_device(ctx, d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr)
+                 : bmx_search_approx_classes_device(ctx, d_text, n, 0, 0, classes, m, k, d_ends, d_dist, dev_cap, &total, nullptr);
     if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
         const uint64_t stored = std::min(total, dev_cap);
         hipError_t e = hipSuccess;
@@ -1679,8 +1702,77 @@ int bmx_search_approx(bmx_ctx *ctx_in, const char *text, uint64_t n, const char 
     if (!ctx_in) bmx_ctx_destroy(ctx);
     return rc;
 }
+} // namespace
+
+int bmx_search_approx(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t *ends,
+                      uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_approx_host(ctx, text, n, pat, nullptr, m, k, ends, dist, capacity, n_matches);
+}
+
+int bmx_search_approx_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
+                              uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!classes) return BMX_ERR_ARG;
+    return search_approx_host(ctx, text, n, nullptr, classes, m, k, ends, dist, capacity, n_matches);
+}
 
 float bmx_last_approx_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_approx_ms(ctx->approx) : -1.0f; }
+
+// ---- class-pattern search (bmx_classes.hip; bmx_compile_classes is bmx_classes_compile.cpp) -----
+namespace {
+// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
+bool classes_args_ok(uint64_t n, const uint8_t *classes, int32_t m, const void *starts, uint64_t capacity)
+{
+    return classes && m >= 1 && m <= BMX_MAX_CLASS_PATTERN && n < (1ull << 40) && (capacity == 0 || starts);
+}
+} // namespace
+
+int bmx_search_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                              const uint8_t *classes, int32_t m, uint64_t *d_match_positions, uint64_t capacity,
+                              uint64_t *n_matches, void *stream_v)
+{
+    if (!classes_args_ok(n, classes, m, d_match_positions, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_classes(&ctx->classes, ctx->num_cu, d_text, n, n_own, base_offset, classes, m, d_match_positions,
+                                capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_search_classes(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                       uint64_t *match_positions, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!classes_args_ok(n, classes, m, match_positions, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n < (uint64_t)m) return BMX_OK;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        int rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    void *d_text = nullptr;
+    uint64_t *d_starts = nullptr;
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n - (uint64_t)m + 1);
+    uint64_t total = 0;
+    int rc = bmx_text_upload(ctx, text, n, &d_text);
+    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_starts);
+    if (rc == BMX_OK) rc = bmx_search_classes_device(ctx, d_text, n, n, 0, classes, m, d_starts, dev_cap, &total, nullptr);
+    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
+        const uint64_t stored = std::min(total, dev_cap);
+        if (stored && hipMemcpy(match_positions, d_starts, stored * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) {
+            set_err("download of class matches failed");
+            rc = BMX_ERR_HIP;
+        }
+        if (n_matches) *n_matches = total;
+        if (rc == BMX_OK && total > capacity) rc = BMX_ERR_CAPACITY;
+    }
+    if (d_starts) (void)hipFree(d_starts);
+    if (d_text) (void)hipFree(d_text);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+
+float bmx_last_classes_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_classes_ms(ctx->classes) : -1.0f; }
 
 // ---- dictionary search (bmx_dict.hip) ----------------------------------------------------------
 namespace {

@@ -33,6 +33,10 @@ EXP_LIB_PATH = os.path.join(_HERE, "lib", "libbmx_exp.so")
 MAX_PATTERN = 512
 MAX_MULTI = 8
 MAX_APPROX_PATTERN = 64
+MAX_CLASS_PATTERN = 64
+CLASS_BYTES = 32
+CLASS_ICASE = 1
+CLASS_IUPAC = 2
 MAX_DICT = 65536
 ED_BATCH_WORD = 64
 ED_BATCH_LONG = 65536
@@ -112,6 +116,17 @@ SYMBOLS = [
     ("bmx_search_approx", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_last_approx_ms", C.c_float, [C.c_void_p]),
+    ("bmx_compile_classes", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, _i32p]),
+    ("bmx_search_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_classes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64,
+                                     _u64p]),
+    ("bmx_last_classes_ms", C.c_float, [C.c_void_p]),
+    ("bmx_search_approx_classes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_approx_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p,
+                                                   C.c_void_p]),
     ("bmx_dict_create", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), _i32p, C.c_int32, C.POINTER(C.c_void_p)]),
     ("bmx_dict_destroy", None, [C.c_void_p]),
     ("bmx_dict_search_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -235,6 +250,26 @@ def build_tables(pattern) -> Tuple[np.ndarray, np.ndarray]:
     good = np.zeros(max(m, 1), dtype=np.int32)
     _check(lib().bmx_build_tables(pat, m, bad.ctypes.data_as(_i32p), good.ctypes.data_as(_i32p)), "bmx_build_tables")
     return bad, good[:m]
+
+
+def compile_classes(expr, flags: int = 0) -> np.ndarray:
+    """A class expression (bmx_compile_classes: ``.``, ``[a-c]``, ``[^x]``, ``\\xHH``, ``\\c``; flags CLASS_ICASE, CLASS_IUPAC)
+    -> uint8 array [m, 32]: byte value b belongs to class i iff bit (b & 7) of row i's byte (b >> 3) is set."""
+    e = _pat_bytes(expr)
+    buf = np.zeros((MAX_CLASS_PATTERN, CLASS_BYTES), dtype=np.uint8)
+    m = C.c_int32(0)
+    _check(lib().bmx_compile_classes(e, len(e), int(flags), C.c_void_p(buf.ctypes.data), C.byref(m)), "bmx_compile_classes")
+    return buf[: int(m.value)].copy()
+
+
+def _classes(classes_or_expr, flags: int = 0) -> np.ndarray:
+    """[m, 32] uint8 classes from an expression (str / bytes) or from such an array, passed through."""
+    if isinstance(classes_or_expr, (str, bytes, bytearray)):
+        return compile_classes(classes_or_expr, flags)
+    arr = np.ascontiguousarray(classes_or_expr, dtype=np.uint8)
+    if arr.ndim != 2 or arr.shape[1] != CLASS_BYTES:
+        raise ValueError("classes: a uint8 array of shape [m, 32]")
+    return arr
 
 
 class Context:
@@ -599,6 +634,80 @@ class Context:
     def last_approx_ms(self) -> float:
         return float(self._L.bmx_last_approx_ms(self._h))
 
+    # -- class-pattern search: wildcards, sets, case folding, IUPAC codes -----------------
+    def search_classes_device(self, d_text, classes_or_expr, *, flags: int = 0, n: Optional[int] = None,
+                              n_own: Optional[int] = None, base_offset: int = 0, capacity: Optional[int] = None, out=None,
+                              stream=None):
+        """Every start p < n_own of the view ``d_text[0:n)`` with text[p + i] in class i for all i, ascending, reported as
+        base_offset + p (bmx_search_classes_device).  ``classes_or_expr``: an expression for compile_classes(expr, flags)
+        or a [m, 32] uint8 array.  ``out``: int64/uint64 CUDA tensor (allocated if None); ``stream``: a torch.cuda.Stream
+        (None: torch's current stream).  Returns (starts view, true total); the view holds the lowest min(total, capacity)
+        starts.  A capacity below the total is not an error here (the total says so)."""
+        import torch
+
+        cls = _classes(classes_or_expr, flags)
+        if n is None:
+            n = d_text.numel()
+        if n_own is None:
+            n_own = n
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_classes_device(self._h, C.c_void_p(d_text.data_ptr()), n, n_own, base_offset,
+                                               C.c_void_p(cls.ctypes.data), cls.shape[0], C.c_void_p(out.data_ptr()), cap,
+                                               C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_classes_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def search_classes(self, text, classes_or_expr, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_classes): ascending starts, uint64.  With ``capacity`` given and too small, raises
+        BmxError(ERR_CAPACITY); without it the list is always complete."""
+        cls = _classes(classes_or_expr, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_classes(self._h, tptr, n, C.c_void_p(cls.ctypes.data), cls.shape[0],
+                                            C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_classes")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_approx_classes_device(self, d_text, classes_or_expr, k: int, *, flags: int = 0, n: Optional[int] = None,
+                                     lead: int = 0, base_offset: int = 0, out=None, dist_out=None,
+                                     capacity: Optional[int] = None, stream=None):
+        """search_approx_device with a class per pattern position (bmx_search_approx_classes_device): (ends view,
+        distances view, true total).  ``stream``: a torch.cuda.Stream (None: torch's current stream)."""
+        import torch
+
+        cls = _classes(classes_or_expr, flags)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            cap = capacity if capacity is not None else 1 << 16
+            out = torch.empty(max(cap, 1), dtype=torch.int64, device=d_text.device)
+        if dist_out is None:
+            dist_out = torch.empty(max(out.numel(), 1), dtype=torch.uint8, device=d_text.device)
+        cap = min(out.numel(), dist_out.numel()) if capacity is None else min(capacity, out.numel(), dist_out.numel())
+        stream = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(d_text.device)).cuda_stream)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_approx_classes_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset,
+                                                      C.c_void_p(cls.ctypes.data), cls.shape[0], int(k),
+                                                      C.c_void_p(out.data_ptr()), C.c_void_p(dist_out.data_ptr()), cap,
+                                                      C.byref(total), stream)
+        self._chk(rc, "bmx_search_approx_classes_device", allow=(ERR_CAPACITY,))
+        got = min(int(total.value), cap)
+        return out[:got], dist_out[:got], int(total.value)
+
+    def last_classes_ms(self) -> float:
+        return float(self._L.bmx_last_classes_ms(self._h))
+
     # -- dictionary search: many patterns in one pass ----------------------------------
     def dictionary(self, patterns) -> "Dictionary":
         """Build a dictionary of ``patterns`` (str / bytes each) on this context's device (bmx_dict_create)."""
@@ -889,6 +998,11 @@ def default_context() -> Context:
 def search(text, pattern) -> np.ndarray:
     """(text, pattern) -> match_positions, the north-star entry point."""
     return default_context().search(text, pattern)
+
+
+def search_classes(text, expr, flags: int = 0) -> np.ndarray:
+    """(text, class expression) -> ascending starts of every window whose bytes belong to the classes (bmx_search_classes)."""
+    return default_context().search_classes(text, expr, flags)
 
 
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
