@@ -439,6 +439,63 @@ int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t 
 int bmx_search_approx_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
                               int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
 
+/* ---- match spans of the approximate search: (start, end, distance) ------------------------- */
+
+/* The approximate search reports ENDS, and every qualifying end, so one occurrence shows as a run of adjacent ends.
+ * This post-pass over a device-resident list of ends gives what a caller slices at: the START of every match and, with
+ * BMX_SPANS_BEST, one entry per occurrence.  It changes nothing in the search and in what the search returns.
+ *
+ * The list: d_ends[i] = base_offset + j_i with d_dist[i] = min over s of ED(pat, text[s..j_i]) <= k, as
+ * bmx_search_approx[_classes]_device returns it for the same view, pattern, k and base_offset (the lists of shards
+ * concatenate by contract; select on the whole).
+ * Start: for an end j with distance d, the LARGEST s with ED(pat, text[s..j]) == d, the shortest span that attains the
+ * minimum, reported as base_offset + s.  Its length L = j - s + 1 satisfies m - d <= L <= m + d, so start <= end.
+ * BMX_SPANS_BEST: entry i is kept iff dist[i] <= dprev and dist[i] < dnext, where dprev = dist[i-1] if i > 0 and
+ * ends[i-1] == ends[i] - 1, else k + 1, and dnext = dist[i+1] if i + 1 < count and ends[i+1] == ends[i] + 1, else k + 1:
+ * the last end of every local minimum of the distance along a run of adjacent ends (an end that is not in the list
+ * counts as k + 1).  The rule takes LIST neighbours literally, so it is defined for any list.  Adjacent ends differ by
+ * at most 1 in distance, so a rising plateau (1,2,2,3) also keeps its last 2: the price of a rule without look-back.
+ * Example: text xxabcdxxabxdxxacdxx, pattern abcd, k = 1; the search returns ends [4,5,6,11,16], dist [1,0,1,1,1].
+ *   flags 0           (2,4,1) (2,5,0) (2,6,1) (8,11,1) (14,16,1)      as (start, end, dist)
+ *   BMX_SPANS_BEST    (2,5,0) (8,11,1) (14,16,1)
+ *
+ * Outputs: buffers with room for `count` entries that do not overlap the inputs; *n_spans is the number written.  With
+ * flags == 0 that is `count` and d_starts[i] belongs to d_ends[i], in whatever order the list has (d_sel_ends and
+ * d_sel_dist are not written).  With BMX_SPANS_BEST the kept entries go to d_sel_ends / d_sel_dist / d_starts in list
+ * order: ascending in, ascending out.
+ * Domain: that of the search (1 <= m <= BMX_MAX_APPROX_PATTERN, 0 <= k < m, n < 2^40, any alignment of d_text, any byte
+ * values); count is 64-bit.
+ * Errors: NULL pointers where needed, m / k / n out of range and unknown flag bits return BMX_ERR_ARG before any HIP
+ * call, with ctx = NULL too; count == 0 returns BMX_OK and launches nothing.  An entry whose end is not in
+ * [base_offset, base_offset + n) reads no byte and raises a status word, and so does an entry whose minimum over its
+ * window is above k or (where a distance is at hand) differs from it: a list of another pattern or text.  The call then
+ * returns BMX_ERR_ARG and the outputs are unspecified.
+ * No byte outside the aligned 16-byte lines that hold text[0..n) is read, none below text[0]'s line.
+ * All device work goes on `stream` (NULL = the null stream); the call returns after synchronising it (with
+ * BMX_SPANS_BEST also once in between, to read the kept count). */
+#define BMX_SPANS_BEST 1u
+int bmx_approx_spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, int32_t m,
+                            int32_t k, const uint64_t *d_ends, const uint8_t *d_dist /* may be NULL iff flags == 0 */,
+                            uint64_t count, uint32_t flags, uint64_t *d_starts,
+                            uint64_t *d_sel_ends /* may be NULL iff flags == 0 */, uint8_t *d_sel_dist /* may be NULL */,
+                            uint64_t *n_spans, void *stream);
+/* The same with a class per pattern position (the list of bmx_search_approx_classes_device). */
+int bmx_approx_spans_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset,
+                                    const uint8_t *classes, int32_t m, int32_t k, const uint64_t *d_ends,
+                                    const uint8_t *d_dist, uint64_t count, uint32_t flags, uint64_t *d_starts,
+                                    uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_approx[_classes]_device (counting first where `capacity` cannot
+ * hold every end), the spans, download.  ctx may be NULL; dist may be NULL.  *n_spans is the true number of spans; more
+ * than `capacity` returns BMX_ERR_CAPACITY with the lowest `capacity` spans stored (capacity 0 counts only). */
+int bmx_search_approx_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *pat, int32_t m,
+                            int32_t k, uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
+                            uint64_t *n_spans);
+int bmx_search_approx_spans_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes,
+                                    int32_t m, int32_t k, uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist,
+                                    uint64_t capacity, uint64_t *n_spans);
+/* Device time (ms, HIP events around the spans kernels) of the last call on ctx; < 0 if none. */
+float bmx_last_spans_ms(bmx_ctx *ctx);
+
 /* ---- dictionary search: many patterns in one pass ------------------------------------------ */
 
 /* What `grep -F -f words.txt` asks: every occurrence of every pattern of a word list, a block list or a set of primers,

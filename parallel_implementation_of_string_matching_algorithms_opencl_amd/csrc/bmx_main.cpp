@@ -29,6 +29,10 @@
 //                             --icase folds the case of ASCII letters, --iupac reads R Y S W K M B D H V N as
 //                             nucleotide sets; prints the hit count, the first and last starts and the mean time.
 //                             With --approx K: the ends within K edits of the class pattern, printed as --approx does
+//   bmx_cli --approx K --spans [--best] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--max-print K]
+//                             after what --approx prints: the span of every match (bmx_search_approx_spans), the total
+//                             and one `start end dist` line per span (at most --max-print of them); --best keeps one
+//                             span per occurrence (BMX_SPANS_BEST) instead of one per qualifying end
 //   bmx_cli --dict F [--text F] [--iters N] [--positions] [--max-print K]
 //                             dictionary search (no counterpart in the reference): every occurrence of every
 //                             pattern of F, one per line as `grep -F -f` reads it (empty lines skipped), in
@@ -117,7 +121,7 @@ int main(int argc, char **argv)
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
-    bool positions = false;
+    bool positions = false, spans = false, spans_best = false;
     uint64_t max_print = 32;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -137,6 +141,8 @@ int main(int argc, char **argv)
         else if (a == "--max-print") max_print = strtoull(need("--max-print"), nullptr, 10);
         else if (a == "--positions") positions = true;
         else if (a == "--approx") approx_k = atoi(need("--approx"));
+        else if (a == "--spans") spans = true;
+        else if (a == "--best") spans_best = true;
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
         else if (a == "--icase") class_flags |= BMX_CLASS_ICASE;
@@ -153,6 +159,11 @@ int main(int argc, char **argv)
             fprintf(stderr, "unknown option %s\n", a.c_str());
             return 2;
         }
+    }
+
+    if ((spans && approx_k < 0) || (spans_best && !spans)) {
+        fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
+        return 2;
     }
 
     if (!edb_a.empty()) {
@@ -460,6 +471,28 @@ int main(int argc, char **argv)
         }
         if (iters > 0)
             printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        if (spans) { // (text, pattern, k) -> (starts, ends, distances) through the host-buffer entry point
+            const uint32_t flags = spans_best ? BMX_SPANS_BEST : 0u;
+            const uint64_t room = hits ? hits : 1; // never more spans than ends
+            std::vector<uint64_t> s_starts(room), s_ends(room);
+            std::vector<uint8_t> s_dist(room);
+            uint64_t n_spans = 0;
+            if (have_classes)
+                rc = bmx_search_approx_spans_classes(ctx, text.data(), n, classes.data(), m, approx_k, flags, s_starts.data(),
+                                                     s_ends.data(), s_dist.data(), room, &n_spans);
+            else
+                rc = bmx_search_approx_spans(ctx, text.data(), n, pat.data(), m, approx_k, flags, s_starts.data(), s_ends.data(),
+                                             s_dist.data(), room, &n_spans);
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_search_approx_spans failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            printf("match spans%s: %llu  (spans kernels %.3f ms)\n", spans_best ? " (best)" : "", (unsigned long long)n_spans,
+                   n_spans ? bmx_last_spans_ms(ctx) : 0.0);
+            for (uint64_t i = 0; i < n_spans && i < max_print; ++i)
+                printf("%llu %llu %d\n", (unsigned long long)s_starts[i], (unsigned long long)s_ends[i], s_dist[i]);
+            if (n_spans > max_print) printf("... %llu more\n", (unsigned long long)(n_spans - max_print));
+        }
         bmx_device_free(ctx, d_dist);
         bmx_device_free(ctx, d_ends);
         bmx_device_free(ctx, d_text);

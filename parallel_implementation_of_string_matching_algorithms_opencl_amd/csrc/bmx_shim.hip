@@ -63,6 +63,13 @@ int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t 
 void bmx_internal_ed_batch_free(void *state);
 float bmx_internal_ed_batch_ms(const void *state);
 int64_t bmx_internal_ed_batch_fallbacks(const void *state);
+// bmx_spans.hip
+int bmx_internal_spans(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, const uint8_t *classes,
+                       int32_t m, int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
+                       uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, hipStream_t stream,
+                       char *err, size_t errlen);
+void bmx_internal_spans_free(void *state);
+float bmx_internal_spans_ms(const void *state);
 // bmx_dict.hip
 int bmx_internal_dict_create(const void *owner, int device, const char *const *pats, const int32_t *ms, int32_t K,
                              bmx_dict **out, char *err, size_t errlen);
@@ -235,6 +242,7 @@ struct bmx_ctx {
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
+    void *spans = nullptr; // match spans: status words, tile counts of the selection, events (bmx_spans.hip)
     void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
     int blocks_per_cu = 0; // 0 = as many as LDS and the 32-wave limit admit
     unsigned long long *d_count = nullptr; // live match counter; re-armed by order_kernel
@@ -582,6 +590,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_approx_free(ctx->approx);
     bmx_internal_classes_free(ctx->classes);
     bmx_internal_ed_batch_free(ctx->ed_batch);
+    bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
     for (int i = 0; i < bmx_ctx::EV_RING; ++i) {
@@ -1773,6 +1782,134 @@ int bmx_search_classes(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint
 }
 
 float bmx_last_classes_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_classes_ms(ctx->classes) : -1.0f; }
+
+// ---- match spans of the approximate search (bmx_spans.hip) --------------------------------------
+namespace {
+// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
+bool spans_args_ok(uint64_t n, const void *pat, int32_t m, int32_t k, const uint64_t *ends, const uint8_t *dist, uint64_t count,
+                   uint32_t flags, const uint64_t *starts, const uint64_t *sel_ends)
+{
+    if (!pat || m < 1 || m > BMX_MAX_APPROX_PATTERN || k < 0 || k >= m || n >= (1ull << 40) || (flags & ~BMX_SPANS_BEST)) return false;
+    if (count == 0) return true;
+    return ends && starts && (flags == 0 || (dist && sel_ends));
+}
+
+int spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, const uint8_t *classes,
+                 int32_t m, int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
+                 uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, void *stream_v)
+{
+    if (!spans_args_ok(n, pat ? (const void *)pat : (const void *)classes, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends))
+        return BMX_ERR_ARG;
+    if (n_spans) *n_spans = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_spans(&ctx->spans, d_text, n, base_offset, pat, classes, m, k, d_ends, d_dist, count, flags, d_starts,
+                              d_sel_ends, d_sel_dist, n_spans, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+} // namespace
+
+int bmx_approx_spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, int32_t m,
+                            int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
+                            uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, void *stream_v)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return spans_device(ctx, d_text, n, base_offset, pat, nullptr, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends,
+                        d_sel_dist, n_spans, stream_v);
+}
+
+int bmx_approx_spans_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint8_t *classes,
+                                    int32_t m, int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count,
+                                    uint32_t flags, uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist,
+                                    uint64_t *n_spans, void *stream_v)
+{
+    if (!classes) return BMX_ERR_ARG;
+    return spans_device(ctx, d_text, n, base_offset, nullptr, classes, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends,
+                        d_sel_dist, n_spans, stream_v);
+}
+
+namespace {
+// host buffers in, host buffers out, for a string (classes == NULL) or for classes (pat == NULL)
+int search_spans_host(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes, int32_t m, int32_t k,
+                      uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_spans)
+{
+    if (!approx_args_ok(n, 0, pat ? pat : (const char *)classes, m, k, ends, capacity) || (flags & ~BMX_SPANS_BEST) ||
+        (capacity && !starts) || (n > 0 && !text))
+        return BMX_ERR_ARG;
+    if (n_spans) *n_spans = 0;
+    if (n == 0) return BMX_OK;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        int rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    void *d_text = nullptr;
+    uint64_t *d_ends = nullptr, *d_starts = nullptr, *d_sel_ends = nullptr;
+    uint8_t *d_dist = nullptr, *d_sel_dist = nullptr;
+    uint64_t total = 0, spans = 0;
+    auto search = [&](uint64_t cap) {
+        return pat ? bmx_search_approx_device(ctx, d_text, n, 0, 0, pat, m, k, d_ends, d_dist, cap, &total, nullptr)
+                   : bmx_search_approx_classes_device(ctx, d_text, n, 0, 0, classes, m, k, d_ends, d_dist, cap, &total, nullptr);
+    };
+    int rc = bmx_text_upload(ctx, text, n, &d_text);
+    // counting only if `capacity` cannot hold a single end; else in one go if it holds them all
+    uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
+    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
+    if (rc == BMX_OK) rc = search(dev_cap);
+    if (rc == BMX_ERR_CAPACITY) { // again, with room for all ends
+        if (d_ends) (void)hipFree(d_ends);
+        if (d_dist) (void)hipFree(d_dist);
+        d_ends = nullptr, d_dist = nullptr;
+        dev_cap = total;
+        rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
+        if (rc == BMX_OK) rc = search(dev_cap);
+    }
+    if (rc == BMX_OK && total) {
+        rc = bmx_device_alloc(ctx, total * sizeof(uint64_t), (void **)&d_starts);
+        if (rc == BMX_OK && flags) rc = bmx_device_alloc(ctx, total * sizeof(uint64_t), (void **)&d_sel_ends);
+        if (rc == BMX_OK && flags) rc = bmx_device_alloc(ctx, total, (void **)&d_sel_dist);
+        if (rc == BMX_OK)
+            rc = spans_device(ctx, d_text, n, 0, pat, classes, m, k, d_ends, d_dist, total, flags, d_starts, d_sel_ends, d_sel_dist,
+                              &spans, nullptr);
+    }
+    if (rc == BMX_OK) {
+        const uint64_t stored = std::min(spans, capacity);
+        hipError_t e = hipSuccess;
+        if (stored) e = hipMemcpy(starts, d_starts, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (stored && e == hipSuccess) e = hipMemcpy(ends, flags ? d_sel_ends : d_ends, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (stored && dist && e == hipSuccess) e = hipMemcpy(dist, flags ? d_sel_dist : d_dist, stored, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_err("download of match spans: %s", hipGetErrorString(e));
+            rc = BMX_ERR_HIP;
+        }
+        if (n_spans) *n_spans = spans;
+        if (rc == BMX_OK && spans > capacity) rc = BMX_ERR_CAPACITY;
+    }
+    for (void *p : {(void *)d_sel_dist, (void *)d_sel_ends, (void *)d_starts, (void *)d_dist, (void *)d_ends, d_text})
+        if (p) (void)hipFree(p);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+} // namespace
+
+int bmx_search_approx_spans(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint32_t flags,
+                            uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_spans)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_spans_host(ctx, text, n, pat, nullptr, m, k, flags, starts, ends, dist, capacity, n_spans);
+}
+
+int bmx_search_approx_spans_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
+                                    uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
+                                    uint64_t *n_spans)
+{
+    if (!classes) return BMX_ERR_ARG;
+    return search_spans_host(ctx, text, n, nullptr, classes, m, k, flags, starts, ends, dist, capacity, n_spans);
+}
+
+float bmx_last_spans_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_spans_ms(ctx->spans) : -1.0f; }
 
 // ---- dictionary search (bmx_dict.hip) ----------------------------------------------------------
 namespace {

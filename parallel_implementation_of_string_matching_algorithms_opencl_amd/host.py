@@ -37,6 +37,9 @@ MAX_CLASS_PATTERN = 64
 CLASS_BYTES = 32
 CLASS_ICASE = 1
 CLASS_IUPAC = 2
+SPANS_BEST = 1
+SPANS_BLOCK = 256  # list entries per workgroup of the starts kernel (csrc/bmx_spans_kernel.h)
+SPANS_TILE = 2048  # list entries per workgroup of the selection
 MAX_DICT = 65536
 ED_BATCH_WORD = 64
 ED_BATCH_LONG = 65536
@@ -127,6 +130,17 @@ SYMBOLS = [
     ("bmx_search_approx_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p,
                                                    C.c_void_p]),
+    ("bmx_approx_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          _u64p, C.c_void_p]),
+    ("bmx_approx_spans_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
+                                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
+    ("bmx_search_approx_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_approx_spans_classes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_spans_ms", C.c_float, [C.c_void_p]),
     ("bmx_dict_create", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), _i32p, C.c_int32, C.POINTER(C.c_void_p)]),
     ("bmx_dict_destroy", None, [C.c_void_p]),
     ("bmx_dict_search_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -708,6 +722,82 @@ class Context:
     def last_classes_ms(self) -> float:
         return float(self._L.bmx_last_classes_ms(self._h))
 
+    # -- match spans of the approximate search: (start, end, distance) -------------------
+    def approx_spans_device(self, d_text, pattern_or_classes, k: int, ends, dist=None, *, best: bool = False, flags: int = 0,
+                            n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """The start of every match of a list of ends (bmx_approx_spans[_classes]_device): ``ends`` (int64 / uint64) and
+        ``dist`` (uint8, may be None without ``best``) are CUDA tensors as search_approx[_classes]_device returns them for
+        the same view, pattern, k and base_offset.  ``pattern_or_classes``: str / bytes are a STRING, a [m, 32] uint8
+        array is a class pattern (compile_classes(expr, class_flags) makes one).  ``best`` sets SPANS_BEST (one entry per
+        occurrence); ``flags`` are further SPANS_* bits, passed as they are.  Returns (starts, ends, dist, total) as
+        tensors of ``total`` entries: without SPANS_BEST the list itself with its starts, with it the kept entries in list
+        order.  ``stream``: a torch.cuda.Stream (None: torch's current one)."""
+        import torch
+
+        flags = int(flags) | (SPANS_BEST if best else 0)
+        best = bool(flags & SPANS_BEST)
+        count = ends.numel()
+        if n is None:
+            n = d_text.numel()
+        if ends.element_size() != 8 or (dist is not None and (dist.element_size() != 1 or dist.numel() < count)):
+            raise ValueError("ends: 8-byte entries; dist: 1-byte entries, one per end")
+        dev = ends.device
+        starts = torch.empty(max(count, 1), dtype=ends.dtype, device=dev)
+        sel_ends = torch.empty(max(count, 1), dtype=ends.dtype, device=dev) if best else None
+        sel_dist = torch.empty(max(count, 1), dtype=torch.uint8, device=dev) if best else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(dev)).cuda_stream)
+        total = C.c_uint64(0)
+        tail = (int(k), ptr(ends), ptr(dist), count, flags, ptr(starts), ptr(sel_ends), ptr(sel_dist),
+                C.byref(total), s)
+        if isinstance(pattern_or_classes, (str, bytes, bytearray)):
+            pat = _pat_bytes(pattern_or_classes)
+            rc = self._L.bmx_approx_spans_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, pat, len(pat), *tail)
+        else:
+            cls = _classes(pattern_or_classes)
+            rc = self._L.bmx_approx_spans_classes_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset,
+                                                         C.c_void_p(cls.ctypes.data), cls.shape[0], *tail)
+        self._chk(rc, "bmx_approx_spans_device")
+        t = int(total.value)
+        if best:
+            return starts[:t], sel_ends[:t], sel_dist[:t], t
+        return starts[:t], ends[:t], (dist[:t] if dist is not None else None), t
+
+    def _search_spans_host(self, fn, what, text, pat_arg, m: int, k: int, best: bool):
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            dist = np.empty(cap, dtype=np.uint8)
+            total = C.c_uint64(0)
+            rc = fn(self._h, tptr, n, pat_arg, m, int(k), SPANS_BEST if best else 0, C.c_void_p(starts.ctypes.data),
+                    C.c_void_p(ends.ctypes.data), C.c_void_p(dist.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, what)
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy(), dist[:t].copy()
+
+    def search_approx_spans(self, text, pattern, k: int, best: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_approx_spans): (starts uint64, ends uint64, distances uint8) of every match of
+        ``pattern`` within k edits, ascending; ``best``: one entry per occurrence, else every qualifying end."""
+        pat = _pat_bytes(pattern)
+        return self._search_spans_host(self._L.bmx_search_approx_spans, "bmx_search_approx_spans", text, pat, len(pat), k, best)
+
+    def search_approx_spans_classes(self, text, classes_or_expr, k: int, flags: int = 0,
+                                    best: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """search_approx_spans with a class per pattern position (bmx_search_approx_spans_classes): an expression for
+        compile_classes(expr, flags) or a [m, 32] uint8 array, like search_classes."""
+        cls = _classes(classes_or_expr, flags)
+        return self._search_spans_host(self._L.bmx_search_approx_spans_classes, "bmx_search_approx_spans_classes", text,
+                                       C.c_void_p(cls.ctypes.data), cls.shape[0], k, best)
+
+    def last_spans_ms(self) -> float:
+        return float(self._L.bmx_last_spans_ms(self._h))
+
     # -- dictionary search: many patterns in one pass ----------------------------------
     def dictionary(self, patterns) -> "Dictionary":
         """Build a dictionary of ``patterns`` (str / bytes each) on this context's device (bmx_dict_create)."""
@@ -1008,6 +1098,12 @@ def search_classes(text, expr, flags: int = 0) -> np.ndarray:
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
     """(text, pattern, k) -> (ends, distances): every end of a match with at most k edits (bmx_search_approx)."""
     return default_context().search_approx(text, pattern, k)
+
+
+def search_approx_spans(text, pattern, k: int, best: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(text, pattern, k) -> (starts, ends, distances): the span of every match with at most k edits, one per occurrence
+    with ``best`` (bmx_search_approx_spans)."""
+    return default_context().search_approx_spans(text, pattern, k, best)
 
 
 def edit_distance_batch(a, b, limit: Optional[int] = None) -> np.ndarray:
