@@ -31,6 +31,8 @@
  *                         bit-parallel form with kernel1.cl:24's one report per hit (section below)
  *   bmx_search_classes    no counterpart in the reference: a pattern position is a set of byte values (wildcards,
  *                         sets, case folding, IUPAC codes), matched by Shift-And (section below)
+ *   bmx_index_*           no counterpart: pattern count and locate by binary search over the array bmx_suffix_array
+ *                         builds, in the order it builds it (section below)
  *
  * Semantics (bit-exact with the reference kernel run as one work-item over
  * [0, n-1]): match_positions receives, in ascending order, every
@@ -550,6 +552,69 @@ float bmx_last_suffix_array_ms(bmx_ctx *ctx);
 int bmx_last_suffix_array_rounds(bmx_ctx *ctx);
 /* ... of which done by the one-kernel LDS path (every group of tied suffixes fitted a workgroup's window). */
 int bmx_last_suffix_array_lds_rounds(bmx_ctx *ctx);
+
+/* ---- text index: batched pattern count and locate over the suffix array ------------------- */
+
+/* What consumes bmx_suffix_array_device: a column of 10^5 .. 10^7 queries against ONE resident text (k-mer counts, read
+ * seeding, log-key lookups), each answered in O(m + log n) reads with no pass over the text.  Every other search of the
+ * library reads the whole text per call.  The reference has no such program; its array is SuffixArrays.cpp:101-154.
+ *
+ * The order that is searched is the builder's, not memcmp's: outside lower-case text the array keeps the reference's
+ * "past the end ranks as character 96" rule (above).  For a text that does not end in two or more bytes 96 it is the
+ * sorted order of, per suffix i: text[i..n) as signed char; then, if n - 1 - i is even, ONE virtual symbol strictly
+ * between byte 95 and byte 96; then "nothing", below everything.  A suffix that runs out before the query is never a
+ * match.  The suffixes that begin with a query are one interval [lo, lo + cnt) of the array and exactly its true
+ * occurrences: those p with p + m <= n and text[p..p+m) == query (csrc/bmx_index_kernel.h has the comparator).
+ *
+ * Text and ownership: 1 <= n < 2^31, any byte values, any alignment.  The index BORROWS d_text and a caller's d_sa (the
+ * array bmx_suffix_array_device gives for this text): both stay alive and unchanged until bmx_index_destroy.  With d_sa
+ * == NULL the array is built here (bmx_suffix_array_device on `stream`) and owned.  The index owns its directory: for
+ * each of the 128 x 128 two-byte prefixes the (start, count) of its interval, 128 KiB in device memory, made at creation
+ * by the count kernel itself.  A text that ends in two or more bytes 96 returns BMX_ERR_DOMAIN (the reference leaves
+ * such suffixes tied).  Several indexes may live on one context.
+ * Queries: one string column in the Arrow layout of bmx_edit_distance_batch_device, a byte blob plus count + 1
+ * non-decreasing uint64 offsets.  Every query has 1 .. BMX_MAX_PATTERN bytes, all < 0x80; duplicates and queries longer
+ * than the text are fine.
+ * count: d_cnt[i] = occurrences of query i (overlapping ones count); d_lo[i] (d_lo may be NULL) = its first index in the
+ * array, so sa[d_lo[i] .. d_lo[i] + d_cnt[i]) are its occurrences in array order.  With d_cnt[i] == 0, d_lo[i] is the
+ * query's insertion point.
+ * locate: d_out_off (count + 1 entries) = the exclusive prefix sum of the counts, always written in full, so
+ * d_out_off[count] == *n_matches == the true total.  d_pos[d_out_off[i] .. d_out_off[i+1]) = base_offset + p for every
+ * occurrence of query i, ASCENDING: for one query the list of bmx_search_device.  A total above `capacity` returns
+ * BMX_ERR_CAPACITY; every query whose segment ends at or below capacity is then stored complete and ascending and the
+ * rest of d_pos is unspecified.  capacity 0 counts only (d_pos may be NULL).  One call stores fewer than 2^31 - 1
+ * positions and takes fewer than 2^31 - 1 queries (BMX_ERR_ARG beyond; pass fewer queries at a time).
+ * Errors: NULL pointers where count > 0, n == 0 or n >= 2^31 and an index of another context return BMX_ERR_ARG before
+ * any HIP call, with ctx = NULL too; count == 0 returns BMX_OK and launches nothing (*n_matches = 0,
+ * d_out_off untouched).  The host entry checks offsets, lengths and bytes on the host.  The device entries check them in
+ * the kernel: a lane that finds a decreasing offset, an end past pat_bytes, a length of 0 or above BMX_MAX_PATTERN, or
+ * a byte >= 0x80 reads no text and raises a status word; the call then returns BMX_ERR_ARG (BMX_ERR_DOMAIN for the
+ * byte) and the outputs are unspecified.
+ * No text or query byte is read except as part of the aligned 8-byte word that holds it.
+ * All device work goes on `stream` (NULL = the null stream); the calls return after synchronising it (locate also once
+ * in between, to read the total). */
+typedef struct bmx_index bmx_index;
+int bmx_index_create_device(bmx_ctx *ctx, const void *d_text, uint64_t n, const int32_t *d_sa /* NULL: built here and owned */,
+                            void *stream, bmx_index **out);
+void bmx_index_destroy(bmx_index *ix);
+/* The array the index searches (the caller's, or the one built here): n int32 in device memory. */
+int bmx_index_sa(const bmx_index *ix, const int32_t **d_sa_out);
+int bmx_index_count_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                           uint64_t count, uint32_t *d_lo /* may be NULL */, uint32_t *d_cnt, void *stream);
+int bmx_index_locate_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                            uint64_t count, uint64_t base_offset, uint64_t *d_out_off /* count + 1 */, uint64_t *d_pos,
+                            uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_index_create_device, bmx_index_count_device, download, destroy). */
+int bmx_index_count(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
+                    const uint64_t *pat_off, uint64_t count, uint32_t *cnt);
+/* The same for bmx_index_locate_device with base_offset 0 (what bmx_cli --index-count prints comes through it). */
+int bmx_index_locate(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
+                     const uint64_t *pat_off, uint64_t count, uint64_t *out_off /* count + 1 */, uint64_t *pos, uint64_t capacity,
+                     uint64_t *n_matches);
+/* Device time (ms, HIP events around the query kernels) of the last count / locate call on ctx; < 0 if none. */
+float bmx_last_index_ms(bmx_ctx *ctx);
+/* Device time (ms) of the index's creation: the suffix array if it was built here, plus the directory. */
+float bmx_index_build_ms(const bmx_index *ix);
 
 /* ---- synthetic corpus, generated in HBM ---------------------- */
 

@@ -15,7 +15,9 @@ extern "C" {
  * then reach the stolen tail), "no_dense" (no fill pass), "no_text_sample" (the walker goes by the pattern's symbols),
  * "multi_no_qgram" (multi-pattern pass byte-wise only), "ed_lag" (rows a column band is assumed to trail its
  * predecessor by; < 0: the measured default), "ed_group" (16 | 32 rows per hand-over), "ed_step_x" (1..8: ed variant 13 with parts of its step left out, timing only), "sa_flags" (1 library rounds
- * only, 2 a host wait per round, 4 per-round trace on stderr).  BMX_ERR_ARG for an unknown name. */
+ * only, 2 a host wait per round, 4 per-round trace on stderr), "index_no_dir" (the text index's queries search the whole
+ * array instead of their directory bucket: same answers, tools/index_rate.py measures the difference).  BMX_ERR_ARG for an
+ * unknown name. */
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
 
 /* Read-only sweep of n bytes at d_text (16-byte aligned) with plain global loads into registers, XOR-folded: no LDS,

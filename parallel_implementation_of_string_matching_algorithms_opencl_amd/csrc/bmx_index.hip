@@ -1,0 +1,338 @@
+// bmx_index.hip -- host side of the text index (bmx_index_*, include/bmx.h): the index object (borrowed text, borrowed or
+// owned suffix array, owned directory), and per context the status words, events and workspace of the two queries, kept
+// between calls.  count = one launch of index_count_kernel; locate = that, rocPRIM's exclusive scan of the counts, the
+// fill, rocPRIM's segmented radix sort of the 32-bit positions within their segments and the widening to base_offset + p.
+// The argument checks and the context are the shim's (bmx_shim.hip); everything here runs on valid arguments.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "bmx.h"
+#include "bmx_index_kernel.h"
+
+static_assert(bmx::INDEX_MAX_PATTERN == BMX_MAX_PATTERN, "header and kernel disagree");
+
+struct bmx_index {
+    const void *owner = nullptr; // the context it was created on
+    int device = 0;
+    const uint8_t *d_text = nullptr; // borrowed
+    uint32_t n = 0;
+    const int32_t *d_sa = nullptr; // borrowed, or own_sa
+    int32_t *own_sa = nullptr;
+    uint32_t *d_dir = nullptr; // INDEX_DIR_ENTRIES starts, then INDEX_DIR_ENTRIES counts
+    float build_ms = 0.0f;
+};
+
+namespace {
+
+struct IndexHost {
+    uint64_t *d_ws = nullptr; // {bad offsets, bad byte, total, stored queries, stored positions}
+    uint64_t *h_ws = nullptr; // pinned copy
+    uint32_t *d_q = nullptr;  // per query: lo, cnt, 32-bit segment offsets (q_cap + 1 each)
+    uint64_t q_cap = 0;
+    void *d_p = nullptr; // per stored position: two 32-bit key buffers, then rocPRIM's temporary storage
+    size_t p_bytes = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float last_ms = -1.0f;
+};
+
+constexpr int WS_WORDS = 5;
+constexpr size_t KEEP_BYTES = 256ull << 20; // a larger per-position workspace is not kept between calls
+
+struct ToU64 {
+    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
+};
+
+#define XHIP(expr)                                                                              \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            snprintf(err, errlen, "%s: %s failed: %s", what, #expr, hipGetErrorString(e__)); \
+            return BMX_ERR_HIP;                                                                 \
+        }                                                                                       \
+    } while (0)
+
+int state_ready(void **state_v, uint64_t count, IndexHost **out, const char *what, char *err, size_t errlen)
+{
+    if (!*state_v) *state_v = new IndexHost();
+    IndexHost *st = static_cast<IndexHost *>(*state_v);
+    st->last_ms = -1.0f;
+    if (!st->d_ws) XHIP(hipMalloc(&st->d_ws, WS_WORDS * sizeof(uint64_t)));
+    if (!st->h_ws) XHIP(hipHostMalloc(&st->h_ws, WS_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    for (hipEvent_t &e : st->ev)
+        if (!e) XHIP(hipEventCreate(&e));
+    if (count > st->q_cap) {
+        if (st->d_q) (void)hipFree(st->d_q);
+        st->d_q = nullptr;
+        st->q_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(count, 1u << 16);
+        XHIP(hipMalloc(&st->d_q, 3 * (cap + 1) * sizeof(uint32_t)));
+        st->q_cap = cap;
+    }
+    *out = st;
+    return BMX_OK;
+}
+
+bmx::IndexArgs make_args(const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off, uint64_t count,
+                         uint32_t *d_lo, uint32_t *d_cnt, bool use_dir, uint64_t *status)
+{
+    bmx::IndexArgs a = {};
+    a.text = ix->d_text;
+    a.n = ix->n;
+    a.sa = ix->d_sa;
+    a.pat = static_cast<const uint8_t *>(d_pat);
+    a.pat_bytes = pat_bytes;
+    a.pat_off = d_pat_off;
+    a.count = count;
+    a.dir_lo = use_dir ? ix->d_dir : nullptr;
+    a.dir_cnt = use_dir ? ix->d_dir + bmx::INDEX_DIR_ENTRIES : nullptr;
+    a.lo = d_lo;
+    a.cnt = d_cnt;
+    a.status = status;
+    return a;
+}
+
+int status_rc(const uint64_t *h_ws, const char *what, char *err, size_t errlen)
+{
+    if (h_ws[0]) {
+        snprintf(err, errlen, "%s: offsets that decrease or end past the blob, or a query of 0 or more than %d bytes", what,
+                 BMX_MAX_PATTERN);
+        return BMX_ERR_ARG;
+    }
+    if (h_ws[1]) {
+        snprintf(err, errlen, "%s: a query byte >= 0x80", what);
+        return BMX_ERR_DOMAIN;
+    }
+    return BMX_OK;
+}
+
+uint32_t blocks_for(uint64_t items) { return (uint32_t)((items + bmx::INDEX_BLOCK - 1) / bmx::INDEX_BLOCK); }
+
+} // namespace
+
+void bmx_internal_index_state_free(void *state_v)
+{
+    IndexHost *st = static_cast<IndexHost *>(state_v);
+    if (!st) return;
+    if (st->d_ws) (void)hipFree(st->d_ws);
+    if (st->h_ws) (void)hipHostFree(st->h_ws);
+    if (st->d_q) (void)hipFree(st->d_q);
+    if (st->d_p) (void)hipFree(st->d_p);
+    for (hipEvent_t e : st->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete st;
+}
+
+float bmx_internal_index_ms(const void *state_v)
+{
+    const IndexHost *st = static_cast<const IndexHost *>(state_v);
+    return st ? st->last_ms : -1.0f;
+}
+
+const void *bmx_internal_index_owner(const bmx_index *ix) { return ix->owner; }
+const int32_t *bmx_internal_index_sa(const bmx_index *ix) { return ix->d_sa; }
+float bmx_internal_index_build_ms(const bmx_index *ix) { return ix->build_ms; }
+
+void bmx_internal_index_destroy(bmx_index *ix)
+{
+    if (!ix) return;
+    (void)hipSetDevice(ix->device);
+    if (ix->own_sa) (void)hipFree(ix->own_sa);
+    if (ix->d_dir) (void)hipFree(ix->d_dir);
+    delete ix;
+}
+
+int bmx_internal_index_create(void **state_v, bmx_ctx *ctx, int device, const void *d_text, uint64_t n, const int32_t *d_sa,
+                              hipStream_t stream, bmx_index **out, char *err, size_t errlen)
+{
+    const char *what = "bmx_index_create_device";
+    IndexHost *st = nullptr;
+    int rc = state_ready(state_v, 0, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    // A text that ends in two or more bytes 96 leaves suffixes tied in the builder's order: no interval to search.
+    if (n >= 2) {
+        uint8_t tail[2] = {0, 0};
+        XHIP(hipMemcpyAsync(tail, static_cast<const uint8_t *>(d_text) + (n - 2), 2, hipMemcpyDeviceToHost, stream));
+        XHIP(hipStreamSynchronize(stream));
+        if (tail[0] == 96 && tail[1] == 96) {
+            snprintf(err, errlen, "%s: the text ends in two or more bytes 96; the suffix array's order is unspecified there", what);
+            return BMX_ERR_DOMAIN;
+        }
+    }
+    bmx_index *ix = new bmx_index();
+    ix->owner = ctx;
+    ix->device = device;
+    ix->d_text = static_cast<const uint8_t *>(d_text);
+    ix->n = (uint32_t)n;
+    ix->d_sa = d_sa;
+    auto fail = [&](int code) {
+        bmx_internal_index_destroy(ix);
+        return code;
+    };
+    if (!d_sa) {
+        hipError_t e = hipMalloc(&ix->own_sa, n * sizeof(int32_t));
+        if (e != hipSuccess) {
+            snprintf(err, errlen, "%s: %llu bytes for the suffix array: %s", what, (unsigned long long)(n * sizeof(int32_t)),
+                     hipGetErrorString(e));
+            return fail(BMX_ERR_HIP);
+        }
+        rc = bmx_suffix_array_device(ctx, d_text, n, ix->own_sa, stream);
+        if (rc != BMX_OK) return fail(rc);
+        ix->d_sa = ix->own_sa;
+        ix->build_ms += std::max(0.0f, bmx_last_suffix_array_ms(ctx));
+    }
+    // The directory: the count kernel itself, without a directory, over all two-byte patterns.  Its boundary cases
+    // then follow the comparator by construction.
+    const uint32_t E = bmx::INDEX_DIR_ENTRIES;
+    std::vector<uint8_t> blob(2 * E);
+    std::vector<uint64_t> off(E + 1);
+    for (uint32_t b = 0; b < E; ++b) blob[2 * b] = (uint8_t)(b / bmx::INDEX_DIR_SIDE), blob[2 * b + 1] = (uint8_t)(b % bmx::INDEX_DIR_SIDE);
+    for (uint32_t b = 0; b <= E; ++b) off[b] = 2ull * b;
+    uint8_t *d_tmp = nullptr;
+    const size_t off_at = 2 * E; // (a multiple of 8)
+    hipError_t e = hipMalloc(&d_tmp, off_at + (E + 1) * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc(&ix->d_dir, 2 * E * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tmp, blob.data(), blob.size(), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tmp + off_at, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream);
+    if (e == hipSuccess) e = hipEventRecord(st->ev[0], stream);
+    if (e == hipSuccess) {
+        const bmx::IndexArgs a = make_args(ix, d_tmp, 2 * E, reinterpret_cast<const uint64_t *>(d_tmp + off_at), E, ix->d_dir,
+                                           ix->d_dir + E, false, st->d_ws);
+        hipLaunchKernelGGL(bmx::index_count_kernel, dim3(blocks_for(E)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(st->ev[1], stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream); // (the host blobs above are read until here)
+    if (d_tmp) (void)hipFree(d_tmp);
+    if (e != hipSuccess) {
+        snprintf(err, errlen, "%s: directory: %s", what, hipGetErrorString(e));
+        return fail(BMX_ERR_HIP);
+    }
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, st->ev[0], st->ev[1]) == hipSuccess) ix->build_ms += ms;
+    *out = ix;
+    return BMX_OK;
+}
+
+int bmx_internal_index_count(void **state_v, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t *d_lo, uint32_t *d_cnt, int use_dir, hipStream_t stream, char *err,
+                             size_t errlen)
+{
+    const char *what = "bmx_index_count_device";
+    if (blocks_for(count) == 0 || count > 0x7fffffffull * bmx::INDEX_BLOCK) {
+        snprintf(err, errlen, "%s: too many queries for one launch", what);
+        return BMX_ERR_ARG;
+    }
+    IndexHost *st = nullptr;
+    const int rc = state_ready(state_v, 0, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    XHIP(hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    XHIP(hipEventRecord(st->ev[0], stream));
+    const bmx::IndexArgs a = make_args(ix, d_pat, pat_bytes, d_pat_off, count, d_lo, d_cnt, use_dir != 0, st->d_ws);
+    hipLaunchKernelGGL(bmx::index_count_kernel, dim3(blocks_for(count)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+    XHIP(hipGetLastError());
+    XHIP(hipEventRecord(st->ev[1], stream));
+    XHIP(hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    XHIP(hipStreamSynchronize(stream));
+    if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
+    return status_rc(st->h_ws, what, err, errlen);
+}
+
+int bmx_internal_index_locate(void **state_v, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes,
+                              const uint64_t *d_pat_off, uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos,
+                              uint64_t capacity, uint64_t *n_matches, int use_dir, hipStream_t stream, char *err, size_t errlen)
+{
+    const char *what = "bmx_index_locate_device";
+    if (count >= 0x7fffffffull) { // the scan and the segmented sort take 32-bit sizes
+        snprintf(err, errlen, "%s: 2^31 - 1 queries or more in one call", what);
+        return BMX_ERR_ARG;
+    }
+    IndexHost *st = nullptr;
+    int rc = state_ready(state_v, count, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    uint32_t *d_lo = st->d_q, *d_cnt = d_lo + (st->q_cap + 1), *d_seg = d_cnt + (st->q_cap + 1);
+
+    // counts, their exclusive scan (count + 1 entries: the last one is the total), the stored prefix of the queries
+    XHIP(hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    XHIP(hipMemsetAsync(d_cnt, 0, (count + 1) * sizeof(uint32_t), stream)); // (entry `count` stays 0; so does a lane's that fails)
+    XHIP(hipEventRecord(st->ev[0], stream));
+    const bmx::IndexArgs a = make_args(ix, d_pat, pat_bytes, d_pat_off, count, d_lo, d_cnt, use_dir != 0, st->d_ws);
+    hipLaunchKernelGGL(bmx::index_count_kernel, dim3(blocks_for(count)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+    XHIP(hipGetLastError());
+    auto counts64 = rocprim::make_transform_iterator(static_cast<const uint32_t *>(d_cnt), ToU64());
+    size_t scan_bytes = 0;
+    XHIP(rocprim::exclusive_scan(nullptr, scan_bytes, counts64, d_out_off, uint64_t(0), (size_t)count + 1, rocprim::plus<uint64_t>(),
+                                 stream));
+    if (scan_bytes > st->p_bytes) {
+        if (st->d_p) (void)hipFree(st->d_p);
+        st->d_p = nullptr;
+        st->p_bytes = 0;
+        XHIP(hipMalloc(&st->d_p, scan_bytes));
+        st->p_bytes = scan_bytes;
+    }
+    XHIP(rocprim::exclusive_scan(st->d_p, scan_bytes, counts64, d_out_off, uint64_t(0), (size_t)count + 1, rocprim::plus<uint64_t>(),
+                                 stream));
+    hipLaunchKernelGGL(bmx::index_prefix_kernel, dim3(blocks_for(count + 1)), dim3(bmx::INDEX_BLOCK), 0, stream, d_out_off, count,
+                       capacity, d_seg, st->d_ws + 2);
+    XHIP(hipGetLastError());
+    XHIP(hipEventRecord(st->ev[1], stream));
+    XHIP(hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    XHIP(hipStreamSynchronize(stream));
+    if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
+    rc = status_rc(st->h_ws, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    const uint64_t total = st->h_ws[2], stored_queries = st->h_ws[3], stored = st->h_ws[4];
+    if (n_matches) *n_matches = total;
+    const int rc_done = total > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+    if (stored == 0) return rc_done;
+    if (stored >= 0x7fffffffull) {
+        snprintf(err, errlen, "%s: 2^31 - 1 positions or more to store in one call (%llu); pass fewer queries at a time", what,
+                 (unsigned long long)stored);
+        return BMX_ERR_ARG;
+    }
+
+    // fill, ascending order within every segment, widen
+    const size_t keys_bytes = ((stored * sizeof(uint32_t)) + 255) & ~(size_t)255;
+    uint32_t end_bit = 1;
+    while (end_bit < 32 && (ix->n - 1) >> end_bit) ++end_bit;
+    size_t sort_bytes = 0;
+    XHIP(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned)stored,
+                                            (unsigned)stored_queries, d_seg, d_seg + 1, 0, end_bit, stream));
+    const size_t need = 2 * keys_bytes + sort_bytes;
+    if (need > st->p_bytes) {
+        if (st->d_p) (void)hipFree(st->d_p);
+        st->d_p = nullptr;
+        st->p_bytes = 0;
+        XHIP(hipMalloc(&st->d_p, need));
+        st->p_bytes = need;
+    }
+    uint32_t *keys_in = static_cast<uint32_t *>(st->d_p);
+    uint32_t *keys_out = reinterpret_cast<uint32_t *>(static_cast<char *>(st->d_p) + keys_bytes);
+    void *sort_tmp = static_cast<char *>(st->d_p) + 2 * keys_bytes;
+    XHIP(hipEventRecord(st->ev[2], stream));
+    hipLaunchKernelGGL(bmx::index_fill_kernel, dim3(blocks_for(stored_queries)), dim3(bmx::INDEX_BLOCK), 0, stream, ix->d_sa, d_lo,
+                       d_cnt, d_out_off, stored_queries, keys_in);
+    XHIP(hipGetLastError());
+    XHIP(rocprim::segmented_radix_sort_keys(sort_tmp, sort_bytes, keys_in, keys_out, (unsigned)stored, (unsigned)stored_queries, d_seg,
+                                            d_seg + 1, 0, end_bit, stream));
+    hipLaunchKernelGGL(bmx::index_widen_kernel, dim3(blocks_for(stored)), dim3(bmx::INDEX_BLOCK), 0, stream, keys_out, stored,
+                       base_offset, d_pos);
+    XHIP(hipGetLastError());
+    XHIP(hipEventRecord(st->ev[3], stream));
+    XHIP(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    if (st->last_ms >= 0.0f && hipEventElapsedTime(&ms, st->ev[2], st->ev[3]) == hipSuccess) st->last_ms += ms;
+    if (st->p_bytes > KEEP_BYTES) {
+        (void)hipFree(st->d_p);
+        st->d_p = nullptr;
+        st->p_bytes = 0;
+    }
+    return rc_done;
+}

@@ -42,6 +42,12 @@
 //                             batched edit distance (EditDistance-1.cpp:278-345 looped by the caller): the files
 //                             paired line by line, a one-line FILE_A against every line of FILE_B; one distance per
 //                             line on stdout (min(d, T + 1) with --limit), the mean time on stderr
+//   bmx_cli --index-count PATTERNS_FILE --text F [--positions] [--iters N] [--max-print K]
+//                             text index (no counterpart in the reference): the suffix array of the text and a
+//                             directory built once (bmx_index_create_device), then every line of PATTERNS_FILE
+//                             (empty lines skipped) counted in one call; one `pattern<TAB>count` line per pattern
+//                             on stdout, with --positions followed by a third tab-separated field of its ascending
+//                             offsets (at most --max-print of them, blank-separated); build and mean query time on stderr
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -117,7 +123,7 @@ void split_lines(const std::string &text, std::string &blob, std::vector<uint64_
 
 int main(int argc, char **argv)
 {
-    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr;
+    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path;
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
@@ -144,6 +150,7 @@ int main(int argc, char **argv)
         else if (a == "--spans") spans = true;
         else if (a == "--best") spans_best = true;
         else if (a == "--dict") dict_path = need("--dict");
+        else if (a == "--index-count") index_path = need("--index-count");
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
         else if (a == "--icase") class_flags |= BMX_CLASS_ICASE;
         else if (a == "--iupac") class_flags |= BMX_CLASS_IUPAC;
@@ -164,6 +171,84 @@ int main(int argc, char **argv)
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
         return 2;
+    }
+
+    if (!index_path.empty()) {
+        std::string text, lines, raw, blob;
+        std::vector<uint64_t> raw_off, off(1, 0);
+        if (!read_file(text_path, text) || !read_file(index_path, lines)) {
+            fprintf(stderr, "File Not Found!\n");
+            return 1;
+        }
+        split_lines(lines, raw, raw_off);
+        for (size_t i = 0; i + 1 < raw_off.size(); ++i) { // empty lines skipped, a trailing \r dropped
+            uint64_t b = raw_off[i], e = raw_off[i + 1];
+            if (e > b && raw[e - 1] == '\r') --e;
+            if (e == b) continue;
+            blob.append(raw, b, e - b);
+            off.push_back(blob.size());
+        }
+        const uint64_t count = off.size() - 1, n = text.size();
+        if (count == 0) {
+            fprintf(stderr, "no pattern in %s\n", index_path.c_str());
+            return 1;
+        }
+        bmx_ctx *ctx = nullptr;
+        bmx_index *ix = nullptr;
+        void *d_text = nullptr, *d_pat = nullptr, *d_off = nullptr, *d_cnt = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, blob.data(), blob.size(), &d_pat);
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)off.data(), off.size() * sizeof(uint64_t), &d_off);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, (count + 1) * sizeof(uint32_t), &d_cnt);
+        if (rc == BMX_OK) rc = bmx_index_create_device(ctx, d_text, n, nullptr, nullptr, &ix);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "index setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        const float build_ms = bmx_index_build_ms(ix);
+        double total = 0.0, kernel_ms = 0.0;
+        if (iters < 1) iters = 1;
+        for (int it = 0; it < iters; ++it) { // the timed calls: the resident index, results left on the device
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_index_count_device(ctx, ix, d_pat, blob.size(), (const uint64_t *)d_off, count, nullptr, (uint32_t *)d_cnt, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_index_count_device failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_index_ms(ctx);
+        }
+        bmx_index_destroy(ix);
+        for (void *p : {d_text, d_pat, d_off, d_cnt})
+            if (p) bmx_device_free(ctx, p);
+        // what is printed comes through the host-buffer entry points: (text, patterns) -> counts, positions
+        std::vector<uint64_t> out_off(count + 1, 0), pos(1);
+        uint64_t hits = 0;
+        rc = bmx_index_locate(ctx, text.data(), n, blob.data(), blob.size(), off.data(), count, out_off.data(), nullptr, 0, &hits);
+        if (rc == BMX_ERR_CAPACITY && positions) {
+            pos.resize(hits);
+            rc = bmx_index_locate(ctx, text.data(), n, blob.data(), blob.size(), off.data(), count, out_off.data(), pos.data(), hits, &hits);
+        }
+        if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) {
+            fprintf(stderr, "bmx_index_locate failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        for (uint64_t i = 0; i < count; ++i) {
+            fwrite(blob.data() + off[i], 1, off[i + 1] - off[i], stdout);
+            printf("\t%llu", (unsigned long long)(out_off[i + 1] - out_off[i]));
+            if (positions) {
+                printf("\t");
+                for (uint64_t j = out_off[i]; j < out_off[i + 1] && j - out_off[i] < max_print; ++j)
+                    printf(j == out_off[i] ? "%llu" : " %llu", (unsigned long long)pos[j]);
+            }
+            printf("\n");
+        }
+        fprintf(stderr, "Average time = %.6f s  (kernel %.3f ms, %llu patterns, %llu occurrences, index built in %.3f ms)\n",
+                total / iters, kernel_ms / iters, (unsigned long long)count, (unsigned long long)hits, build_ms);
+        bmx_ctx_destroy(ctx);
+        return 0;
     }
 
     if (!edb_a.empty()) {

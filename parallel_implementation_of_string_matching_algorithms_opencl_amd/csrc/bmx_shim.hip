@@ -81,6 +81,21 @@ int bmx_internal_dict_search(void **state, int num_cu, const bmx_dict *d, const 
 void bmx_internal_dict_state_free(void *state);
 float bmx_internal_dict_ms(const void *state);
 int64_t bmx_internal_dict_candidates(const void *state);
+// bmx_index.hip
+int bmx_internal_index_create(void **state, bmx_ctx *ctx, int device, const void *d_text, uint64_t n, const int32_t *d_sa,
+                              hipStream_t stream, bmx_index **out, char *err, size_t errlen);
+void bmx_internal_index_destroy(bmx_index *ix);
+const void *bmx_internal_index_owner(const bmx_index *ix);
+const int32_t *bmx_internal_index_sa(const bmx_index *ix);
+float bmx_internal_index_build_ms(const bmx_index *ix);
+int bmx_internal_index_count(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t *d_lo, uint32_t *d_cnt, int use_dir, hipStream_t stream, char *err,
+                             size_t errlen);
+int bmx_internal_index_locate(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                              uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos, uint64_t capacity,
+                              uint64_t *n_matches, int use_dir, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_index_state_free(void *state);
+float bmx_internal_index_ms(const void *state);
 
 namespace {
 
@@ -244,6 +259,8 @@ struct bmx_ctx {
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
     void *spans = nullptr; // match spans: status words, tile counts of the selection, events (bmx_spans.hip)
     void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
+    void *index = nullptr;  // text index: status words, events, workspace of count / locate (bmx_index.hip)
+    bool index_no_dir = false; // libbmx_exp.so: queries search the whole array, not their directory bucket
     int blocks_per_cu = 0; // 0 = as many as LDS and the 32-wave limit admit
     unsigned long long *d_count = nullptr; // live match counter; re-armed by order_kernel
     uint32_t *d_tile_count = nullptr;      // matches per tile of the last scan (dense results: input of the fill pass)
@@ -592,6 +609,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
+    bmx_internal_index_state_free(ctx->index);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
     for (int i = 0; i < bmx_ctx::EV_RING; ++i) {
         if (ctx->ev0[i]) (void)hipEventDestroy(ctx->ev0[i]);
@@ -1996,6 +2014,152 @@ float bmx_last_dict_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_dict_ms(ctx->di
 
 int64_t bmx_last_dict_candidates(bmx_ctx *ctx) { return ctx ? bmx_internal_dict_candidates(ctx->dict) : -1; }
 
+// ---- text index (bmx_index.hip) ------------------------------------------------------------------
+namespace {
+// every argument error of a query call, before any HIP call (the CPU suite calls these with ctx = NULL)
+bool index_query_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, const void *out)
+{
+    return count == 0 || (pat && pat_off && out);
+}
+// the host entry's queries: BMX_ERR_ARG for offsets that decrease or end past the blob and for a length of 0 or above
+// BMX_MAX_PATTERN, BMX_ERR_DOMAIN for a byte >= 0x80
+int index_queries_ok(const void *pat, uint64_t pat_bytes, const uint64_t *off, uint64_t count)
+{
+    for (uint64_t i = 0; i < count; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] > pat_bytes || off[i + 1] == off[i] || off[i + 1] - off[i] > BMX_MAX_PATTERN)
+            return BMX_ERR_ARG;
+    const uint8_t *p = static_cast<const uint8_t *>(pat);
+    for (uint64_t j = off[0]; j < off[count]; ++j)
+        if (p[j] >= 0x80) return BMX_ERR_DOMAIN;
+    return BMX_OK;
+}
+} // namespace
+
+int bmx_index_create_device(bmx_ctx *ctx, const void *d_text, uint64_t n, const int32_t *d_sa, void *stream_v, bmx_index **out)
+{
+    if (!ctx || !d_text || !out || n == 0 || n >= (1ull << 31)) return BMX_ERR_ARG;
+    *out = nullptr;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_index_create(&ctx->index, ctx, ctx->device, d_text, n, d_sa, (hipStream_t)stream_v, out, g_err,
+                                     sizeof g_err);
+}
+
+void bmx_index_destroy(bmx_index *ix) { bmx_internal_index_destroy(ix); }
+
+int bmx_index_sa(const bmx_index *ix, const int32_t **d_sa_out)
+{
+    if (!ix || !d_sa_out) return BMX_ERR_ARG;
+    *d_sa_out = bmx_internal_index_sa(ix);
+    return BMX_OK;
+}
+
+float bmx_index_build_ms(const bmx_index *ix) { return ix ? bmx_internal_index_build_ms(ix) : -1.0f; }
+
+int bmx_index_count_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                           uint64_t count, uint32_t *d_lo, uint32_t *d_cnt, void *stream_v)
+{
+    if (!index_query_args_ok(d_pat, d_pat_off, count, d_cnt)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_index_count(&ctx->index, ix, d_pat, pat_bytes, d_pat_off, count, d_lo, d_cnt, !ctx->index_no_dir,
+                                    (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_index_locate_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                            uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos, uint64_t capacity,
+                            uint64_t *n_matches, void *stream_v)
+{
+    if (!index_query_args_ok(d_pat, d_pat_off, count, d_out_off) || (count > 0 && capacity > 0 && !d_pos)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_index_locate(&ctx->index, ix, d_pat, pat_bytes, d_pat_off, count, base_offset, d_out_off, d_pos, capacity,
+                                     n_matches, !ctx->index_no_dir, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_index_count(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                    uint64_t count, uint32_t *cnt)
+{
+    if (!text || n == 0 || n >= (1ull << 31) || !index_query_args_ok(pat, pat_off, count, cnt)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    int rc = index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (rc != BMX_OK) return rc;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    void *d_text = nullptr, *d_pat = nullptr, *d_off = nullptr, *d_cnt = nullptr;
+    bmx_index *ix = nullptr;
+    rc = bmx_text_upload(ctx, text, n, &d_text);
+    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat, pat_bytes, &d_pat);
+    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat_off, (count + 1) * sizeof(uint64_t), &d_off);
+    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, count * sizeof(uint32_t), &d_cnt);
+    if (rc == BMX_OK) rc = bmx_index_create_device(ctx, d_text, n, nullptr, nullptr, &ix);
+    if (rc == BMX_OK)
+        rc = bmx_index_count_device(ctx, ix, d_pat, pat_bytes, (const uint64_t *)d_off, count, nullptr, (uint32_t *)d_cnt, nullptr);
+    if (rc == BMX_OK) {
+        hipError_t e = hipMemcpy(cnt, d_cnt, count * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_err("download of the counts: %s", hipGetErrorString(e));
+            rc = BMX_ERR_HIP;
+        }
+    }
+    bmx_index_destroy(ix);
+    for (void *p : {d_text, d_pat, d_off, d_cnt})
+        if (p) (void)hipFree(p);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+
+int bmx_index_locate(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                     uint64_t count, uint64_t *out_off, uint64_t *pos, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!text || n == 0 || n >= (1ull << 31) || !index_query_args_ok(pat, pat_off, count, out_off) ||
+        (count > 0 && capacity > 0 && !pos))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (count == 0) return BMX_OK;
+    int rc = index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (rc != BMX_OK) return rc;
+    bmx_ctx *ctx = ctx_in;
+    if (!ctx) {
+        rc = bmx_ctx_create(0, &ctx);
+        if (rc != BMX_OK) return rc;
+    }
+    void *d_text = nullptr, *d_pat = nullptr, *d_off = nullptr, *d_out_off = nullptr, *d_pos = nullptr;
+    bmx_index *ix = nullptr;
+    uint64_t total = 0;
+    rc = bmx_text_upload(ctx, text, n, &d_text);
+    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat, pat_bytes, &d_pat);
+    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat_off, (count + 1) * sizeof(uint64_t), &d_off);
+    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, (count + 1) * sizeof(uint64_t), &d_out_off);
+    if (rc == BMX_OK && capacity) rc = bmx_device_alloc(ctx, capacity * sizeof(uint64_t), &d_pos);
+    if (rc == BMX_OK) rc = bmx_index_create_device(ctx, d_text, n, nullptr, nullptr, &ix);
+    if (rc == BMX_OK)
+        rc = bmx_index_locate_device(ctx, ix, d_pat, pat_bytes, (const uint64_t *)d_off, count, 0, (uint64_t *)d_out_off,
+                                     (uint64_t *)d_pos, capacity, &total, nullptr);
+    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
+        hipError_t e = hipMemcpy(out_off, d_out_off, (count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        const uint64_t stored = std::min(total, capacity); // (behind the stored segments: unspecified, as in the device entry)
+        if (e == hipSuccess && stored) e = hipMemcpy(pos, d_pos, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            set_err("download of the positions: %s", hipGetErrorString(e));
+            rc = BMX_ERR_HIP;
+        }
+        if (n_matches) *n_matches = total;
+    }
+    bmx_index_destroy(ix);
+    for (void *p : {d_text, d_pat, d_off, d_out_off, d_pos})
+        if (p) (void)hipFree(p);
+    if (!ctx_in) bmx_ctx_destroy(ctx);
+    return rc;
+}
+
+float bmx_last_index_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_index_ms(ctx->index) : -1.0f; }
+
 int bmx_device_alloc(bmx_ctx *ctx, uint64_t bytes, void **d_ptr_out)
 {
     if (!ctx || !d_ptr_out) return BMX_ERR_ARG;
@@ -2139,6 +2303,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "ed_step_x") ctx->ed_step_x = value;
     else if (k == "ed_stamp_block") ctx->ed_stamp_block = value;
     else if (k == "sa_flags") ctx->sa_flags = value;
+    else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else return BMX_ERR_ARG;
     return BMX_OK;
 }

@@ -154,6 +154,19 @@ SYMBOLS = [
     ("bmx_last_suffix_array_ms", C.c_float, [C.c_void_p]),
     ("bmx_last_suffix_array_rounds", C.c_int, [C.c_void_p]),
     ("bmx_last_suffix_array_lds_rounds", C.c_int, [C.c_void_p]),
+    ("bmx_index_create_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("bmx_index_destroy", None, [C.c_void_p]),
+    ("bmx_index_sa", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("bmx_index_count_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    ("bmx_index_locate_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+                                          C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_index_count", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                  C.c_void_p]),
+    ("bmx_index_locate", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_index_ms", C.c_float, [C.c_void_p]),
+    ("bmx_index_build_ms", C.c_float, [C.c_void_p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     ("bmx_plant_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, _u64p,
                                    C.c_uint64, C.c_void_p]),
@@ -830,6 +843,27 @@ class Context:
         """Positions of the last dictionary search that passed the LDS filters (false positives + matching positions)."""
         return int(self._L.bmx_last_dict_candidates(self._h))
 
+    # -- text index: batched pattern count and locate over the suffix array -------------
+    def index(self, d_text, sa=None) -> "Index":
+        """An index over the resident text ``d_text`` (uint8 CUDA tensor) and its suffix array (bmx_index_create_device):
+        ``sa`` an int32 CUDA tensor as suffix_array_device returns it, or None to have it built and owned by the index."""
+        return Index(self, d_text, sa)
+
+    def index_count(self, text, patterns) -> np.ndarray:
+        """Host buffers (bmx_index_count): occurrences of every pattern in ``text``, uint32."""
+        tptr, n, keep = _host_text(text)
+        blob, off = pack_strings(patterns)
+        count = off.size - 1
+        cnt = np.empty(max(count, 1), dtype=np.uint32)
+        rc = self._L.bmx_index_count(self._h, tptr, n, C.c_void_p(blob.ctypes.data), blob.size, C.c_void_p(off.ctypes.data),
+                                     count, C.c_void_p(cnt.ctypes.data))
+        self._chk(rc, "bmx_index_count")
+        del keep
+        return cnt[:count]
+
+    def last_index_ms(self) -> float:
+        return float(self._L.bmx_last_index_ms(self._h))
+
     # -- suffix array (the reference's third program) -----------------------------
     def suffix_array(self, text) -> np.ndarray:
         """int32 suffix array in the reference's order (SuffixArrays.cpp:101-154)."""
@@ -960,6 +994,128 @@ class Dictionary:
             if total <= cap:
                 return pos.cpu().numpy().astype(np.uint64), pid.cpu().numpy().astype(np.uint32)
             cap = total
+
+
+class _DeviceArray:
+    """A raw device pointer in the shape torch.as_tensor takes as a view (the CUDA array interface, version 2)."""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2,
+                                         "strides": None}
+
+
+class Index:
+    """A text index on one context's device (bmx_index_create_device): a resident text, its suffix array (the caller's, or
+    built here and owned) and a directory of the 128 x 128 two-byte prefixes.  The text tensor (and a caller's array) is
+    borrowed: this object keeps a reference to both until close()."""
+
+    def __init__(self, ctx: "Context", d_text, sa=None):
+        import torch
+
+        if d_text.element_size() != 1 or (sa is not None and (sa.element_size() != 4 or sa.numel() < d_text.numel())):
+            raise ValueError("d_text: 1-byte entries; sa: 4-byte entries, one per text byte")
+        self._ctx = ctx
+        self._L = ctx._L
+        self._text, self._sa_in = d_text, sa
+        self.n = d_text.numel()
+        self._h = C.c_void_p()
+        stream = C.c_void_p(torch.cuda.current_stream(d_text.device).cuda_stream)
+        rc = self._L.bmx_index_create_device(ctx._h, C.c_void_p(d_text.data_ptr()), self.n,
+                                             None if sa is None else C.c_void_p(sa.data_ptr()), stream, C.byref(self._h))
+        ctx._chk(rc, "bmx_index_create_device")
+        self.build_ms = float(self._L.bmx_index_build_ms(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.bmx_index_destroy(self._h)
+            self._h = C.c_void_p()
+            self._text = self._sa_in = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def sa(self):
+        """The array that is searched, as an int32 CUDA tensor: the caller's tensor, or a view of the index's own (valid
+        until close())."""
+        import torch
+
+        if self._sa_in is not None:
+            return self._sa_in[: self.n]
+        p = C.c_void_p()
+        self._ctx._chk(self._L.bmx_index_sa(self._h, C.byref(p)), "bmx_index_sa")
+        return torch.as_tensor(_DeviceArray(p.value, self.n, "<i4"), device=self._text.device)
+
+    def _queries(self, patterns):
+        """(blob tensor, offsets tensor, count) on the text's device; CUDA tensors are passed through."""
+        import torch
+
+        if isinstance(patterns, tuple) and len(patterns) == 2 and hasattr(patterns[0], "data_ptr"):
+            d_blob, d_off = patterns
+            if d_blob.element_size() != 1 or d_off.element_size() != 8:
+                raise ValueError("patterns: a 1-byte blob and 8-byte offsets")
+            return d_blob, d_off, d_off.numel() - 1
+        blob, off = pack_strings(patterns)
+        dev = self._text.device
+        d_blob = torch.from_numpy(blob.copy() if blob.size else np.zeros(1, np.uint8)).to(dev)
+        return d_blob[: blob.size], torch.from_numpy(off.astype(np.int64)).to(dev), off.size - 1
+
+    def count(self, patterns, lo_out=None, cnt_out=None):
+        """(lo, cnt) int32 CUDA tensors, one entry per pattern (bmx_index_count_device): cnt[i] occurrences of pattern i,
+        which are sa[lo[i] : lo[i] + cnt[i]].  ``patterns``: a list of bytes / str, a (blob, offsets) numpy pair as
+        pack_strings makes, or such a pair of CUDA tensors.  Runs on torch's current stream."""
+        import torch
+
+        d_blob, d_off, count = self._queries(patterns)
+        dev = self._text.device
+        lo = lo_out if lo_out is not None else torch.empty(max(count, 1), dtype=torch.int32, device=dev)
+        cnt = cnt_out if cnt_out is not None else torch.empty(max(count, 1), dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self._L.bmx_index_count_device(self._ctx._h, self._h, C.c_void_p(d_blob.data_ptr()), d_blob.numel(),
+                                            C.c_void_p(d_off.data_ptr()), count, C.c_void_p(lo.data_ptr()),
+                                            C.c_void_p(cnt.data_ptr()), stream)
+        self._ctx._chk(rc, "bmx_index_count_device")
+        return lo[:count], cnt[:count]
+
+    def locate(self, patterns, capacity: Optional[int] = None, base_offset: int = 0):
+        """(offsets, positions, total) (bmx_index_locate_device): ``offsets`` int64 CUDA tensor of count + 1 entries, the
+        exclusive prefix sum of the counts; positions[offsets[i] : offsets[i + 1]] = base_offset + p for every occurrence
+        of pattern i, ascending.  Without ``capacity`` the list is complete (a counting call first).  With a capacity
+        below the total the positions hold every pattern whose segment ends at or below it; that is no error here (the
+        total says so)."""
+        import torch
+
+        d_blob, d_off, count = self._queries(patterns)
+        dev = self._text.device
+        out_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        total = C.c_uint64(0)
+
+        def call(pos, cap):
+            return self._L.bmx_index_locate_device(self._ctx._h, self._h, C.c_void_p(d_blob.data_ptr()), d_blob.numel(),
+                                                   C.c_void_p(d_off.data_ptr()), count, base_offset,
+                                                   C.c_void_p(out_off.data_ptr()), None if pos is None else C.c_void_p(pos.data_ptr()),
+                                                   cap, C.byref(total), stream)
+
+        counted = capacity is None
+        if counted:
+            self._ctx._chk(call(None, 0), "bmx_index_locate_device", allow=(ERR_CAPACITY,))
+            capacity = int(total.value)
+        pos = torch.empty(max(capacity, 1), dtype=torch.int64, device=dev)
+        if capacity > 0:
+            self._ctx._chk(call(pos, capacity), "bmx_index_locate_device", allow=(ERR_CAPACITY,))
+        elif not counted:
+            self._ctx._chk(call(None, 0), "bmx_index_locate_device", allow=(ERR_CAPACITY,))
+        return out_off, pos[: min(int(total.value), capacity)], int(total.value)
 
 
 class PreparedSearch:
@@ -1109,6 +1265,11 @@ def search_approx_spans(text, pattern, k: int, best: bool = True) -> Tuple[np.nd
 def edit_distance_batch(a, b, limit: Optional[int] = None) -> np.ndarray:
     """(a, b) -> uint32 distances, pair by pair, or one ``a`` against every string of ``b`` (bmx_edit_distance_batch)."""
     return default_context().edit_distance_batch(a, b, limit)
+
+
+def index_count(text, patterns) -> np.ndarray:
+    """Occurrences of every pattern in ``text`` through a text index built for the call (bmx_index_count), uint32."""
+    return default_context().index_count(text, patterns)
 
 
 def search_dict(text, patterns) -> Tuple[np.ndarray, np.ndarray]:
