@@ -16,8 +16,10 @@ extern "C" {
  * "multi_no_qgram" (multi-pattern pass byte-wise only), "ed_lag" (rows a column band is assumed to trail its
  * predecessor by; < 0: the measured default), "ed_group" (16 | 32 rows per hand-over), "ed_step_x" (1..8: ed variant 13 with parts of its step left out, timing only), "sa_flags" (1 library rounds
  * only, 2 a host wait per round, 4 per-round trace on stderr), "index_no_dir" (the text index's queries search the whole
- * array instead of their directory bucket: same answers, tools/index_rate.py measures the difference).  BMX_ERR_ARG for an
- * unknown name. */
+ * array instead of their directory bucket: same answers, tools/index_rate.py measures the difference), "ordered_seq"
+ * (>= 0: the sequence number of every ordered-output session the context already has -- approximate, class-pattern and
+ * dictionary search; the next call takes the one after it, so (1 << 22) - 1 puts that call on the wrap of the status
+ * words' 22-bit tag).  BMX_ERR_ARG for an unknown name and for a negative "ordered_seq". */
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
 
 /* Read-only sweep of n bytes at d_text (16-byte aligned) with plain global loads into registers, XOR-folded: no LDS,

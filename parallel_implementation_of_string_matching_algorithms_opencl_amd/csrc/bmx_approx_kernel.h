@@ -15,8 +15,8 @@
 //
 // Ordered output in one pass.  While it walks, a lane counts its hits and parks (position in tile, ordinal in lane,
 // distance) in a pool of APPROX_STAGE entries per tile.  The workgroup then scans the lane counts, publishes the
-// tile's aggregate and finds its exclusive prefix by decoupled look-back over per-tile status words (relaxed
-// agent-scope atomics; the word is its own payload: {epoch tag, kind, value}), so every parked hit goes straight to
+// tile's aggregate and finds its exclusive prefix by decoupled look-back over per-tile status words
+// (bmx_ordered_out.h; the word is its own payload: {epoch tag, kind, value}), so every parked hit goes straight to
 // its final slot prefix + lane base + ordinal.  A tile with more hits than the pool walks itself a second time and
 // writes directly.  Slots at or past the capacity are dropped: the stored entries are the lowest ends.
 #pragma once
@@ -24,17 +24,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmx_ordered_out.h"
+
 namespace bmx {
 
 constexpr int APPROX_BLOCK = 256;  // lanes per workgroup
 constexpr int APPROX_STAGE = 2048; // hits parked per tile (16 KiB of LDS)
 constexpr int MAX_APPROX_PATTERN = 64; // == BMX_MAX_APPROX_PATTERN
-
-// Per-tile status word: [63:42] epoch tag (the call's sequence number mod 2^22, never 0), [41:40] kind, [39:0] value.
-constexpr uint32_t APPROX_TAG_SHIFT = 42;
-constexpr uint64_t APPROX_TAG_MASK = (1ull << 22) - 1;
-constexpr uint64_t APPROX_KIND_AGG = 1, APPROX_KIND_PREFIX = 2;
-constexpr uint64_t APPROX_VALUE_MASK = (1ull << 40) - 1;
 
 struct ApproxArgs {
     const uint8_t *text16; // caller's pointer rounded down to a multiple of 16
@@ -57,55 +53,6 @@ struct ApproxArgs {
     uint32_t p_shift;      // P = 1 << p_shift ends per lane
     uint64_t peq[256];     // bit i set: pattern[i] == byte (low word used when m <= 32)
 };
-
-__device__ __forceinline__ uint64_t approx_load_status(uint64_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void approx_store_status(uint64_t *p, uint64_t v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The look-back of one tile, for kernels that share this design (bmx_classes_kernel.h; approx_kernel below keeps its own
-// copy: its code object is recorded).  Lane 0 of the workgroup that holds tile t publishes the tile's aggregate, finds
-// the exclusive prefix over the status words of tiles t - 1 .. 0 and publishes the inclusive one; the last tile writes the
-// total and the call's sequence number to pinned memory.  Tiles t - 1 .. 0 were handed out before this one, so each is
-// owned by a running workgroup and publishes.  The bound (~1 s) only keeps a wave from spinning for ever: a waiter that
-// reaches it raises the give-up word (the host returns BMX_ERR_HIP, never this list) and goes on.  Returns the prefix.
-__device__ __forceinline__ uint64_t approx_lookback(const ApproxArgs &a, uint64_t t, uint64_t agg)
-{
-    const uint64_t tagbits = a.tag << APPROX_TAG_SHIFT;
-    uint64_t prefix = 0;
-    if (t == 0) {
-        approx_store_status(&a.status[0], tagbits | (APPROX_KIND_PREFIX << 40) | agg);
-    } else {
-        approx_store_status(&a.status[t], tagbits | (APPROX_KIND_AGG << 40) | agg);
-        uint64_t i = t - 1;
-        uint32_t spins = 0;
-        for (;;) {
-            const uint64_t w = approx_load_status(&a.status[i]);
-            const uint64_t kind = (w >> 40) & 3u;
-            if ((w >> APPROX_TAG_SHIFT) != a.tag || kind == 0) {
-                if (++spins > (1u << 24)) {
-                    __hip_atomic_store(&a.host_status[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-                continue;
-            }
-            prefix += w & APPROX_VALUE_MASK;
-            if (kind == APPROX_KIND_PREFIX || i == 0) break;
-            --i;
-        }
-        approx_store_status(&a.status[t], tagbits | (APPROX_KIND_PREFIX << 40) | ((prefix + agg) & APPROX_VALUE_MASK));
-    }
-    if (t == a.n_tiles - 1) {
-        __hip_atomic_store(&a.host_status[0], prefix + agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&a.host_status[2], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return prefix;
-}
 
 // Column state of Myers' recurrence for one lane.
 template <typename W>
@@ -247,39 +194,9 @@ __global__ __launch_bounds__(APPROX_BLOCK) void approx_kernel(const ApproxArgs a
             for (int q = 0; q < 4; ++q) lane_base[4 * tid + q] = run, run += v[q];
             const uint64_t agg = (uint64_t)__shfl(incl, 63);
             if (tid == 0) {
-                const uint64_t tagbits = a.tag << APPROX_TAG_SHIFT;
-                uint64_t prefix = 0;
-                if (t == 0) {
-                    approx_store_status(&a.status[0], tagbits | (APPROX_KIND_PREFIX << 40) | agg);
-                } else {
-                    approx_store_status(&a.status[t], tagbits | (APPROX_KIND_AGG << 40) | agg);
-                    // Decoupled look-back.  Tile t - 1 .. 0 were handed out before this one, so each is owned by a running
-                    // workgroup and publishes.  The bound (~1 s) only keeps a wave from spinning for ever: a waiter that
-                    // reaches it raises the give-up word (the host returns BMX_ERR_HIP, never this list) and goes on.
-                    uint64_t i = t - 1;
-                    uint32_t spins = 0;
-                    for (;;) {
-                        const uint64_t w = approx_load_status(&a.status[i]);
-                        const uint64_t kind = (w >> 40) & 3u;
-                        if ((w >> APPROX_TAG_SHIFT) != a.tag || kind == 0) {
-                            if (++spins > (1u << 24)) {
-                                __hip_atomic_store(&a.host_status[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                                break;
-                            }
-                            __builtin_amdgcn_s_sleep(2);
-                            continue;
-                        }
-                        prefix += w & APPROX_VALUE_MASK;
-                        if (kind == APPROX_KIND_PREFIX || i == 0) break;
-                        --i;
-                    }
-                    approx_store_status(&a.status[t], tagbits | (APPROX_KIND_PREFIX << 40) | ((prefix + agg) & APPROX_VALUE_MASK));
-                }
+                const uint64_t prefix = ordered_lookback(a, t, agg);
                 sh_prefix = prefix;
-                if (t == a.n_tiles - 1) {
-                    __hip_atomic_store(&a.host_status[0], prefix + agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(&a.host_status[2], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                ordered_publish_total(a, t, prefix + agg);
             }
         }
         __syncthreads();

@@ -11,7 +11,7 @@
 //
 // Geometry, tile ticket, tagged status words, look-back, parking pool, second walk of a dense tile and the pinned total
 // are the approximate search's (bmx_approx_kernel.h), in end coordinates with lead = m - 1: the argument
-// block and the status helpers are shared with it.  Two things differ:
+// block is shared with it, the look-back is bmx_ordered_out.h.  Two things differ:
 //  * gather first, then step: a 16-byte chunk reads its 16 B words into registers, then runs its 16 steps with no
 //    branch, LDS atomic or store between them; the chunk's 16 hit bits are ANDed with its ownership mask once and only a
 //    non-zero mask enters the hit code;
@@ -162,7 +162,11 @@ __global__ __launch_bounds__(CLASSES_BLOCK) void classes_kernel(const ApproxArgs
 #pragma unroll
             for (int q = 0; q < 4; ++q) lane_base[4 * tid + q] = run, run += v[q];
             const uint64_t agg = (uint64_t)__shfl(incl, 63);
-            if (tid == 0) sh_prefix = approx_lookback(a, t, agg);
+            if (tid == 0) {
+                const uint64_t prefix = ordered_lookback(a, t, agg);
+                ordered_publish_total(a, t, prefix + agg);
+                sh_prefix = prefix;
+            }
         }
         __syncthreads();
         const uint64_t prefix = sh_prefix;

@@ -1,10 +1,11 @@
 // bmx_dict.hip -- host side of the dictionary search (bmx_dict_*, include/bmx.h): builds a dictionary's tables in plain
-// C++ (the LDS bitmaps, the exact-prefix table, the id order, the pattern blob) and uploads them once; keeps the
-// per-tile status words, the ticket counter and the pinned result words of a context between calls; launches
-// bmx_dict_kernel.h once per search and waits for the stream.  The argument checks are the shim's (bmx_shim.hip).
+// C++ (the LDS bitmaps, the exact-prefix table, the id order, the pattern blob) and uploads them once; launches
+// bmx_dict_kernel.h once per search inside an ordered-output call (bmx_ordered_out.h: status words, ticket, pinned result
+// words, the wait for the stream).  The argument checks are the shim's (bmx_shim.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -12,6 +13,7 @@
 
 #include "bmx.h"
 #include "bmx_dict_kernel.h"
+#include "bmx_internal.h"
 
 static_assert(bmx::DICT_MAX == BMX_MAX_DICT, "header and kernel disagree");
 static_assert(bmx::DICT_ROUND == 1 << 13, "tile_shift assumes 8 KiB rounds");
@@ -32,39 +34,16 @@ struct bmx_dict {
 namespace {
 
 struct DictState {
-    uint64_t *d_status = nullptr; // per-tile look-back words, tagged with the call's epoch
-    uint64_t status_cap = 0;
-    unsigned long long *d_ticket = nullptr; // monotonic: a call hands out n_tiles + grid tickets
-    uint64_t ticket_base = 0;
+    bmx::OrderedOut oo; // (first: bmx_ordered_out.h)
     unsigned long long *d_cand = nullptr; // candidates of the last call
-    uint64_t *h_status = nullptr;         // pinned, device-visible: {total, give-up, seq}
-    uint64_t *h_status_dev = nullptr;
-    uint64_t seq = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float last_ms = -1.0f;
     bool launched = false;
     int blocks_per_cu = 0;
 };
-
-#define DHIP(expr)                                                                                 \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            snprintf(err, errlen, "%s: %s failed: %s", where, #expr, hipGetErrorString(e__));      \
-            return BMX_ERR_HIP;                                                                    \
-        }                                                                                          \
-    } while (0)
+static_assert(offsetof(DictState, oo) == 0, "ordered_set_seq");
 
 void set_bit(std::vector<uint32_t> &bm, uint32_t base, uint32_t word, uint32_t bit)
 {
     bm[base + word] |= 1u << (bit & 31u);
-}
-
-uint32_t ceil_log2(uint64_t x)
-{
-    uint32_t s = 0;
-    while ((1ull << s) < x) ++s;
-    return s;
 }
 
 void free_dict(bmx_dict *d)
@@ -126,7 +105,7 @@ int bmx_internal_dict_create(const void *owner, int device, const char *const *p
         blob.insert(blob.end(), p, p + m);
     }
     // exact-prefix table: open addressing, linear probing, at most half full
-    const uint32_t bits = std::max<uint32_t>(ceil_log2(2 * groups.size()), 4);
+    const uint32_t bits = std::max<uint32_t>(bmx::ceil_log2(2 * groups.size()), 4);
     const uint32_t size = 1u << bits;
     std::vector<uint4> table(size, make_uint4(bmx::DICT_EMPTY, 0, 0, 0));
     std::vector<uint32_t> ids;
@@ -178,19 +157,15 @@ void bmx_internal_dict_state_free(void *state_v)
 {
     DictState *st = static_cast<DictState *>(state_v);
     if (!st) return;
-    if (st->d_status) (void)hipFree(st->d_status);
-    if (st->d_ticket) (void)hipFree(st->d_ticket);
+    st->oo.free();
     if (st->d_cand) (void)hipFree(st->d_cand);
-    if (st->h_status) (void)hipHostFree(st->h_status);
-    if (st->ev0) (void)hipEventDestroy(st->ev0);
-    if (st->ev1) (void)hipEventDestroy(st->ev1);
     delete st;
 }
 
 float bmx_internal_dict_ms(const void *state_v)
 {
     const DictState *st = static_cast<const DictState *>(state_v);
-    return st ? st->last_ms : -1.0f;
+    return st ? st->oo.last_ms : -1.0f;
 }
 
 // Positions of the last search that passed the LDS filters and were looked up in the exact-prefix table.
@@ -213,26 +188,13 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
     if (!*state_v) *state_v = new DictState();
     DictState *st = static_cast<DictState *>(*state_v);
     if (n_matches) *n_matches = 0;
-    st->last_ms = 0.0f;
+    st->oo.last_ms = 0.0f;
     st->launched = false;
     const uint64_t own = std::min(n_own, n);
-    if (own == 0) return BMX_OK; // no start to report (before anything is put on `stream`: what is cleared below is cleared
-                                 // in front of the kernel that reads it, on the same stream)
-    if (!st->d_ticket) {
-        DHIP(hipMalloc(&st->d_ticket, sizeof(unsigned long long)));
-        DHIP(hipMemsetAsync(st->d_ticket, 0, sizeof(unsigned long long), stream));
-        st->ticket_base = 0;
-    }
-    if (!st->d_cand) DHIP(hipMalloc(&st->d_cand, sizeof(unsigned long long)));
-    if (!st->h_status) {
-        DHIP(hipHostMalloc(&st->h_status, 4 * sizeof(uint64_t), hipHostMallocMapped));
-        std::memset(st->h_status, 0, 4 * sizeof(uint64_t));
-        DHIP(hipHostGetDevicePointer((void **)&st->h_status_dev, st->h_status, 0));
-    }
-    if (!st->ev0) DHIP(hipEventCreate(&st->ev0));
-    if (!st->ev1) DHIP(hipEventCreate(&st->ev1));
+    if (own == 0) return BMX_OK; // no start to report (before anything is put on `stream`)
+    if (!st->d_cand) BMX_HIP(where, hipMalloc(&st->d_cand, sizeof(unsigned long long)));
     if (st->blocks_per_cu == 0) {
-        DHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&st->blocks_per_cu, bmx::dict_kernel, bmx::DICT_BLOCK, 0));
+        BMX_HIP(where, hipOccupancyMaxActiveBlocksPerMultiprocessor(&st->blocks_per_cu, bmx::dict_kernel, bmx::DICT_BLOCK, 0));
         st->blocks_per_cu = std::max(1, std::min(st->blocks_per_cu, 4));
     }
 
@@ -264,51 +226,13 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
     a.classes = d->classes;
     a.rounds_shift = rs;
 
-    if (a.n_tiles > st->status_cap) {
-        if (st->d_status) (void)hipFree(st->d_status);
-        st->d_status = nullptr;
-        st->status_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(a.n_tiles, 1024);
-        DHIP(hipMalloc(&st->d_status, cap * sizeof(uint64_t)));
-        DHIP(hipMemsetAsync(st->d_status, 0, cap * sizeof(uint64_t), stream)); // tag 0 is never a call's
-        st->status_cap = cap;
-    }
-    ++st->seq;
-    if ((st->seq & bmx::DICT_TAG_MASK) == 0) { // the tag wraps: old words could carry this call's tag
-        DHIP(hipMemsetAsync(st->d_status, 0, st->status_cap * sizeof(uint64_t), stream));
-        ++st->seq;
-    }
-    a.status = st->d_status;
-    a.ticket = st->d_ticket;
-    a.ticket_base = st->ticket_base;
-    a.host_status = st->h_status_dev;
-    a.seq = st->seq;
-    a.tag = st->seq & bmx::DICT_TAG_MASK;
     a.cand = st->d_cand;
-    st->h_status[0] = st->h_status[1] = st->h_status[2] = 0;
 
+    BMX_HIP(where, hipMemsetAsync(st->d_cand, 0, sizeof(unsigned long long), stream));
+    int rc = st->oo.begin(where, stream, a, err, errlen);
+    if (rc != BMX_OK) return rc;
     const uint64_t grid = std::min<uint64_t>(a.n_tiles, resident);
-    DHIP(hipMemsetAsync(st->d_cand, 0, sizeof(unsigned long long), stream));
-    DHIP(hipEventRecord(st->ev0, stream));
     hipLaunchKernelGGL(bmx::dict_kernel, dim3((uint32_t)grid), dim3(bmx::DICT_BLOCK), 0, stream, a);
-    DHIP(hipGetLastError());
-    DHIP(hipEventRecord(st->ev1, stream));
-    DHIP(hipStreamSynchronize(stream));
-    st->ticket_base += a.n_tiles + grid; // every workgroup draws one ticket past the last tile
     st->launched = true;
-    (void)hipEventElapsedTime(&st->last_ms, st->ev0, st->ev1);
-
-    volatile uint64_t *hs = st->h_status;
-    if (hs[2] != st->seq) {
-        snprintf(err, errlen, "%s: the kernel did not report its total (seq %llu, want %llu)", where,
-                 (unsigned long long)hs[2], (unsigned long long)st->seq);
-        return BMX_ERR_HIP;
-    }
-    if (hs[1] != 0) {
-        snprintf(err, errlen, "%s: a tile waited longer than its bound for its predecessors' counts; result discarded", where);
-        return BMX_ERR_HIP;
-    }
-    const uint64_t total = hs[0];
-    if (n_matches) *n_matches = total;
-    return total > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+    return st->oo.finish(where, grid, a.n_tiles, stream, capacity, n_matches, err, errlen);
 }

@@ -15,13 +15,16 @@
 //
 // Ordered output in one pass, as bmx_approx_kernel.h does it: a workgroup takes tiles of 2^rounds_shift rounds from an
 // atomic ticket, parks its tile's pairs as ((p - tile0) << 16 | i) in a pool in LDS, publishes the tile's count and
-// finds its exclusive prefix by decoupled look-back over tagged status words.  A pair's slot is the prefix plus its rank
-// among the tile's parked keys.  A tile with more pairs than the pool walks itself a second time round by round: count,
-// workgroup scan, write.  Slots at or past the capacity are dropped: the stored pairs are the lowest ones.
+// finds its exclusive prefix by decoupled look-back over tagged status words (bmx_ordered_out.h).  A pair's slot is the
+// prefix plus its rank among the tile's parked keys.  A tile with more pairs than the pool walks itself a second time
+// round by round: count, workgroup scan, write.  Slots at or past the capacity are dropped: the stored pairs are the
+// lowest ones.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "bmx_ordered_out.h"
 
 namespace bmx {
 
@@ -39,12 +42,6 @@ constexpr uint32_t DICT_HAS1 = 1, DICT_HAS2 = 2, DICT_HAS3 = 4, DICT_HAS4 = 8;
 
 // Exact-prefix table: EMPTY is never a key (a class-4 key has no byte >= 0x80; the others carry 0xff in byte 3).
 constexpr uint32_t DICT_EMPTY = 0x80808080u;
-
-// Per-tile status word, as the approximate search's: [63:42] epoch tag, [41:40] kind, [39:0] value.
-constexpr uint32_t DICT_TAG_SHIFT = 42;
-constexpr uint64_t DICT_TAG_MASK = (1ull << 22) - 1;
-constexpr uint64_t DICT_KIND_AGG = 1, DICT_KIND_PREFIX = 2;
-constexpr uint64_t DICT_VALUE_MASK = (1ull << 40) - 1;
 
 // The hashes, shared with the host builder.  The multiplies are 24 x 24 bits (full rate); the word comes from the high
 // bits of the product, the bit from the low 5 bits of the folded key.  k: the key bytes, little-endian (class 3: 3 bytes).
@@ -94,15 +91,6 @@ struct DictArgs {
     uint32_t classes;         // DICT_HAS*
     uint32_t rounds_shift;
 };
-
-__device__ __forceinline__ uint64_t dict_load_status(uint64_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void dict_store_status(uint64_t *p, uint64_t v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __device__ __forceinline__ uint32_t dict_bit(const uint32_t *bm, uint32_t word, uint32_t bit)
 {
@@ -349,39 +337,9 @@ __global__ __launch_bounds__(DICT_BLOCK) void dict_kernel(const DictArgs a)
         if (tid == 0) {
             const uint64_t agg = stage_n;
             if (cand_n) atomicAdd(a.cand, (unsigned long long)cand_n);
-            const uint64_t tagbits = a.tag << DICT_TAG_SHIFT;
-            uint64_t prefix = 0;
-            if (t == 0) {
-                dict_store_status(&a.status[0], tagbits | (DICT_KIND_PREFIX << 40) | agg);
-            } else {
-                dict_store_status(&a.status[t], tagbits | (DICT_KIND_AGG << 40) | agg);
-                // Decoupled look-back.  Tiles t - 1 .. 0 were handed out before this one, so each is owned by a running
-                // workgroup and publishes.  The bound (~1 s) only keeps a wave from spinning for ever: a waiter that
-                // reaches it raises the give-up word (the host returns BMX_ERR_HIP, never this list) and goes on.
-                uint64_t i = t - 1;
-                uint32_t spins = 0;
-                for (;;) {
-                    const uint64_t w = dict_load_status(&a.status[i]);
-                    const uint64_t kind = (w >> 40) & 3u;
-                    if ((w >> DICT_TAG_SHIFT) != a.tag || kind == 0) {
-                        if (++spins > (1u << 24)) {
-                            __hip_atomic_store(&a.host_status[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(2);
-                        continue;
-                    }
-                    prefix += w & DICT_VALUE_MASK;
-                    if (kind == DICT_KIND_PREFIX || i == 0) break;
-                    --i;
-                }
-                dict_store_status(&a.status[t], tagbits | (DICT_KIND_PREFIX << 40) | ((prefix + agg) & DICT_VALUE_MASK));
-            }
+            const uint64_t prefix = ordered_lookback(a, t, agg);
             sh_prefix = prefix;
-            if (t == a.n_tiles - 1) {
-                __hip_atomic_store(&a.host_status[0], prefix + agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(&a.host_status[2], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            ordered_publish_total(a, t, prefix + agg);
         }
         __syncthreads();
         const uint64_t prefix = sh_prefix;

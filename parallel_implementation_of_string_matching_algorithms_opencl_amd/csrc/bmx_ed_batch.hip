@@ -12,12 +12,15 @@
 
 #include "bmx.h"
 #include "bmx_ed_batch_kernel.h"
+#include "bmx_internal.h"
 
 static_assert(bmx::ED_BATCH_WORD == BMX_ED_BATCH_WORD, "header and kernel disagree");
 static_assert(bmx::ED_BATCH_LONG == BMX_ED_BATCH_LONG, "header and kernel disagree");
 static_assert(bmx::ED_BATCH_NO_LIMIT == BMX_ED_NO_LIMIT, "header and kernel disagree");
 
 namespace {
+
+constexpr const char *WHERE = "bmx_edit_distance_batch_device";
 
 struct EdBatchHost {
     uint64_t *d_ws = nullptr;   // {bad offsets seen, pairs listed}
@@ -28,15 +31,6 @@ struct EdBatchHost {
     float last_ms = -1.0f;
     int64_t last_fallbacks = -1;
 };
-
-#define EHIP(expr)                                                                                                   \
-    do {                                                                                                             \
-        hipError_t e__ = (expr);                                                                                     \
-        if (e__ != hipSuccess) {                                                                                     \
-            snprintf(err, errlen, "bmx_edit_distance_batch_device: %s failed: %s", #expr, hipGetErrorString(e__)); \
-            return BMX_ERR_HIP;                                                                                      \
-        }                                                                                                            \
-    } while (0)
 
 } // namespace
 
@@ -77,13 +71,13 @@ int bmx_internal_ed_batch(void **state_v, bmx_ctx *ctx, const void *d_a, uint64_
         snprintf(err, errlen, "bmx_edit_distance_batch_device: more than 2^31 workgroups of pairs in one call");
         return BMX_ERR_ARG;
     }
-    if (!st->d_ws) EHIP(hipMalloc(&st->d_ws, 2 * sizeof(uint64_t)));
-    if (!st->h_ws) EHIP(hipHostMalloc(&st->h_ws, 2 * sizeof(uint64_t), hipHostMallocDefault));
-    if (!st->ev0) EHIP(hipEventCreate(&st->ev0));
-    if (!st->ev1) EHIP(hipEventCreate(&st->ev1));
+    if (!st->d_ws) BMX_HIP(WHERE, hipMalloc(&st->d_ws, 2 * sizeof(uint64_t)));
+    if (!st->h_ws) BMX_HIP(WHERE, hipHostMalloc(&st->h_ws, 2 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!st->ev0) BMX_HIP(WHERE, hipEventCreate(&st->ev0));
+    if (!st->ev1) BMX_HIP(WHERE, hipEventCreate(&st->ev1));
     if (!st->d_list) {
         const uint64_t cap = 4096;
-        EHIP(hipMalloc(&st->d_list, cap * (bmx::ED_BATCH_LIST_WORDS * sizeof(uint64_t) + sizeof(uint32_t))));
+        BMX_HIP(WHERE, hipMalloc(&st->d_list, cap * (bmx::ED_BATCH_LIST_WORDS * sizeof(uint64_t) + sizeof(uint32_t))));
         st->list_cap = cap;
     }
 
@@ -104,13 +98,13 @@ int bmx_internal_ed_batch(void **state_v, bmx_ctx *ctx, const void *d_a, uint64_
     for (int pass = 0; pass < 2; ++pass) { // a second pass only if the list was too short for the first
         a.list = st->d_list;
         a.list_cap = st->list_cap;
-        EHIP(hipMemsetAsync(st->d_ws, 0, 2 * sizeof(uint64_t), stream));
-        EHIP(hipEventRecord(st->ev0, stream));
+        BMX_HIP(WHERE, hipMemsetAsync(st->d_ws, 0, 2 * sizeof(uint64_t), stream));
+        BMX_HIP(WHERE, hipEventRecord(st->ev0, stream));
         hipLaunchKernelGGL(bmx::ed_batch_kernel, dim3((uint32_t)n_blocks), dim3(bmx::ED_BATCH_BLOCK), 0, stream, a);
-        EHIP(hipGetLastError());
-        EHIP(hipEventRecord(st->ev1, stream));
-        EHIP(hipMemcpyAsync(st->h_ws, st->d_ws, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        EHIP(hipStreamSynchronize(stream));
+        BMX_HIP(WHERE, hipGetLastError());
+        BMX_HIP(WHERE, hipEventRecord(st->ev1, stream));
+        BMX_HIP(WHERE, hipMemcpyAsync(st->h_ws, st->d_ws, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        BMX_HIP(WHERE, hipStreamSynchronize(stream));
         if (hipEventElapsedTime(&st->last_ms, st->ev0, st->ev1) != hipSuccess) st->last_ms = -1.0f;
         if (st->h_ws[0] != 0) {
             snprintf(err, errlen, "bmx_edit_distance_batch_device: offsets that decrease, end past their blob or span 2^31 bytes");
@@ -121,7 +115,7 @@ int bmx_internal_ed_batch(void **state_v, bmx_ctx *ctx, const void *d_a, uint64_
         (void)hipFree(st->d_list);
         st->d_list = nullptr;
         st->list_cap = 0;
-        EHIP(hipMalloc(&st->d_list, n_fb * (bmx::ED_BATCH_LIST_WORDS * sizeof(uint64_t) + sizeof(uint32_t))));
+        BMX_HIP(WHERE, hipMalloc(&st->d_list, n_fb * (bmx::ED_BATCH_LIST_WORDS * sizeof(uint64_t) + sizeof(uint32_t))));
         st->list_cap = n_fb;
     }
     st->last_fallbacks = (int64_t)n_fb;
@@ -131,8 +125,8 @@ int bmx_internal_ed_batch(void **state_v, bmx_ctx *ctx, const void *d_a, uint64_
     // That path keeps its own time: bmx_last_edit_distance_ms reports the last of these pairs afterwards (bmx.h says so).
     std::vector<uint64_t> list(n_fb * bmx::ED_BATCH_LIST_WORDS);
     std::vector<uint32_t> vals(n_fb);
-    EHIP(hipMemcpyAsync(list.data(), st->d_list, list.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    EHIP(hipStreamSynchronize(stream));
+    BMX_HIP(WHERE, hipMemcpyAsync(list.data(), st->d_list, list.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(WHERE, hipStreamSynchronize(stream));
     for (uint64_t j = 0; j < n_fb; ++j) {
         const uint64_t *e = &list[j * bmx::ED_BATCH_LIST_WORDS];
         uint64_t d = 0;
@@ -141,10 +135,10 @@ int bmx_internal_ed_batch(void **state_v, bmx_ctx *ctx, const void *d_a, uint64_
         vals[j] = (uint32_t)(limit != BMX_ED_NO_LIMIT ? std::min<uint64_t>(d, (uint64_t)limit + 1) : d);
     }
     uint32_t *d_vals = reinterpret_cast<uint32_t *>(st->d_list + st->list_cap * bmx::ED_BATCH_LIST_WORDS);
-    EHIP(hipMemcpyAsync(d_vals, vals.data(), n_fb * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    BMX_HIP(WHERE, hipMemcpyAsync(d_vals, vals.data(), n_fb * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(bmx::ed_batch_scatter_kernel, dim3((uint32_t)((n_fb + 255) / 256)), dim3(256), 0, stream, st->d_list, d_vals,
                        n_fb, d_dist);
-    EHIP(hipGetLastError());
-    EHIP(hipStreamSynchronize(stream));
+    BMX_HIP(WHERE, hipGetLastError());
+    BMX_HIP(WHERE, hipStreamSynchronize(stream));
     return BMX_OK;
 }

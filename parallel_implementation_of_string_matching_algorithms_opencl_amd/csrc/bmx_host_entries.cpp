@@ -1,0 +1,409 @@
+// bmx_host_entries.cpp -- the host-buffer entries of the C ABI (include/bmx.h): host buffers in, host buffers out, over
+// the public device API.  Each checks its arguments (every BMX_ERR_ARG and BMX_ERR_DOMAIN before any HIP call: the CPU
+// suite calls these with ctx = NULL on a machine without a GPU), uploads, runs the device entry and downloads.  Plain
+// host C++: no kernel, one object for both libraries.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <vector>
+
+#include "bmx.h"
+#include "bmx_internal.h"
+
+namespace {
+
+// One host-buffer call: the context (the caller's, or one on device 0 that lives as long as the call), the device buffers
+// the call hands out and the running return code.  upload() and alloc() do nothing once a step has failed; everything is
+// freed when the call leaves scope.  Handles that must go before the context (bmx_dict, bmx_index) are the entry's to
+// destroy, before this object.
+class HostCall {
+public:
+    int rc = BMX_OK;
+
+    HostCall(const char *entry, bmx_ctx *ctx_in) : entry_(entry), ctx_(ctx_in), own_ctx_(!ctx_in)
+    {
+        if (!ctx_) rc = bmx_ctx_create(0, &ctx_);
+    }
+    ~HostCall()
+    {
+        for (void *p : bufs_) (void)hipFree(p);
+        if (own_ctx_ && ctx_) bmx_ctx_destroy(ctx_);
+    }
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+
+    bmx_ctx *ctx() const { return ctx_; }
+
+    template <typename T = void>
+    T *upload(const void *src, uint64_t bytes)
+    {
+        void *p = nullptr;
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx_, static_cast<const char *>(src), bytes, &p);
+        return static_cast<T *>(keep(p));
+    }
+    template <typename T = void>
+    T *alloc(uint64_t bytes)
+    {
+        void *p = nullptr;
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx_, bytes, &p);
+        return static_cast<T *>(keep(p));
+    }
+    void release(void *p)
+    {
+        const auto it = std::find(bufs_.begin(), bufs_.end(), p);
+        if (it == bufs_.end()) return;
+        (void)hipFree(p);
+        bufs_.erase(it);
+    }
+    // (also behind BMX_ERR_CAPACITY: the stored prefix is still the caller's)
+    void download(void *dst, const void *d_src, uint64_t bytes, const char *what)
+    {
+        if ((rc != BMX_OK && rc != BMX_ERR_CAPACITY) || bytes == 0) return;
+        const hipError_t e = hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) return;
+        char text[256];
+        snprintf(text, sizeof text, "%s: download of %s: %s", entry_, what, hipGetErrorString(e));
+        bmx_internal_set_error(text);
+        rc = BMX_ERR_HIP;
+    }
+
+private:
+    void *keep(void *p)
+    {
+        if (p) bufs_.push_back(p);
+        return p;
+    }
+    const char *entry_;
+    bmx_ctx *ctx_;
+    bool own_ctx_;
+    std::vector<void *> bufs_;
+};
+
+// table errors (a pattern outside the ASCII domain) before any device work
+int pattern_tables_ok(const char *pat, int32_t m)
+{
+    int32_t bad[BMX_BAD_TABLE_SIZE];
+    std::vector<int32_t> good(m);
+    return bmx_build_tables(pat, m, bad, good.data());
+}
+
+} // namespace
+
+extern "C" {
+
+int bmx_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, int32_t m, uint64_t *match_positions,
+               uint64_t capacity, uint64_t *n_matches)
+{
+    if (!pat || m < 1 || m > BMX_MAX_PATTERN || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (capacity > 0 && !match_positions) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    const int trc = pattern_tables_ok(pat, m);
+    if (trc != BMX_OK) return trc;
+    if (n < (uint64_t)m) return BMX_OK;
+
+    HostCall c("bmx_search", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n - (uint64_t)m + 1);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_out = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_device(c.ctx(), d_text, n, n, 0, pat, m, nullptr, nullptr, d_out, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(match_positions, d_out, std::min(total, dev_cap) * sizeof(uint64_t), "matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+// (bmx_search_multi and the resident multi-GPU search with its RCCL exchange: bmx_multi.hip)
+
+int bmx_search_ranges(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const int32_t *se, int32_t P,
+                      int32_t *ans, const int32_t *good, const int32_t *bad, int32_t m)
+{
+    if (!text || !pat || !se || !ans || P < 0 || m < 1 || m > BMX_MAX_PATTERN) return BMX_ERR_ARG;
+    if ((good == nullptr) != (bad == nullptr)) return BMX_ERR_ARG;
+    for (int r = 0; r < P; ++r) {
+        ans[r] = 0;
+        const int64_t s = se[2 * r], e = se[2 * r + 1];
+        if (s < 0 || (e >= s && (uint64_t)e >= n)) return BMX_ERR_ARG;
+    }
+    if (!good) {
+        const int trc = pattern_tables_ok(pat, m);
+        if (trc != BMX_OK) return trc;
+    }
+    HostCall c("bmx_search_ranges", ctx_in);
+    const char *d_text = c.upload<char>(text, n);
+    for (int r = 0; r < P && c.rc == BMX_OK; ++r) {
+        const int64_t s = se[2 * r], e = se[2 * r + 1];
+        if (e < s) continue;
+        // inclusive range [s, e] as in kernel1.cl:14-19: windows wholly inside it
+        const uint64_t len = (uint64_t)(e - s) + 1;
+        uint64_t total = 0;
+        c.rc = bmx_search_device(c.ctx(), d_text + s, len, len, (uint64_t)s, pat, m, good, bad, nullptr, 0, &total, nullptr);
+        if (c.rc == BMX_ERR_CAPACITY) c.rc = BMX_OK; // (a count-only call: the total is all it asks for)
+        ans[r] = (int32_t)total;
+    }
+    return c.rc;
+}
+
+int bmx_edit_distance(bmx_ctx *ctx_in, const char *a, uint64_t la, const char *b, uint64_t lb, uint64_t *distance)
+{
+    if (!distance || (la > 0 && !a) || (lb > 0 && !b)) return BMX_ERR_ARG;
+    if (la == 0 || lb == 0) {
+        *distance = la + lb;
+        return BMX_OK;
+    }
+    HostCall c("bmx_edit_distance", ctx_in);
+    void *d_a = c.upload(a, la);
+    void *d_b = c.upload(b, lb);
+    if (c.rc == BMX_OK) c.rc = bmx_edit_distance_device(c.ctx(), d_a, la, d_b, lb, distance, nullptr);
+    return c.rc;
+}
+
+int bmx_edit_distance_batch(bmx_ctx *ctx_in, const void *a, uint64_t a_bytes, const uint64_t *a_off, uint64_t a_count,
+                            const void *b, uint64_t b_bytes, const uint64_t *b_off, uint64_t count, uint32_t limit, uint32_t *dist)
+{
+    if (!bmx_ed_batch_args_ok(a, a_bytes, a_off, a_count, b, b_bytes, b_off, count, dist)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!bmx_ed_batch_offsets_ok(a_off, a_count, a_bytes) || !bmx_ed_batch_offsets_ok(b_off, count, b_bytes)) return BMX_ERR_ARG;
+    HostCall c("bmx_edit_distance_batch", ctx_in);
+    void *d_a = a_bytes ? c.upload(a, a_bytes) : nullptr;
+    void *d_b = b_bytes ? c.upload(b, b_bytes) : nullptr;
+    const uint64_t *d_a_off = c.upload<uint64_t>(a_off, (a_count + 1) * sizeof(uint64_t));
+    const uint64_t *d_b_off = c.upload<uint64_t>(b_off, (count + 1) * sizeof(uint64_t));
+    uint32_t *d_dist = c.alloc<uint32_t>(count * sizeof(uint32_t));
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_edit_distance_batch_device(c.ctx(), d_a, a_bytes, d_a_off, a_count, d_b, b_bytes, d_b_off, count, limit, d_dist,
+                                          nullptr);
+    if (c.rc == BMX_OK) c.download(dist, d_dist, count * sizeof(uint32_t), "the distances");
+    return c.rc;
+}
+
+int bmx_suffix_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out)
+{
+    if ((n > 0 && (!text || !sa_out)) || n >= (1ull << 31)) return BMX_ERR_ARG;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_suffix_array", ctx_in);
+    void *d_text = c.upload(text, n);
+    int32_t *d_sa = c.alloc<int32_t>(n * sizeof(int32_t));
+    if (c.rc == BMX_OK) c.rc = bmx_suffix_array_device(c.ctx(), d_text, n, d_sa, nullptr);
+    if (c.rc == BMX_OK) c.download(sa_out, d_sa, n * sizeof(int32_t), "the suffix array");
+    return c.rc;
+}
+
+} // extern "C"
+
+namespace {
+
+// the approximate search for a string (classes == NULL) or for classes (pat == NULL)
+int search_approx_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes,
+                       int32_t m, int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_approx_args_ok(n, 0, pat ? (const void *)pat : (const void *)classes, m, k, ends, capacity) || (n > 0 && !text))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c(entry, ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint8_t *d_dist = dev_cap && dist ? c.alloc<uint8_t>(dev_cap) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = pat ? bmx_search_approx_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr)
+               : bmx_search_approx_classes_device(c.ctx(), d_text, n, 0, 0, classes, m, k, d_ends, d_dist, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    c.download(ends, d_ends, stored * sizeof(uint64_t), "approximate matches");
+    if (dist) c.download(dist, d_dist, stored, "approximate matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+// ... and its match spans
+int search_spans_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes,
+                      int32_t m, int32_t k, uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
+                      uint64_t *n_spans)
+{
+    if (!bmx_approx_args_ok(n, 0, pat ? (const void *)pat : (const void *)classes, m, k, ends, capacity) ||
+        (flags & ~BMX_SPANS_BEST) || (capacity && !starts) || (n > 0 && !text))
+        return BMX_ERR_ARG;
+    if (n_spans) *n_spans = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c(entry, ctx_in);
+    uint64_t *d_ends = nullptr;
+    uint8_t *d_dist = nullptr;
+    uint64_t total = 0, spans = 0;
+    void *d_text = c.upload(text, n);
+    auto search = [&](uint64_t cap) {
+        d_ends = cap ? c.alloc<uint64_t>(cap * sizeof(uint64_t)) : nullptr;
+        d_dist = cap ? c.alloc<uint8_t>(cap) : nullptr;
+        if (c.rc != BMX_OK) return;
+        c.rc = pat ? bmx_search_approx_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, cap, &total, nullptr)
+                   : bmx_search_approx_classes_device(c.ctx(), d_text, n, 0, 0, classes, m, k, d_ends, d_dist, cap, &total, nullptr);
+    };
+    // counting only if `capacity` cannot hold a single end; else in one go if it holds them all
+    search(std::min<uint64_t>(capacity, n));
+    if (c.rc == BMX_ERR_CAPACITY) { // again, with room for all ends
+        c.release(d_ends);
+        c.release(d_dist);
+        c.rc = BMX_OK;
+        search(total);
+    }
+    uint64_t *d_starts = nullptr, *d_sel_ends = nullptr;
+    uint8_t *d_sel_dist = nullptr;
+    if (c.rc == BMX_OK && total) {
+        d_starts = c.alloc<uint64_t>(total * sizeof(uint64_t));
+        if (flags) d_sel_ends = c.alloc<uint64_t>(total * sizeof(uint64_t));
+        if (flags) d_sel_dist = c.alloc<uint8_t>(total);
+        if (c.rc == BMX_OK)
+            c.rc = pat ? bmx_approx_spans_device(c.ctx(), d_text, n, 0, pat, m, k, d_ends, d_dist, total, flags, d_starts, d_sel_ends,
+                                                 d_sel_dist, &spans, nullptr)
+                       : bmx_approx_spans_classes_device(c.ctx(), d_text, n, 0, classes, m, k, d_ends, d_dist, total, flags, d_starts,
+                                                         d_sel_ends, d_sel_dist, &spans, nullptr);
+    }
+    if (c.rc != BMX_OK) return c.rc;
+    const uint64_t stored = std::min(spans, capacity);
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "match spans");
+    c.download(ends, flags ? d_sel_ends : d_ends, stored * sizeof(uint64_t), "match spans");
+    if (dist) c.download(dist, flags ? d_sel_dist : d_dist, stored, "match spans");
+    if (n_spans) *n_spans = spans;
+    if (c.rc == BMX_OK && spans > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int bmx_search_approx(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t *ends,
+                      uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_approx_host("bmx_search_approx", ctx, text, n, pat, nullptr, m, k, ends, dist, capacity, n_matches);
+}
+
+int bmx_search_approx_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
+                              uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!classes) return BMX_ERR_ARG;
+    return search_approx_host("bmx_search_approx_classes", ctx, text, n, nullptr, classes, m, k, ends, dist, capacity, n_matches);
+}
+
+int bmx_search_approx_spans(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint32_t flags,
+                            uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_spans)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_spans_host("bmx_search_approx_spans", ctx, text, n, pat, nullptr, m, k, flags, starts, ends, dist, capacity,
+                             n_spans);
+}
+
+int bmx_search_approx_spans_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
+                                    uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
+                                    uint64_t *n_spans)
+{
+    if (!classes) return BMX_ERR_ARG;
+    return search_spans_host("bmx_search_approx_spans_classes", ctx, text, n, nullptr, classes, m, k, flags, starts, ends, dist,
+                             capacity, n_spans);
+}
+
+int bmx_search_classes(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                       uint64_t *match_positions, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_classes_args_ok(n, classes, m, match_positions, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n < (uint64_t)m) return BMX_OK;
+    HostCall c("bmx_search_classes", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n - (uint64_t)m + 1);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_classes_device(c.ctx(), d_text, n, n, 0, classes, m, d_starts, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(match_positions, d_starts, std::min(total, dev_cap) * sizeof(uint64_t), "class matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+int bmx_dict_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *const *pats, const int32_t *ms, int32_t K,
+                    uint64_t *pos, uint32_t *pid, uint64_t capacity, uint64_t *n_matches)
+{
+    const int prc = bmx_dict_patterns_ok(pats, ms, K);
+    if (prc != BMX_OK) return prc;
+    if ((n > 0 && !text) || n >= (1ull << 40) || (capacity > 0 && !pos)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    HostCall c("bmx_dict_search", ctx_in);
+    bmx_dict *d = nullptr;
+    uint64_t total = 0;
+    if (c.rc == BMX_OK) c.rc = bmx_dict_create(c.ctx(), pats, ms, K, &d);
+    void *d_text = n ? c.upload(text, n) : nullptr;
+    uint64_t *d_pos = capacity ? c.alloc<uint64_t>(capacity * sizeof(uint64_t)) : nullptr;
+    uint32_t *d_pid = capacity && pid ? c.alloc<uint32_t>(capacity * sizeof(uint32_t)) : nullptr;
+    if (c.rc == BMX_OK) c.rc = bmx_dict_search_device(c.ctx(), d, d_text, n, n, 0, d_pos, d_pid, capacity, &total, nullptr);
+    if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
+        const uint64_t stored = std::min(total, capacity);
+        c.download(pos, d_pos, stored * sizeof(uint64_t), "dictionary matches");
+        if (pid) c.download(pid, d_pid, stored * sizeof(uint32_t), "dictionary matches");
+        if (n_matches) *n_matches = total;
+    }
+    bmx_dict_destroy(d); // before the context
+    return c.rc;
+}
+
+int bmx_index_count(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                    uint64_t count, uint32_t *cnt)
+{
+    if (!text || n == 0 || n >= (1ull << 31) || !bmx_index_query_args_ok(pat, pat_off, count, cnt)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (qrc != BMX_OK) return qrc;
+    HostCall c("bmx_index_count", ctx_in);
+    bmx_index *ix = nullptr;
+    void *d_text = c.upload(text, n);
+    void *d_pat = c.upload(pat, pat_bytes);
+    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+    uint32_t *d_cnt = c.alloc<uint32_t>(count * sizeof(uint32_t));
+    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
+    if (c.rc == BMX_OK) c.rc = bmx_index_count_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, nullptr, d_cnt, nullptr);
+    if (c.rc == BMX_OK) c.download(cnt, d_cnt, count * sizeof(uint32_t), "the counts");
+    bmx_index_destroy(ix); // before the context
+    return c.rc;
+}
+
+int bmx_index_locate(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                     uint64_t count, uint64_t *out_off, uint64_t *pos, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!text || n == 0 || n >= (1ull << 31) || !bmx_index_query_args_ok(pat, pat_off, count, out_off) ||
+        (count > 0 && capacity > 0 && !pos))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (count == 0) return BMX_OK;
+    const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (qrc != BMX_OK) return qrc;
+    HostCall c("bmx_index_locate", ctx_in);
+    bmx_index *ix = nullptr;
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    void *d_pat = c.upload(pat, pat_bytes);
+    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+    uint64_t *d_out_off = c.alloc<uint64_t>((count + 1) * sizeof(uint64_t));
+    uint64_t *d_pos = capacity ? c.alloc<uint64_t>(capacity * sizeof(uint64_t)) : nullptr;
+    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
+    if (c.rc == BMX_OK)
+        c.rc = bmx_index_locate_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, 0, d_out_off, d_pos, capacity, &total, nullptr);
+    if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
+        c.download(out_off, d_out_off, (count + 1) * sizeof(uint64_t), "the positions");
+        // (behind the stored segments: unspecified, as in the device entry)
+        c.download(pos, d_pos, std::min(total, capacity) * sizeof(uint64_t), "the positions");
+        if (n_matches) *n_matches = total;
+    }
+    bmx_index_destroy(ix); // before the context
+    return c.rc;
+}
+
+} // extern "C"

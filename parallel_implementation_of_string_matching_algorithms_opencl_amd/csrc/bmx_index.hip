@@ -15,6 +15,7 @@
 
 #include "bmx.h"
 #include "bmx_index_kernel.h"
+#include "bmx_internal.h"
 
 static_assert(bmx::INDEX_MAX_PATTERN == BMX_MAX_PATTERN, "header and kernel disagree");
 
@@ -49,30 +50,21 @@ struct ToU64 {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
 };
 
-#define XHIP(expr)                                                                              \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            snprintf(err, errlen, "%s: %s failed: %s", what, #expr, hipGetErrorString(e__)); \
-            return BMX_ERR_HIP;                                                                 \
-        }                                                                                       \
-    } while (0)
-
 int state_ready(void **state_v, uint64_t count, IndexHost **out, const char *what, char *err, size_t errlen)
 {
     if (!*state_v) *state_v = new IndexHost();
     IndexHost *st = static_cast<IndexHost *>(*state_v);
     st->last_ms = -1.0f;
-    if (!st->d_ws) XHIP(hipMalloc(&st->d_ws, WS_WORDS * sizeof(uint64_t)));
-    if (!st->h_ws) XHIP(hipHostMalloc(&st->h_ws, WS_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    if (!st->d_ws) BMX_HIP(what, hipMalloc(&st->d_ws, WS_WORDS * sizeof(uint64_t)));
+    if (!st->h_ws) BMX_HIP(what, hipHostMalloc(&st->h_ws, WS_WORDS * sizeof(uint64_t), hipHostMallocDefault));
     for (hipEvent_t &e : st->ev)
-        if (!e) XHIP(hipEventCreate(&e));
+        if (!e) BMX_HIP(what, hipEventCreate(&e));
     if (count > st->q_cap) {
         if (st->d_q) (void)hipFree(st->d_q);
         st->d_q = nullptr;
         st->q_cap = 0;
         const uint64_t cap = std::max<uint64_t>(count, 1u << 16);
-        XHIP(hipMalloc(&st->d_q, 3 * (cap + 1) * sizeof(uint32_t)));
+        BMX_HIP(what, hipMalloc(&st->d_q, 3 * (cap + 1) * sizeof(uint32_t)));
         st->q_cap = cap;
     }
     *out = st;
@@ -158,8 +150,8 @@ int bmx_internal_index_create(void **state_v, bmx_ctx *ctx, int device, const vo
     // A text that ends in two or more bytes 96 leaves suffixes tied in the builder's order: no interval to search.
     if (n >= 2) {
         uint8_t tail[2] = {0, 0};
-        XHIP(hipMemcpyAsync(tail, static_cast<const uint8_t *>(d_text) + (n - 2), 2, hipMemcpyDeviceToHost, stream));
-        XHIP(hipStreamSynchronize(stream));
+        BMX_HIP(what, hipMemcpyAsync(tail, static_cast<const uint8_t *>(d_text) + (n - 2), 2, hipMemcpyDeviceToHost, stream));
+        BMX_HIP(what, hipStreamSynchronize(stream));
         if (tail[0] == 96 && tail[1] == 96) {
             snprintf(err, errlen, "%s: the text ends in two or more bytes 96; the suffix array's order is unspecified there", what);
             return BMX_ERR_DOMAIN;
@@ -233,14 +225,14 @@ int bmx_internal_index_count(void **state_v, const bmx_index *ix, const void *d_
     IndexHost *st = nullptr;
     const int rc = state_ready(state_v, 0, &st, what, err, errlen);
     if (rc != BMX_OK) return rc;
-    XHIP(hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
-    XHIP(hipEventRecord(st->ev[0], stream));
+    BMX_HIP(what, hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    BMX_HIP(what, hipEventRecord(st->ev[0], stream));
     const bmx::IndexArgs a = make_args(ix, d_pat, pat_bytes, d_pat_off, count, d_lo, d_cnt, use_dir != 0, st->d_ws);
     hipLaunchKernelGGL(bmx::index_count_kernel, dim3(blocks_for(count)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
-    XHIP(hipGetLastError());
-    XHIP(hipEventRecord(st->ev[1], stream));
-    XHIP(hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    XHIP(hipStreamSynchronize(stream));
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, hipEventRecord(st->ev[1], stream));
+    BMX_HIP(what, hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
     if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
     return status_rc(st->h_ws, what, err, errlen);
 }
@@ -260,31 +252,32 @@ int bmx_internal_index_locate(void **state_v, const bmx_index *ix, const void *d
     uint32_t *d_lo = st->d_q, *d_cnt = d_lo + (st->q_cap + 1), *d_seg = d_cnt + (st->q_cap + 1);
 
     // counts, their exclusive scan (count + 1 entries: the last one is the total), the stored prefix of the queries
-    XHIP(hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
-    XHIP(hipMemsetAsync(d_cnt, 0, (count + 1) * sizeof(uint32_t), stream)); // (entry `count` stays 0; so does a lane's that fails)
-    XHIP(hipEventRecord(st->ev[0], stream));
+    BMX_HIP(what, hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    // (entry `count` stays 0; so does a lane's that fails)
+    BMX_HIP(what, hipMemsetAsync(d_cnt, 0, (count + 1) * sizeof(uint32_t), stream));
+    BMX_HIP(what, hipEventRecord(st->ev[0], stream));
     const bmx::IndexArgs a = make_args(ix, d_pat, pat_bytes, d_pat_off, count, d_lo, d_cnt, use_dir != 0, st->d_ws);
     hipLaunchKernelGGL(bmx::index_count_kernel, dim3(blocks_for(count)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
-    XHIP(hipGetLastError());
+    BMX_HIP(what, hipGetLastError());
     auto counts64 = rocprim::make_transform_iterator(static_cast<const uint32_t *>(d_cnt), ToU64());
     size_t scan_bytes = 0;
-    XHIP(rocprim::exclusive_scan(nullptr, scan_bytes, counts64, d_out_off, uint64_t(0), (size_t)count + 1, rocprim::plus<uint64_t>(),
-                                 stream));
+    BMX_HIP(what, rocprim::exclusive_scan(nullptr, scan_bytes, counts64, d_out_off, uint64_t(0), (size_t)count + 1,
+                                          rocprim::plus<uint64_t>(), stream));
     if (scan_bytes > st->p_bytes) {
         if (st->d_p) (void)hipFree(st->d_p);
         st->d_p = nullptr;
         st->p_bytes = 0;
-        XHIP(hipMalloc(&st->d_p, scan_bytes));
+        BMX_HIP(what, hipMalloc(&st->d_p, scan_bytes));
         st->p_bytes = scan_bytes;
     }
-    XHIP(rocprim::exclusive_scan(st->d_p, scan_bytes, counts64, d_out_off, uint64_t(0), (size_t)count + 1, rocprim::plus<uint64_t>(),
-                                 stream));
+    BMX_HIP(what, rocprim::exclusive_scan(st->d_p, scan_bytes, counts64, d_out_off, uint64_t(0), (size_t)count + 1,
+                                          rocprim::plus<uint64_t>(), stream));
     hipLaunchKernelGGL(bmx::index_prefix_kernel, dim3(blocks_for(count + 1)), dim3(bmx::INDEX_BLOCK), 0, stream, d_out_off, count,
                        capacity, d_seg, st->d_ws + 2);
-    XHIP(hipGetLastError());
-    XHIP(hipEventRecord(st->ev[1], stream));
-    XHIP(hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    XHIP(hipStreamSynchronize(stream));
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, hipEventRecord(st->ev[1], stream));
+    BMX_HIP(what, hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
     if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
     rc = status_rc(st->h_ws, what, err, errlen);
     if (rc != BMX_OK) return rc;
@@ -303,30 +296,31 @@ int bmx_internal_index_locate(void **state_v, const bmx_index *ix, const void *d
     uint32_t end_bit = 1;
     while (end_bit < 32 && (ix->n - 1) >> end_bit) ++end_bit;
     size_t sort_bytes = 0;
-    XHIP(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned)stored,
-                                            (unsigned)stored_queries, d_seg, d_seg + 1, 0, end_bit, stream));
+    BMX_HIP(what, rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                     (unsigned)stored, (unsigned)stored_queries, d_seg, d_seg + 1, 0, end_bit,
+                                                     stream));
     const size_t need = 2 * keys_bytes + sort_bytes;
     if (need > st->p_bytes) {
         if (st->d_p) (void)hipFree(st->d_p);
         st->d_p = nullptr;
         st->p_bytes = 0;
-        XHIP(hipMalloc(&st->d_p, need));
+        BMX_HIP(what, hipMalloc(&st->d_p, need));
         st->p_bytes = need;
     }
     uint32_t *keys_in = static_cast<uint32_t *>(st->d_p);
     uint32_t *keys_out = reinterpret_cast<uint32_t *>(static_cast<char *>(st->d_p) + keys_bytes);
     void *sort_tmp = static_cast<char *>(st->d_p) + 2 * keys_bytes;
-    XHIP(hipEventRecord(st->ev[2], stream));
+    BMX_HIP(what, hipEventRecord(st->ev[2], stream));
     hipLaunchKernelGGL(bmx::index_fill_kernel, dim3(blocks_for(stored_queries)), dim3(bmx::INDEX_BLOCK), 0, stream, ix->d_sa, d_lo,
                        d_cnt, d_out_off, stored_queries, keys_in);
-    XHIP(hipGetLastError());
-    XHIP(rocprim::segmented_radix_sort_keys(sort_tmp, sort_bytes, keys_in, keys_out, (unsigned)stored, (unsigned)stored_queries, d_seg,
-                                            d_seg + 1, 0, end_bit, stream));
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, rocprim::segmented_radix_sort_keys(sort_tmp, sort_bytes, keys_in, keys_out, (unsigned)stored,
+                                                     (unsigned)stored_queries, d_seg, d_seg + 1, 0, end_bit, stream));
     hipLaunchKernelGGL(bmx::index_widen_kernel, dim3(blocks_for(stored)), dim3(bmx::INDEX_BLOCK), 0, stream, keys_out, stored,
                        base_offset, d_pos);
-    XHIP(hipGetLastError());
-    XHIP(hipEventRecord(st->ev[3], stream));
-    XHIP(hipStreamSynchronize(stream));
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, hipEventRecord(st->ev[3], stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
     float ms = 0.0f;
     if (st->last_ms >= 0.0f && hipEventElapsedTime(&ms, st->ev[2], st->ev[3]) == hipSuccess) st->last_ms += ms;
     if (st->p_bytes > KEEP_BYTES) {

@@ -1,0 +1,163 @@
+// bmx_internal.h -- what the library's translation units share and the C ABI (include/bmx.h) does not show: the
+// bmx_internal_* functions the shim calls (included by the shim and by every file that defines one, so a changed
+// signature fails to compile), the HIP-check macro of the per-feature files, and the argument checks that the device
+// entries (bmx_shim.hip) and the host-buffer entries (bmx_host_entries.cpp) both make before any HIP call.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include <cstddef>
+#include <cstdio>
+
+#include "bmx.h"
+
+// In a function with `char *err, size_t errlen` that returns a BMX_* code: `where` names the entry point.
+#define BMX_HIP(where, expr)                                                                      \
+    do {                                                                                          \
+        hipError_t e__ = (expr);                                                                  \
+        if (e__ != hipSuccess) {                                                                  \
+            snprintf(err, errlen, "%s: %s failed: %s", (where), #expr, hipGetErrorString(e__)); \
+            return BMX_ERR_HIP;                                                                   \
+        }                                                                                         \
+    } while (0)
+
+namespace bmx {
+inline uint32_t ceil_log2(uint64_t x)
+{
+    uint32_t s = 0;
+    while ((1ull << s) < x) ++s;
+    return s;
+}
+} // namespace bmx
+
+// bmx_shim.hip: the text bmx_last_error() returns on this thread
+void bmx_internal_set_error(const char *text);
+// bmx_sort.hip
+int bmx_internal_radix_sort(uint64_t *d_keys, uint64_t n, unsigned end_bit, void **scratch, size_t *scratch_bytes, hipStream_t stream,
+                            char *err, size_t errlen);
+// bmx_sa.hip
+int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, float *ms_out,
+                              int *rounds_out, void **ws, size_t *ws_bytes, uint32_t **pinned, int flags, char *err, size_t errlen);
+// bmx_approx.hip
+int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                        const char *pat, const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
+                        uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_approx_free(void *state);
+float bmx_internal_approx_ms(const void *state);
+// bmx_classes.hip
+int bmx_internal_classes(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                         const uint8_t *classes, int32_t m, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
+                         hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_classes_free(void *state);
+float bmx_internal_classes_ms(const void *state);
+// bmx_ed_batch.hip
+int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
+                          const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
+                          uint32_t *d_dist, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_ed_batch_free(void *state);
+float bmx_internal_ed_batch_ms(const void *state);
+int64_t bmx_internal_ed_batch_fallbacks(const void *state);
+// bmx_spans.hip
+int bmx_internal_spans(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, const uint8_t *classes,
+                       int32_t m, int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
+                       uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, hipStream_t stream,
+                       char *err, size_t errlen);
+void bmx_internal_spans_free(void *state);
+float bmx_internal_spans_ms(const void *state);
+// bmx_dict.hip
+int bmx_internal_dict_create(const void *owner, int device, const char *const *pats, const int32_t *ms, int32_t K,
+                             bmx_dict **out, char *err, size_t errlen);
+void bmx_internal_dict_destroy(bmx_dict *d);
+const void *bmx_internal_dict_owner(const bmx_dict *d);
+int bmx_internal_dict_search(void **state, int num_cu, const bmx_dict *d, const void *d_text, uint64_t n, uint64_t n_own,
+                             uint64_t base_offset, uint64_t *d_pos, uint32_t *d_pid, uint64_t capacity,
+                             uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_dict_state_free(void *state);
+float bmx_internal_dict_ms(const void *state);
+int64_t bmx_internal_dict_candidates(const void *state);
+// bmx_index.hip
+int bmx_internal_index_create(void **state, bmx_ctx *ctx, int device, const void *d_text, uint64_t n, const int32_t *d_sa,
+                              hipStream_t stream, bmx_index **out, char *err, size_t errlen);
+void bmx_internal_index_destroy(bmx_index *ix);
+const void *bmx_internal_index_owner(const bmx_index *ix);
+const int32_t *bmx_internal_index_sa(const bmx_index *ix);
+float bmx_internal_index_build_ms(const bmx_index *ix);
+int bmx_internal_index_count(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t *d_lo, uint32_t *d_cnt, int use_dir, hipStream_t stream, char *err,
+                             size_t errlen);
+int bmx_internal_index_locate(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                              uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos, uint64_t capacity,
+                              uint64_t *n_matches, int use_dir, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_index_state_free(void *state);
+float bmx_internal_index_ms(const void *state);
+
+// ---- argument checks: every argument error, before any HIP call (the CPU suite calls the entries with ctx = NULL) ----
+
+// batched edit distance
+inline bool bmx_ed_batch_args_ok(const void *a, uint64_t a_bytes, const uint64_t *a_off, uint64_t a_count, const void *b,
+                                 uint64_t b_bytes, const uint64_t *b_off, uint64_t count, const uint32_t *dist)
+{
+    if (count == 0) return true;
+    return (a_count == 1 || a_count == count) && a_off && b_off && dist && (a || a_bytes == 0) && (b || b_bytes == 0);
+}
+// ... the host entry's offsets: monotone, the last one inside the blob, every string below 2^31 bytes
+inline bool bmx_ed_batch_offsets_ok(const uint64_t *off, uint64_t strings, uint64_t bytes)
+{
+    for (uint64_t i = 0; i < strings; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ull << 31)) return false;
+    return off[strings] <= bytes;
+}
+
+// approximate search (pat: the string or the classes)
+inline bool bmx_approx_args_ok(uint64_t n, uint64_t lead, const void *pat, int32_t m, int32_t k, const void *ends, uint64_t capacity)
+{
+    return pat && m >= 1 && m <= BMX_MAX_APPROX_PATTERN && k >= 0 && k < m && lead <= n && n < (1ull << 40) &&
+           (capacity == 0 || ends);
+}
+
+// class-pattern search
+inline bool bmx_classes_args_ok(uint64_t n, const uint8_t *classes, int32_t m, const void *starts, uint64_t capacity)
+{
+    return classes && m >= 1 && m <= BMX_MAX_CLASS_PATTERN && n < (1ull << 40) && (capacity == 0 || starts);
+}
+
+// match spans (pat: the string or the classes)
+inline bool bmx_spans_args_ok(uint64_t n, const void *pat, int32_t m, int32_t k, const uint64_t *ends, const uint8_t *dist,
+                              uint64_t count, uint32_t flags, const uint64_t *starts, const uint64_t *sel_ends)
+{
+    if (!pat || m < 1 || m > BMX_MAX_APPROX_PATTERN || k < 0 || k >= m || n >= (1ull << 40) || (flags & ~BMX_SPANS_BEST)) return false;
+    if (count == 0) return true;
+    return ends && starts && (flags == 0 || (dist && sel_ends));
+}
+
+// a dictionary's patterns: BMX_ERR_ARG for NULL arrays or a count or length out of range, BMX_ERR_DOMAIN for a byte >= 0x80
+// (as bmx_build_tables)
+inline int bmx_dict_patterns_ok(const char *const *pats, const int32_t *ms, int32_t K)
+{
+    if (!pats || !ms || K < 1 || K > BMX_MAX_DICT) return BMX_ERR_ARG;
+    for (int32_t i = 0; i < K; ++i)
+        if (!pats[i] || ms[i] < 1 || ms[i] > BMX_MAX_PATTERN) return BMX_ERR_ARG;
+    for (int32_t i = 0; i < K; ++i)
+        for (int32_t j = 0; j < ms[i]; ++j)
+            if ((uint8_t)pats[i][j] >= 0x80) return BMX_ERR_DOMAIN;
+    return BMX_OK;
+}
+
+// a query call of the text index
+inline bool bmx_index_query_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, const void *out)
+{
+    return count == 0 || (pat && pat_off && out);
+}
+// ... the host entry's queries: BMX_ERR_ARG for offsets that decrease or end past the blob and for a length of 0 or above
+// BMX_MAX_PATTERN, BMX_ERR_DOMAIN for a byte >= 0x80
+inline int bmx_index_queries_ok(const void *pat, uint64_t pat_bytes, const uint64_t *off, uint64_t count)
+{
+    for (uint64_t i = 0; i < count; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] > pat_bytes || off[i + 1] == off[i] || off[i + 1] - off[i] > BMX_MAX_PATTERN)
+            return BMX_ERR_ARG;
+    const uint8_t *p = static_cast<const uint8_t *>(pat);
+    for (uint64_t j = off[0]; j < off[count]; ++j)
+        if (p[j] >= 0x80) return BMX_ERR_DOMAIN;
+    return BMX_OK;
+}

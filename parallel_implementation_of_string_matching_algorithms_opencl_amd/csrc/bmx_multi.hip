@@ -22,6 +22,7 @@
 // lists a device twice -- the tests do, a 1-GPU box has nothing else -- and the slots are then staged through host
 // memory instead; everything else is the same code.
 #include "bmx.h"
+#include "bmx_internal.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -34,9 +35,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-// bmx_shim.hip
-void bmx_internal_set_error(const char *text);
 
 namespace {
 

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "bmx.h"
+#include "bmx_internal.h"
 
 #ifndef SA_EXP
 #define SA_EXP 0 // (timing builds, never shipped: 1 = no sort, 8 = phase times of sa_segsort_kernel on stderr)

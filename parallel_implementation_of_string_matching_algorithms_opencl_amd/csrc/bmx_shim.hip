@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "bmx_internal.h"
 #include "bmx_scan_kernel.h"
 
 #include "bmx_aux_kernels.h"
@@ -32,70 +33,12 @@
 #include "bmx_scan_ring_kernel.h"
 #include "bmx_scan_wave_kernel.h"
 #include "bmx_exp.h"
+#include "bmx_ordered_out.h"
 #include "bmx_probe_kernel.h"
 #endif
 
 static_assert(bmx::MAX_PATTERN == BMX_MAX_PATTERN, "header and kernel disagree");
 static_assert(bmx::MAX_MULTI == BMX_MAX_MULTI, "header and kernel disagree");
-
-// bmx_sort.hip
-int bmx_internal_radix_sort(uint64_t *d_keys, uint64_t n, unsigned end_bit, void **scratch, size_t *scratch_bytes, hipStream_t stream,
-                            char *err, size_t errlen);
-// bmx_sa.hip
-int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, float *ms_out,
-                              int *rounds_out, void **ws, size_t *ws_bytes, uint32_t **pinned, int flags, char *err, size_t errlen);
-// bmx_approx.hip
-int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
-                        const char *pat, const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
-                        uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
-void bmx_internal_approx_free(void *state);
-float bmx_internal_approx_ms(const void *state);
-// bmx_classes.hip
-int bmx_internal_classes(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
-                         const uint8_t *classes, int32_t m, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
-                         hipStream_t stream, char *err, size_t errlen);
-void bmx_internal_classes_free(void *state);
-float bmx_internal_classes_ms(const void *state);
-// bmx_ed_batch.hip
-int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
-                          const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
-                          uint32_t *d_dist, hipStream_t stream, char *err, size_t errlen);
-void bmx_internal_ed_batch_free(void *state);
-float bmx_internal_ed_batch_ms(const void *state);
-int64_t bmx_internal_ed_batch_fallbacks(const void *state);
-// bmx_spans.hip
-int bmx_internal_spans(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, const uint8_t *classes,
-                       int32_t m, int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
-                       uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, hipStream_t stream,
-                       char *err, size_t errlen);
-void bmx_internal_spans_free(void *state);
-float bmx_internal_spans_ms(const void *state);
-// bmx_dict.hip
-int bmx_internal_dict_create(const void *owner, int device, const char *const *pats, const int32_t *ms, int32_t K,
-                             bmx_dict **out, char *err, size_t errlen);
-void bmx_internal_dict_destroy(bmx_dict *d);
-const void *bmx_internal_dict_owner(const bmx_dict *d);
-int bmx_internal_dict_search(void **state, int num_cu, const bmx_dict *d, const void *d_text, uint64_t n, uint64_t n_own,
-                             uint64_t base_offset, uint64_t *d_pos, uint32_t *d_pid, uint64_t capacity,
-                             uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
-void bmx_internal_dict_state_free(void *state);
-float bmx_internal_dict_ms(const void *state);
-int64_t bmx_internal_dict_candidates(const void *state);
-// bmx_index.hip
-int bmx_internal_index_create(void **state, bmx_ctx *ctx, int device, const void *d_text, uint64_t n, const int32_t *d_sa,
-                              hipStream_t stream, bmx_index **out, char *err, size_t errlen);
-void bmx_internal_index_destroy(bmx_index *ix);
-const void *bmx_internal_index_owner(const bmx_index *ix);
-const int32_t *bmx_internal_index_sa(const bmx_index *ix);
-float bmx_internal_index_build_ms(const bmx_index *ix);
-int bmx_internal_index_count(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
-                             uint64_t count, uint32_t *d_lo, uint32_t *d_cnt, int use_dir, hipStream_t stream, char *err,
-                             size_t errlen);
-int bmx_internal_index_locate(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
-                              uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos, uint64_t capacity,
-                              uint64_t *n_matches, int use_dir, hipStream_t stream, char *err, size_t errlen);
-void bmx_internal_index_state_free(void *state);
-float bmx_internal_index_ms(const void *state);
 
 namespace {
 
@@ -111,7 +54,8 @@ void set_err(const char *fmt, ...)
 
 } // namespace
 
-// for the library's other translation units (bmx_multi.hip): the text bmx_last_error() returns on this thread
+// for the library's other translation units (bmx_multi.hip, bmx_host_entries.cpp): the text bmx_last_error() returns on
+// this thread
 void bmx_internal_set_error(const char *text) { snprintf(g_err, sizeof g_err, "%s", text ? text : ""); }
 
 namespace {
@@ -1517,90 +1461,17 @@ int bmx_edit_distance_device(bmx_ctx *ctx, const void *d_a, uint64_t la, const v
     return BMX_OK;
 }
 
-int bmx_edit_distance(bmx_ctx *ctx_in, const char *a, uint64_t la, const char *b, uint64_t lb, uint64_t *distance)
-{
-    if (!distance || (la > 0 && !a) || (lb > 0 && !b)) return BMX_ERR_ARG;
-    if (la == 0 || lb == 0) {
-        *distance = la + lb;
-        return BMX_OK;
-    }
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_a = nullptr, *d_b = nullptr;
-    int rc = bmx_text_upload(ctx, a, la, &d_a);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, b, lb, &d_b);
-    if (rc == BMX_OK) rc = bmx_edit_distance_device(ctx, d_a, la, d_b, lb, distance, nullptr);
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-
 // ---- batched edit distance (bmx_ed_batch.hip) --------------------------------------------------
-namespace {
-// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
-bool ed_batch_args_ok(const void *a, uint64_t a_bytes, const uint64_t *a_off, uint64_t a_count, const void *b, uint64_t b_bytes,
-                      const uint64_t *b_off, uint64_t count, const uint32_t *dist)
-{
-    if (count == 0) return true;
-    return (a_count == 1 || a_count == count) && a_off && b_off && dist && (a || a_bytes == 0) && (b || b_bytes == 0);
-}
-// the host entry's offsets: monotone, the last one inside the blob, every string below 2^31 bytes
-bool ed_batch_offsets_ok(const uint64_t *off, uint64_t strings, uint64_t bytes)
-{
-    for (uint64_t i = 0; i < strings; ++i)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ull << 31)) return false;
-    return off[strings] <= bytes;
-}
-} // namespace
-
 int bmx_edit_distance_batch_device(bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
                                    const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
                                    uint32_t *d_dist, void *stream_v)
 {
-    if (!ed_batch_args_ok(d_a, a_bytes, d_a_off, a_count, d_b, b_bytes, d_b_off, count, d_dist)) return BMX_ERR_ARG;
+    if (!bmx_ed_batch_args_ok(d_a, a_bytes, d_a_off, a_count, d_b, b_bytes, d_b_off, count, d_dist)) return BMX_ERR_ARG;
     if (count == 0) return BMX_OK;
     if (!ctx) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_ed_batch(&ctx->ed_batch, ctx, d_a, a_bytes, d_a_off, a_count, d_b, b_bytes, d_b_off, count, limit, d_dist,
                                  (hipStream_t)stream_v, g_err, sizeof g_err);
-}
-
-int bmx_edit_distance_batch(bmx_ctx *ctx_in, const void *a, uint64_t a_bytes, const uint64_t *a_off, uint64_t a_count,
-                            const void *b, uint64_t b_bytes, const uint64_t *b_off, uint64_t count, uint32_t limit, uint32_t *dist)
-{
-    if (!ed_batch_args_ok(a, a_bytes, a_off, a_count, b, b_bytes, b_off, count, dist)) return BMX_ERR_ARG;
-    if (count == 0) return BMX_OK;
-    if (!ed_batch_offsets_ok(a_off, a_count, a_bytes) || !ed_batch_offsets_ok(b_off, count, b_bytes)) return BMX_ERR_ARG;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_a = nullptr, *d_b = nullptr, *d_a_off = nullptr, *d_b_off = nullptr, *d_dist = nullptr;
-    int rc = BMX_OK;
-    if (a_bytes) rc = bmx_text_upload(ctx, (const char *)a, a_bytes, &d_a);
-    if (rc == BMX_OK && b_bytes) rc = bmx_text_upload(ctx, (const char *)b, b_bytes, &d_b);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)a_off, (a_count + 1) * sizeof(uint64_t), &d_a_off);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)b_off, (count + 1) * sizeof(uint64_t), &d_b_off);
-    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, count * sizeof(uint32_t), &d_dist);
-    if (rc == BMX_OK)
-        rc = bmx_edit_distance_batch_device(ctx, d_a, a_bytes, (const uint64_t *)d_a_off, a_count, d_b, b_bytes,
-                                            (const uint64_t *)d_b_off, count, limit, (uint32_t *)d_dist, nullptr);
-    if (rc == BMX_OK) {
-        hipError_t e = hipMemcpy(dist, d_dist, count * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of the distances: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-    }
-    for (void *p : {d_a, d_b, d_a_off, d_b_off, d_dist})
-        if (p) (void)hipFree(p);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
 }
 
 float bmx_last_ed_batch_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_ed_batch_ms(ctx->ed_batch) : -1.0f; }
@@ -1625,52 +1496,16 @@ int bmx_suffix_array_device(bmx_ctx *ctx, const void *d_text, uint64_t n, int32_
     return rc;
 }
 
-int bmx_suffix_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out)
-{
-    if ((n > 0 && (!text || !sa_out)) || n >= (1ull << 31)) return BMX_ERR_ARG;
-    if (n == 0) return BMX_OK;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr;
-    int32_t *d_sa = nullptr;
-    int rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, n * sizeof(int32_t), (void **)&d_sa);
-    if (rc == BMX_OK) rc = bmx_suffix_array_device(ctx, d_text, n, d_sa, nullptr);
-    if (rc == BMX_OK) {
-        hipError_t e = hipMemcpy(sa_out, d_sa, n * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of the suffix array: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-    }
-    if (d_sa) (void)hipFree(d_sa);
-    if (d_text) (void)hipFree(d_text);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-
 float bmx_last_suffix_array_ms(bmx_ctx *ctx) { return ctx ? ctx->sa_last_ms : -1.0f; }
 int bmx_last_suffix_array_rounds(bmx_ctx *ctx) { return ctx ? ctx->sa_last_rounds : 0; }
 int bmx_last_suffix_array_lds_rounds(bmx_ctx *ctx) { return ctx ? ctx->sa_last_lds_rounds : 0; }
 
 // ---- approximate search (bmx_approx.hip) -------------------------------------------------------
-namespace {
-// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
-bool approx_args_ok(uint64_t n, uint64_t lead, const char *pat, int32_t m, int32_t k, const void *ends, uint64_t capacity)
-{
-    return pat && m >= 1 && m <= BMX_MAX_APPROX_PATTERN && k >= 0 && k < m && lead <= n && n < (1ull << 40) &&
-           (capacity == 0 || ends);
-}
-} // namespace
-
 int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                              const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
                              uint64_t *n_matches, void *stream_v)
 {
-    if (!approx_args_ok(n, lead, pat, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    if (!bmx_approx_args_ok(n, lead, pat, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, pat, nullptr, m, k, d_ends, d_dist,
                                capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
@@ -1681,142 +1516,34 @@ int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t 
                                      const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,
                                      uint64_t capacity, uint64_t *n_matches, void *stream_v)
 {
-    if (!approx_args_ok(n, lead, (const char *)classes, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    if (!bmx_approx_args_ok(n, lead, classes, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, nullptr, classes, m, k, d_ends, d_dist,
                                capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
-namespace {
-// host buffers in, host buffers out, for a string (classes == NULL) or for classes (pat == NULL)
-int search_approx_host(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes, int32_t m, int32_t k,
-                       uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
-{
-    if (!approx_args_ok(n, 0, pat ? pat : (const char *)classes, m, k, ends, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
-    if (n_matches) *n_matches = 0;
-    if (n == 0) return BMX_OK;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr;
-    uint64_t *d_ends = nullptr;
-    uint8_t *d_dist = nullptr;
-    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
-    uint64_t total = 0;
-    int rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
-    if (rc == BMX_OK && dev_cap && dist) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
-    if (rc == BMX_OK)
-        rc = pat ? bmx_search_approx_device(ctx, d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr)
-                 : bmx_search_approx_classes_device(ctx, d_text, n, 0, 0, classes, m, k, d_ends, d_dist, dev_cap, &total, nullptr);
-    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
-        const uint64_t stored = std::min(total, dev_cap);
-        hipError_t e = hipSuccess;
-        if (stored) e = hipMemcpy(ends, d_ends, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (stored && dist && e == hipSuccess) e = hipMemcpy(dist, d_dist, stored, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of approximate matches: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-        if (n_matches) *n_matches = total;
-        if (rc == BMX_OK && total > capacity) rc = BMX_ERR_CAPACITY;
-    }
-    if (d_dist) (void)hipFree(d_dist);
-    if (d_ends) (void)hipFree(d_ends);
-    if (d_text) (void)hipFree(d_text);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-} // namespace
-
-int bmx_search_approx(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t *ends,
-                      uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
-{
-    if (!pat) return BMX_ERR_ARG;
-    return search_approx_host(ctx, text, n, pat, nullptr, m, k, ends, dist, capacity, n_matches);
-}
-
-int bmx_search_approx_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
-                              uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
-{
-    if (!classes) return BMX_ERR_ARG;
-    return search_approx_host(ctx, text, n, nullptr, classes, m, k, ends, dist, capacity, n_matches);
-}
-
 float bmx_last_approx_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_approx_ms(ctx->approx) : -1.0f; }
 
 // ---- class-pattern search (bmx_classes.hip; bmx_compile_classes is bmx_classes_compile.cpp) -----
-namespace {
-// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
-bool classes_args_ok(uint64_t n, const uint8_t *classes, int32_t m, const void *starts, uint64_t capacity)
-{
-    return classes && m >= 1 && m <= BMX_MAX_CLASS_PATTERN && n < (1ull << 40) && (capacity == 0 || starts);
-}
-} // namespace
-
 int bmx_search_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
                               const uint8_t *classes, int32_t m, uint64_t *d_match_positions, uint64_t capacity,
                               uint64_t *n_matches, void *stream_v)
 {
-    if (!classes_args_ok(n, classes, m, d_match_positions, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    if (!bmx_classes_args_ok(n, classes, m, d_match_positions, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_classes(&ctx->classes, ctx->num_cu, d_text, n, n_own, base_offset, classes, m, d_match_positions,
                                 capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
-}
-
-int bmx_search_classes(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
-                       uint64_t *match_positions, uint64_t capacity, uint64_t *n_matches)
-{
-    if (!classes_args_ok(n, classes, m, match_positions, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
-    if (n_matches) *n_matches = 0;
-    if (n < (uint64_t)m) return BMX_OK;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr;
-    uint64_t *d_starts = nullptr;
-    const uint64_t dev_cap = std::min<uint64_t>(capacity, n - (uint64_t)m + 1);
-    uint64_t total = 0;
-    int rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_starts);
-    if (rc == BMX_OK) rc = bmx_search_classes_device(ctx, d_text, n, n, 0, classes, m, d_starts, dev_cap, &total, nullptr);
-    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
-        const uint64_t stored = std::min(total, dev_cap);
-        if (stored && hipMemcpy(match_positions, d_starts, stored * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_err("download of class matches failed");
-            rc = BMX_ERR_HIP;
-        }
-        if (n_matches) *n_matches = total;
-        if (rc == BMX_OK && total > capacity) rc = BMX_ERR_CAPACITY;
-    }
-    if (d_starts) (void)hipFree(d_starts);
-    if (d_text) (void)hipFree(d_text);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
 }
 
 float bmx_last_classes_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_classes_ms(ctx->classes) : -1.0f; }
 
 // ---- match spans of the approximate search (bmx_spans.hip) --------------------------------------
 namespace {
-// every argument error, before any HIP call (the CPU suite calls these with ctx = NULL)
-bool spans_args_ok(uint64_t n, const void *pat, int32_t m, int32_t k, const uint64_t *ends, const uint8_t *dist, uint64_t count,
-                   uint32_t flags, const uint64_t *starts, const uint64_t *sel_ends)
-{
-    if (!pat || m < 1 || m > BMX_MAX_APPROX_PATTERN || k < 0 || k >= m || n >= (1ull << 40) || (flags & ~BMX_SPANS_BEST)) return false;
-    if (count == 0) return true;
-    return ends && starts && (flags == 0 || (dist && sel_ends));
-}
-
 int spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, const uint8_t *classes,
                  int32_t m, int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
                  uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, void *stream_v)
 {
-    if (!spans_args_ok(n, pat ? (const void *)pat : (const void *)classes, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends))
+    if (!bmx_spans_args_ok(n, pat ? (const void *)pat : (const void *)classes, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends))
         return BMX_ERR_ARG;
     if (n_spans) *n_spans = 0;
     if (count == 0) return BMX_OK;
@@ -1846,108 +1573,12 @@ int bmx_approx_spans_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n
                         d_sel_dist, n_spans, stream_v);
 }
 
-namespace {
-// host buffers in, host buffers out, for a string (classes == NULL) or for classes (pat == NULL)
-int search_spans_host(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes, int32_t m, int32_t k,
-                      uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_spans)
-{
-    if (!approx_args_ok(n, 0, pat ? pat : (const char *)classes, m, k, ends, capacity) || (flags & ~BMX_SPANS_BEST) ||
-        (capacity && !starts) || (n > 0 && !text))
-        return BMX_ERR_ARG;
-    if (n_spans) *n_spans = 0;
-    if (n == 0) return BMX_OK;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr;
-    uint64_t *d_ends = nullptr, *d_starts = nullptr, *d_sel_ends = nullptr;
-    uint8_t *d_dist = nullptr, *d_sel_dist = nullptr;
-    uint64_t total = 0, spans = 0;
-    auto search = [&](uint64_t cap) {
-        return pat ? bmx_search_approx_device(ctx, d_text, n, 0, 0, pat, m, k, d_ends, d_dist, cap, &total, nullptr)
-                   : bmx_search_approx_classes_device(ctx, d_text, n, 0, 0, classes, m, k, d_ends, d_dist, cap, &total, nullptr);
-    };
-    int rc = bmx_text_upload(ctx, text, n, &d_text);
-    // counting only if `capacity` cannot hold a single end; else in one go if it holds them all
-    uint64_t dev_cap = std::min<uint64_t>(capacity, n);
-    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
-    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
-    if (rc == BMX_OK) rc = search(dev_cap);
-    if (rc == BMX_ERR_CAPACITY) { // again, with room for all ends
-        if (d_ends) (void)hipFree(d_ends);
-        if (d_dist) (void)hipFree(d_dist);
-        d_ends = nullptr, d_dist = nullptr;
-        dev_cap = total;
-        rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_ends);
-        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, dev_cap, (void **)&d_dist);
-        if (rc == BMX_OK) rc = search(dev_cap);
-    }
-    if (rc == BMX_OK && total) {
-        rc = bmx_device_alloc(ctx, total * sizeof(uint64_t), (void **)&d_starts);
-        if (rc == BMX_OK && flags) rc = bmx_device_alloc(ctx, total * sizeof(uint64_t), (void **)&d_sel_ends);
-        if (rc == BMX_OK && flags) rc = bmx_device_alloc(ctx, total, (void **)&d_sel_dist);
-        if (rc == BMX_OK)
-            rc = spans_device(ctx, d_text, n, 0, pat, classes, m, k, d_ends, d_dist, total, flags, d_starts, d_sel_ends, d_sel_dist,
-                              &spans, nullptr);
-    }
-    if (rc == BMX_OK) {
-        const uint64_t stored = std::min(spans, capacity);
-        hipError_t e = hipSuccess;
-        if (stored) e = hipMemcpy(starts, d_starts, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (stored && e == hipSuccess) e = hipMemcpy(ends, flags ? d_sel_ends : d_ends, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (stored && dist && e == hipSuccess) e = hipMemcpy(dist, flags ? d_sel_dist : d_dist, stored, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of match spans: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-        if (n_spans) *n_spans = spans;
-        if (rc == BMX_OK && spans > capacity) rc = BMX_ERR_CAPACITY;
-    }
-    for (void *p : {(void *)d_sel_dist, (void *)d_sel_ends, (void *)d_starts, (void *)d_dist, (void *)d_ends, d_text})
-        if (p) (void)hipFree(p);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-} // namespace
-
-int bmx_search_approx_spans(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint32_t flags,
-                            uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_spans)
-{
-    if (!pat) return BMX_ERR_ARG;
-    return search_spans_host(ctx, text, n, pat, nullptr, m, k, flags, starts, ends, dist, capacity, n_spans);
-}
-
-int bmx_search_approx_spans_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
-                                    uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
-                                    uint64_t *n_spans)
-{
-    if (!classes) return BMX_ERR_ARG;
-    return search_spans_host(ctx, text, n, nullptr, classes, m, k, flags, starts, ends, dist, capacity, n_spans);
-}
-
 float bmx_last_spans_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_spans_ms(ctx->spans) : -1.0f; }
 
 // ---- dictionary search (bmx_dict.hip) ----------------------------------------------------------
-namespace {
-// the patterns, before any HIP call: BMX_ERR_ARG for NULL arrays or a count or length out of range, BMX_ERR_DOMAIN for a
-// byte >= 0x80 (as bmx_build_tables)
-int dict_patterns_ok(const char *const *pats, const int32_t *ms, int32_t K)
-{
-    if (!pats || !ms || K < 1 || K > BMX_MAX_DICT) return BMX_ERR_ARG;
-    for (int32_t i = 0; i < K; ++i)
-        if (!pats[i] || ms[i] < 1 || ms[i] > BMX_MAX_PATTERN) return BMX_ERR_ARG;
-    for (int32_t i = 0; i < K; ++i)
-        for (int32_t j = 0; j < ms[i]; ++j)
-            if ((uint8_t)pats[i][j] >= 0x80) return BMX_ERR_DOMAIN;
-    return BMX_OK;
-}
-} // namespace
-
 int bmx_dict_create(bmx_ctx *ctx, const char *const *pats, const int32_t *ms, int32_t K, bmx_dict **out)
 {
-    const int rc = dict_patterns_ok(pats, ms, K);
+    const int rc = bmx_dict_patterns_ok(pats, ms, K);
     if (rc != BMX_OK) return rc;
     if (!ctx || !out) return BMX_ERR_ARG;
     *out = nullptr;
@@ -1969,72 +1600,11 @@ int bmx_dict_search_device(bmx_ctx *ctx, const bmx_dict *d, const void *d_text, 
                                     n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
-int bmx_dict_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *const *pats, const int32_t *ms, int32_t K,
-                    uint64_t *pos, uint32_t *pid, uint64_t capacity, uint64_t *n_matches)
-{
-    int rc = dict_patterns_ok(pats, ms, K);
-    if (rc != BMX_OK) return rc;
-    if ((n > 0 && !text) || n >= (1ull << 40) || (capacity > 0 && !pos)) return BMX_ERR_ARG;
-    if (n_matches) *n_matches = 0;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    bmx_dict *d = nullptr;
-    void *d_text = nullptr;
-    uint64_t *d_pos = nullptr;
-    uint32_t *d_pid = nullptr;
-    uint64_t total = 0;
-    rc = bmx_dict_create(ctx, pats, ms, K, &d);
-    if (rc == BMX_OK && n) rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK && capacity) rc = bmx_device_alloc(ctx, capacity * sizeof(uint64_t), (void **)&d_pos);
-    if (rc == BMX_OK && capacity && pid) rc = bmx_device_alloc(ctx, capacity * sizeof(uint32_t), (void **)&d_pid);
-    if (rc == BMX_OK) rc = bmx_dict_search_device(ctx, d, d_text, n, n, 0, d_pos, d_pid, capacity, &total, nullptr);
-    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
-        const uint64_t stored = std::min(total, capacity);
-        hipError_t e = hipSuccess;
-        if (stored) e = hipMemcpy(pos, d_pos, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (stored && pid && e == hipSuccess) e = hipMemcpy(pid, d_pid, stored * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of dictionary matches: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-        if (n_matches) *n_matches = total;
-    }
-    if (d_pid) (void)hipFree(d_pid);
-    if (d_pos) (void)hipFree(d_pos);
-    if (d_text) (void)hipFree(d_text);
-    bmx_dict_destroy(d);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-
 float bmx_last_dict_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_dict_ms(ctx->dict) : -1.0f; }
 
 int64_t bmx_last_dict_candidates(bmx_ctx *ctx) { return ctx ? bmx_internal_dict_candidates(ctx->dict) : -1; }
 
 // ---- text index (bmx_index.hip) ------------------------------------------------------------------
-namespace {
-// every argument error of a query call, before any HIP call (the CPU suite calls these with ctx = NULL)
-bool index_query_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, const void *out)
-{
-    return count == 0 || (pat && pat_off && out);
-}
-// the host entry's queries: BMX_ERR_ARG for offsets that decrease or end past the blob and for a length of 0 or above
-// BMX_MAX_PATTERN, BMX_ERR_DOMAIN for a byte >= 0x80
-int index_queries_ok(const void *pat, uint64_t pat_bytes, const uint64_t *off, uint64_t count)
-{
-    for (uint64_t i = 0; i < count; ++i)
-        if (off[i + 1] < off[i] || off[i + 1] > pat_bytes || off[i + 1] == off[i] || off[i + 1] - off[i] > BMX_MAX_PATTERN)
-            return BMX_ERR_ARG;
-    const uint8_t *p = static_cast<const uint8_t *>(pat);
-    for (uint64_t j = off[0]; j < off[count]; ++j)
-        if (p[j] >= 0x80) return BMX_ERR_DOMAIN;
-    return BMX_OK;
-}
-} // namespace
-
 int bmx_index_create_device(bmx_ctx *ctx, const void *d_text, uint64_t n, const int32_t *d_sa, void *stream_v, bmx_index **out)
 {
     if (!ctx || !d_text || !out || n == 0 || n >= (1ull << 31)) return BMX_ERR_ARG;
@@ -2058,7 +1628,7 @@ float bmx_index_build_ms(const bmx_index *ix) { return ix ? bmx_internal_index_b
 int bmx_index_count_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
                            uint64_t count, uint32_t *d_lo, uint32_t *d_cnt, void *stream_v)
 {
-    if (!index_query_args_ok(d_pat, d_pat_off, count, d_cnt)) return BMX_ERR_ARG;
+    if (!bmx_index_query_args_ok(d_pat, d_pat_off, count, d_cnt)) return BMX_ERR_ARG;
     if (count == 0) return BMX_OK;
     if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2070,92 +1640,13 @@ int bmx_index_locate_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat
                             uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos, uint64_t capacity,
                             uint64_t *n_matches, void *stream_v)
 {
-    if (!index_query_args_ok(d_pat, d_pat_off, count, d_out_off) || (count > 0 && capacity > 0 && !d_pos)) return BMX_ERR_ARG;
+    if (!bmx_index_query_args_ok(d_pat, d_pat_off, count, d_out_off) || (count > 0 && capacity > 0 && !d_pos)) return BMX_ERR_ARG;
     if (n_matches) *n_matches = 0;
     if (count == 0) return BMX_OK;
     if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_index_locate(&ctx->index, ix, d_pat, pat_bytes, d_pat_off, count, base_offset, d_out_off, d_pos, capacity,
                                      n_matches, !ctx->index_no_dir, (hipStream_t)stream_v, g_err, sizeof g_err);
-}
-
-int bmx_index_count(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
-                    uint64_t count, uint32_t *cnt)
-{
-    if (!text || n == 0 || n >= (1ull << 31) || !index_query_args_ok(pat, pat_off, count, cnt)) return BMX_ERR_ARG;
-    if (count == 0) return BMX_OK;
-    int rc = index_queries_ok(pat, pat_bytes, pat_off, count);
-    if (rc != BMX_OK) return rc;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr, *d_pat = nullptr, *d_off = nullptr, *d_cnt = nullptr;
-    bmx_index *ix = nullptr;
-    rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat, pat_bytes, &d_pat);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat_off, (count + 1) * sizeof(uint64_t), &d_off);
-    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, count * sizeof(uint32_t), &d_cnt);
-    if (rc == BMX_OK) rc = bmx_index_create_device(ctx, d_text, n, nullptr, nullptr, &ix);
-    if (rc == BMX_OK)
-        rc = bmx_index_count_device(ctx, ix, d_pat, pat_bytes, (const uint64_t *)d_off, count, nullptr, (uint32_t *)d_cnt, nullptr);
-    if (rc == BMX_OK) {
-        hipError_t e = hipMemcpy(cnt, d_cnt, count * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of the counts: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-    }
-    bmx_index_destroy(ix);
-    for (void *p : {d_text, d_pat, d_off, d_cnt})
-        if (p) (void)hipFree(p);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-
-int bmx_index_locate(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
-                     uint64_t count, uint64_t *out_off, uint64_t *pos, uint64_t capacity, uint64_t *n_matches)
-{
-    if (!text || n == 0 || n >= (1ull << 31) || !index_query_args_ok(pat, pat_off, count, out_off) ||
-        (count > 0 && capacity > 0 && !pos))
-        return BMX_ERR_ARG;
-    if (n_matches) *n_matches = 0;
-    if (count == 0) return BMX_OK;
-    int rc = index_queries_ok(pat, pat_bytes, pat_off, count);
-    if (rc != BMX_OK) return rc;
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr, *d_pat = nullptr, *d_off = nullptr, *d_out_off = nullptr, *d_pos = nullptr;
-    bmx_index *ix = nullptr;
-    uint64_t total = 0;
-    rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat, pat_bytes, &d_pat);
-    if (rc == BMX_OK) rc = bmx_text_upload(ctx, (const char *)pat_off, (count + 1) * sizeof(uint64_t), &d_off);
-    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, (count + 1) * sizeof(uint64_t), &d_out_off);
-    if (rc == BMX_OK && capacity) rc = bmx_device_alloc(ctx, capacity * sizeof(uint64_t), &d_pos);
-    if (rc == BMX_OK) rc = bmx_index_create_device(ctx, d_text, n, nullptr, nullptr, &ix);
-    if (rc == BMX_OK)
-        rc = bmx_index_locate_device(ctx, ix, d_pat, pat_bytes, (const uint64_t *)d_off, count, 0, (uint64_t *)d_out_off,
-                                     (uint64_t *)d_pos, capacity, &total, nullptr);
-    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
-        hipError_t e = hipMemcpy(out_off, d_out_off, (count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        const uint64_t stored = std::min(total, capacity); // (behind the stored segments: unspecified, as in the device entry)
-        if (e == hipSuccess && stored) e = hipMemcpy(pos, d_pos, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_err("download of the positions: %s", hipGetErrorString(e));
-            rc = BMX_ERR_HIP;
-        }
-        if (n_matches) *n_matches = total;
-    }
-    bmx_index_destroy(ix);
-    for (void *p : {d_text, d_pat, d_off, d_out_off, d_pos})
-        if (p) (void)hipFree(p);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
 }
 
 float bmx_last_index_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_index_ms(ctx->index) : -1.0f; }
@@ -2193,93 +1684,6 @@ int bmx_text_upload(bmx_ctx *ctx, const char *text, uint64_t n, void **d_text_ou
     return BMX_OK;
 }
 
-int bmx_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, int32_t m,
-               uint64_t *match_positions, uint64_t capacity, uint64_t *n_matches)
-{
-    if (!pat || m < 1 || m > BMX_MAX_PATTERN || (n > 0 && !text)) return BMX_ERR_ARG;
-    if (capacity > 0 && !match_positions) return BMX_ERR_ARG;
-    if (n_matches) *n_matches = 0;
-    // table errors (pattern outside the ASCII domain) before any device work
-    {
-        int32_t bad[BMX_BAD_TABLE_SIZE];
-        std::vector<int32_t> good(m);
-        int rc = bmx_build_tables(pat, m, bad, good.data());
-        if (rc != BMX_OK) return rc;
-    }
-    if (n < (uint64_t)m) return BMX_OK;
-
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr;
-    uint64_t *d_out = nullptr;
-    const uint64_t dev_cap = std::min<uint64_t>(capacity, n - (uint64_t)m + 1);
-    uint64_t total = 0;
-    int rc = bmx_text_upload(ctx, text, n, &d_text);
-    if (rc == BMX_OK && dev_cap) rc = bmx_device_alloc(ctx, dev_cap * sizeof(uint64_t), (void **)&d_out);
-    if (rc == BMX_OK)
-        rc = bmx_search_device(ctx, d_text, n, n, 0, pat, m, nullptr, nullptr, d_out, dev_cap, &total, nullptr);
-    if (rc == BMX_OK || rc == BMX_ERR_CAPACITY) {
-        const uint64_t stored = std::min(total, dev_cap);
-        if (stored) {
-            hipError_t e = hipMemcpy(match_positions, d_out, stored * sizeof(uint64_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) {
-                set_err("download of matches: %s", hipGetErrorString(e));
-                rc = BMX_ERR_HIP;
-            }
-        }
-        if (n_matches) *n_matches = total;
-        if (rc == BMX_OK && total > capacity) rc = BMX_ERR_CAPACITY;
-    }
-    if (d_out) (void)hipFree(d_out);
-    if (d_text) (void)hipFree(d_text);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-
-// (bmx_search_multi and the resident multi-GPU search with its RCCL exchange: bmx_multi.hip)
-
-int bmx_search_ranges(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const int32_t *se,
-                      int32_t P, int32_t *ans, const int32_t *good, const int32_t *bad, int32_t m)
-{
-    if (!text || !pat || !se || !ans || P < 0 || m < 1 || m > BMX_MAX_PATTERN) return BMX_ERR_ARG;
-    if ((good == nullptr) != (bad == nullptr)) return BMX_ERR_ARG;
-    for (int r = 0; r < P; ++r) {
-        ans[r] = 0;
-        const int64_t s = se[2 * r], e = se[2 * r + 1];
-        if (s < 0 || (e >= s && (uint64_t)e >= n)) return BMX_ERR_ARG;
-    }
-    if (!good) {
-        int32_t tb[BMX_BAD_TABLE_SIZE];
-        std::vector<int32_t> tg(m);
-        int rc = bmx_build_tables(pat, m, tb, tg.data());
-        if (rc != BMX_OK) return rc;
-    }
-    bmx_ctx *ctx = ctx_in;
-    if (!ctx) {
-        int rc = bmx_ctx_create(0, &ctx);
-        if (rc != BMX_OK) return rc;
-    }
-    void *d_text = nullptr;
-    int rc = bmx_text_upload(ctx, text, n, &d_text);
-    for (int r = 0; r < P && rc == BMX_OK; ++r) {
-        const int64_t s = se[2 * r], e = se[2 * r + 1];
-        if (e < s) continue;
-        // inclusive range [s, e] as in kernel1.cl:14-19: windows wholly inside it
-        const uint64_t len = (uint64_t)(e - s) + 1;
-        uint64_t total = 0;
-        rc = bmx_search_device(ctx, (const char *)d_text + s, len, len, (uint64_t)s, pat, m, good, bad, nullptr,
-                               0, &total, nullptr);
-        if (rc == BMX_ERR_CAPACITY) rc = BMX_OK; // (a count-only call: the total is all it asks for)
-        ans[r] = (int32_t)total;
-    }
-    if (d_text) (void)hipFree(d_text);
-    if (!ctx_in) bmx_ctx_destroy(ctx);
-    return rc;
-}
-
 #ifdef BMX_EXPERIMENTS
 // libbmx_exp.so only: the measurement / test switches of a context (round 2 read them from the environment on every call,
 // in the product library too).  Returns BMX_ERR_ARG for an unknown name.
@@ -2304,7 +1708,9 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "ed_stamp_block") ctx->ed_stamp_block = value;
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
-    else return BMX_ERR_ARG;
+    else if (k == "ordered_seq" && value >= 0) {
+        for (void *session : {ctx->approx, ctx->classes, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+    } else return BMX_ERR_ARG;
     return BMX_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "bmx.h"
+#include "bmx_internal.h"
 
 // end_bit: the keys are < 2^end_bit (a match position is below base offset + text length: 33 bits for 4 GiB, where all 64 cost
 // eight passes instead of five).  *scratch / *scratch_bytes: the caller's (the context's) buffer for the second key array and

@@ -10,10 +10,13 @@
 
 #include "bmx.h"
 #include "bmx_spans_kernel.h"
+#include "bmx_internal.h"
 
 static_assert(sizeof(bmx::SpansArgs) <= 4096, "kernel arguments");
 
 namespace {
+
+constexpr const char *WHERE = "bmx_approx_spans_device";
 
 struct SpansHost {
     uint64_t *d_ws = nullptr;    // {status bits, kept entries}
@@ -25,15 +28,6 @@ struct SpansHost {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the selection's first two kernels, around the rest
     float last_ms = -1.0f;
 };
-
-#define SHIP(expr)                                                                                            \
-    do {                                                                                                      \
-        hipError_t e__ = (expr);                                                                              \
-        if (e__ != hipSuccess) {                                                                              \
-            snprintf(err, errlen, "bmx_approx_spans_device: %s failed: %s", #expr, hipGetErrorString(e__)); \
-            return BMX_ERR_HIP;                                                                               \
-        }                                                                                                     \
-    } while (0)
 
 } // namespace
 
@@ -72,11 +66,11 @@ int bmx_internal_spans(void **state_v, const void *d_text, uint64_t n, uint64_t 
         snprintf(err, errlen, "bmx_approx_spans_device: more than 2^31 workgroups of list entries in one call");
         return BMX_ERR_ARG;
     }
-    if (!st->d_ws) SHIP(hipMalloc(&st->d_ws, 2 * sizeof(uint64_t)));
-    if (!st->h_ws) SHIP(hipHostMalloc(&st->h_ws, 2 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!st->d_ws) BMX_HIP(WHERE, hipMalloc(&st->d_ws, 2 * sizeof(uint64_t)));
+    if (!st->h_ws) BMX_HIP(WHERE, hipHostMalloc(&st->h_ws, 2 * sizeof(uint64_t), hipHostMallocDefault));
     for (hipEvent_t &e : st->ev)
-        if (!e) SHIP(hipEventCreate(&e));
-    SHIP(hipMemsetAsync(st->d_ws, 0, 2 * sizeof(uint64_t), stream)); // the status word starts clean in every call
+        if (!e) BMX_HIP(WHERE, hipEventCreate(&e));
+    BMX_HIP(WHERE, hipMemsetAsync(st->d_ws, 0, 2 * sizeof(uint64_t), stream)); // the status word starts clean in every call
 
     const uint64_t *list_ends = d_ends;
     const uint8_t *list_dist = d_dist;
@@ -89,7 +83,7 @@ int bmx_internal_spans(void **state_v, const void *d_text, uint64_t n, uint64_t 
             st->d_tiles = nullptr;
             st->tiles_cap = 0;
             const uint64_t cap = std::max<uint64_t>(n_tiles, 1024);
-            SHIP(hipMalloc(&st->d_tiles, cap * sizeof(uint64_t)));
+            BMX_HIP(WHERE, hipMalloc(&st->d_tiles, cap * sizeof(uint64_t)));
             st->tiles_cap = cap;
         }
         bmx::SpansSelectArgs s = {};
@@ -98,15 +92,15 @@ int bmx_internal_spans(void **state_v, const void *d_text, uint64_t n, uint64_t 
         s.count = count;
         s.k = (uint32_t)k;
         s.tiles = st->d_tiles;
-        SHIP(hipEventRecord(st->ev[0], stream));
+        BMX_HIP(WHERE, hipEventRecord(st->ev[0], stream));
         hipLaunchKernelGGL(bmx::spans_select_kernel<false>, dim3((uint32_t)n_tiles), dim3(bmx::SPANS_BLOCK), 0, stream, s);
-        SHIP(hipGetLastError());
+        BMX_HIP(WHERE, hipGetLastError());
         hipLaunchKernelGGL(bmx::spans_scan_kernel, dim3(1), dim3(bmx::SPANS_SCAN_BLOCK), 0, stream, st->d_tiles, n_tiles,
                            st->d_ws + 1);
-        SHIP(hipGetLastError());
-        SHIP(hipEventRecord(st->ev[1], stream));
-        SHIP(hipMemcpyAsync(st->h_ws, st->d_ws, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SHIP(hipStreamSynchronize(stream)); // the kept count sizes the rest
+        BMX_HIP(WHERE, hipGetLastError());
+        BMX_HIP(WHERE, hipEventRecord(st->ev[1], stream));
+        BMX_HIP(WHERE, hipMemcpyAsync(st->h_ws, st->d_ws, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        BMX_HIP(WHERE, hipStreamSynchronize(stream)); // the kept count sizes the rest
         if (hipEventElapsedTime(&ms_select, st->ev[0], st->ev[1]) != hipSuccess) ms_select = 0.0f;
         list_count = st->h_ws[1];
         if (list_count > count) {
@@ -124,20 +118,20 @@ int bmx_internal_spans(void **state_v, const void *d_text, uint64_t n, uint64_t 
                 st->d_sel_dist = nullptr;
                 st->sel_dist_cap = 0;
                 const uint64_t cap = std::max<uint64_t>(list_count, 1 << 16);
-                SHIP(hipMalloc(&st->d_sel_dist, cap));
+                BMX_HIP(WHERE, hipMalloc(&st->d_sel_dist, cap));
                 st->sel_dist_cap = cap;
             }
             d_sel_dist = st->d_sel_dist;
         }
         s.sel_ends = d_sel_ends;
         s.sel_dist = d_sel_dist;
-        SHIP(hipEventRecord(st->ev[2], stream));
+        BMX_HIP(WHERE, hipEventRecord(st->ev[2], stream));
         hipLaunchKernelGGL(bmx::spans_select_kernel<true>, dim3((uint32_t)n_tiles), dim3(bmx::SPANS_BLOCK), 0, stream, s);
-        SHIP(hipGetLastError());
+        BMX_HIP(WHERE, hipGetLastError());
         list_ends = d_sel_ends;
         list_dist = d_sel_dist;
     } else {
-        SHIP(hipEventRecord(st->ev[2], stream));
+        BMX_HIP(WHERE, hipEventRecord(st->ev[2], stream));
     }
 
     const uint64_t addr = reinterpret_cast<uint64_t>(d_text);
@@ -166,10 +160,10 @@ int bmx_internal_spans(void **state_v, const void *d_text, uint64_t n, uint64_t 
     void (*kernel)(const bmx::SpansArgs) = m > 32 ? bmx::spans_starts_kernel<uint64_t> : bmx::spans_starts_kernel<uint32_t>;
     const uint64_t n_blocks = (list_count + bmx::SPANS_BLOCK - 1) / bmx::SPANS_BLOCK;
     hipLaunchKernelGGL(kernel, dim3((uint32_t)n_blocks), dim3(bmx::SPANS_BLOCK), 0, stream, a);
-    SHIP(hipGetLastError());
-    SHIP(hipEventRecord(st->ev[3], stream));
-    SHIP(hipMemcpyAsync(st->h_ws, st->d_ws, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SHIP(hipStreamSynchronize(stream));
+    BMX_HIP(WHERE, hipGetLastError());
+    BMX_HIP(WHERE, hipEventRecord(st->ev[3], stream));
+    BMX_HIP(WHERE, hipMemcpyAsync(st->h_ws, st->d_ws, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(WHERE, hipStreamSynchronize(stream));
     float ms_rest = 0.0f;
     if (hipEventElapsedTime(&ms_rest, st->ev[2], st->ev[3]) == hipSuccess) st->last_ms = ms_select + ms_rest;
 

@@ -426,3 +426,69 @@ def test_two_host_threads_each_with_its_own_context_and_streams(ctx, port):
         assert q.done == len(sc.SEQUENCE)
     for q in seqs:
         q.close()
+
+
+# ---- the wrap of the status words' 22-bit tag ----------------------------------------------------------------------------
+
+WRAP_N = 128 << 10  # 8 tiles of the approximate and the class-pattern search, 16 of the dictionary search
+WRAP_PATTERN = b"ACG"
+
+
+def _wrap_search(c, kind):
+    """text -> None: one search of `kind` on context c, its whole list compared with the Python oracle."""
+    import torch
+
+    import classes_oracle as co
+    from approx_oracle import approx_ends
+    from dict_oracle import dict_matches
+
+    def dev(text):
+        return torch.from_numpy(np.frombuffer(text, np.uint8).copy()).to(f"cuda:{c.device}")
+
+    def same(got, want, what):
+        assert np.array_equal(got.cpu().numpy().astype(np.int64), want), (kind, what)
+
+    if kind == "approx":
+        def search(text):
+            want_e, want_d = approx_ends(text, WRAP_PATTERN, 1)
+            e, d, total = c.search_approx_device(dev(text), WRAP_PATTERN, 1, capacity=len(text))
+            assert total == want_e.size > 1000
+            same(e, want_e, "ends"), same(d, want_d, "distances")
+        return search, lambda: None
+    if kind == "classes":
+        member = co.singletons(WRAP_PATTERN)
+
+        def search(text):
+            want = co.class_starts(text, member)
+            pos, total = c.search_classes_device(dev(text), co.pack(member), capacity=len(text))
+            assert total == want.size > 1000
+            same(pos, want, "starts")
+        return search, lambda: None
+    d = c.dictionary([WRAP_PATTERN])
+
+    def search(text):
+        want_p, want_i = dict_matches(text, [WRAP_PATTERN])
+        pos, pid, total = d.search_device(dev(text), capacity=len(text))
+        assert total == want_p.size > 1000
+        same(pos, want_p, "positions"), same(pid, want_i, "pattern ids")
+    return search, d.close
+
+
+@pytest.mark.parametrize("kind", ["approx", "classes", "dict"])
+def test_tag_wrap_clears_the_status_words(exp_ctx, kind):
+    """The status words of an ordered-output session carry the call's sequence number mod 2^22 and are cleared only when
+    that tag wraps.  The first search leaves a tag-1 prefix in every word; "ordered_seq" then puts the next call on the
+    wrap, so it takes tag 1 again: without the clear its tiles would read the first search's prefixes as their
+    predecessors' (a wrong list, or BMX_ERR_HIP from the bounded wait -- never a hang)."""
+    rng = np.random.default_rng(0x7A6)
+    texts = [np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, WRAP_N)].tobytes() for _ in range(3)]
+    search, close = _wrap_search(exp_ctx, kind)
+    try:
+        search(texts[0])
+        with pytest.raises(host.BmxError):  # (BMX_ERR_ARG, as for an unknown name)
+            exp_ctx.set_knob("ordered_seq", -1)
+        exp_ctx.set_knob("ordered_seq", (1 << 22) - 1)
+        search(texts[1])
+        search(texts[2])
+    finally:
+        close()
