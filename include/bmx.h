@@ -297,7 +297,7 @@ int bmx_edit_distance(bmx_ctx *ctx, const char *a, uint64_t la, const char *b, u
                       uint64_t *distance);
 int bmx_edit_distance_device(bmx_ctx *ctx, const void *d_a, uint64_t la, const void *d_b, uint64_t lb,
                              uint64_t *distance, void *stream);
-/* Device time (ms, HIP events around the kernels) of the last call. */
+/* Device time (ms, HIP events around the kernels) of the last call; -1 if it ran none. */
 float bmx_last_edit_distance_ms(bmx_ctx *ctx);
 /* Schedule, for experiments: 0 = the library's choice (one launch: a pipeline of bit-parallel
  * column bands of 2,048 columns from both corners of the table, a band = a workgroup of four waves,
@@ -305,7 +305,9 @@ float bmx_last_edit_distance_ms(bmx_ctx *ctx);
  * shapes; 8..10 = the first bit-parallel band, 1 / 2 / 4 rows per step; 11, 12 = one wave per
  * band with everything but the recurrence out of the step; +32 = one launch per pair of tile
  * diagonals from both corners; +16 = one launch per tile diagonal from the top-left corner only.
- * Every schedule returns the same distance. */
+ * Every schedule returns the same distance.  The slot numbers are stable, and bmx_set_variant's rule
+ * holds: libbmx.so builds 0 and 13 (the same schedule) with their +16 / +32 tiles and refuses
+ * every other value with BMX_ERR_ARG; the schedules that lost exist in libbmx_exp.so alone. */
 int bmx_set_ed_variant(bmx_ctx *ctx, int variant);
 
 /* ---- batched edit distance: many string pairs in one call ------------------------------------ */

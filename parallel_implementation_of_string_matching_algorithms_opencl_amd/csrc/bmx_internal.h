@@ -36,9 +36,28 @@ void bmx_internal_set_error(const char *text);
 // bmx_sort.hip
 int bmx_internal_radix_sort(uint64_t *d_keys, uint64_t n, unsigned end_bit, void **scratch, size_t *scratch_bytes, hipStream_t stream,
                             char *err, size_t errlen);
-// bmx_sa.hip
-int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, float *ms_out,
-                              int *rounds_out, void **ws, size_t *ws_bytes, uint32_t **pinned, int flags, char *err, size_t errlen);
+// bmx_sa.hip (flags: 1 = library rounds only, 2 = a host wait per round, 4 = per-round trace on stderr)
+int bmx_internal_suffix_array(void **state, const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, int flags, char *err,
+                              size_t errlen);
+void bmx_internal_sa_free(void *state);
+float bmx_internal_sa_ms(const void *state);
+int bmx_internal_sa_rounds(const void *state);
+int bmx_internal_sa_lds_rounds(const void *state);
+// bmx_ed.hip: the single-pair edit distance.  What bmx_set_ed_variant and (libbmx_exp.so) bmx_exp_set_knob set:
+struct bmx_ed_knobs {
+    int variant = 0;      // schedule (include/bmx.h, bmx_set_ed_variant)
+    int lag = -1;         // rows a band is assumed to trail its predecessor by (< 0: the schedule's measured one)
+    int group = 32;       // hand-over group of the band pipeline (16 or 32 rows)
+    int stamp_block = -1; // the band whose cycle counts bmx_exp_ed_stamps returns (< 0: the middle forward band)
+    int step_x = 0;       // timing experiment on the helper-wave band's step (index into g_ed_step_experiments)
+};
+int bmx_internal_ed(void **state, const bmx_ed_knobs *knobs, const void *d_a, uint64_t la, const void *d_b, uint64_t lb,
+                    uint64_t *distance, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_ed_free(void *state);
+float bmx_internal_ed_ms(const void *state);
+void bmx_internal_ed_no_kernel(void *state); // a call the shim answered itself (an empty string): the last ms is -1 again
+bool bmx_internal_ed_variant_ok(int variant); // what bmx_set_ed_variant accepts in THIS library
+int bmx_internal_ed_stamps(const void *state, uint64_t *out280); // libbmx_exp.so only
 // bmx_approx.hip
 int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                         const char *pat, const uint8_t *classes, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist,

@@ -489,16 +489,39 @@ __global__ __launch_bounds__(SEG_T, SEG_LOGK == 3 ? 8 : 4) void sa_segsort_kerne
     }
 }
 
+constexpr size_t SA_WS_KEEP = (size_t)1 << 30; // a workspace up to this size stays in the state between calls
+
+struct SaHost {
+    void *ws = nullptr; // kept between calls (eight hipMalloc + hipFree per call cost 2 ms next to a 6 ms construction)
+    size_t ws_bytes = 0;
+    uint32_t *pinned = nullptr; // pinned host block the queued LDS rounds report into (allocated on first use)
+    float last_ms = -1.0f;
+    int last_rounds = 0, last_lds_rounds = 0;
+};
+
 } // namespace
 
-// d_sa[j] = start of the j-th suffix in the reference's order.  Returns BMX_OK / BMX_ERR_HIP.
-// *ws / *ws_bytes: the caller's workspace slot (the context keeps it between calls: eight hipMalloc +
-// hipFree per call cost 2 ms next to a 6 ms construction); grown here when too small.
-int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, float *ms_out,
-                              int *rounds_out, void **ws, size_t *ws_bytes, uint32_t **pinned, int switches, char *err, size_t errlen)
+void bmx_internal_sa_free(void *state_v)
 {
-    if (ms_out) *ms_out = -1.0f;
-    if (rounds_out) *rounds_out = 0;
+    SaHost *st = static_cast<SaHost *>(state_v);
+    if (!st) return;
+    if (st->ws) (void)hipFree(st->ws);
+    if (st->pinned) (void)hipHostFree(st->pinned);
+    delete st;
+}
+
+float bmx_internal_sa_ms(const void *state_v) { return state_v ? static_cast<const SaHost *>(state_v)->last_ms : -1.0f; }
+int bmx_internal_sa_rounds(const void *state_v) { return state_v ? static_cast<const SaHost *>(state_v)->last_rounds : 0; }
+int bmx_internal_sa_lds_rounds(const void *state_v) { return state_v ? static_cast<const SaHost *>(state_v)->last_lds_rounds : 0; }
+
+// d_sa[j] = start of the j-th suffix in the reference's order.  Returns BMX_OK / BMX_ERR_HIP.
+int bmx_internal_suffix_array(void **state_v, const uint8_t *d_text, uint32_t n, int32_t *d_sa, hipStream_t stream, int switches,
+                              char *err, size_t errlen)
+{
+    if (!*state_v) *state_v = new SaHost();
+    SaHost *st = static_cast<SaHost *>(*state_v);
+    st->last_ms = -1.0f;
+    st->last_rounds = st->last_lds_rounds = 0;
     if (n == 0) return BMX_OK;
     uint64_t *keys[2] = {nullptr, nullptr};
     uint32_t *idx[2] = {nullptr, nullptr};
@@ -517,15 +540,15 @@ int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, 
     const size_t b_tmp = up(tmp_sort > tmp_scan ? tmp_sort : tmp_scan);
     const size_t b_cnt = 1024; // four counters per round of the LDS path
     const size_t need = 2 * b_keys + 5 * b_u32 + b_tmp + b_cnt;
-    if (ok() && *ws_bytes < need) {
-        if (*ws) (void)hipFree(*ws);
-        *ws = nullptr;
-        *ws_bytes = 0;
-        e = hipMalloc(ws, need);
-        if (ok()) *ws_bytes = need;
+    if (ok() && st->ws_bytes < need) {
+        if (st->ws) (void)hipFree(st->ws);
+        st->ws = nullptr;
+        st->ws_bytes = 0;
+        e = hipMalloc(&st->ws, need);
+        if (ok()) st->ws_bytes = need;
     }
     if (ok()) {
-        char *p = (char *)*ws;
+        char *p = (char *)st->ws;
         keys[0] = (uint64_t *)p, p += b_keys;
         keys[1] = (uint64_t *)p, p += b_keys;
         idx[0] = (uint32_t *)p, p += b_u32;
@@ -589,7 +612,7 @@ int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, 
     if (ok()) e = hipMemsetAsync(counters, 0, b_cnt, stream);
     if (ok()) renumber_from_sorted_keys();
     const bool allow_lds = (switches & 1) == 0, allow_pipeline = (switches & 2) == 0;
-    uint32_t *&hp = *pinned; // pinned, owned by the caller's context: 4 words per round, written by the round's kernel
+    uint32_t *&hp = st->pinned; // pinned: 4 words per round, written by the round's kernel
     for (uint64_t k = 8; ok() && groups < n && k < 2 * (uint64_t)n; k *= 2) {
         const uint32_t h = (uint32_t)(k / 2);
         const bool fits = allow_lds && rounds < 30 && longest_group <= SEG_W - 1024;
@@ -693,8 +716,14 @@ int bmx_internal_suffix_array(const uint8_t *d_text, uint32_t n, int32_t *d_sa, 
         (void)hipMemcpyToSymbol(HIP_SYMBOL(sa_dbg), z, sizeof z);
     }
 #endif
-    if (ok() && ms_out) (void)hipEventElapsedTime(ms_out, e0, e1);
-    if (rounds_out) *rounds_out = rounds | (lds_rounds << 16); // (the shim takes them apart)
+    if (ok()) (void)hipEventElapsedTime(&st->last_ms, e0, e1);
+    st->last_rounds = rounds;
+    st->last_lds_rounds = lds_rounds;
+    if (st->ws_bytes > SA_WS_KEEP) { // a large one is not kept
+        (void)hipFree(st->ws);
+        st->ws = nullptr;
+        st->ws_bytes = 0;
+    }
 
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);

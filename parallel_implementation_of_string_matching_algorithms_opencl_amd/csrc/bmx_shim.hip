@@ -11,7 +11,6 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -24,11 +23,6 @@
 #include "bmx_scan_kernel.h"
 
 #include "bmx_aux_kernels.h"
-#include "bmx_ed_band_kernel.h"
-#include "bmx_ed_bits_kernel.h"
-#include "bmx_ed_bits2_kernel.h"
-#include "bmx_ed_bits3_kernel.h"
-#include "bmx_ed_kernel.h"
 #ifdef BMX_EXPERIMENTS
 #include "bmx_scan_ring_kernel.h"
 #include "bmx_scan_wave_kernel.h"
@@ -178,26 +172,13 @@ struct bmx_ctx {
     int max_grid = 0;            // > 0: at most this many workgroups per scan (small texts then reach the stolen tail)
     bool no_dense = false;       // true: no fill pass (a full parking buffer appends the direct way)
     bool multi_no_qgram = false; // true: the multi-pattern pass walks byte-wise only
-    int ed_lag = 0;              // >= 0 with ed_lag_set: rows a band is assumed to trail its predecessor by
-    bool ed_lag_set = false;
-    int ed_group = 32;           // hand-over group of the band pipeline (16 or 32 rows)
-    int ed_stamp_block = -1;     // libbmx_exp.so: the band whose cycle counts bmx_exp_ed_stamps returns (< 0: the middle forward band)
-    int ed_step_x = 0;           // libbmx_exp.so: timing experiment on the helper-wave band's step (index into g_ed_step_experiments)
+    bmx_ed_knobs ed_knobs;       // edit distance: the schedule (bmx_set_ed_variant) and the band pipeline's switches
     int sa_flags = 0;            // suffix array: 1 = library rounds only, 2 = a host wait per round, 4 = per-round trace on stderr
     const void *last_text = nullptr; // the text of the search whose status is awaited (its order_kernel samples it again)
     uint64_t last_text_n = 0;
     int last_variant = 0;    // what the most recent search ran (bmx_scan_geometry reports it)
-    int ed_variant = 0;      // edit-distance tile shape (bmx_set_ed_variant)
-    uint64_t ed_stamps[24 + 64 * 4] = {}; // libbmx_exp.so: cycle counts of one band of the last band-pipeline run + a hand-over's timeline
-    float ed_last_ms = -1.0f;
-    void *ed_ws = nullptr;   // band pipeline workspace, kept between calls while it is small
-    uint64_t ed_ws_bytes = 0;
-    uint64_t ed_ws_shape[3] = {0, 0, 0}; // (la, lb, W) of the call that last used it: same layout, stale tags only
-    float sa_last_ms = -1.0f;
-    void *sa_ws = nullptr; // suffix-array workspace, kept between calls while it is small
-    size_t sa_ws_bytes = 0;
-    uint32_t *sa_pinned = nullptr; // pinned host block the queued LDS rounds report into (allocated on first use, freed with the context)
-    int sa_last_rounds = 0, sa_last_lds_rounds = 0;
+    void *ed = nullptr; // edit distance: the band pipeline's workspace, last ms, stamps, events (bmx_ed.hip)
+    void *sa = nullptr; // suffix array: workspace, pinned round counters, last ms and round counts (bmx_sa.hip)
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
@@ -545,9 +526,8 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     if (ctx->d_sort_scratch) (void)hipFree(ctx->d_sort_scratch);
     if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
     if (ctx->order_stream) (void)hipStreamDestroy(ctx->order_stream);
-    if (ctx->ed_ws) (void)hipFree(ctx->ed_ws);
-    if (ctx->sa_ws) (void)hipFree(ctx->sa_ws);
-    if (ctx->sa_pinned) (void)hipHostFree(ctx->sa_pinned);
+    bmx_internal_ed_free(ctx->ed);
+    bmx_internal_sa_free(ctx->sa);
     bmx_internal_approx_free(ctx->approx);
     bmx_internal_classes_free(ctx->classes);
     bmx_internal_ed_batch_free(ctx->ed_batch);
@@ -1152,313 +1132,32 @@ int bmx_scan_stamps(bmx_ctx *ctx, uint64_t *out, uint64_t max_words)
     return (int)std::min<uint64_t>(n, 0x7fffffff);
 }
 
-// ---- edit distance ---------------------------------------------------
-namespace {
-struct EdVariant {
-    int c, r;                              // tile schedules: 64*c columns x r rows per wave
-    void (*kernel)(const bmx::EdArgs);     // one tile diagonal per launch, from the top-left corner
-    void (*dual)(const bmx::EdArgs);       // a forward and a mirrored tile diagonal per launch (nullptr: none)
-    int band_c;                            // band pipeline: 64*band_c columns per wave
-    void (*band)(const bmx::EdBandArgs);   // the whole table in one launch: pipeline of column bands, both directions
-    void (*band16)(const bmx::EdBandArgs); // same with 16-row hand-over groups (libbmx_exp.so: knob ed_group)
-    uint32_t band_lds = 0;                 // dynamic LDS of the band kernel (the bit-parallel band's Eq table)
-    int band_lag = 180;                    // rows a band trails its predecessor by (measured; places the cut rows)
-    double step_cost = 0.0;                // instructions per row step, for the choice of the band (0: 25 + 3 band_c)
-    int band_threads = 64;                 // threads of a band's workgroup (128: a main and a helper wave)
-};
-#define BMX_ED(C_, R_, BC_)                                                                                     \
-    {C_, R_, bmx::ed_tile_kernel<C_, R_, true>, bmx::ed_dual_kernel<C_, R_>, BC_, bmx::ed_band_kernel<BC_, 32>, \
-     bmx::ed_band_kernel<BC_, 16>}
-const EdVariant g_ed_variants[] = {
-    BMX_ED(4, 256, 6), // 0: default: bands of 384 columns; tiles (fallback, +16, +32) of 256 rows x 256 columns
-    BMX_ED(4, 128, 4), // 1
-    BMX_ED(8, 256, 8), // 2
-    BMX_ED(4, 384, 5), // 3
-    BMX_ED(6, 256, 6), // 4
-    {4, 256, bmx::ed_tile_kernel<4, 256, false>, nullptr, 0, nullptr, nullptr}, // 5: the first version (ds_bpermute
-                                                                                // shuffle, predicated steps)
-    BMX_ED(4, 512, 7), // 6
-    BMX_ED(3, 256, 3), // 7
-    // 8: the bit-parallel band (bmx_ed_bits_kernel.h): 2048 columns per wave, 32 per lane as two words of differences
-    {4, 256, bmx::ed_tile_kernel<4, 256, true>, bmx::ed_dual_kernel<4, 256>, 32, bmx::ed_bits_kernel<32, 1>, bmx::ed_bits_kernel<16, 1>,
-     bmx::ED_BITS_LDS, 190, 34.0},
-    // 9: ... two rows per step (a window entry = two rows); 10: four.  Measured at 64k x 64k (profiles/r03_ed_*.jsonl), ms at the
-    // best assumed lag: one row 2.80-2.97 (lag 180-200), two rows 2.58 (350-400), four 2.67 (800): a step is ~40 / 57 / 90
-    // instructions at ~5.5 cycles each for a lone wave (the recurrence is one dependent chain), so rows per step only
-    // amortise the ~17 instructions around it
-    {4, 256, bmx::ed_tile_kernel<4, 256, true>, bmx::ed_dual_kernel<4, 256>, 32, bmx::ed_bits_kernel<32, 2>, bmx::ed_bits_kernel<16, 2>,
-     bmx::ED_BITS_LDS, 380, 28.5},
-    {4, 256, bmx::ed_tile_kernel<4, 256, true>, bmx::ed_dual_kernel<4, 256>, 32, bmx::ed_bits_kernel<32, 4>, bmx::ed_bits_kernel<16, 4>,
-     bmx::ED_BITS_LDS, 800, 27.0},
-    // 11, 12: the bit-parallel band with the hand-over, the edge collector and the row windows out of the step
-    // (bmx_ed_bits2_kernel.h): two rows / one row per step
-    {4, 256, bmx::ed_tile_kernel<4, 256, true>, bmx::ed_dual_kernel<4, 256>, 32, bmx::ed_bits2_kernel<32, 2>, bmx::ed_bits2_kernel<16, 2>,
-     bmx::ed_bits2_lds(32, 2), 380, 20.5},
-    {4, 256, bmx::ed_tile_kernel<4, 256, true>, bmx::ed_dual_kernel<4, 256>, 32, bmx::ed_bits2_kernel<32, 1>, bmx::ed_bits2_kernel<16, 1>,
-     bmx::ed_bits2_lds(32, 1), 190, 25.0},
-    // 13: ... with a helper wave per band that talks to the neighbouring bands (bmx_ed_bits3_kernel.h): groups of 32 / 16 steps
-    {4, 256, bmx::ed_tile_kernel<4, 256, true>, bmx::ed_dual_kernel<4, 256>, 32, bmx::ed_bits3_kernel<32, 2>, bmx::ed_bits3_kernel<16, 2>,
-     bmx::ed_bits3_lds(32, 2), 310, 14.0, 256},
-};
-#ifdef BMX_EXPERIMENTS
-void (*const g_ed_step_experiments[])(const bmx::EdBandArgs) = {
-    bmx::ed_bits3_kernel<32, 2, 0>,  bmx::ed_bits3_kernel<32, 2, 1>,  bmx::ed_bits3_kernel<32, 2, 2>,  bmx::ed_bits3_kernel<32, 2, 4>,
-    bmx::ed_bits3_kernel<32, 2, 8>,  bmx::ed_bits3_kernel<32, 2, 16>, bmx::ed_bits3_kernel<32, 2, 3>,  bmx::ed_bits3_kernel<32, 2, 11>,
-    bmx::ed_bits3_kernel<32, 2, 27>,
-};
-#endif
-constexpr int N_ED_VARIANTS = sizeof(g_ed_variants) / sizeof(g_ed_variants[0]);
-constexpr int ED_ONE_DIRECTION = 16; // flag on the variant number: tiles, from the top-left corner only
-constexpr int ED_TILES = 32;         // flag: tiles from both corners (one launch per pair of tile diagonals)
-constexpr int ED_FLAGS = ED_ONE_DIRECTION | ED_TILES;
-constexpr uint64_t ED_BAND_WS_LIMIT = 16ull << 30; // bytes of right-column storage the band pipeline may take
-constexpr uint64_t ED_BAND_WS_KEEP = 1ull << 30;   // workspaces up to this size stay in the context between calls
-
-// Band pipeline (bmx_ed_band_kernel.h).  Returns BMX_OK with *used = false if it does not apply
-// (workspace too large / allocation refused): the caller then takes the tile schedule.
-int ed_band_run(bmx_ctx *ctx, const EdVariant &v, const void *d_a, uint64_t la, const void *d_b, uint64_t lb,
-                hipStream_t stream, uint32_t *h_result, bool *used)
-{
-    *used = false;
-    const uint32_t W = 64u * v.band_c;
-    const uint32_t bands = (uint32_t)((la + W - 1) / W);
-    // [right columns: 2 x (bands + 1) x (lb + 1) entries of 8 B | cut rows: 2 x bands x (W + 1) | cut | err | result]
-    const uint64_t rc_entries = 2ull * (bands + 1) * (lb + 1), stair_words = 2ull * bands * (W + 1);
-    const uint64_t stamp_at = (rc_entries * sizeof(uint64_t) + (stair_words + bands + 2) * sizeof(uint32_t) + 7) / 8 * 8;
-    const uint64_t bytes = stamp_at + (24 + 64 * 4) * sizeof(uint64_t);
-    if (bytes > ED_BAND_WS_LIMIT || la + lb >= (1ull << 31)) return BMX_OK; // (the kernel's F = D - r - c is an int32)
-    // Workspace: kept in the context between calls while it is small (a fresh hipMalloc + hipFree per
-    // call costs 0.3 ms next to a 4 ms kernel).  Entries are valid only with this call's tag; tags are
-    // unique per process, so a workspace reused for the same shape needs no clearing -- a new allocation
-    // (or another shape) is zeroed first.
-    static std::atomic<uint32_t> g_tag{0};
-    uint32_t tag = ++g_tag;
-    bool fresh = false;
-    uint64_t *ws = nullptr;
-    if (ctx->ed_ws && ctx->ed_ws_bytes >= bytes && tag != 0) {
-        ws = (uint64_t *)ctx->ed_ws;
-        // another shape lays the regions out differently: what was a cut row or a result word may now
-        // be read as an entry, so the storage is cleared like a new one
-        fresh = ctx->ed_ws_shape[0] != la || ctx->ed_ws_shape[1] != lb || ctx->ed_ws_shape[2] != W;
-    } else {
-        if (ctx->ed_ws) (void)hipFree(ctx->ed_ws);
-        ctx->ed_ws = nullptr;
-        ctx->ed_ws_bytes = 0;
-        if (hipMalloc(&ws, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return BMX_OK;
-        }
-        fresh = true;
-        if (tag == 0) tag = ++g_tag; // 2^32 calls later: start over on zeroed storage
-        if (bytes <= ED_BAND_WS_KEEP) {
-            ctx->ed_ws = ws;
-            ctx->ed_ws_bytes = bytes;
-        }
-    }
-    const bool keep = ctx->ed_ws == (void *)ws;
-    if (keep) {
-        ctx->ed_ws_shape[0] = la;
-        ctx->ed_ws_shape[1] = lb;
-        ctx->ed_ws_shape[2] = W;
-    }
-    const int lag = ctx->ed_lag_set ? ctx->ed_lag : v.band_lag;
-    bmx::EdBandArgs a = {};
-    a.a = (const uint8_t *)d_a;
-    a.b = (const uint8_t *)d_b;
-    a.la = (uint32_t)la;
-    a.lb = (uint32_t)lb;
-    a.bands = bands;
-    a.rc[0] = ws;
-    a.rc[1] = ws + rc_entries / 2;
-    uint32_t *tail = (uint32_t *)(ws + rc_entries);
-    a.stair_row[0] = tail;
-    a.stair_row[1] = tail + stair_words / 2;
-    uint32_t *d_cut = tail + stair_words;
-    a.cut = d_cut;
-    a.err = d_cut + bands;
-    uint32_t *d_result = a.err + 1;
-    a.tag = tag;
-    a.lag = lag;
-#ifdef BMX_EXPERIMENTS
-    a.stamps = (uint64_t *)((char *)ws + stamp_at);
-    a.stamp_block = ctx->ed_stamp_block >= 0 ? (uint32_t)ctx->ed_stamp_block : bands / 2;
-    (void)hipMemsetAsync(a.stamps, 0, (24 + 64 * 4) * sizeof(uint64_t), stream);
-#endif
-    // generous: 10 s + 100x the time the tile schedule would need (100 MHz ticks)
-    a.timeout_ticks = 1000000000ull + (uint64_t)((double)la * (double)lb / 2.0e9 * 100.0);
-    const int slot = (int)(ctx->n_timed % bmx_ctx::EV_RING);
-    hipError_t e = hipEventRecord(ctx->ev0[slot], stream);
-    if (e == hipSuccess && fresh) e = hipMemsetAsync(ws, 0, rc_entries * sizeof(uint64_t), stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(bmx::ed_band_init_kernel, dim3(64), dim3(256), 0, stream, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        auto kern = ctx->ed_group == 16 ? v.band16 : v.band;
-#ifdef BMX_EXPERIMENTS
-        if (ctx->ed_step_x > 0 && v.band_threads == 256 && ctx->ed_step_x < (int)(sizeof g_ed_step_experiments / sizeof g_ed_step_experiments[0]))
-            kern = g_ed_step_experiments[ctx->ed_step_x];
-#endif
-        if (v.band_lds > 64 * 1024) e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.band_lds);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(kern, dim3(2 * bands), dim3(v.band_threads), v.band_lds, stream, a);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(bmx::ed_band_meet_kernel, dim3(bands), dim3(256), 0, stream, a, W, (int32_t *)d_result);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev1[slot], stream);
-    uint32_t h_tail[2] = {0, 0}; // err, result
-    if (e == hipSuccess) e = hipMemcpyAsync(h_tail, a.err, sizeof h_tail, hipMemcpyDeviceToHost, stream);
-#ifdef BMX_EXPERIMENTS
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->ed_stamps, a.stamps, sizeof ctx->ed_stamps, hipMemcpyDeviceToHost, stream);
-#endif
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ed_last_ms, ctx->ev0[slot], ctx->ev1[slot]);
-    if (!keep) (void)hipFree(ws);
-    if (e != hipSuccess) {
-        set_err("bmx_edit_distance_device (band pipeline): %s", hipGetErrorString(e));
-        return BMX_ERR_HIP;
-    }
-    if (h_tail[0] != 0) {
-        set_err("bmx_edit_distance_device: a column band waited longer than the time limit for its neighbour");
-        return BMX_ERR_HIP;
-    }
-    *h_result = (uint32_t)((int64_t)(int32_t)h_tail[1] + (int64_t)la + (int64_t)lb); // min(F_fwd + F_mir) + la + lb
-    *used = true;
-    return BMX_OK;
-}
-} // namespace
-
+// ---- edit distance (bmx_ed.hip) -------------------------------------------
 int bmx_set_ed_variant(bmx_ctx *ctx, int variant)
 {
-    if (!ctx || variant < 0 || (variant & ~ED_FLAGS) >= N_ED_VARIANTS) return BMX_ERR_ARG;
-    ctx->ed_variant = variant;
+    if (!ctx) return BMX_ERR_ARG;
+    if (!bmx_internal_ed_variant_ok(variant)) { // a schedule of libbmx_exp.so only, or none at all
+        set_err("bmx_set_ed_variant: schedule %d is not part of this library (experiments: libbmx_exp.so)", variant);
+        return BMX_ERR_ARG;
+    }
+    ctx->ed_knobs.variant = variant;
     return BMX_OK;
 }
 
-float bmx_last_edit_distance_ms(bmx_ctx *ctx) { return ctx ? ctx->ed_last_ms : -1.0f; }
+float bmx_last_edit_distance_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_ed_ms(ctx->ed) : -1.0f; }
 
 int bmx_edit_distance_device(bmx_ctx *ctx, const void *d_a, uint64_t la, const void *d_b, uint64_t lb,
                              uint64_t *distance, void *stream_v)
 {
     if (!ctx || !distance || (la > 0 && !d_a) || (lb > 0 && !d_b)) return BMX_ERR_ARG;
     if (la >= (1ull << 31) || lb >= (1ull << 31)) return BMX_ERR_ARG;
-    ctx->ed_last_ms = -1.0f;
     if (la == 0 || lb == 0) { // D[0][c] = c, D[r][0] = r (sequential.c:28-32)
+        bmx_internal_ed_no_kernel(ctx->ed);
         *distance = la + lb;
         return BMX_OK;
     }
-    hipStream_t stream = (hipStream_t)stream_v;
     HIPCHK(hipSetDevice(ctx->device));
-    const EdVariant &v = g_ed_variants[ctx->ed_variant & ~ED_FLAGS];
-    if (v.band && !(ctx->ed_variant & ED_FLAGS)) {
-        // The distance is symmetric and the pipeline is not: a row costs a step of every band, a column only its
-        // share of one more band's lag (0.5 vs lag / (128 C) = 0.23 steps per character).  So the longer string
-        // provides the columns; and with the default variant the band is the one the step model likes best
-        // (lb/2 + bands * lag / 2 steps of step_cost instructions).  Among the value bands alone that was C = 6 at
-        // 64k x 64k and C = 3 at 8k x 128k; with the table as it stands schedule 13 has the least step cost, the least
-        // step cost x lag and the fewest bands, so it is the pick at every shape (tests/test_gpu_ed_shapes.py).
-        if (lb > la) {
-            std::swap(d_a, d_b);
-            std::swap(la, lb);
-        }
-        const EdVariant *pick = &v;
-        if (ctx->ed_variant == 0) {
-            double best = 0.0;
-            for (const EdVariant &c : g_ed_variants) {
-                if (!c.band) continue;
-                const double bands = (double)((la + 64 * c.band_c - 1) / (64 * c.band_c));
-                const double t = ((double)lb / 2 + bands * c.band_lag / 2) * (c.step_cost > 0.0 ? c.step_cost : 25.0 + 3.0 * c.band_c);
-                if (best == 0.0 || t < best) {
-                    best = t;
-                    pick = &c;
-                }
-            }
-        }
-        uint32_t h = 0;
-        bool used = false;
-        const int rc = ed_band_run(ctx, *pick, d_a, la, d_b, lb, stream, &h, &used);
-        if (rc != BMX_OK) return rc;
-        if (used) {
-            *distance = h;
-            return BMX_OK;
-        }
-    }
-    const uint32_t W = 64u * v.c, R = (uint32_t)v.r;
-    bmx::EdArgs a = {};
-    a.a = (const uint8_t *)d_a;
-    a.b = (const uint8_t *)d_b;
-    a.la = (uint32_t)la;
-    a.lb = (uint32_t)lb;
-    a.tile_cols = (a.la + W - 1) / W;
-    a.tile_rows = (a.lb + R - 1) / R;
-    const uint32_t ndiag = a.tile_rows + a.tile_cols - 1;
-    // Two-ended schedule: forward tile diagonals 0..K, mirrored ones for the rest, pairwise in one
-    // launch; worth it as soon as there are three diagonals.
-    const bool two_ended = v.dual && !(ctx->ed_variant & ED_ONE_DIRECTION) && ndiag >= 3;
-    const uint64_t n_srow = (uint64_t)a.tile_cols * (W + 1), n_scol = (uint64_t)a.tile_rows * (R + 1);
-    // [3 x (la+1) bottom rows | lb+1 right column] per direction | staircase F/G rows, F/G columns | result
-    const uint64_t per_dir = 3 * (la + 1) + (lb + 1);
-    const uint64_t words = (two_ended ? 2 * per_dir + 2 * n_srow + 2 * n_scol : per_dir) + 1;
-    uint32_t *ws = nullptr;
-    HIPCHK(hipMalloc(&ws, words * sizeof(uint32_t)));
-    a.bottom = ws;
-    a.rightcol = ws + 3 * (la + 1);
-    a.result = ws + words - 1;
-    const int slot = (int)(ctx->n_timed % bmx_ctx::EV_RING); // borrow an event pair, outside the scan history
-    hipError_t e = hipEventRecord(ctx->ev0[slot], stream);
-    auto blocks_on = [&](uint32_t d) { // tiles on (logical) tile diagonal d
-        const uint32_t i_lo = d >= a.tile_cols ? d - (a.tile_cols - 1) : 0;
-        return std::min(d, a.tile_rows - 1) - i_lo + 1;
-    };
-    if (!two_ended) {
-        for (uint32_t d = 0; d < ndiag && e == hipSuccess; ++d) {
-            a.diag = d;
-            hipLaunchKernelGGL(v.kernel, dim3(blocks_on(d)), dim3(64), 0, stream, a);
-            e = hipGetLastError();
-        }
-    } else {
-        a.bottom_m = ws + per_dir;
-        a.rightcol_m = a.bottom_m + 3 * (la + 1);
-        uint32_t *stair = ws + 2 * per_dir;
-        a.stair_row[0] = stair;
-        a.stair_row[1] = stair + n_srow;
-        a.stair_col[0] = stair + 2 * n_srow;
-        a.stair_col[1] = stair + 2 * n_srow + n_scol;
-        if (e == hipSuccess) // 0xFF.. = bmx::ED_NONE: edges only one direction reaches never pair up
-            e = hipMemsetAsync(stair, 0xFF, (2 * n_srow + 2 * n_scol) * sizeof(uint32_t), stream);
-        const uint32_t K = (ndiag - 2) / 2;     // forward: diagonals 0..K
-        const uint32_t last_m = ndiag - 2 - K;  // mirrored: its own diagonals 0..last_m (= table diagonals ndiag-1 .. K+1)
-        for (uint32_t t = 0; t <= std::max(K, last_m) && e == hipSuccess; ++t) {
-            const uint32_t nf = t <= K ? blocks_on(t) : 0, nm = t <= last_m ? blocks_on(t) : 0;
-            a.diag = a.diag_m = t;
-            a.n_fwd = nf;
-            a.stair_fwd = t == K;
-            a.stair_m = t == last_m;
-            hipLaunchKernelGGL(v.dual, dim3(nf + nm), dim3(64), 0, stream, a);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(bmx::ed_meet_kernel, dim3(1), dim3(1024), 0, stream, a.stair_row[0], a.stair_row[1],
-                               (uint32_t)n_srow, a.stair_col[0], a.stair_col[1], (uint32_t)n_scol, a.result);
-            e = hipGetLastError();
-        }
-    }
-    uint32_t h_result = 0;
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev1[slot], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_result, a.result, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ed_last_ms, ctx->ev0[slot], ctx->ev1[slot]);
-    (void)hipFree(ws);
-    if (e != hipSuccess) {
-        set_err("bmx_edit_distance_device: %s", hipGetErrorString(e));
-        return BMX_ERR_HIP;
-    }
-    *distance = h_result;
-    return BMX_OK;
+    return bmx_internal_ed(&ctx->ed, &ctx->ed_knobs, d_a, la, d_b, lb, distance, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
 // ---- batched edit distance (bmx_ed_batch.hip) --------------------------------------------------
@@ -1478,27 +1177,18 @@ float bmx_last_ed_batch_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_ed_batch_ms
 
 int64_t bmx_last_ed_batch_fallbacks(bmx_ctx *ctx) { return ctx ? bmx_internal_ed_batch_fallbacks(ctx->ed_batch) : -1; }
 
-// ---- suffix array -------------------------------------------------------
+// ---- suffix array (bmx_sa.hip) ---------------------------------------------
 int bmx_suffix_array_device(bmx_ctx *ctx, const void *d_text, uint64_t n, int32_t *d_sa, void *stream_v)
 {
     if (!ctx || (n > 0 && (!d_text || !d_sa)) || n >= (1ull << 31)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
-    const int rc = bmx_internal_suffix_array((const uint8_t *)d_text, (uint32_t)n, d_sa, (hipStream_t)stream_v,
-                                             &ctx->sa_last_ms, &ctx->sa_last_rounds, &ctx->sa_ws, &ctx->sa_ws_bytes, &ctx->sa_pinned,
-                                             ctx->sa_flags, g_err, sizeof g_err);
-    ctx->sa_last_lds_rounds = ctx->sa_last_rounds >> 16;
-    ctx->sa_last_rounds &= 0xffff;
-    if (ctx->sa_ws_bytes > ED_BAND_WS_KEEP) { // a large one is not kept
-        (void)hipFree(ctx->sa_ws);
-        ctx->sa_ws = nullptr;
-        ctx->sa_ws_bytes = 0;
-    }
-    return rc;
+    return bmx_internal_suffix_array(&ctx->sa, (const uint8_t *)d_text, (uint32_t)n, d_sa, (hipStream_t)stream_v, ctx->sa_flags, g_err,
+                                     sizeof g_err);
 }
 
-float bmx_last_suffix_array_ms(bmx_ctx *ctx) { return ctx ? ctx->sa_last_ms : -1.0f; }
-int bmx_last_suffix_array_rounds(bmx_ctx *ctx) { return ctx ? ctx->sa_last_rounds : 0; }
-int bmx_last_suffix_array_lds_rounds(bmx_ctx *ctx) { return ctx ? ctx->sa_last_lds_rounds : 0; }
+float bmx_last_suffix_array_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_sa_ms(ctx->sa) : -1.0f; }
+int bmx_last_suffix_array_rounds(bmx_ctx *ctx) { return ctx ? bmx_internal_sa_rounds(ctx->sa) : 0; }
+int bmx_last_suffix_array_lds_rounds(bmx_ctx *ctx) { return ctx ? bmx_internal_sa_lds_rounds(ctx->sa) : 0; }
 
 // ---- approximate search (bmx_approx.hip) -------------------------------------------------------
 int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
@@ -1690,8 +1380,7 @@ int bmx_text_upload(bmx_ctx *ctx, const char *text, uint64_t n, void **d_text_ou
 int bmx_exp_ed_stamps(bmx_ctx *ctx, uint64_t *out280)
 {
     if (!ctx || !out280) return BMX_ERR_ARG;
-    for (int i = 0; i < 24 + 64 * 4; ++i) out280[i] = ctx->ed_stamps[i];
-    return BMX_OK;
+    return bmx_internal_ed_stamps(ctx->ed, out280);
 }
 
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
@@ -1702,10 +1391,10 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "no_dense") ctx->no_dense = value != 0;
     else if (k == "no_text_sample") ctx->text_sample = value == 0;
     else if (k == "multi_no_qgram") ctx->multi_no_qgram = value != 0;
-    else if (k == "ed_lag") ctx->ed_lag = value, ctx->ed_lag_set = value >= 0;
-    else if (k == "ed_group") ctx->ed_group = value;
-    else if (k == "ed_step_x") ctx->ed_step_x = value;
-    else if (k == "ed_stamp_block") ctx->ed_stamp_block = value;
+    else if (k == "ed_lag") ctx->ed_knobs.lag = value;
+    else if (k == "ed_group") ctx->ed_knobs.group = value;
+    else if (k == "ed_step_x") ctx->ed_knobs.step_x = value;
+    else if (k == "ed_stamp_block") ctx->ed_knobs.stamp_block = value;
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "ordered_seq" && value >= 0) {

@@ -25,7 +25,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libbmx.so")
 # libbmx_exp.so: the same sources built with -DBMX_EXPERIMENTS -- every slot of the kernel table (losing schedules, timing-only
-# kernels whose match lists are not valid) and the measurement switches (bmx_exp_set_knob).  tools/ and a few tests load it
+# kernels whose match lists are not valid), every edit-distance schedule (the product library builds 13, 0 as its alias and
+# their tiles behind +16 / +32; set_ed_variant refuses the rest there) and the measurement switches (bmx_exp_set_knob).  tools/ and a few tests load it
 # through exp_lib() / Context(library=exp_lib()); the product path, bench.py and smoke() never do.  Nothing here reads
 # the environment: tools/ that want another build call use_library() themselves.
 EXP_LIB_PATH = os.path.join(_HERE, "lib", "libbmx_exp.so")
@@ -560,6 +561,8 @@ class Context:
         return float(self._L.bmx_last_edit_distance_ms(self._h))
 
     def set_ed_variant(self, v: int):
+        """Edit-distance schedule (include/bmx.h).  The product library accepts 0 and 13 with the flags +16 / +32; every other
+        slot raises BmxError(ERR_ARG) unless this context is one of exp_lib()."""
         self._chk(self._L.bmx_set_ed_variant(self._h, v), "bmx_set_ed_variant")
 
     # -- batched edit distance: many string pairs in one call ---------------------------

@@ -92,6 +92,12 @@ def test_thresholded_oracle_agrees_with_the_full_oracle(port):
 
 
 # ------------------------------------------------------------------ GPU
+def _ctx_for(v, ctx, exp_ctx):
+    """The product library builds schedule 13, 0 as its alias and their tiles (+16 / +32); every schedule that lost is
+    libbmx_exp.so's alone (test_product_library_accepts_only_its_ed_schedules)."""
+    return ctx if (v & ~48) in (0, 13) else exp_ctx
+
+
 @pytest.mark.gpu
 def test_gpu_golden(ctx):
     for case in load_golden("edit_distance.json"):
@@ -100,7 +106,7 @@ def test_gpu_golden(ctx):
 
 
 @pytest.mark.gpu
-def test_gpu_vs_oracle_around_tile_edges_all_tile_shapes(ctx, port):
+def test_gpu_vs_oracle_around_tile_edges_all_tile_shapes(ctx, exp_ctx, port):
     """Lengths straddling the tile width/height (64*C columns, R rows) of every tile shape,
     unequal lengths included (the reference itself is only right for equal lengths)."""
     rng = np.random.default_rng(7)
@@ -110,24 +116,26 @@ def test_gpu_vs_oracle_around_tile_edges_all_tile_shapes(ctx, port):
         # columns per wave) with one / two / four rows per step; +32: tiles filled from both corners at once where there are three tile diagonals or more; +16:
         # tiles from the top-left corner only
         for v in [0, 8, 9, 10, 11, 12, 13, 2, 4, 7, 5, 32, 33, 34, 35, 16, 17, 18, 20]:
-            ctx.set_ed_variant(v)
+            c = _ctx_for(v, ctx, exp_ctx)
+            c.set_ed_variant(v)
             for it in range(14 if v not in (8, 9, 10, 11, 12, 13) else 40):
                 ls = lens if v not in (8, 9, 10, 11, 12, 13) else lens + [3, 4, 5, 31, 32, 33, 2016, 2047, 2048, 2049, 2080, 4095, 4097, 6200]
                 la, lb = int(rng.choice(ls)), int(rng.choice(ls))
                 al = int(rng.integers(2, 5))
                 x = (rng.integers(0, al, la) + 97).astype(np.uint8)
                 y = (rng.integers(0, al, lb) + 97).astype(np.uint8)
-                assert ctx.edit_distance(x, y) == port.edit_distance(x, y), (v, la, lb)
+                assert c.edit_distance(x, y) == port.edit_distance(x, y), (v, la, lb)
     finally:
         ctx.set_ed_variant(0)
 
 
 @pytest.mark.gpu
-def test_gpu_two_ended_schedule_on_every_grid_shape(ctx, port):
+def test_gpu_two_ended_schedule_on_every_grid_shape(exp_ctx, port):
     """The forward and the mirrored half meet on a staircase of tile edges: grids of 1..9 x
-    1..9 tiles (128 x 256 tiles, variant 1), full and ragged last tiles, strings that are
+    1..9 tiles (128 x 256 tiles, variant 1: a tile shape of libbmx_exp.so), full and ragged last tiles, strings that are
     related (long shared runs: the optimal path hugs the diagonal) and unrelated."""
     rng = np.random.default_rng(11)
+    ctx = exp_ctx
     ctx.set_ed_variant(33)
     try:
         for tr in (1, 2, 3, 5, 9):
@@ -187,7 +195,7 @@ def test_gpu_degenerate(ctx):
 
 
 @pytest.mark.gpu
-def test_gpu_every_byte_value_on_the_bit_parallel_bands(ctx, port):
+def test_gpu_every_byte_value_on_the_bit_parallel_bands(ctx, exp_ctx, port):
     """The bit-parallel bands index their Eq table by the character: all 256 byte values, NUL and 0xff included, on shapes with a
     narrow last band, fewer rows than a group, rows that are not whole steps, and a band whose lanes have not all started when the
     rows end (schedules 13 = the default, 11, 9)."""
@@ -195,7 +203,8 @@ def test_gpu_every_byte_value_on_the_bit_parallel_bands(ctx, port):
     shapes = [(2048, 2048), (2049, 5), (4096 + 33, 127), (300, 4097), (6145, 2047), (70, 70), (2047, 129), (5000, 63)]
     try:
         for v in (13, 11, 9, 0):
-            ctx.set_ed_variant(v)
+            c = _ctx_for(v, ctx, exp_ctx)
+            c.set_ed_variant(v)
             for la, lb in shapes:
                 x = rng.integers(0, 256, la).astype(np.uint8)
                 y = rng.integers(0, 256, lb).astype(np.uint8)
@@ -204,7 +213,7 @@ def test_gpu_every_byte_value_on_the_bit_parallel_bands(ctx, port):
                 x[la // 3] = 0
                 y[lb // 2] = 0
                 x[-1] = 255
-                assert ctx.edit_distance(x, y) == port.edit_distance(x, y), (v, la, lb)
+                assert c.edit_distance(x, y) == port.edit_distance(x, y), (v, la, lb)
     finally:
         ctx.set_ed_variant(0)
 
@@ -222,7 +231,7 @@ def test_gpu_mid_size_vs_oracle(ctx, port):
 
 
 @pytest.mark.gpu
-def test_gpu_config5_64k_properties(ctx, port):
+def test_gpu_config5_64k_properties(ctx, exp_ctx, port):
     """BASELINE config 5: 64k x 64k.  Known-by-construction answers plus one full
     comparison with the two-row oracle (13 s of CPU)."""
     import torch
@@ -244,8 +253,63 @@ def test_gpu_config5_64k_properties(ctx, port):
     assert d1 == ctx.edit_distance_device(dz, dx)
     try:
         for v in (16, 32, 4, 8, 9, 10, 11, 12, 13):  # tiles from one corner (the first schedule) / from both corners; value bands; bit-parallel bands
-            ctx.set_ed_variant(v)
-            assert d1 == ctx.edit_distance_device(dx, dz)
+            c = _ctx_for(v, ctx, exp_ctx)
+            c.set_ed_variant(v)
+            assert d1 == c.edit_distance_device(dx, dz)
     finally:
         ctx.set_ed_variant(0)
     assert d1 == port.edit_distance(x, z)
+
+
+@pytest.mark.gpu
+def test_product_library_accepts_only_its_ed_schedules(ctx, exp_ctx):
+    """bmx_set_ed_variant follows the scan kernels' rule (test_gpu_parity.py::test_product_library_accepts_only_its_variants):
+    libbmx.so builds schedule 13, slot 0 as its alias and their tiles behind +16 / +32, and refuses every other slot with
+    BMX_ERR_ARG; libbmx_exp.so accepts all fourteen.  No kernel runs."""
+    from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
+
+    def refused(c, v):
+        with pytest.raises(host.BmxError) as e:
+            c.set_ed_variant(v)
+        return e.value.rc == host.ERR_ARG
+
+    try:
+        for base in range(14):
+            for flags in (0, 16, 32, 48):
+                if base in (0, 13):
+                    ctx.set_ed_variant(base + flags)
+                else:
+                    assert refused(ctx, base + flags), (base, flags)
+                exp_ctx.set_ed_variant(base + flags)
+        for v in [b + f for b in (14, 20) for f in (0, 16, 32, 48)] + [14, 27, -1]:
+            assert refused(ctx, v), v
+    finally:
+        ctx.set_ed_variant(0)
+
+
+@pytest.mark.gpu
+def test_edit_distance_leaves_the_scan_history_alone(built, port):
+    """The edit distance times itself with events of its own.  It used to re-record the scan history's next ring slot,
+    which -- once 64 scans had been timed -- is the history's oldest entry: [63] then read the edit distance's time.
+    Elapsed times of recorded events do not change, so all 64 floats are bit-equal before and after."""
+    from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
+
+    rng = np.random.default_rng(43)
+    text = (rng.integers(0, 26, 64 * 1024) + 97).astype(np.uint8)
+    with host.Context(0) as c:
+        for _ in range(70):  # (the ring of 64 has wrapped)
+            c.search(text, b"abcd")
+        before = np.asarray(c.scan_ms_history(64), dtype=np.float32)
+        last = c.last_scan_ms()
+        assert before.size == 64
+        try:
+            for v, la, lb in ((0, 300, 70), (0, 3000, 3000), (32, 600, 600)):  # band path twice, then the tile path
+                c.set_ed_variant(v)
+                x = (rng.integers(0, 4, la) + 97).astype(np.uint8)
+                y = (rng.integers(0, 4, lb) + 97).astype(np.uint8)
+                assert c.edit_distance(x, y) == port.edit_distance(x, y), (v, la, lb)
+        finally:
+            c.set_ed_variant(0)
+        after = np.asarray(c.scan_ms_history(64), dtype=np.float32)
+        assert before.tobytes() == after.tobytes(), np.flatnonzero(before != after)
+        assert c.last_scan_ms() == last

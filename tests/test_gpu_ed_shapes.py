@@ -1,10 +1,11 @@
-"""GPU suite: the edit distance beyond the benchmark's shapes (bmx_edit_distance_device, `ed_band_run` in csrc/bmx_shim.hip).
+"""GPU suite: the edit distance beyond the benchmark's shapes (bmx_edit_distance_device, `ed_band_run` in csrc/bmx_ed.hip).
 
 tests/test_edit_distance.py stops at 65,536 x 65,536: 32 column bands of 2,048, 64 workgroups.  The default kernel
 (csrc/bmx_ed_bits3_kernel.h) is a pipeline in which band b spins on band b - 1, launched as 2 x bands workgroups of
 ed_bits3_lds(32, 2) = 142,000 bytes of LDS each: one workgroup per CU (160 KiB), 256 resident on the card's 256 CUs.  Here:
 more workgroups than that, the workspace rules of the host side (kept up to 1 GiB, reused without clearing for the same shape,
-cleared for another), the band width the cost model picks, and the argument limits.
+cleared for another), every band schedule at shapes that favoured different band widths, and the argument limits.  The product
+library builds the default schedule alone; the ones that lost run on a context of libbmx_exp.so.
 
 References: the two-row oracle (port.edit_distance) and, for long related strings, its diagonal-band version
 (port.edit_distance_within: exact whenever it answers at all; "more than t" fails the test).  Nothing is compared with the
@@ -18,24 +19,9 @@ from parallel_implementation_of_string_matching_algorithms_opencl_amd import hos
 
 pytestmark = pytest.mark.gpu
 
-# The band schedules of g_ed_variants (csrc/bmx_shim.hip), copied as data: schedule -> (band_c, band_lag, step_cost; 0.0 = 25 + 3 band_c).
-BAND_VARIANTS = {0: (6, 180, 0.0), 1: (4, 180, 0.0), 2: (8, 180, 0.0), 3: (5, 180, 0.0), 4: (6, 180, 0.0), 6: (7, 180, 0.0),
-                 7: (3, 180, 0.0), 8: (32, 190, 34.0), 9: (32, 380, 28.5), 10: (32, 800, 27.0), 11: (32, 380, 20.5),
-                 12: (32, 190, 25.0), 13: (32, 310, 14.0)}
-
-
-def model_pick(la, lb):
-    """The choice of bmx_edit_distance_device on schedule 0: the longer string gives the columns, then the first variant with
-    the least (lb / 2 + bands * lag / 2) * step cost."""
-    la, lb = max(la, lb), min(la, lb)
-    best, pick = 0.0, None
-    for v in sorted(BAND_VARIANTS):
-        c, lag, cost = BAND_VARIANTS[v]
-        bands = float((la + 64 * c - 1) // (64 * c))
-        t = (lb / 2 + bands * lag / 2) * (cost if cost > 0.0 else 25.0 + 3.0 * c)
-        if best == 0.0 or t < best:
-            best, pick = t, v
-    return pick
+# The band schedules of g_ed_variants (csrc/bmx_ed.hip): every slot but 5, which has tiles only.  0 (= 13) and 13 are the
+# product library's; the others exist in libbmx_exp.so alone.
+BAND_SCHEDULES = [0, 1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13]
 
 
 def _dev(ctx, x):
@@ -73,9 +59,10 @@ FEW_ROWS = [(300_000, (1, 31, 500), (31, 500)), ((1 << 20) + 5, (1, 31, 200), (2
 
 
 @pytest.mark.parametrize("la,lbs,related", FEW_ROWS)
-def test_more_bands_than_resident_workgroups_few_rows(ctx, port, la, lbs, related):
+def test_more_bands_than_resident_workgroups_few_rows(ctx, exp_ctx, port, la, lbs, related):
     """Unrelated strings over 4 letters and related ones, both argument orders, schedule 0, against the full oracle.  The
-    largest la also on schedules 11 (one-wave bit-parallel bands) and 4 (value bands of 384 columns: 10,918 bands)."""
+    largest la also on schedules 11 (one-wave bit-parallel bands) and 4 (value bands of 384 columns: 10,918 bands), which are
+    libbmx_exp.so's."""
     rng = np.random.default_rng(la % 9973)
     a = _acgt(rng, la)
     da = _dev(ctx, a)
@@ -84,21 +71,17 @@ def test_more_bands_than_resident_workgroups_few_rows(ctx, port, la, lbs, relate
         for where, at in (("start", 0), ("middle", la // 2 - 7), ("end", la - lb - lb // 8 - 3)):
             piece, _ = _edited(rng, a[at:at + lb + lb // 8 + 2], lb // 10, lb // 16, 1 if lb > 40 else 0)
             cases.append((where, lb, piece[:lb].copy()))
-    try:
-        for name, lb, b in cases:
-            assert b.size == lb
-            want = port.edit_distance(a, b)
-            assert la - lb <= want <= la
-            db = _dev(ctx, b)
-            assert ctx.edit_distance_device(da, db) == want, (name, la, lb)
-            assert ctx.edit_distance_device(db, da) == want, (name, lb, la)
-            if la > 4_000_000 and lb == lbs[-1]:
-                for v in (11, 4):
-                    ctx.set_ed_variant(v)
-                    assert ctx.edit_distance_device(da, db) == want, (v, name, la, lb)
-                ctx.set_ed_variant(0)
-    finally:
-        ctx.set_ed_variant(0)
+    for name, lb, b in cases:
+        assert b.size == lb
+        want = port.edit_distance(a, b)
+        assert la - lb <= want <= la
+        db = _dev(ctx, b)
+        assert ctx.edit_distance_device(da, db) == want, (name, la, lb)
+        assert ctx.edit_distance_device(db, da) == want, (name, lb, la)
+        if la > 4_000_000 and lb == lbs[-1]:
+            for v in (11, 4):
+                exp_ctx.set_ed_variant(v)
+                assert exp_ctx.edit_distance_device(da, db) == want, (v, name, la, lb)
 
 
 def test_many_bands_many_rows_and_the_workspace_that_is_not_kept(built, port):
@@ -134,42 +117,40 @@ def test_many_bands_many_rows_and_the_workspace_that_is_not_kept(built, port):
 def test_workspace_reuse_sequence(built, port):
     """One context, a fixed sequence of shapes that all fit the workspace of the first call: same shape (reused without
     clearing: only this call's tag makes entries valid), other contents, other shapes (cleared), back again; then the same on
-    schedule 4, whose band width lays the same storage out differently.  Each call against the full oracle."""
+    schedule 4, whose band width lays the same storage out differently.  Each call against the full oracle.  Schedule 4 is
+    libbmx_exp.so's, so the whole sequence runs on a context of that library; its schedule-0 part runs on the product
+    library too, on the same strings."""
     import torch
 
     assert torch.cuda.is_available()
-    rng = np.random.default_rng(808)
     shapes = [(4096, 4096), (4096, 4096), (2048, 8000), (8000, 2048), (4096, 4096), (100, 100), (6200, 5), (4096, 4096)]
-    c = host.Context(0)
-    try:
-        for v in (0, 4):
-            c.set_ed_variant(v)
-            for step, (la, lb) in enumerate(shapes):
-                x = _acgt(rng, la)
-                if la == lb:  # related: the answer is far from max(la, lb), stale entries would show
-                    y = x.copy()
-                    y[rng.integers(0, la, la // 9 + 1)] = ord("N")
-                    y = np.resize(np.delete(y, rng.integers(0, la, la // 40 + 1)), lb)
-                else:
-                    y = _acgt(rng, lb)
-                assert _gpu(c, x, y) == port.edit_distance(x, y), (v, step, la, lb)
-    finally:
-        c.close()
+    for library, schedules in ((None, (0,)), (host.exp_lib(), (0, 4))):
+        rng = np.random.default_rng(808)
+        c = host.Context(0, library=library)
+        try:
+            for v in schedules:
+                c.set_ed_variant(v)
+                for step, (la, lb) in enumerate(shapes):
+                    x = _acgt(rng, la)
+                    if la == lb:  # related: the answer is far from max(la, lb), stale entries would show
+                        y = x.copy()
+                        y[rng.integers(0, la, la // 9 + 1)] = ord("N")
+                        y = np.resize(np.delete(y, rng.integers(0, la, la // 40 + 1)), lb)
+                    else:
+                        y = _acgt(rng, lb)
+                    assert _gpu(c, x, y) == port.edit_distance(x, y), (library is not None, v, step, la, lb)
+        finally:
+            c.close()
 
 
 PICK_SHAPES = [(8 * 1024, 128 * 1024), (20_000, 20_000), (300, 70_000)]
 
 
-def test_cost_model_picks(ctx, port):
-    """The formula of bmx_edit_distance_device, evaluated here from the table above.  With the table as committed it picks
-    schedule 13 at EVERY shape: 13 has the lowest step cost (14.0) and the lowest step cost x lag (4,340; next: 12 with 4,750)
-    and no variant has fewer bands, so both terms of the model are least for it; the shim's comment that names C = 3 at
-    8k x 128k describes the table before the bit-parallel bands.  So three shapes with three different picks do not exist, and
-    the library does not report its pick: the test asserts what the formula says (13 on a grid of shapes) and, at three shapes
-    with 8k x 128k among them, that schedule 0 equals the oracle and that every explicit band schedule does too."""
-    for la in (1, 63, 64, 65, 2048, 2049, 8192, 65_536, 131_072, 1 << 20, 1 << 22, (1 << 31) - 2):
-        for lb in (1, 31, 500, 8192, 65_536, 140_000, 1 << 20):
-            assert model_pick(la, lb) == 13, (la, lb)
+def test_every_band_schedule_equals_the_oracle_at_three_shapes(ctx, exp_ctx, port):
+    """Three shapes at which the step model that once chose among the value bands preferred different widths (C = 3 at
+    8k x 128k, C = 6 at 64k x 64k), 8k x 128k among them.  Schedule 0 is schedule 13 at every shape now, and
+    the library does not report a pick: the test asserts that schedule 0 equals the oracle and that every explicit band
+    schedule does too, in both argument orders."""
     rng = np.random.default_rng(1313)
     try:
         for lb, la in PICK_SHAPES:
@@ -182,10 +163,11 @@ def test_cost_model_picks(ctx, port):
                 y = _acgt(rng, lb)
                 want = port.edit_distance(x, y)
             dx, dy = _dev(ctx, x), _dev(ctx, y)
-            for v in [0] + sorted(BAND_VARIANTS):
-                ctx.set_ed_variant(v)
-                assert ctx.edit_distance_device(dx, dy) == want, (v, la, y.size)
-                assert ctx.edit_distance_device(dy, dx) == want, (v, y.size, la)
+            for v in BAND_SCHEDULES:
+                c = ctx if v in (0, 13) else exp_ctx
+                c.set_ed_variant(v)
+                assert c.edit_distance_device(dx, dy) == want, (v, la, y.size)
+                assert c.edit_distance_device(dy, dx) == want, (v, y.size, la)
     finally:
         ctx.set_ed_variant(0)
 
@@ -208,5 +190,7 @@ def test_argument_limits(ctx):
     assert L.bmx_edit_distance_device(ctx._h, None, 0, p, (1 << 31) - 1, C.byref(d), None) == host.OK
     assert d.value == (1 << 31) - 1
     big = torch.zeros(3_000_000, dtype=torch.uint8, device=one.device)
+    assert ctx.edit_distance_device(big[:100], big[:300]) == 200 and ctx.last_edit_distance_ms() > 0.0
     assert ctx.edit_distance_device(big[:0], big) == 3_000_000
+    assert ctx.last_edit_distance_ms() == -1.0  # (no kernel ran: the time of the call before is gone)
     assert ctx.edit_distance_device(big, big[:0]) == 3_000_000

@@ -3,6 +3,7 @@ import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
+host.use_library("exp")  # the schedules that lost exist in libbmx_exp.so alone
 rng = np.random.default_rng(5)
 ctx = host.Context(0)
 for n in (512, 2048, 4096, 8192, 16384, 32768):

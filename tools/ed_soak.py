@@ -6,6 +6,7 @@ import numpy as np, torch
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
 ap = argparse.ArgumentParser(); ap.add_argument("--reps", type=int, default=40)
 args = ap.parse_args()
+host.use_library("exp")  # the schedules that lost exist in libbmx_exp.so alone
 rng = np.random.default_rng(9)
 ctx = host.Context(0)
 bad = 0

@@ -5,6 +5,7 @@ import numpy as np, torch
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
 ap = argparse.ArgumentParser(); ap.add_argument("--n", type=int, default=65536); ap.add_argument("--rounds", type=int, default=3)
 args = ap.parse_args()
+host.use_library("exp")  # the schedules that lost exist in libbmx_exp.so alone
 rng = np.random.default_rng(5)
 x = torch.from_numpy((rng.integers(0, 4, args.n) + 65).astype(np.uint8)).cuda()
 z = torch.from_numpy((rng.integers(0, 4, args.n) + 65).astype(np.uint8)).cuda()
