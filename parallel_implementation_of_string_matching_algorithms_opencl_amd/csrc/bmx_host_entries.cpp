@@ -193,6 +193,20 @@ int bmx_suffix_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_
     return c.rc;
 }
 
+int bmx_lcp_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out, int32_t *lcp_out)
+{
+    if (!bmx_lcp_args_ok(text, n, lcp_out)) return BMX_ERR_ARG;
+    HostCall c("bmx_lcp_array", ctx_in);
+    void *d_text = c.upload(text, n);
+    int32_t *d_sa = c.alloc<int32_t>(n * sizeof(int32_t));
+    int32_t *d_lcp = c.alloc<int32_t>(n * sizeof(int32_t));
+    if (c.rc == BMX_OK) c.rc = bmx_suffix_array_device(c.ctx(), d_text, n, d_sa, nullptr);
+    if (c.rc == BMX_OK) c.rc = bmx_lcp_array_device(c.ctx(), d_text, n, d_sa, d_lcp, nullptr);
+    if (c.rc == BMX_OK) c.download(lcp_out, d_lcp, n * sizeof(int32_t), "the LCP array");
+    if (c.rc == BMX_OK && sa_out) c.download(sa_out, d_sa, n * sizeof(int32_t), "the suffix array");
+    return c.rc;
+}
+
 } // extern "C"
 
 namespace {

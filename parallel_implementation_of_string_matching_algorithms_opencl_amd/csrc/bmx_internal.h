@@ -110,6 +110,14 @@ int bmx_internal_index_locate(void **state, const bmx_index *ix, const void *d_p
                               uint64_t *n_matches, int use_dir, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_index_state_free(void *state);
 float bmx_internal_index_ms(const void *state);
+// bmx_lcp.hip
+int bmx_internal_lcp(void **state, const uint8_t *d_text, uint32_t n, const int32_t *d_sa, int32_t *d_lcp, hipStream_t stream,
+                     char *err, size_t errlen);
+int bmx_internal_lcp_stats(void **state, const int32_t *d_lcp, uint32_t n, uint32_t min_len, uint64_t out[4], hipStream_t stream,
+                           char *err, size_t errlen);
+void bmx_internal_lcp_free(void *state);
+float bmx_internal_lcp_ms(const void *state);
+int64_t bmx_internal_lcp_long_pairs(const void *state);
 
 // ---- argument checks: every argument error, before any HIP call (the CPU suite calls the entries with ctx = NULL) ----
 
@@ -162,6 +170,9 @@ inline int bmx_dict_patterns_ok(const char *const *pats, const int32_t *ms, int3
             if ((uint8_t)pats[i][j] >= 0x80) return BMX_ERR_DOMAIN;
     return BMX_OK;
 }
+
+// the LCP array: the text (host or device), its length, the output
+inline bool bmx_lcp_args_ok(const void *text, uint64_t n, const void *lcp) { return text && lcp && n >= 1 && n < (1ull << 31); }
 
 // a query call of the text index
 inline bool bmx_index_query_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, const void *out)

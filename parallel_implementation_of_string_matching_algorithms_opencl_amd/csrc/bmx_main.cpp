@@ -17,8 +17,11 @@
 //   bmx_cli --edit-distance A B [--iters N]   the reference's second program (EditDistance-1.cpp:
 //                             two strings from files -- it opens str1.txt twice, :94-95 -- the mean time
 //                             of the runs and the distance, :358-383)
-//   bmx_cli --suffix-array F [--iters N] [--max-print K]   its third (SuffixArrays.cpp: text from
-//                             input.txt, :181; array printed, :155-161; mean time, :514)
+//   bmx_cli --suffix-array F [--lcp] [--iters N] [--max-print K]   its third (SuffixArrays.cpp: text from
+//                             input.txt, :181; array printed, :155-161; mean time, :514).  With --lcp (no counterpart
+//                             in the reference) the LCP array is computed as well (bmx_lcp_array): its first --max-print
+//                             values follow the array's, and one more line gives the longest repeat (length and two
+//                             positions), the number of distinct substrings and the LCP kernels' time
 //   bmx_cli --approx K [--text F] [--pattern F] [--iters N] [--positions] [--max-print K]
 //                             approximate search (no counterpart in the reference): every end of a match
 //                             with at most K edits, on the resident text; prints the hit count, the first
@@ -127,7 +130,7 @@ int main(int argc, char **argv)
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
-    bool positions = false, spans = false, spans_best = false;
+    bool positions = false, spans = false, spans_best = false, with_lcp = false;
     uint64_t max_print = 32;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -149,6 +152,7 @@ int main(int argc, char **argv)
         else if (a == "--approx") approx_k = atoi(need("--approx"));
         else if (a == "--spans") spans = true;
         else if (a == "--best") spans_best = true;
+        else if (a == "--lcp") with_lcp = true;
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--index-count") index_path = need("--index-count");
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
@@ -328,13 +332,16 @@ int main(int argc, char **argv)
                 fprintf(stderr, "File Not Found!\n"); // SuffixArrays.cpp:185
                 return 1;
             }
-            std::vector<int32_t> sa(t.size() ? t.size() : 1);
-            for (int it = 0; it < iters; ++it) {
+            std::vector<int32_t> sa(t.size() ? t.size() : 1), lcp;
+            with_lcp = with_lcp && !t.empty(); // (an empty text has neither)
+            if (with_lcp) lcp.resize(t.size());
+            for (int it = 0; it < iters || (with_lcp && it == 0); ++it) {
                 auto t0 = std::chrono::steady_clock::now();
-                rc = bmx_suffix_array(ctx, t.data(), t.size(), sa.data());
+                rc = with_lcp ? bmx_lcp_array(ctx, t.data(), t.size(), sa.data(), lcp.data())
+                              : bmx_suffix_array(ctx, t.data(), t.size(), sa.data());
                 auto t1 = std::chrono::steady_clock::now();
                 if (rc != BMX_OK) {
-                    fprintf(stderr, "bmx_suffix_array failed: %d (%s)\n", rc, bmx_last_error());
+                    fprintf(stderr, "%s failed: %d (%s)\n", with_lcp ? "bmx_lcp_array" : "bmx_suffix_array", rc, bmx_last_error());
                     return 1;
                 }
                 total += std::chrono::duration<double>(t1 - t0).count();
@@ -342,6 +349,20 @@ int main(int argc, char **argv)
             printf("%llu\n", (unsigned long long)t.size()); // :198
             for (uint64_t i = 0; i < t.size() && i < max_print; ++i) printf("%d ", sa[i]); // :158-160
             printf("\n");
+            if (with_lcp) {
+                uint64_t sum = 0, best = 0;
+                for (uint64_t j = 0; j < lcp.size(); ++j) {
+                    sum += (uint64_t)lcp[j];
+                    if (lcp[j] > lcp[best]) best = j;
+                }
+                const uint64_t n = t.size();
+                for (uint64_t i = 0; i < n && i < max_print; ++i) printf("%d ", lcp[i]);
+                printf("\n");
+                if (lcp[best] > 0) printf("Longest repeat = %d at %d and %d", lcp[best], sa[best - 1], sa[best]);
+                else printf("Longest repeat = 0");
+                printf(", distinct substrings = %llu, LCP kernels = %f ms\n", (unsigned long long)(n * (n + 1) / 2 - sum),
+                       bmx_last_lcp_ms(ctx));
+            }
             if (iters > 0) printf("Average Time  = %f\n", total / iters); // :514
         }
         bmx_ctx_destroy(ctx);

@@ -179,6 +179,7 @@ struct bmx_ctx {
     int last_variant = 0;    // what the most recent search ran (bmx_scan_geometry reports it)
     void *ed = nullptr; // edit distance: the band pipeline's workspace, last ms, stamps, events (bmx_ed.hip)
     void *sa = nullptr; // suffix array: workspace, pinned round counters, last ms and round counts (bmx_sa.hip)
+    void *lcp = nullptr; // LCP array: workspace, status words, statistics partials, events, last ms and long pairs (bmx_lcp.hip)
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
@@ -528,6 +529,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     if (ctx->order_stream) (void)hipStreamDestroy(ctx->order_stream);
     bmx_internal_ed_free(ctx->ed);
     bmx_internal_sa_free(ctx->sa);
+    bmx_internal_lcp_free(ctx->lcp);
     bmx_internal_approx_free(ctx->approx);
     bmx_internal_classes_free(ctx->classes);
     bmx_internal_ed_batch_free(ctx->ed_batch);
@@ -1189,6 +1191,24 @@ int bmx_suffix_array_device(bmx_ctx *ctx, const void *d_text, uint64_t n, int32_
 float bmx_last_suffix_array_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_sa_ms(ctx->sa) : -1.0f; }
 int bmx_last_suffix_array_rounds(bmx_ctx *ctx) { return ctx ? bmx_internal_sa_rounds(ctx->sa) : 0; }
 int bmx_last_suffix_array_lds_rounds(bmx_ctx *ctx) { return ctx ? bmx_internal_sa_lds_rounds(ctx->sa) : 0; }
+
+// ---- LCP array over the suffix array (bmx_lcp.hip) ---------------------------------------------
+int bmx_lcp_array_device(bmx_ctx *ctx, const void *d_text, uint64_t n, const int32_t *d_sa, int32_t *d_lcp, void *stream_v)
+{
+    if (!bmx_lcp_args_ok(d_text, n, d_lcp) || !d_sa || !ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_lcp(&ctx->lcp, (const uint8_t *)d_text, (uint32_t)n, d_sa, d_lcp, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_lcp_stats_device(bmx_ctx *ctx, const int32_t *d_lcp, uint64_t n, uint32_t min_len, uint64_t out[4], void *stream_v)
+{
+    if (!d_lcp || !out || n == 0 || n >= (1ull << 31) || !ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_lcp_stats(&ctx->lcp, d_lcp, (uint32_t)n, min_len, out, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_lcp_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_lcp_ms(ctx->lcp) : -1.0f; }
+int64_t bmx_last_lcp_long_pairs(bmx_ctx *ctx) { return ctx ? bmx_internal_lcp_long_pairs(ctx->lcp) : -1; }
 
 // ---- approximate search (bmx_approx.hip) -------------------------------------------------------
 int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,

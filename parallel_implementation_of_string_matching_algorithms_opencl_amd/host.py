@@ -43,6 +43,7 @@ SPANS_BLOCK = 256  # list entries per workgroup of the starts kernel (csrc/bmx_s
 SPANS_TILE = 2048  # list entries per workgroup of the selection
 MAX_DICT = 65536
 ED_BATCH_WORD = 64
+LCP_LANE_BYTES = 64  # a pair with a longer common prefix leaves the one-lane path of the LCP array (BMX_LCP_LANE_BYTES)
 ED_BATCH_LONG = 65536
 ED_NO_LIMIT = 0xFFFFFFFF
 BAD_TABLE_SIZE = 128
@@ -155,6 +156,11 @@ SYMBOLS = [
     ("bmx_last_suffix_array_ms", C.c_float, [C.c_void_p]),
     ("bmx_last_suffix_array_rounds", C.c_int, [C.c_void_p]),
     ("bmx_last_suffix_array_lds_rounds", C.c_int, [C.c_void_p]),
+    ("bmx_lcp_array_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("bmx_lcp_array", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("bmx_lcp_stats_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p]),
+    ("bmx_last_lcp_ms", C.c_float, [C.c_void_p]),
+    ("bmx_last_lcp_long_pairs", C.c_int64, [C.c_void_p]),
     ("bmx_index_create_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("bmx_index_destroy", None, [C.c_void_p]),
     ("bmx_index_sa", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -894,6 +900,53 @@ class Context:
     def last_suffix_array_lds_rounds(self) -> int:
         return int(self._L.bmx_last_suffix_array_lds_rounds(self._h))
 
+    # -- LCP array over the suffix array, with repeat statistics ---------------------
+    def lcp_array_device(self, d_text, sa, *, n: Optional[int] = None, out=None):
+        """int32 CUDA tensor (bmx_lcp_array_device): lcp[0] = 0, lcp[j] = the common prefix, in plain bytes, of the suffixes
+        sa[j - 1] and sa[j] of the resident text ``d_text`` (uint8 CUDA tensor).  ``sa``: an int32 CUDA tensor, any
+        permutation of 0..n-1.  Runs on torch's current stream."""
+        import torch
+
+        n = d_text.numel() if n is None else n
+        if d_text.element_size() != 1 or sa.element_size() != 4 or sa.numel() < n or d_text.numel() < n:
+            raise ValueError("d_text: 1-byte entries; sa: 4-byte entries, one per text byte")
+        lcp = out if out is not None else torch.empty(max(n, 1), dtype=torch.int32, device=d_text.device)
+        if lcp.element_size() != 4 or lcp.numel() < n:
+            raise ValueError("out: 4-byte entries, one per text byte")
+        stream = C.c_void_p(torch.cuda.current_stream(d_text.device).cuda_stream)
+        self._chk(self._L.bmx_lcp_array_device(self._h, C.c_void_p(d_text.data_ptr()), n, C.c_void_p(sa.data_ptr()),
+                                               C.c_void_p(lcp.data_ptr()), stream), "bmx_lcp_array_device")
+        return lcp[:n]
+
+    def lcp_array(self, text) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_lcp_array): (sa, lcp), both int32, the array in the order suffix_array gives."""
+        pt, n, keep = _host_text(text)
+        sa = np.empty(max(n, 1), dtype=np.int32)
+        lcp = np.empty(max(n, 1), dtype=np.int32)
+        self._chk(self._L.bmx_lcp_array(self._h, pt, n, C.c_void_p(sa.ctypes.data), C.c_void_p(lcp.ctypes.data)), "bmx_lcp_array")
+        del keep
+        return sa[:n].copy(), lcp[:n].copy()
+
+    def lcp_stats_device(self, lcp, min_len: int = 0) -> dict:
+        """{max, argmax (the smallest j that attains the max), sum, count (entries >= min_len)} of an int32 CUDA tensor
+        (bmx_lcp_stats_device), Python ints.  Runs on torch's current stream."""
+        import torch
+
+        if lcp.element_size() != 4:
+            raise ValueError("lcp: 4-byte entries")
+        out = (C.c_uint64 * 4)()
+        stream = C.c_void_p(torch.cuda.current_stream(lcp.device).cuda_stream)
+        self._chk(self._L.bmx_lcp_stats_device(self._h, C.c_void_p(lcp.data_ptr()), lcp.numel(), min_len, out, stream),
+                  "bmx_lcp_stats_device")
+        return {"max": int(out[0]), "argmax": int(out[1]), "sum": int(out[2]), "count": int(out[3])}
+
+    def last_lcp_ms(self) -> float:
+        return float(self._L.bmx_last_lcp_ms(self._h))
+
+    def last_lcp_long_pairs(self) -> int:
+        """Pairs of the last lcp_array_device whose common prefix exceeded LCP_LANE_BYTES."""
+        return int(self._L.bmx_last_lcp_long_pairs(self._h))
+
     # -- synthetic corpus in HBM ------------------------------------------
     def gen_text(self, d_dst, start: int, seed: int, kind: int = 0, length: Optional[int] = None):
         import torch
@@ -1020,6 +1073,7 @@ class Index:
         self._ctx = ctx
         self._L = ctx._L
         self._text, self._sa_in = d_text, sa
+        self._lcp = None
         self.n = d_text.numel()
         self._h = C.c_void_p()
         stream = C.c_void_p(torch.cuda.current_stream(d_text.device).cuda_stream)
@@ -1032,7 +1086,7 @@ class Index:
         if self._h:
             self._L.bmx_index_destroy(self._h)
             self._h = C.c_void_p()
-            self._text = self._sa_in = None
+            self._text = self._sa_in = self._lcp = None
 
     def __del__(self):
         try:
@@ -1045,6 +1099,27 @@ class Index:
 
     def __exit__(self, *exc):
         self.close()
+
+    def lcp(self):
+        """The LCP array of the index's suffix array (Context.lcp_array_device), an int32 CUDA tensor: computed on first
+        use, kept until close()."""
+        if self._lcp is None:
+            self._lcp = self._ctx.lcp_array_device(self._text, self.sa, n=self.n)
+        return self._lcp
+
+    def longest_repeat(self) -> Tuple[int, Optional[int], Optional[int]]:
+        """(length, p, q): the longest substring that occurs twice, at p = sa[j - 1] and q = sa[j] for the smallest such j;
+        (0, None, None) if no byte occurs twice."""
+        st = self._ctx.lcp_stats_device(self.lcp())
+        if st["max"] == 0:
+            return 0, None, None
+        j = st["argmax"]
+        pq = self.sa[j - 1:j + 1].cpu().tolist()
+        return st["max"], int(pq[0]), int(pq[1])
+
+    def distinct_substrings(self) -> int:
+        """The number of distinct non-empty substrings of the text: n (n + 1) / 2 - sum(lcp)."""
+        return self.n * (self.n + 1) // 2 - self._ctx.lcp_stats_device(self.lcp())["sum"]
 
     @property
     def sa(self):
@@ -1273,6 +1348,21 @@ def edit_distance_batch(a, b, limit: Optional[int] = None) -> np.ndarray:
 def index_count(text, patterns) -> np.ndarray:
     """Occurrences of every pattern in ``text`` through a text index built for the call (bmx_index_count), uint32."""
     return default_context().index_count(text, patterns)
+
+
+def lcp_array(text) -> Tuple[np.ndarray, np.ndarray]:
+    """text -> (sa, lcp): the suffix array and the LCP array over it (bmx_lcp_array), int32."""
+    return default_context().lcp_array(text)
+
+
+def longest_repeat(text) -> Tuple[int, Optional[int], Optional[int]]:
+    """text -> (length, p, q): the longest substring that occurs twice and two of its positions, or (0, None, None).
+    (For a text that does not end in two or more bytes 96, as the text index.)"""
+    sa, lcp = lcp_array(text)
+    if lcp.size == 0 or int(lcp.max()) == 0:
+        return 0, None, None
+    j = int(lcp.argmax())
+    return int(lcp[j]), int(sa[j - 1]), int(sa[j])
 
 
 def search_dict(text, patterns) -> Tuple[np.ndarray, np.ndarray]:
