@@ -1,7 +1,7 @@
-// bmx_internal.h -- what the library's translation units share and the C ABI (include/bmx.h) does not show: the
-// bmx_internal_* functions the shim calls (included by the shim and by every file that defines one, so a changed
+// bmx_internal.h -- what the library's translation units share and the C ABI (include/bmx.h) does not show: the context
+// (struct bmx_ctx), the bmx_internal_* functions the shim calls (included by the shim and by every file that defines one, so a changed
 // signature fails to compile), the HIP-check macro of the per-feature files, and the argument checks that the device
-// entries (bmx_shim.hip) and the host-buffer entries (bmx_host_entries.cpp) both make before any HIP call.
+// entries (bmx_shim.hip, bmx_scan.hip) and the host-buffer entries (bmx_host_entries.cpp) both make before any HIP call.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -33,6 +33,17 @@ inline uint32_t ceil_log2(uint64_t x)
 
 // bmx_shim.hip: the text bmx_last_error() returns on this thread
 void bmx_internal_set_error(const char *text);
+char *bmx_internal_error_buffer(size_t *len); // ... and its buffer (thread-local), for a file that formats its own messages
+// bmx_scan.hip: the exact search's state, made eagerly with the context (the first HIP error, or hipSuccess; *state is
+// set either way).  Its entry points of the C ABI are defined in that file.  What (libbmx_exp.so) bmx_exp_set_knob sets:
+struct bmx_scan_knobs {
+    bool text_sample = true;     // false: the walker goes by the pattern's symbols, not the text's
+    int max_grid = 0;            // > 0: at most this many workgroups per scan (small texts then reach the stolen tail)
+    bool no_dense = false;       // true: no fill pass (a full parking buffer appends the direct way)
+    bool multi_no_qgram = false; // true: the multi-pattern pass walks byte-wise only
+};
+hipError_t bmx_internal_scan_create(void **state);
+void bmx_internal_scan_free(void *state);
 // bmx_sort.hip
 int bmx_internal_radix_sort(uint64_t *d_keys, uint64_t n, unsigned end_bit, void **scratch, size_t *scratch_bytes, hipStream_t stream,
                             char *err, size_t errlen);
@@ -118,6 +129,29 @@ int bmx_internal_lcp_stats(void **state, const int32_t *d_lcp, uint32_t n, uint3
 void bmx_internal_lcp_free(void *state);
 float bmx_internal_lcp_ms(const void *state);
 int64_t bmx_internal_lcp_long_pairs(const void *state);
+
+// ---- the context: the device, the switches and one opaque state per feature (made on first use and owned by the
+// feature's file; the exact search's eagerly) ----
+struct bmx_ctx {
+    int device = 0;
+    int num_cu = 256;
+    // Measurement / test switches.  Only libbmx_exp.so can change them (bmx_exp_set_knob); in the product library they keep
+    // these values and nothing reads the environment.
+    bmx_scan_knobs scan_knobs;
+    bmx_ed_knobs ed_knobs;     // edit distance: the schedule (bmx_set_ed_variant) and the band pipeline's switches
+    int sa_flags = 0;          // suffix array: 1 = library rounds only, 2 = a host wait per round, 4 = per-round trace on stderr
+    bool index_no_dir = false; // libbmx_exp.so: queries search the whole array, not their directory bucket
+    void *scan = nullptr; // exact search: variant choice, counters, buckets, status words, event ring, last launch (bmx_scan.hip)
+    void *ed = nullptr; // edit distance: the band pipeline's workspace, last ms, stamps, events (bmx_ed.hip)
+    void *sa = nullptr; // suffix array: workspace, pinned round counters, last ms and round counts (bmx_sa.hip)
+    void *lcp = nullptr; // LCP array: workspace, status words, statistics partials, events, last ms and long pairs (bmx_lcp.hip)
+    void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
+    void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
+    void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
+    void *spans = nullptr; // match spans: status words, tile counts of the selection, events (bmx_spans.hip)
+    void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
+    void *index = nullptr;  // text index: status words, events, workspace of count / locate (bmx_index.hip)
+};
 
 // ---- argument checks: every argument error, before any HIP call (the CPU suite calls the entries with ctx = NULL) ----
 

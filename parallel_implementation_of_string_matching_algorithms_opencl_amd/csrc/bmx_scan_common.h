@@ -782,7 +782,7 @@ __device__ __forceinline__ void fill_tile_short(const ScanArgs &a, const LdsTabl
     uint64_t at = tile_out + before;
     ShortTile<BLOCK, TILE> st;
     st.setup(tb, lo_t, hi_t, wave, lane, false);
-    constexpr uint32_t BATCH = TILE <= 68u * 1024u ? 512u : 128u; // (what fits beside two tiles: bmx_shim.hip sizes the launch by it)
+    constexpr uint32_t BATCH = TILE <= 68u * 1024u ? 512u : 128u; // (what fits beside two tiles: bmx_scan.hip sizes the launch by it)
     static_assert(BLOCK == 1024, "sixteen waves share the area");
     const uint32_t area = (uint32_t)(uintptr_t)tb.fill_area + wave * (BATCH * 2u); // this wave's two-byte slots (LDS byte address)
 #pragma unroll

@@ -2,7 +2,7 @@
 // path: a dense-hit text (e.g. "aaaa..." / "aa") yields about one match per byte.
 // rocPRIM's device radix sort is used as a library here; it is not the hot op
 // (the scan is) and it only runs when bmx_search_device_finish() finds that the
-// in-LDS bitonic sort of bmx_aux_kernels.h did not apply.  Kept in its own
+// in-LDS bitonic sort of bmx_order_kernels.h did not apply.  Kept in its own
 // translation unit because the rocPRIM headers dominate compile time.
 #include <hip/hip_runtime.h>
 #include <cstring>

@@ -1,4 +1,4 @@
-// bmx_variants_product.inc -- the slots of the kernel table that libbmx.so contains (included by bmx_shim.hip inside the
+// bmx_variants_product.inc -- the slots of the kernel table that libbmx.so contains (included by bmx_scan.hip inside the
 // table's constructor; SLOT(i, entry) fills slot i).  Slot numbers are stable: tools/ and DESIGN.md refer to them.
 // Everything here is parity-tested (tests/test_gpu_parity.py::PRODUCT_VARIANTS) and selectable with bmx_set_variant.
     SLOT(0, BMX_TILE_F(1024, 68, 2, 0)); // 0: PRODUCT -- 16 waves share a 68 KiB tile, nt DMA, byte-wise walker

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 AUTO = -1
 SAD_SLOTS = (87, 88)  # quad-SAD skip loops: lanes own 80-byte filter segments
 SAD_SEG = 80  # bmx_scan_common.h SAD_SEG: a constant of the walker that bmx_scan_geometry does not report
-# Matches in one tile: every stage_cap that stage_cap_for (bmx_shim.hip) can choose, and its neighbours.
+# Matches in one tile: every stage_cap that stage_cap_for (bmx_scan.hip) can choose, and its neighbours.
 KS = [63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025]
 # The slots pick_variant can return.  Slots 79 and 82 need safe non-canonical tables on a large alphabet (82 only once the
 # text's alphabet is known, i.e. on a resident text); 54 needs a text over 2 or 3 symbols and m = 6..8.
@@ -435,7 +435,7 @@ def _scans(ctx):
 
 def _multi_check(rig, text, pats, what, cap=None):
     """One bmx_search_device_multi call against the oracle.  Returns (total, scan kernels the call launched): 1 when the
-    one-pass kernel's result stood, 1 + K when the call went the exact way pattern by pattern (bmx_shim.hip: one_by_one)."""
+    one-pass kernel's result stood, 1 + K when the call went the exact way pattern by pattern (bmx_scan.hip: one_by_one)."""
     d = rig.put(text)
     wants = [rig.port.search(text, p) for p in pats]
     total = sum(w.size for w in wants)
@@ -455,7 +455,7 @@ def _multi_check(rig, text, pats, what, cap=None):
     return total, launched
 
 
-# The multi-pattern pass parks up to 512 matches per tile (bmx_shim.hip, the stage_cap loop of bmx_search_device_multi:
+# The multi-pattern pass parks up to 512 matches per tile (bmx_scan.hip, the stage_cap loop of bmx_search_device_multi:
 # the largest of 512/256/128/64 with lds_fixed + 2 x cap x 8 + 32 <= 160 KiB).  On these backgrounds (sigma 128: no 8-gram
 # rule, 68 KiB tiles) lds_fixed = 2 x (69632 + halo16) + tables + 512 + 2 x ceil8(m_max) + ceil16(m_max) + 512, and the
 # tables are 512 + ceil16(2m) + ceil16(m) bytes per pattern:
