@@ -32,7 +32,8 @@
  *   bmx_search_classes    no counterpart in the reference: a pattern position is a set of byte values (wildcards,
  *                         sets, case folding, IUPAC codes), matched by Shift-And (section below)
  *   bmx_index_*           no counterpart: pattern count and locate by binary search over the array bmx_suffix_array
- *                         builds, in the order it builds it (section below)
+ *                         builds, in the order it builds it; the longest match at every query position and the
+ *                         seeds among them (section below)
  *
  * Semantics (bit-exact with the reference kernel run as one work-item over
  * [0, n-1]): match_positions receives, in ascending order, every
@@ -660,7 +661,45 @@ int bmx_index_count(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_
 int bmx_index_locate(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
                      const uint64_t *pat_off, uint64_t count, uint64_t *out_off /* count + 1 */, uint64_t *pos, uint64_t capacity,
                      uint64_t *n_matches);
-/* Device time (ms, HIP events around the query kernels) of the last count / locate call on ctx; < 0 if none. */
+/* Matching statistics and seeds: what read seeding needs when the whole query does not occur (a 150-byte read with one
+ * substitution has a count of 0).  Index, text and query column are those of bmx_index_count_device.
+ * match: entry b of each output belongs to blob byte b.  For byte b of query q, at position i = b - off[q] with
+ * m = off[q+1] - off[q]: d_len[b] = the largest l <= m - i such that query[i .. i+l) occurs in the text (p + l <= n, plain
+ * byte equality; the match never runs into the next query); 0 if query[i] occurs nowhere.  d_lo[b], d_cnt[b] (either may
+ * be NULL) = the interval of the array whose suffixes begin with query[i .. i+len): cnt occurrences, sa[lo .. lo+cnt)
+ * their starts; both 0 with len 0.  Within a query len[b+1] >= len[b] - 1.  Entries of blob bytes outside every query
+ * (b < off[0] or b >= off[count]) are left untouched.
+ * seeds: position i of query q is a seed for (min_len, max_occ) iff len >= min_len, and i == 0 or len[i-1] <= len[i] (the
+ * match is not contained in the match of the position before it, hence in none of that query: the query's super-maximal
+ * exact matches, each maximal in the text in both directions), and max_occ == 0 or cnt <= max_occ (a dropped seed is
+ * not replaced by anything).  d_seed_off (count + 1 entries) = the exclusive prefix sum of the seeds per query, always
+ * written in full, so d_seed_off[count] == *n_seeds == the true total.  The seeds are listed in order of (query,
+ * position) as four parallel arrays of `capacity` entries: position in the query, len, lo, cnt.  capacity 0 counts only
+ * (the four pointers may be NULL).  A total above `capacity` returns BMX_ERR_CAPACITY with the first `capacity` seeds of
+ * that order stored.  The list is the same in every run (no atomics).  The text positions of a seed are
+ * sa[lo .. lo+cnt) of bmx_index_sa, in array order.
+ * One call takes fewer than 2^31 - 1 blob bytes and fewer than 2^31 - 1 queries (BMX_ERR_ARG beyond).
+ * Errors: NULL pointers where count > 0, min_len == 0 and an index of another context return BMX_ERR_ARG before any HIP
+ * call, with ctx = NULL too (the host entries: n == 0 or n >= 2^31 as well); count == 0 returns BMX_OK and launches
+ * nothing (*n_seeds = 0).  Offsets, lengths and bytes are checked as by count: on the host by the host entries, in the
+ * kernel by the device entries (a bad lane reads neither text nor array; BMX_ERR_ARG, or BMX_ERR_DOMAIN for a byte >=
+ * 0x80; outputs unspecified).  All device work goes on `stream`; the calls return after synchronising it, once. */
+int bmx_index_match_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes,
+                           const uint64_t *d_pat_off, uint64_t count, uint32_t *d_len /* pat_bytes entries */,
+                           uint32_t *d_lo /* may be NULL */, uint32_t *d_cnt /* may be NULL */, void *stream);
+int bmx_index_seeds_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes,
+                           const uint64_t *d_pat_off, uint64_t count, uint32_t min_len, uint32_t max_occ /* 0: no limit */,
+                           uint64_t *d_seed_off /* count + 1 */, uint32_t *d_qpos, uint32_t *d_len, uint32_t *d_lo,
+                           uint32_t *d_cnt, uint64_t capacity, uint64_t *n_seeds, void *stream);
+/* Host buffers in, host buffers out, an index built for the call (len, lo, cnt: pat_bytes entries; lo, cnt may be NULL). */
+int bmx_index_match(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
+                    const uint64_t *pat_off, uint64_t count, uint32_t *len, uint32_t *lo, uint32_t *cnt);
+/* The same for bmx_index_seeds_device (what bmx_cli --index-seeds prints comes through it). */
+int bmx_index_seeds(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
+                    const uint64_t *pat_off, uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *seed_off,
+                    uint32_t *qpos, uint32_t *len, uint32_t *lo, uint32_t *cnt, uint64_t capacity, uint64_t *n_seeds);
+/* Device time (ms, HIP events around the query kernels) of the last count / locate / match / seeds call on ctx; < 0 if
+ * none. */
 float bmx_last_index_ms(bmx_ctx *ctx);
 /* Device time (ms) of the index's creation: the suffix array if it was built here, plus the directory. */
 float bmx_index_build_ms(const bmx_index *ix);

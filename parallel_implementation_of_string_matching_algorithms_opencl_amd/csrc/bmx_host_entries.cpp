@@ -420,4 +420,71 @@ int bmx_index_locate(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *
     return c.rc;
 }
 
+int bmx_index_match(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                    uint64_t count, uint32_t *len, uint32_t *lo, uint32_t *cnt)
+{
+    if (!text || n == 0 || n >= (1ull << 31) || !bmx_index_query_args_ok(pat, pat_off, count, len)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (qrc != BMX_OK) return qrc;
+    HostCall c("bmx_index_match", ctx_in);
+    bmx_index *ix = nullptr;
+    // (only the bytes inside the queries come back: the caller's entries outside them stay as they are)
+    const uint64_t at = pat_off[0], used = pat_off[count] - at;
+    void *d_text = c.upload(text, n);
+    void *d_pat = c.upload(pat, pat_bytes);
+    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+    uint32_t *d_len = c.alloc<uint32_t>(pat_bytes * sizeof(uint32_t));
+    uint32_t *d_lo = lo ? c.alloc<uint32_t>(pat_bytes * sizeof(uint32_t)) : nullptr;
+    uint32_t *d_cnt = cnt ? c.alloc<uint32_t>(pat_bytes * sizeof(uint32_t)) : nullptr;
+    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
+    if (c.rc == BMX_OK) c.rc = bmx_index_match_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, d_len, d_lo, d_cnt, nullptr);
+    if (c.rc == BMX_OK) {
+        c.download(len + at, d_len + at, used * sizeof(uint32_t), "the match lengths");
+        if (lo) c.download(lo + at, d_lo + at, used * sizeof(uint32_t), "the interval starts");
+        if (cnt) c.download(cnt + at, d_cnt + at, used * sizeof(uint32_t), "the interval sizes");
+    }
+    bmx_index_destroy(ix); // before the context
+    return c.rc;
+}
+
+int bmx_index_seeds(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                    uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *seed_off, uint32_t *qpos, uint32_t *len,
+                    uint32_t *lo, uint32_t *cnt, uint64_t capacity, uint64_t *n_seeds)
+{
+    if (!text || n == 0 || n >= (1ull << 31) ||
+        !bmx_index_seeds_args_ok(pat, pat_off, count, min_len, seed_off, qpos, len, lo, cnt, capacity))
+        return BMX_ERR_ARG;
+    if (n_seeds) *n_seeds = 0;
+    if (count == 0) return BMX_OK;
+    const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (qrc != BMX_OK) return qrc;
+    HostCall c("bmx_index_seeds", ctx_in);
+    bmx_index *ix = nullptr;
+    uint64_t total = 0;
+    // (no more seeds than blob bytes: a larger capacity needs no larger device lists)
+    const uint64_t dev_cap = std::min(capacity, pat_bytes);
+    void *d_text = c.upload(text, n);
+    void *d_pat = c.upload(pat, pat_bytes);
+    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+    uint64_t *d_seed_off = c.alloc<uint64_t>((count + 1) * sizeof(uint64_t));
+    uint32_t *d_out = dev_cap ? c.alloc<uint32_t>(4 * dev_cap * sizeof(uint32_t)) : nullptr;
+    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
+    if (c.rc == BMX_OK)
+        c.rc = bmx_index_seeds_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, min_len, max_occ, d_seed_off, d_out,
+                                      d_out ? d_out + dev_cap : nullptr, d_out ? d_out + 2 * dev_cap : nullptr,
+                                      d_out ? d_out + 3 * dev_cap : nullptr, dev_cap, &total, nullptr);
+    if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
+        const uint64_t stored = std::min(total, dev_cap) * sizeof(uint32_t);
+        c.download(seed_off, d_seed_off, (count + 1) * sizeof(uint64_t), "the seed offsets");
+        c.download(qpos, d_out, stored, "the seeds");
+        c.download(len, d_out + dev_cap, stored, "the seeds");
+        c.download(lo, d_out + 2 * dev_cap, stored, "the seeds");
+        c.download(cnt, d_out + 3 * dev_cap, stored, "the seeds");
+        if (n_seeds) *n_seeds = total;
+    }
+    bmx_index_destroy(ix); // before the context
+    return c.rc;
+}
+
 } // extern "C"

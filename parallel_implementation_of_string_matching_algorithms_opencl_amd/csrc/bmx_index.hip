@@ -2,10 +2,13 @@
 // owned suffix array, owned directory), and per context the status words, events and workspace of the two queries, kept
 // between calls.  count = one launch of index_count_kernel; locate = that, rocPRIM's exclusive scan of the counts, the
 // fill, rocPRIM's segmented radix sort of the 32-bit positions within their segments and the widening to base_offset + p.
+// match = one launch of index_match_kernel (one lane per blob byte); seeds = that into workspace, rocPRIM's exclusive scan
+// of the seed flags, the fill and the per-query offsets, with one wait at the end (bmx_index_match_kernel.h).
 // The argument checks and the context are the shim's (bmx_shim.hip); everything here runs on valid arguments.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
@@ -15,6 +18,7 @@
 
 #include "bmx.h"
 #include "bmx_index_kernel.h"
+#include "bmx_index_match_kernel.h"
 #include "bmx_internal.h"
 
 static_assert(bmx::INDEX_MAX_PATTERN == BMX_MAX_PATTERN, "header and kernel disagree");
@@ -105,6 +109,43 @@ int status_rc(const uint64_t *h_ws, const char *what, char *err, size_t errlen)
 }
 
 uint32_t blocks_for(uint64_t items) { return (uint32_t)((items + bmx::INDEX_BLOCK - 1) / bmx::INDEX_BLOCK); }
+
+// the per-position workspace (locate's keys, the seeds' per-byte arrays), grown when a call needs more
+int positions_ready(IndexHost *st, size_t need, const char *what, char *err, size_t errlen)
+{
+    if (need <= st->p_bytes) return BMX_OK;
+    if (st->d_p) (void)hipFree(st->d_p);
+    st->d_p = nullptr;
+    st->p_bytes = 0;
+    BMX_HIP(what, hipMalloc(&st->d_p, need));
+    st->p_bytes = need;
+    return BMX_OK;
+}
+
+bmx::IndexMatchArgs make_match_args(const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                                    uint64_t count, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, uint32_t *d_qpos, bool use_dir,
+                                    uint64_t *status)
+{
+    bmx::IndexMatchArgs a = {};
+    a.text = ix->d_text;
+    a.n = ix->n;
+    a.sa = ix->d_sa;
+    a.pat = static_cast<const uint8_t *>(d_pat);
+    a.pat_bytes = pat_bytes;
+    a.pat_off = d_pat_off;
+    a.count = count;
+    a.dir_lo = use_dir ? ix->d_dir : nullptr;
+    a.dir_cnt = use_dir ? ix->d_dir + bmx::INDEX_DIR_ENTRIES : nullptr;
+    a.len = d_len;
+    a.lo = d_lo;
+    a.cnt = d_cnt;
+    a.qpos = d_qpos;
+    a.status = status;
+    return a;
+}
+
+// one lane per blob byte, and one per query for its offsets
+bool match_sizes_ok(uint64_t pat_bytes, uint64_t count) { return pat_bytes < 0x7fffffffull && count < 0x7fffffffull; }
 
 } // namespace
 
@@ -329,4 +370,92 @@ int bmx_internal_index_locate(void **state_v, const bmx_index *ix, const void *d
         st->p_bytes = 0;
     }
     return rc_done;
+}
+
+int bmx_internal_index_match(void **state_v, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, int use_dir, hipStream_t stream,
+                             char *err, size_t errlen)
+{
+    const char *what = "bmx_index_match_device";
+    if (!match_sizes_ok(pat_bytes, count)) {
+        snprintf(err, errlen, "%s: 2^31 - 1 blob bytes or queries or more in one call", what);
+        return BMX_ERR_ARG;
+    }
+    IndexHost *st = nullptr;
+    const int rc = state_ready(state_v, 0, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    BMX_HIP(what, hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    BMX_HIP(what, hipEventRecord(st->ev[0], stream));
+    const bmx::IndexMatchArgs a =
+        make_match_args(ix, d_pat, pat_bytes, d_pat_off, count, d_len, d_lo, d_cnt, nullptr, use_dir != 0, st->d_ws);
+    hipLaunchKernelGGL(bmx::index_match_kernel, dim3(blocks_for(std::max(pat_bytes, count))), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, hipEventRecord(st->ev[1], stream));
+    BMX_HIP(what, hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
+    if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
+    return status_rc(st->h_ws, what, err, errlen);
+}
+
+int bmx_internal_index_seeds(void **state_v, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *d_seed_off, uint32_t *d_qpos,
+                             uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, uint64_t capacity, uint64_t *n_seeds, int use_dir,
+                             hipStream_t stream, char *err, size_t errlen)
+{
+    const char *what = "bmx_index_seeds_device";
+    if (!match_sizes_ok(pat_bytes, count)) {
+        snprintf(err, errlen, "%s: 2^31 - 1 blob bytes or queries or more in one call", what);
+        return BMX_ERR_ARG;
+    }
+    IndexHost *st = nullptr;
+    int rc = state_ready(state_v, 0, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+
+    // per blob byte: qpos, len, lo, cnt and the scan's slots (pat_bytes + 1 entries), then rocPRIM's temporary storage
+    const size_t arr_bytes = (((size_t)pat_bytes + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+    bmx::IndexSeedFlag flag = {nullptr, nullptr, nullptr, pat_bytes, min_len, max_occ};
+    auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), flag);
+    size_t scan_bytes = 0;
+    BMX_HIP(what, rocprim::exclusive_scan(nullptr, scan_bytes, flags, (uint32_t *)nullptr, uint32_t(0), (size_t)pat_bytes + 1,
+                                          rocprim::plus<uint32_t>(), stream));
+    rc = positions_ready(st, 5 * arr_bytes + scan_bytes, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    char *base = static_cast<char *>(st->d_p);
+    uint32_t *w_qpos = reinterpret_cast<uint32_t *>(base), *w_len = reinterpret_cast<uint32_t *>(base + arr_bytes);
+    uint32_t *w_lo = reinterpret_cast<uint32_t *>(base + 2 * arr_bytes), *w_cnt = reinterpret_cast<uint32_t *>(base + 3 * arr_bytes);
+    uint32_t *w_slot = reinterpret_cast<uint32_t *>(base + 4 * arr_bytes);
+    void *scan_tmp = base + 5 * arr_bytes;
+    flag.qpos = w_qpos, flag.len = w_len, flag.cnt = w_cnt;
+    flags = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), flag);
+
+    BMX_HIP(what, hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    BMX_HIP(what, hipMemsetAsync(w_qpos, 0xff, arr_bytes, stream)); // INDEX_NO_QUERY: no lane has answered for this byte
+    BMX_HIP(what, hipEventRecord(st->ev[0], stream));
+    const bmx::IndexMatchArgs a =
+        make_match_args(ix, d_pat, pat_bytes, d_pat_off, count, w_len, w_lo, w_cnt, w_qpos, use_dir != 0, st->d_ws);
+    hipLaunchKernelGGL(bmx::index_match_kernel, dim3(blocks_for(std::max(pat_bytes, count))), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, rocprim::exclusive_scan(scan_tmp, scan_bytes, flags, w_slot, uint32_t(0), (size_t)pat_bytes + 1,
+                                          rocprim::plus<uint32_t>(), stream));
+    if (capacity > 0 && pat_bytes > 0) {
+        hipLaunchKernelGGL(bmx::index_seed_fill_kernel, dim3(blocks_for(pat_bytes)), dim3(bmx::INDEX_BLOCK), 0, stream, flag, w_slot,
+                           w_lo, capacity, d_qpos, d_len, d_lo, d_cnt);
+        BMX_HIP(what, hipGetLastError());
+    }
+    hipLaunchKernelGGL(bmx::index_seed_off_kernel, dim3(blocks_for(count + 1)), dim3(bmx::INDEX_BLOCK), 0, stream, d_pat_off, count,
+                       pat_bytes, w_slot, d_seed_off, st->d_ws + 2);
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, hipEventRecord(st->ev[1], stream));
+    BMX_HIP(what, hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
+    if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
+    if (st->p_bytes > KEEP_BYTES) {
+        (void)hipFree(st->d_p);
+        st->d_p = nullptr;
+        st->p_bytes = 0;
+    }
+    rc = status_rc(st->h_ws, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    if (n_seeds) *n_seeds = st->h_ws[2];
+    return st->h_ws[2] > capacity ? BMX_ERR_CAPACITY : BMX_OK;
 }

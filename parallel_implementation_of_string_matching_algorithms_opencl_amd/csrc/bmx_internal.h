@@ -119,6 +119,13 @@ int bmx_internal_index_count(void **state, const bmx_index *ix, const void *d_pa
 int bmx_internal_index_locate(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
                               uint64_t count, uint64_t base_offset, uint64_t *d_out_off, uint64_t *d_pos, uint64_t capacity,
                               uint64_t *n_matches, int use_dir, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_index_match(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, int use_dir, hipStream_t stream,
+                             char *err, size_t errlen);
+int bmx_internal_index_seeds(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                             uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *d_seed_off, uint32_t *d_qpos,
+                             uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, uint64_t capacity, uint64_t *n_seeds, int use_dir,
+                             hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_index_state_free(void *state);
 float bmx_internal_index_ms(const void *state);
 // bmx_lcp.hip
@@ -212,6 +219,13 @@ inline bool bmx_lcp_args_ok(const void *text, uint64_t n, const void *lcp) { ret
 inline bool bmx_index_query_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, const void *out)
 {
     return count == 0 || (pat && pat_off && out);
+}
+// ... of its seeds: the offsets out, the four lists where there is room for any, and a smallest length
+inline bool bmx_index_seeds_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, uint32_t min_len, const void *seed_off,
+                                    const void *qpos, const void *len, const void *lo, const void *cnt, uint64_t capacity)
+{
+    if (min_len == 0) return false;
+    return count == 0 || (pat && pat_off && seed_off && (capacity == 0 || (qpos && len && lo && cnt)));
 }
 // ... the host entry's queries: BMX_ERR_ARG for offsets that decrease or end past the blob and for a length of 0 or above
 // BMX_MAX_PATTERN, BMX_ERR_DOMAIN for a byte >= 0x80

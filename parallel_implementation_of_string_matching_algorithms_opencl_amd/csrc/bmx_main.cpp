@@ -51,6 +51,12 @@
 //                             (empty lines skipped) counted in one call; one `pattern<TAB>count` line per pattern
 //                             on stdout, with --positions followed by a third tab-separated field of its ascending
 //                             offsets (at most --max-print of them, blank-separated); build and mean query time on stderr
+//   bmx_cli --index-seeds QUERIES_FILE --text F --min-len L [--max-occ N]
+//                             seeds of every line of QUERIES_FILE (empty lines skipped) in the text: the matches of at
+//                             least L bytes that no other match inside the same query contains, with at most N
+//                             occurrences (0 or absent: no limit), through bmx_index_seeds; one line
+//                             `query qpos len count first` per seed in order of (query, position), `first` the smallest
+//                             text offset of the seed, and a last line `seeds TOTAL`
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -126,12 +132,13 @@ void split_lines(const std::string &text, std::string &blob, std::vector<uint64_
 
 int main(int argc, char **argv)
 {
-    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path;
+    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path, seeds_path;
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
     bool positions = false, spans = false, spans_best = false, with_lcp = false;
     uint64_t max_print = 32;
+    uint32_t min_len = 0, max_occ = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * {
@@ -155,6 +162,9 @@ int main(int argc, char **argv)
         else if (a == "--lcp") with_lcp = true;
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--index-count") index_path = need("--index-count");
+        else if (a == "--index-seeds") seeds_path = need("--index-seeds");
+        else if (a == "--min-len") min_len = (uint32_t)strtoul(need("--min-len"), nullptr, 10);
+        else if (a == "--max-occ") max_occ = (uint32_t)strtoul(need("--max-occ"), nullptr, 10);
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
         else if (a == "--icase") class_flags |= BMX_CLASS_ICASE;
         else if (a == "--iupac") class_flags |= BMX_CLASS_IUPAC;
@@ -175,6 +185,60 @@ int main(int argc, char **argv)
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
         return 2;
+    }
+
+    if (!seeds_path.empty()) {
+        std::string text, lines, raw, blob;
+        std::vector<uint64_t> raw_off, off(1, 0);
+        if (min_len == 0) {
+            fprintf(stderr, "--index-seeds needs --min-len L with L >= 1\n");
+            return 2;
+        }
+        if (!read_file(text_path, text) || !read_file(seeds_path, lines)) {
+            fprintf(stderr, "File Not Found!\n");
+            return 1;
+        }
+        split_lines(lines, raw, raw_off);
+        for (size_t i = 0; i + 1 < raw_off.size(); ++i) { // empty lines skipped, a trailing \r dropped
+            uint64_t b = raw_off[i], e = raw_off[i + 1];
+            if (e > b && raw[e - 1] == '\r') --e;
+            if (e == b) continue;
+            blob.append(raw, b, e - b);
+            off.push_back(blob.size());
+        }
+        const uint64_t count = off.size() - 1, n = text.size();
+        if (count == 0) {
+            fprintf(stderr, "no query in %s\n", seeds_path.c_str());
+            return 1;
+        }
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        std::vector<uint64_t> seed_off(count + 1, 0);
+        std::vector<uint32_t> qpos, len, lo, cnt;
+        std::vector<int32_t> sa(n);
+        uint64_t total = 0;
+        if (rc == BMX_OK) { // a counting call, then the list
+            rc = bmx_index_seeds(ctx, text.data(), n, blob.data(), blob.size(), off.data(), count, min_len, max_occ, seed_off.data(),
+                                 nullptr, nullptr, nullptr, nullptr, 0, &total);
+            if (rc == BMX_ERR_CAPACITY) {
+                qpos.resize(total), len.resize(total), lo.resize(total), cnt.resize(total);
+                rc = bmx_index_seeds(ctx, text.data(), n, blob.data(), blob.size(), off.data(), count, min_len, max_occ,
+                                     seed_off.data(), qpos.data(), len.data(), lo.data(), cnt.data(), total, &total);
+            }
+        }
+        if (rc == BMX_OK && total > 0) rc = bmx_suffix_array(ctx, text.data(), n, sa.data()); // the array lo and cnt point into
+        if (rc != BMX_OK) {
+            fprintf(stderr, "bmx_index_seeds failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        for (uint64_t q = 0; q < count; ++q)
+            for (uint64_t s = seed_off[q]; s < seed_off[q + 1]; ++s) {
+                const int32_t first = *std::min_element(sa.begin() + lo[s], sa.begin() + lo[s] + cnt[s]);
+                printf("%llu %u %u %u %d\n", (unsigned long long)q, qpos[s], len[s], cnt[s], first);
+            }
+        printf("seeds %llu\n", (unsigned long long)total);
+        bmx_ctx_destroy(ctx);
+        return 0;
     }
 
     if (!index_path.empty()) {

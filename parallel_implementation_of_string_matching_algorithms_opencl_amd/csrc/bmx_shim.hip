@@ -350,6 +350,32 @@ int bmx_index_locate_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat
                                      n_matches, !ctx->index_no_dir, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
+int bmx_index_match_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                           uint64_t count, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, void *stream_v)
+{
+    if (!bmx_index_query_args_ok(d_pat, d_pat_off, count, d_len)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_index_match(&ctx->index, ix, d_pat, pat_bytes, d_pat_off, count, d_len, d_lo, d_cnt, !ctx->index_no_dir,
+                                    (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_index_seeds_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                           uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *d_seed_off, uint32_t *d_qpos,
+                           uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, uint64_t capacity, uint64_t *n_seeds, void *stream_v)
+{
+    if (!bmx_index_seeds_args_ok(d_pat, d_pat_off, count, min_len, d_seed_off, d_qpos, d_len, d_lo, d_cnt, capacity))
+        return BMX_ERR_ARG;
+    if (n_seeds) *n_seeds = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_index_seeds(&ctx->index, ix, d_pat, pat_bytes, d_pat_off, count, min_len, max_occ, d_seed_off, d_qpos,
+                                    d_len, d_lo, d_cnt, capacity, n_seeds, !ctx->index_no_dir, (hipStream_t)stream_v, g_err,
+                                    sizeof g_err);
+}
+
 float bmx_last_index_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_index_ms(ctx->index) : -1.0f; }
 
 int bmx_device_alloc(bmx_ctx *ctx, uint64_t bytes, void **d_ptr_out)

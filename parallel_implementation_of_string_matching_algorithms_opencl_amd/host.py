@@ -172,6 +172,16 @@ SYMBOLS = [
                                   C.c_void_p]),
     ("bmx_index_locate", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                    C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_index_match_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("bmx_index_seeds_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                         _u64p, C.c_void_p]),
+    ("bmx_index_match", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("bmx_index_seeds", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_uint64, _u64p]),
     ("bmx_last_index_ms", C.c_float, [C.c_void_p]),
     ("bmx_index_build_ms", C.c_float, [C.c_void_p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
@@ -870,6 +880,41 @@ class Context:
         del keep
         return cnt[:count]
 
+    def index_match(self, text, patterns) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Host buffers (bmx_index_match): (len, lo, cnt), uint32, one entry per blob byte of the packed patterns: the
+        longest match that starts at that byte and stays inside its query, and its interval of the suffix array."""
+        tptr, n, keep = _host_text(text)
+        blob, off = pack_strings(patterns)
+        count = off.size - 1
+        out = [np.zeros(max(blob.size, 1), dtype=np.uint32) for _ in range(3)]
+        rc = self._L.bmx_index_match(self._h, tptr, n, C.c_void_p(blob.ctypes.data), blob.size, C.c_void_p(off.ctypes.data),
+                                     count, *[C.c_void_p(o.ctypes.data) for o in out])
+        self._chk(rc, "bmx_index_match")
+        del keep
+        return tuple(o[: blob.size] for o in out)
+
+    def index_seeds(self, text, patterns, min_len: int, max_occ: int = 0):
+        """Host buffers (bmx_index_seeds): (seed_off uint64 of count + 1 entries, qpos, len, lo, cnt uint32), the seeds of
+        every pattern in ``text`` in order of (pattern, position): a counting call, then the list."""
+        tptr, n, keep = _host_text(text)
+        blob, off = pack_strings(patterns)
+        count = off.size - 1
+        seed_off = np.zeros(count + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+
+        def call(out, cap):
+            ptrs = [None] * 4 if out is None else [C.c_void_p(o.ctypes.data) for o in out]
+            return self._L.bmx_index_seeds(self._h, tptr, n, C.c_void_p(blob.ctypes.data), blob.size, C.c_void_p(off.ctypes.data),
+                                           count, min_len, max_occ, C.c_void_p(seed_off.ctypes.data), *ptrs, cap, C.byref(total))
+
+        self._chk(call(None, 0), "bmx_index_seeds", allow=(ERR_CAPACITY,))
+        cap = int(total.value)
+        out = [np.empty(max(cap, 1), dtype=np.uint32) for _ in range(4)]
+        if cap > 0:
+            self._chk(call(out, cap), "bmx_index_seeds")
+        del keep
+        return (seed_off,) + tuple(o[:cap] for o in out)
+
     def last_index_ms(self) -> float:
         return float(self._L.bmx_last_index_ms(self._h))
 
@@ -1164,6 +1209,55 @@ class Index:
         self._ctx._chk(rc, "bmx_index_count_device")
         return lo[:count], cnt[:count]
 
+    def match(self, patterns, len_out=None, lo_out=None, cnt_out=None):
+        """(len, lo, cnt) int32 CUDA tensors, one entry per BLOB BYTE (bmx_index_match_device): for byte b of pattern q,
+        len[b] is the longest match in the text that starts at b and stays inside pattern q, and sa[lo[b] : lo[b] + cnt[b]]
+        are its occurrences (both 0 with len 0).  Entries of blob bytes outside every pattern are left as they are (0 in
+        arrays made here).  ``patterns`` as for count.  Runs on torch's current stream."""
+        import torch
+
+        d_blob, d_off, count = self._queries(patterns)
+        dev = self._text.device
+        size = max(d_blob.numel(), 1)
+        ln, lo, cnt = (o if o is not None else torch.zeros(size, dtype=torch.int32, device=dev) for o in (len_out, lo_out, cnt_out))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self._L.bmx_index_match_device(self._ctx._h, self._h, C.c_void_p(d_blob.data_ptr()), d_blob.numel(),
+                                            C.c_void_p(d_off.data_ptr()), count, C.c_void_p(ln.data_ptr()),
+                                            C.c_void_p(lo.data_ptr()), C.c_void_p(cnt.data_ptr()), stream)
+        self._ctx._chk(rc, "bmx_index_match_device")
+        return ln[: d_blob.numel()], lo[: d_blob.numel()], cnt[: d_blob.numel()]
+
+    def seeds(self, patterns, min_len: int, max_occ: int = 0, capacity: Optional[int] = None):
+        """(seed_off, qpos, len, lo, cnt) (bmx_index_seeds_device): the seeds of every pattern for (min_len, max_occ), in
+        order of (pattern, position).  ``seed_off``: int64 CUDA tensor of count + 1 entries, the exclusive prefix sum of
+        the seeds per pattern (seed_off[-1] is the true total); the other four: int32 CUDA tensors, the position inside
+        the pattern, the match length and its interval sa[lo : lo + cnt].  Without ``capacity`` the list is complete (a
+        counting call first).  With a capacity below the total the first ``capacity`` seeds are returned; that is no
+        error here (seed_off[-1] says so)."""
+        import torch
+
+        d_blob, d_off, count = self._queries(patterns)
+        dev = self._text.device
+        seed_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        total = C.c_uint64(0)
+
+        def call(out, cap):
+            ptrs = [None] * 4 if out is None else [C.c_void_p(o.data_ptr()) for o in out]
+            return self._L.bmx_index_seeds_device(self._ctx._h, self._h, C.c_void_p(d_blob.data_ptr()), d_blob.numel(),
+                                                  C.c_void_p(d_off.data_ptr()), count, min_len, max_occ,
+                                                  C.c_void_p(seed_off.data_ptr()), *ptrs, cap, C.byref(total), stream)
+
+        if capacity is None:
+            self._ctx._chk(call(None, 0), "bmx_index_seeds_device", allow=(ERR_CAPACITY,))
+            capacity = int(total.value)
+            if capacity == 0:
+                return (seed_off,) + tuple(torch.empty(0, dtype=torch.int32, device=dev) for _ in range(4))
+        out = [torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+        self._ctx._chk(call(out if capacity > 0 else None, capacity), "bmx_index_seeds_device", allow=(ERR_CAPACITY,))
+        stored = min(int(total.value), capacity)
+        return (seed_off,) + tuple(o[:stored] for o in out)
+
     def locate(self, patterns, capacity: Optional[int] = None, base_offset: int = 0):
         """(offsets, positions, total) (bmx_index_locate_device): ``offsets`` int64 CUDA tensor of count + 1 entries, the
         exclusive prefix sum of the counts; positions[offsets[i] : offsets[i + 1]] = base_offset + p for every occurrence
@@ -1348,6 +1442,12 @@ def edit_distance_batch(a, b, limit: Optional[int] = None) -> np.ndarray:
 def index_count(text, patterns) -> np.ndarray:
     """Occurrences of every pattern in ``text`` through a text index built for the call (bmx_index_count), uint32."""
     return default_context().index_count(text, patterns)
+
+
+def index_seeds(text, patterns, min_len: int, max_occ: int = 0):
+    """The seeds of every pattern in ``text`` through a text index built for the call (bmx_index_seeds): (seed_off, qpos,
+    len, lo, cnt), see Context.index_seeds."""
+    return default_context().index_seeds(text, patterns, min_len, max_occ)
 
 
 def lcp_array(text) -> Tuple[np.ndarray, np.ndarray]:
