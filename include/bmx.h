@@ -33,7 +33,8 @@
  *                         sets, case folding, IUPAC codes), matched by Shift-And (section below)
  *   bmx_index_*           no counterpart: pattern count and locate by binary search over the array bmx_suffix_array
  *                         builds, in the order it builds it; the longest match at every query position and the
- *                         seeds among them (section below)
+ *                         seeds among them; reads mapped by extending the seeds to alignments within k edits
+ *                         (section below)
  *
  * Semantics (bit-exact with the reference kernel run as one work-item over
  * [0, n-1]): match_positions receives, in ascending order, every
@@ -698,8 +699,57 @@ int bmx_index_match(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_
 int bmx_index_seeds(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
                     const uint64_t *pat_off, uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *seed_off,
                     uint32_t *qpos, uint32_t *len, uint32_t *lo, uint32_t *cnt, uint64_t capacity, uint64_t *n_seeds);
-/* Device time (ms, HIP events around the query kernels) of the last count / locate / match / seeds call on ctx; < 0 if
- * none. */
+/* Read mapping: seeds extended to alignments within k edits, one (start, end, distance) per read.
+ * Index, text and query column are those of bmx_index_seeds_device; min_len >= 1, 1 <= max_occ (0 is BMX_ERR_ARG here: an
+ * unbounded seed is never extended), 0 <= k <= BMX_MAP_MAX_K.
+ * Candidates: the seeds of (min_len, max_occ) are exactly those of bmx_index_seeds_device, in its order.  For every seed
+ * (q, i, len, lo, cnt) and every t in [0, cnt) there is one candidate: its occurrence is p = sa[lo + t], its diagonal
+ * d = p - i (signed).  Candidates are listed in order of (query, seed, t) and are NOT de-duplicated: two seeds of a read
+ * on one diagonal give two candidates, so that the list is literal and the same in every run (no atomics).  d_cand_off
+ * (count + 1 entries, may be NULL) = the exclusive prefix sum of the candidates per query, always written in full.
+ * Window of a candidate, with m the query's length: [w0, w1) = [max(0, d - k), min(n, d + m + k)).  Every alignment of the
+ * whole query with at most k edits that contains the seed's exact match lies inside it.
+ * Hit of a candidate: with D(j) = min over s >= w0 of ED(query, text[s..j]) for every j of the window (what
+ * bmx_search_approx defines on the view text[w0..w1)), dist = the minimum of D, end = the LARGEST j that attains it,
+ * start = the LARGEST s >= w0 with ED(query, text[s..end]) == dist (the rule of bmx_approx_spans_device on that view).
+ * The candidate is a hit iff dist <= k; otherwise dist = BMX_MAP_NO_HIT and both positions are BMX_MAP_NO_POS.  Positions
+ * go out as base_offset + position, into three parallel lists of `capacity` entries.
+ * Per query: among its hits the one with the smallest (dist, end) goes to d_best_start[q], d_best_end[q], d_best_dist[q]
+ * (count entries each); a query without a seed or without a hit gets NO_POS, NO_POS, NO_HIT.
+ * *n_candidates is the true total.  A total above a non-zero `capacity` returns BMX_ERR_CAPACITY with the first
+ * `capacity` candidates of the order stored; the per-query results are complete either way.  capacity == 0 (the three
+ * list pointers may be NULL) never returns BMX_ERR_CAPACITY: the per-query answer is the product.  A total above
+ * BMX_MAP_MAX_CANDIDATES returns BMX_ERR_ARG: pass fewer queries at a time or a smaller max_occ.
+ * Errors: NULL pointers where count > 0, min_len == 0, max_occ == 0, k outside [0, BMX_MAP_MAX_K] and an index of another
+ * context return BMX_ERR_ARG before any HIP call, with ctx = NULL too (the host entry: n == 0 or n >= 2^31 as well);
+ * count == 0 returns BMX_OK and launches nothing (*n_candidates = 0).  Offsets, lengths and bytes are checked as by
+ * seeds.  All device work goes on `stream`; the call waits for it once in between, to read the candidate total and the
+ * longest query that has a seed, and once at the end.  No text byte is read except as part of the aligned 8-byte word
+ * that holds it, and none outside the candidate's window's words. */
+#define BMX_MAP_MAX_K 64
+#define BMX_MAP_NO_HIT 255u
+#define BMX_MAP_NO_POS UINT64_MAX
+#define BMX_MAP_MAX_CANDIDATES (1ull << 27)
+int bmx_index_map_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                         uint64_t count, uint32_t min_len, uint32_t max_occ, int32_t k, uint64_t base_offset,
+                         uint64_t *d_best_start, uint64_t *d_best_end, uint8_t *d_best_dist /* count entries each */,
+                         uint64_t *d_cand_off /* count + 1, may be NULL */, uint64_t *d_cand_start, uint64_t *d_cand_end,
+                         uint8_t *d_cand_dist /* `capacity` entries each, may be NULL iff capacity == 0 */, uint64_t capacity,
+                         uint64_t *n_candidates, void *stream);
+/* Host buffers in, host buffers out, an index built for the call, base_offset 0 (what bmx_cli --index-map prints comes
+ * through it). */
+int bmx_index_map(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
+                  const uint64_t *pat_off, uint64_t count, uint32_t min_len, uint32_t max_occ, int32_t k, uint64_t *best_start,
+                  uint64_t *best_end, uint8_t *best_dist, uint64_t *cand_off /* may be NULL */, uint64_t *cand_start,
+                  uint64_t *cand_end, uint8_t *cand_dist, uint64_t capacity, uint64_t *n_candidates);
+/* Candidates of the last bmx_index_map_device on ctx (the true total); < 0 if none. */
+int64_t bmx_last_index_map_candidates(bmx_ctx *ctx);
+/* Where the last bmx_index_map_device on ctx spent its device time (ms, HIP events): out[0] candidate expansion (match
+ * kernel, scan, fill), out[1] verification, out[2] start pass, out[3] per-query best; out[4] = the 64-bit words of the
+ * instance that ran (0: no candidate).  BMX_ERR_ARG if there was no such call.  For tools/index_map_rate.py. */
+int bmx_last_index_map_phases(bmx_ctx *ctx, float out[5]);
+/* Device time (ms, HIP events around the query kernels) of the last count / locate / match / seeds / map call on ctx; < 0
+ * if none. */
 float bmx_last_index_ms(bmx_ctx *ctx);
 /* Device time (ms) of the index's creation: the suffix array if it was built here, plus the directory. */
 float bmx_index_build_ms(const bmx_index *ix);

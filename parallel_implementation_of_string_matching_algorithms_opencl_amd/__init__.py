@@ -11,7 +11,7 @@ AnupBS28/PARALLEL_IMPLEMENTATION_OF_STRING_MATCHING_ALGORITHMS_OPENCL (its
 """
 from . import corpus, host, shard  # noqa: F401
 from .host import (BmxError, CLASS_ICASE, CLASS_IUPAC, Context, Dictionary, Index, MAX_CLASS_PATTERN, build_tables,  # noqa: F401
-                   compile_classes, edit_distance_batch, index_count, index_seeds, lcp_array, longest_repeat, search,
+                   compile_classes, edit_distance_batch, index_count, index_map, index_seeds, lcp_array, longest_repeat, search,
                    search_approx, search_classes, search_dict, search_ranges)
 
 __version__ = "0.1.0"

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmx_eq_kernel.h"
+
 namespace bmx {
 
 constexpr int ED_BATCH_BLOCK = 256;          // lanes (pairs) per workgroup
@@ -65,26 +67,6 @@ __device__ __forceinline__ void ed_batch_step(EdBatchState<W> &s, W eq, uint32_t
     mh <<= 1;
     s.pv = mh | ~(xv | ph);
     s.mv = ph & xv;
-}
-
-// 32 flags: bit 8k + j = (byte k of p[j] == c), c4 = c in all four bytes.
-__device__ __forceinline__ uint32_t ed_batch_eq32(const uint32_t *p, uint32_t c4)
-{
-    uint32_t eq = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t x = p[j] ^ c4;
-        const uint32_t y = ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu; // bit 7 of a byte clear: the byte of x is 0
-        eq |= ~y >> (7 - j);
-    }
-    return eq;
-}
-
-template <typename W>
-__device__ __forceinline__ W ed_batch_eq(const uint32_t *p, uint32_t c4, W mask)
-{
-    if (sizeof(W) == 4) return (W)ed_batch_eq32(p, c4) & mask;
-    return (W)(((uint64_t)ed_batch_eq32(p + 8, c4) << 32) | ed_batch_eq32(p, c4)) & mask;
 }
 
 // The pattern into its registers: byte 8k + j of a 32-byte half -> byte k of register j.  The bytes come in 16-byte loads

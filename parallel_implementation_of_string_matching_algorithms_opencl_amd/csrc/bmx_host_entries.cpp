@@ -487,4 +487,51 @@ int bmx_index_seeds(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *p
     return c.rc;
 }
 
+int bmx_index_map(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes, const uint64_t *pat_off,
+                  uint64_t count, uint32_t min_len, uint32_t max_occ, int32_t k, uint64_t *best_start, uint64_t *best_end,
+                  uint8_t *best_dist, uint64_t *cand_off, uint64_t *cand_start, uint64_t *cand_end, uint8_t *cand_dist,
+                  uint64_t capacity, uint64_t *n_candidates)
+{
+    if (!text || n == 0 || n >= (1ull << 31) ||
+        !bmx_index_map_args_ok(pat, pat_off, count, min_len, max_occ, k, best_start, best_end, best_dist, cand_start, cand_end,
+                               cand_dist, capacity))
+        return BMX_ERR_ARG;
+    if (n_candidates) *n_candidates = 0;
+    if (count == 0) return BMX_OK;
+    const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
+    if (qrc != BMX_OK) return qrc;
+    HostCall c("bmx_index_map", ctx_in);
+    bmx_index *ix = nullptr;
+    uint64_t total = 0;
+    // (a blob byte is at most one seed of at most max_occ occurrences, and no call has more than BMX_MAP_MAX_CANDIDATES:
+    // a larger capacity needs no larger device lists, and one pass fills them)
+    const uint64_t most = pat_bytes > BMX_MAP_MAX_CANDIDATES / max_occ ? BMX_MAP_MAX_CANDIDATES : pat_bytes * max_occ;
+    const uint64_t dev_cap = std::min(capacity, most);
+    void *d_text = c.upload(text, n);
+    void *d_pat = c.upload(pat, pat_bytes);
+    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+    uint64_t *d_best = c.alloc<uint64_t>(2 * count * sizeof(uint64_t) + count);
+    uint64_t *d_cand_off = cand_off ? c.alloc<uint64_t>((count + 1) * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_cand = dev_cap ? c.alloc<uint64_t>(2 * dev_cap * sizeof(uint64_t) + dev_cap) : nullptr;
+    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
+    if (c.rc == BMX_OK)
+        c.rc = bmx_index_map_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, min_len, max_occ, k, 0, d_best, d_best + count,
+                                    reinterpret_cast<uint8_t *>(d_best + 2 * count), d_cand_off, d_cand,
+                                    d_cand ? d_cand + dev_cap : nullptr,
+                                    d_cand ? reinterpret_cast<uint8_t *>(d_cand + 2 * dev_cap) : nullptr, dev_cap, &total, nullptr);
+    const uint64_t lists = std::min(total, dev_cap);
+    if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
+        c.download(best_start, d_best, count * sizeof(uint64_t), "the mappings");
+        c.download(best_end, d_best + count, count * sizeof(uint64_t), "the mappings");
+        c.download(best_dist, d_best + 2 * count, count, "the mappings");
+        if (cand_off) c.download(cand_off, d_cand_off, (count + 1) * sizeof(uint64_t), "the candidate offsets");
+        c.download(cand_start, d_cand, lists * sizeof(uint64_t), "the candidates");
+        c.download(cand_end, d_cand + dev_cap, lists * sizeof(uint64_t), "the candidates");
+        c.download(cand_dist, d_cand + 2 * dev_cap, lists, "the candidates");
+        if (n_candidates) *n_candidates = total;
+    }
+    bmx_index_destroy(ix); // before the context
+    return c.rc;
+}
+
 } // extern "C"

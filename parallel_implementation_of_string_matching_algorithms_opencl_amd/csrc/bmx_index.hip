@@ -4,8 +4,12 @@
 // fill, rocPRIM's segmented radix sort of the 32-bit positions within their segments and the widening to base_offset + p.
 // match = one launch of index_match_kernel (one lane per blob byte); seeds = that into workspace, rocPRIM's exclusive scan
 // of the seed flags, the fill and the per-query offsets, with one wait at the end (bmx_index_match_kernel.h).
+// map = the match kernel into workspace, rocPRIM's exclusive scan of the seeds' occurrence counts and its reduction to the
+// longest seeded query, one wait for the candidate total, then the candidate fill, the verification, the start pass and
+// the per-query best (bmx_index_map_kernel.h), and the wait at the end.
 // The argument checks and the context are the shim's (bmx_shim.hip); everything here runs on valid arguments.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_reduce.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -18,10 +22,12 @@
 
 #include "bmx.h"
 #include "bmx_index_kernel.h"
+#include "bmx_index_map_kernel.h"
 #include "bmx_index_match_kernel.h"
 #include "bmx_internal.h"
 
 static_assert(bmx::INDEX_MAX_PATTERN == BMX_MAX_PATTERN, "header and kernel disagree");
+static_assert(bmx::MAP_NO_HIT == BMX_MAP_NO_HIT && bmx::INDEX_MAX_PATTERN <= 64 * 8, "header and kernel disagree");
 
 struct bmx_index {
     const void *owner = nullptr; // the context it was created on
@@ -43,6 +49,11 @@ struct IndexHost {
     uint64_t q_cap = 0;
     void *d_p = nullptr; // per stored position: two 32-bit key buffers, then rocPRIM's temporary storage
     size_t p_bytes = 0;
+    void *d_c = nullptr; // per candidate of a map call: six 32-bit arrays
+    size_t c_bytes = 0;
+    int64_t map_candidates = -1; // of the last map call
+    hipEvent_t mev[3] = {nullptr, nullptr, nullptr}; // ... behind its fill, its verification and its start pass
+    float map_phase[5] = {-1.0f, -1.0f, -1.0f, -1.0f, 0.0f}; // ... ms of expansion, verification, starts, best; the instance's words
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float last_ms = -1.0f;
 };
@@ -62,6 +73,8 @@ int state_ready(void **state_v, uint64_t count, IndexHost **out, const char *wha
     if (!st->d_ws) BMX_HIP(what, hipMalloc(&st->d_ws, WS_WORDS * sizeof(uint64_t)));
     if (!st->h_ws) BMX_HIP(what, hipHostMalloc(&st->h_ws, WS_WORDS * sizeof(uint64_t), hipHostMallocDefault));
     for (hipEvent_t &e : st->ev)
+        if (!e) BMX_HIP(what, hipEventCreate(&e));
+    for (hipEvent_t &e : st->mev)
         if (!e) BMX_HIP(what, hipEventCreate(&e));
     if (count > st->q_cap) {
         if (st->d_q) (void)hipFree(st->d_q);
@@ -157,7 +170,10 @@ void bmx_internal_index_state_free(void *state_v)
     if (st->h_ws) (void)hipHostFree(st->h_ws);
     if (st->d_q) (void)hipFree(st->d_q);
     if (st->d_p) (void)hipFree(st->d_p);
+    if (st->d_c) (void)hipFree(st->d_c);
     for (hipEvent_t e : st->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : st->mev)
         if (e) (void)hipEventDestroy(e);
     delete st;
 }
@@ -166,6 +182,20 @@ float bmx_internal_index_ms(const void *state_v)
 {
     const IndexHost *st = static_cast<const IndexHost *>(state_v);
     return st ? st->last_ms : -1.0f;
+}
+
+int64_t bmx_internal_index_map_candidates(const void *state_v)
+{
+    const IndexHost *st = static_cast<const IndexHost *>(state_v);
+    return st ? st->map_candidates : -1;
+}
+
+int bmx_internal_index_map_phases(const void *state_v, float out[5])
+{
+    const IndexHost *st = static_cast<const IndexHost *>(state_v);
+    if (!st || st->map_candidates < 0) return BMX_ERR_ARG;
+    std::copy(st->map_phase, st->map_phase + 5, out);
+    return BMX_OK;
 }
 
 const void *bmx_internal_index_owner(const bmx_index *ix) { return ix->owner; }
@@ -458,4 +488,161 @@ int bmx_internal_index_seeds(void **state_v, const bmx_index *ix, const void *d_
     if (rc != BMX_OK) return rc;
     if (n_seeds) *n_seeds = st->h_ws[2];
     return st->h_ws[2] > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+}
+
+namespace {
+
+template <int W>
+hipError_t map_launch(const bmx::IndexMapArgs &a, uint32_t longest, hipEvent_t between, hipStream_t stream)
+{
+    bmx::IndexMapArgs v = a;
+    v.chunks = (longest + 2 * a.k + 7) / 8;
+    hipLaunchKernelGGL(bmx::index_map_verify_kernel<W>, dim3(blocks_for(a.total)), dim3(bmx::INDEX_BLOCK), 0, stream, v);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(between, stream);
+    if (e != hipSuccess) return e;
+    v.chunks = (longest + a.k + 7) / 8;
+    hipLaunchKernelGGL(bmx::index_map_start_kernel<W>, dim3(blocks_for(a.total)), dim3(bmx::INDEX_BLOCK), 0, stream, v);
+    return hipGetLastError();
+}
+
+} // namespace
+
+int bmx_internal_index_map(void **state_v, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                           uint64_t count, uint32_t min_len, uint32_t max_occ, uint32_t k, uint64_t base_offset,
+                           uint64_t *d_best_start, uint64_t *d_best_end, uint8_t *d_best_dist, uint64_t *d_cand_off,
+                           uint64_t *d_cand_start, uint64_t *d_cand_end, uint8_t *d_cand_dist, uint64_t capacity,
+                           uint64_t *n_candidates, int use_dir, hipStream_t stream, char *err, size_t errlen)
+{
+    const char *what = "bmx_index_map_device";
+    if (!match_sizes_ok(pat_bytes, count)) {
+        snprintf(err, errlen, "%s: 2^31 - 1 blob bytes or queries or more in one call", what);
+        return BMX_ERR_ARG;
+    }
+    IndexHost *st = nullptr;
+    int rc = state_ready(state_v, 0, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    st->map_candidates = -1;
+
+    // per blob byte: qpos, len, lo, cnt (32-bit) and the scan of the candidates (64-bit, pat_bytes + 1 entries), then
+    // rocPRIM's temporary storage of the scan and of the reduction
+    const size_t arr_bytes = (((size_t)pat_bytes + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t scan_arr_bytes = (((size_t)pat_bytes + 1) * sizeof(uint64_t) + 255) & ~(size_t)255;
+    bmx::IndexMapCount cand = {{nullptr, nullptr, nullptr, pat_bytes, min_len, max_occ}};
+    bmx::IndexMapSeededLen seeded = {d_pat_off, nullptr, pat_bytes};
+    auto counts = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), cand);
+    auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), seeded);
+    size_t scan_bytes = 0, red_bytes = 0;
+    BMX_HIP(what, rocprim::exclusive_scan(nullptr, scan_bytes, counts, (uint64_t *)nullptr, uint64_t(0), (size_t)pat_bytes + 1,
+                                          rocprim::plus<uint64_t>(), stream));
+    BMX_HIP(what, rocprim::reduce(nullptr, red_bytes, lens, (uint64_t *)nullptr, uint64_t(0), (size_t)count, bmx::IndexMapMax(),
+                                  stream));
+    const size_t tmp_bytes = std::max(scan_bytes, red_bytes);
+    rc = positions_ready(st, 4 * arr_bytes + scan_arr_bytes + tmp_bytes, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    char *base = static_cast<char *>(st->d_p);
+    uint32_t *w_qpos = reinterpret_cast<uint32_t *>(base), *w_len = reinterpret_cast<uint32_t *>(base + arr_bytes);
+    uint32_t *w_lo = reinterpret_cast<uint32_t *>(base + 2 * arr_bytes), *w_cnt = reinterpret_cast<uint32_t *>(base + 3 * arr_bytes);
+    uint64_t *w_scan = reinterpret_cast<uint64_t *>(base + 4 * arr_bytes);
+    void *tmp = base + 4 * arr_bytes + scan_arr_bytes;
+    cand.flag.qpos = w_qpos, cand.flag.len = w_len, cand.flag.cnt = w_cnt;
+    seeded.scan = w_scan;
+    counts = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), cand);
+    lens = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), seeded);
+
+    BMX_HIP(what, hipMemsetAsync(st->d_ws, 0, WS_WORDS * sizeof(uint64_t), stream));
+    BMX_HIP(what, hipMemsetAsync(w_qpos, 0xff, arr_bytes, stream)); // INDEX_NO_QUERY: no lane has answered for this byte
+    BMX_HIP(what, hipEventRecord(st->ev[0], stream));
+    const bmx::IndexMatchArgs ma =
+        make_match_args(ix, d_pat, pat_bytes, d_pat_off, count, w_len, w_lo, w_cnt, w_qpos, use_dir != 0, st->d_ws);
+    hipLaunchKernelGGL(bmx::index_match_kernel, dim3(blocks_for(std::max(pat_bytes, count))), dim3(bmx::INDEX_BLOCK), 0, stream, ma);
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, rocprim::exclusive_scan(tmp, scan_bytes, counts, w_scan, uint64_t(0), (size_t)pat_bytes + 1,
+                                          rocprim::plus<uint64_t>(), stream));
+    hipLaunchKernelGGL(bmx::index_map_off_kernel, dim3(blocks_for(count + 1)), dim3(bmx::INDEX_BLOCK), 0, stream, d_pat_off, count,
+                       pat_bytes, w_scan, d_cand_off, st->d_ws + 2);
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, rocprim::reduce(tmp, red_bytes, lens, st->d_ws + 3, uint64_t(0), (size_t)count, bmx::IndexMapMax(), stream));
+    BMX_HIP(what, hipEventRecord(st->ev[1], stream));
+    BMX_HIP(what, hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
+    if (hipEventElapsedTime(&st->last_ms, st->ev[0], st->ev[1]) != hipSuccess) st->last_ms = -1.0f;
+    auto trim = [&]() { // neither workspace is kept above KEEP_BYTES
+        if (st->p_bytes > KEEP_BYTES) (void)hipFree(st->d_p), st->d_p = nullptr, st->p_bytes = 0;
+        if (st->c_bytes > KEEP_BYTES) (void)hipFree(st->d_c), st->d_c = nullptr, st->c_bytes = 0;
+    };
+    rc = status_rc(st->h_ws, what, err, errlen);
+    if (rc != BMX_OK) {
+        trim();
+        return rc;
+    }
+    const uint64_t total = st->h_ws[2], longest = st->h_ws[3];
+    if (n_candidates) *n_candidates = total;
+    st->map_candidates = (int64_t)total;
+    if (total > BMX_MAP_MAX_CANDIDATES) {
+        trim();
+        snprintf(err, errlen, "%s: %llu candidates, more than %llu; pass fewer queries at a time or a smaller max_occ", what,
+                 (unsigned long long)total, (unsigned long long)BMX_MAP_MAX_CANDIDATES);
+        return BMX_ERR_ARG;
+    }
+
+    bmx::IndexMapArgs a = {};
+    a.text = ix->d_text, a.n = ix->n, a.sa = ix->d_sa;
+    a.pat = static_cast<const uint8_t *>(d_pat), a.pat_bytes = pat_bytes, a.pat_off = d_pat_off, a.count = count;
+    a.scan = w_scan, a.qpos = w_qpos, a.lo = w_lo;
+    a.total = total, a.k = k;
+    a.base_offset = base_offset;
+    a.out_start = d_cand_start, a.out_end = d_cand_end, a.out_dist = d_cand_dist, a.capacity = capacity;
+    a.best_start = d_best_start, a.best_end = d_best_end, a.best_dist = d_best_dist;
+    a.status = st->d_ws; // (both words are 0: the match kernel has raised none)
+    BMX_HIP(what, hipEventRecord(st->ev[2], stream));
+    int words = 0;
+    if (total > 0) {
+        const size_t col_bytes = ((size_t)total * sizeof(uint32_t) + 255) & ~(size_t)255;
+        if (6 * col_bytes > st->c_bytes) {
+            if (st->d_c) (void)hipFree(st->d_c);
+            st->d_c = nullptr, st->c_bytes = 0;
+            BMX_HIP(what, hipMalloc(&st->d_c, 6 * col_bytes));
+            st->c_bytes = 6 * col_bytes;
+        }
+        char *cb = static_cast<char *>(st->d_c);
+        a.cq = reinterpret_cast<uint32_t *>(cb), a.ci = reinterpret_cast<uint32_t *>(cb + col_bytes);
+        a.cp = reinterpret_cast<uint32_t *>(cb + 2 * col_bytes), a.cend = reinterpret_cast<uint32_t *>(cb + 3 * col_bytes);
+        a.cstart = reinterpret_cast<uint32_t *>(cb + 4 * col_bytes), a.cdist = reinterpret_cast<uint32_t *>(cb + 5 * col_bytes);
+        hipLaunchKernelGGL(bmx::index_map_fill_kernel, dim3(blocks_for(total)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+        BMX_HIP(what, hipGetLastError());
+        BMX_HIP(what, hipEventRecord(st->mev[0], stream));
+        // the smallest instance that covers the longest query with a seed
+        const uint32_t M = (uint32_t)std::min<uint64_t>(longest, bmx::INDEX_MAX_PATTERN);
+        BMX_HIP(what, M <= 64    ? map_launch<1>(a, M, st->mev[1], stream)
+                      : M <= 128 ? map_launch<2>(a, M, st->mev[1], stream)
+                      : M <= 256 ? map_launch<4>(a, M, st->mev[1], stream)
+                                 : map_launch<8>(a, M, st->mev[1], stream));
+        BMX_HIP(what, hipEventRecord(st->mev[2], stream));
+        words = M <= 64 ? 1 : M <= 128 ? 2 : M <= 256 ? 4 : 8;
+    }
+    hipLaunchKernelGGL(bmx::index_map_best_kernel, dim3(blocks_for(count)), dim3(bmx::INDEX_BLOCK), 0, stream, a);
+    BMX_HIP(what, hipGetLastError());
+    BMX_HIP(what, hipEventRecord(st->ev[3], stream));
+    BMX_HIP(what, hipMemcpyAsync(st->h_ws, st->d_ws, WS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(what, hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    // the phases, for tools/index_map_rate.py: expansion (seeds, scan, fill), verification, starts, best
+    float *ph = st->map_phase;
+    ph[0] = st->last_ms, ph[1] = ph[2] = 0.0f, ph[3] = -1.0f, ph[4] = (float)words;
+    if (words) {
+        float fill = 0.0f;
+        if (hipEventElapsedTime(&fill, st->ev[2], st->mev[0]) == hipSuccess && ph[0] >= 0.0f) ph[0] += fill;
+        if (hipEventElapsedTime(&ph[1], st->mev[0], st->mev[1]) != hipSuccess) ph[1] = -1.0f;
+        if (hipEventElapsedTime(&ph[2], st->mev[1], st->mev[2]) != hipSuccess) ph[2] = -1.0f;
+    }
+    if (hipEventElapsedTime(&ph[3], words ? st->mev[2] : st->ev[2], st->ev[3]) != hipSuccess) ph[3] = -1.0f;
+    if (st->last_ms >= 0.0f && hipEventElapsedTime(&ms, st->ev[2], st->ev[3]) == hipSuccess) st->last_ms += ms;
+    trim();
+    if (st->h_ws[0] || st->h_ws[1]) {
+        snprintf(err, errlen, "%s: internal: %s", what,
+                 st->h_ws[0] ? "a candidate failed its checks" : "a start pass disagrees with its verification");
+        return BMX_ERR_HIP;
+    }
+    return capacity > 0 && total > capacity ? BMX_ERR_CAPACITY : BMX_OK;
 }

@@ -126,8 +126,15 @@ int bmx_internal_index_seeds(void **state, const bmx_index *ix, const void *d_pa
                              uint64_t count, uint32_t min_len, uint32_t max_occ, uint64_t *d_seed_off, uint32_t *d_qpos,
                              uint32_t *d_len, uint32_t *d_lo, uint32_t *d_cnt, uint64_t capacity, uint64_t *n_seeds, int use_dir,
                              hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_index_map(void **state, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                           uint64_t count, uint32_t min_len, uint32_t max_occ, uint32_t k, uint64_t base_offset,
+                           uint64_t *d_best_start, uint64_t *d_best_end, uint8_t *d_best_dist, uint64_t *d_cand_off,
+                           uint64_t *d_cand_start, uint64_t *d_cand_end, uint8_t *d_cand_dist, uint64_t capacity,
+                           uint64_t *n_candidates, int use_dir, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_index_state_free(void *state);
 float bmx_internal_index_ms(const void *state);
+int64_t bmx_internal_index_map_candidates(const void *state);
+int bmx_internal_index_map_phases(const void *state, float out[5]);
 // bmx_lcp.hip
 int bmx_internal_lcp(void **state, const uint8_t *d_text, uint32_t n, const int32_t *d_sa, int32_t *d_lcp, hipStream_t stream,
                      char *err, size_t errlen);
@@ -226,6 +233,16 @@ inline bool bmx_index_seeds_args_ok(const void *pat, const uint64_t *pat_off, ui
 {
     if (min_len == 0) return false;
     return count == 0 || (pat && pat_off && seed_off && (capacity == 0 || (qpos && len && lo && cnt)));
+}
+// ... of its read mapping: the three per-query outputs, the three lists where there is room for any, min_len and max_occ
+// of at least 1 and at most BMX_MAP_MAX_K edits
+inline bool bmx_index_map_args_ok(const void *pat, const uint64_t *pat_off, uint64_t count, uint32_t min_len, uint32_t max_occ,
+                                  int32_t k, const void *best_start, const void *best_end, const void *best_dist,
+                                  const void *cand_start, const void *cand_end, const void *cand_dist, uint64_t capacity)
+{
+    if (min_len == 0 || max_occ == 0 || k < 0 || k > BMX_MAP_MAX_K) return false;
+    return count == 0 || (pat && pat_off && best_start && best_end && best_dist &&
+                          (capacity == 0 || (cand_start && cand_end && cand_dist)));
 }
 // ... the host entry's queries: BMX_ERR_ARG for offsets that decrease or end past the blob and for a length of 0 or above
 // BMX_MAX_PATTERN, BMX_ERR_DOMAIN for a byte >= 0x80

@@ -57,6 +57,11 @@
 //                             occurrences (0 or absent: no limit), through bmx_index_seeds; one line
 //                             `query qpos len count first` per seed in order of (query, position), `first` the smallest
 //                             text offset of the seed, and a last line `seeds TOTAL`
+//   bmx_cli --index-map READS_FILE --text F --min-len L --max-occ N --approx K
+//                             where every line of READS_FILE (empty lines skipped) lies in the text within K edits, by
+//                             extending its seeds of (L, N >= 1), through bmx_index_map; one line `query start end dist`
+//                             per read (`query - - -` for a read that maps nowhere) and a last line
+//                             `mapped M of COUNT, candidates TOTAL`; not together with --index-seeds
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -132,7 +137,7 @@ void split_lines(const std::string &text, std::string &blob, std::vector<uint64_
 
 int main(int argc, char **argv)
 {
-    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path, seeds_path;
+    std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path, seeds_path, map_path;
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
@@ -163,6 +168,7 @@ int main(int argc, char **argv)
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--index-count") index_path = need("--index-count");
         else if (a == "--index-seeds") seeds_path = need("--index-seeds");
+        else if (a == "--index-map") map_path = need("--index-map");
         else if (a == "--min-len") min_len = (uint32_t)strtoul(need("--min-len"), nullptr, 10);
         else if (a == "--max-occ") max_occ = (uint32_t)strtoul(need("--max-occ"), nullptr, 10);
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
@@ -182,6 +188,11 @@ int main(int argc, char **argv)
         }
     }
 
+    if (!map_path.empty() && !seeds_path.empty()) {
+        fprintf(stderr, "--index-seeds and --index-map exclude each other\n");
+        return 2;
+    }
+    if (!map_path.empty()) seeds_path = map_path; // the same query file, read below
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
         return 2;
@@ -191,7 +202,11 @@ int main(int argc, char **argv)
         std::string text, lines, raw, blob;
         std::vector<uint64_t> raw_off, off(1, 0);
         if (min_len == 0) {
-            fprintf(stderr, "--index-seeds needs --min-len L with L >= 1\n");
+            fprintf(stderr, "--index-seeds and --index-map need --min-len L with L >= 1\n");
+            return 2;
+        }
+        if (!map_path.empty() && (max_occ == 0 || approx_k < 0 || approx_k > BMX_MAP_MAX_K)) {
+            fprintf(stderr, "--index-map needs --max-occ N with N >= 1 and --approx K with 0 <= K <= %d\n", BMX_MAP_MAX_K);
             return 2;
         }
         if (!read_file(text_path, text) || !read_file(seeds_path, lines)) {
@@ -213,6 +228,30 @@ int main(int argc, char **argv)
         }
         bmx_ctx *ctx = nullptr;
         int rc = bmx_ctx_create(device, &ctx);
+        if (!map_path.empty()) {
+            std::vector<uint64_t> start(count), end(count);
+            std::vector<uint8_t> dist(count);
+            uint64_t total = 0, mapped = 0;
+            if (rc == BMX_OK)
+                rc = bmx_index_map(ctx, text.data(), n, blob.data(), blob.size(), off.data(), count, min_len, max_occ, approx_k,
+                                   start.data(), end.data(), dist.data(), nullptr, nullptr, nullptr, nullptr, 0, &total);
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_index_map failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            for (uint64_t q = 0; q < count; ++q) {
+                if (dist[q] == BMX_MAP_NO_HIT) {
+                    printf("%llu - - -\n", (unsigned long long)q);
+                    continue;
+                }
+                printf("%llu %llu %llu %u\n", (unsigned long long)q, (unsigned long long)start[q], (unsigned long long)end[q], dist[q]);
+                ++mapped;
+            }
+            printf("mapped %llu of %llu, candidates %llu\n", (unsigned long long)mapped, (unsigned long long)count,
+                   (unsigned long long)total);
+            bmx_ctx_destroy(ctx);
+            return 0;
+        }
         std::vector<uint64_t> seed_off(count + 1, 0);
         std::vector<uint32_t> qpos, len, lo, cnt;
         std::vector<int32_t> sa(n);

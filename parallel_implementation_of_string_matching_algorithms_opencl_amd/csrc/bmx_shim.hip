@@ -376,6 +376,31 @@ int bmx_index_seeds_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat,
                                     sizeof g_err);
 }
 
+int bmx_index_map_device(bmx_ctx *ctx, const bmx_index *ix, const void *d_pat, uint64_t pat_bytes, const uint64_t *d_pat_off,
+                         uint64_t count, uint32_t min_len, uint32_t max_occ, int32_t k, uint64_t base_offset,
+                         uint64_t *d_best_start, uint64_t *d_best_end, uint8_t *d_best_dist, uint64_t *d_cand_off,
+                         uint64_t *d_cand_start, uint64_t *d_cand_end, uint8_t *d_cand_dist, uint64_t capacity,
+                         uint64_t *n_candidates, void *stream_v)
+{
+    if (!bmx_index_map_args_ok(d_pat, d_pat_off, count, min_len, max_occ, k, d_best_start, d_best_end, d_best_dist, d_cand_start,
+                               d_cand_end, d_cand_dist, capacity))
+        return BMX_ERR_ARG;
+    if (n_candidates) *n_candidates = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !ix || bmx_internal_index_owner(ix) != ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_index_map(&ctx->index, ix, d_pat, pat_bytes, d_pat_off, count, min_len, max_occ, (uint32_t)k, base_offset,
+                                  d_best_start, d_best_end, d_best_dist, d_cand_off, d_cand_start, d_cand_end, d_cand_dist,
+                                  capacity, n_candidates, !ctx->index_no_dir, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int64_t bmx_last_index_map_candidates(bmx_ctx *ctx) { return ctx ? bmx_internal_index_map_candidates(ctx->index) : -1; }
+
+int bmx_last_index_map_phases(bmx_ctx *ctx, float out[5])
+{
+    return ctx && out ? bmx_internal_index_map_phases(ctx->index, out) : BMX_ERR_ARG;
+}
+
 float bmx_last_index_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_index_ms(ctx->index) : -1.0f; }
 
 int bmx_device_alloc(bmx_ctx *ctx, uint64_t bytes, void **d_ptr_out)

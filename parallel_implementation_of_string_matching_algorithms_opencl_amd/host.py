@@ -46,6 +46,10 @@ ED_BATCH_WORD = 64
 LCP_LANE_BYTES = 64  # a pair with a longer common prefix leaves the one-lane path of the LCP array (BMX_LCP_LANE_BYTES)
 ED_BATCH_LONG = 65536
 ED_NO_LIMIT = 0xFFFFFFFF
+MAP_MAX_K = 64  # most edits of Index.map (BMX_MAP_MAX_K)
+MAP_NO_HIT = 255  # distance of a candidate or a read without a hit (BMX_MAP_NO_HIT)
+MAP_NO_POS = 0xFFFFFFFFFFFFFFFF  # ... and its positions (BMX_MAP_NO_POS); -1 in the int64 tensors of Index.map
+MAP_MAX_CANDIDATES = 1 << 27
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -182,6 +186,14 @@ SYMBOLS = [
     ("bmx_index_seeds", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_uint64, _u64p]),
+    ("bmx_index_map_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                       C.c_uint32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_index_map", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_index_map_candidates", C.c_int64, [C.c_void_p]),
+    ("bmx_last_index_map_phases", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("bmx_last_index_ms", C.c_float, [C.c_void_p]),
     ("bmx_index_build_ms", C.c_float, [C.c_void_p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
@@ -915,8 +927,46 @@ class Context:
         del keep
         return (seed_off,) + tuple(o[:cap] for o in out)
 
+    def index_map(self, text, patterns, min_len: int, max_occ: int, k: int, candidates: bool = False):
+        """Host buffers: (best_start, best_end uint64, best_dist uint8), one entry per pattern: where the pattern lies in
+        ``text`` within k edits (MAP_NO_POS, MAP_NO_POS, MAP_NO_HIT if nowhere), by extending its seeds of
+        (min_len, max_occ).  That is one bmx_index_map.  With ``candidates`` also (cand_off uint64 of count + 1 entries,
+        cand_start, cand_end uint64, cand_dist uint8): every seed occurrence's own answer, in order of (pattern, seed,
+        occurrence); the lists are sized by a counting call, so the index is built once here and Index.map makes both."""
+        if candidates:
+            import torch
+
+            d_text = torch.from_numpy(np.frombuffer(_host_text(text)[2], dtype=np.uint8).copy()).cuda(self.device)
+            with self.index(d_text) as idx:
+                res = idx.map(patterns, min_len, max_occ, k, candidates=True)
+                res = tuple(o.cpu().numpy() for o in res)
+            return (res[0].view(np.uint64), res[1].view(np.uint64), res[2], res[3].view(np.uint64), res[4].view(np.uint64),
+                    res[5].view(np.uint64), res[6])
+        tptr, n, keep = _host_text(text)
+        blob, off = pack_strings(patterns)
+        count = off.size - 1
+        best = [np.empty(max(count, 1), dtype=np.uint64), np.empty(max(count, 1), dtype=np.uint64),
+                np.empty(max(count, 1), dtype=np.uint8)]
+        total = C.c_uint64(0)
+        rc = self._L.bmx_index_map(self._h, tptr, n, C.c_void_p(blob.ctypes.data), blob.size, C.c_void_p(off.ctypes.data), count,
+                                   min_len, max_occ, k, *[C.c_void_p(o.ctypes.data) for o in best], None, None, None, None, 0,
+                                   C.byref(total))
+        self._chk(rc, "bmx_index_map")
+        del keep
+        return tuple(o[:count] for o in best)
+
     def last_index_ms(self) -> float:
         return float(self._L.bmx_last_index_ms(self._h))
+
+    def last_index_map_phases(self) -> dict:
+        """Device ms of the last Index.map by phase, and the 64-bit words of the instance that ran (bmx_last_index_map_phases)."""
+        out = (C.c_float * 5)()
+        self._chk(self._L.bmx_last_index_map_phases(self._h, out), "bmx_last_index_map_phases")
+        return {"expand_ms": out[0], "verify_ms": out[1], "start_ms": out[2], "best_ms": out[3], "words": int(out[4])}
+
+    def last_index_map_candidates(self) -> int:
+        """Candidates (seed occurrences) of the last Index.map on this context; < 0 if none."""
+        return int(self._L.bmx_last_index_map_candidates(self._h))
 
     # -- suffix array (the reference's third program) -----------------------------
     def suffix_array(self, text) -> np.ndarray:
@@ -1258,6 +1308,44 @@ class Index:
         stored = min(int(total.value), capacity)
         return (seed_off,) + tuple(o[:stored] for o in out)
 
+    def map(self, patterns, min_len: int, max_occ: int, k: int, base_offset: int = 0, candidates: bool = False, out=None):
+        """(best_start, best_end, best_dist) (bmx_index_map_device): where every pattern lies in the text within k edits,
+        by extending its seeds of (min_len, max_occ >= 1): int64, int64 and uint8 CUDA tensors, one entry per pattern,
+        positions as base_offset + p; a pattern that maps nowhere has MAP_NO_POS (-1 in int64) and MAP_NO_HIT.  With
+        ``candidates`` four more: cand_off (int64, count + 1 entries, the exclusive prefix sum of the candidates per
+        pattern; cand_off[-1] is the true total) and cand_start, cand_end, cand_dist, one entry per seed occurrence in
+        order of (pattern, seed, occurrence), complete (a counting call first).  ``out``: three tensors to take the
+        per-pattern answer, used as given.  ``patterns`` as for count.  Runs on torch's current stream."""
+        import torch
+
+        d_blob, d_off, count = self._queries(patterns)
+        dev = self._text.device
+        if out is None:
+            out = (torch.empty(max(count, 1), dtype=torch.int64, device=dev), torch.empty(max(count, 1), dtype=torch.int64, device=dev),
+                   torch.empty(max(count, 1), dtype=torch.uint8, device=dev))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        total = C.c_uint64(0)
+
+        def call(cand_off, lists, cap):
+            ptrs = [None if o is None else C.c_void_p(o.data_ptr()) for o in (cand_off,) + tuple(lists)]
+            rc = self._L.bmx_index_map_device(self._ctx._h, self._h, C.c_void_p(d_blob.data_ptr()), d_blob.numel(),
+                                              C.c_void_p(d_off.data_ptr()), count, min_len, max_occ, k, base_offset,
+                                              *[C.c_void_p(o.data_ptr()) for o in out], *ptrs, cap, C.byref(total), stream)
+            self._ctx._chk(rc, "bmx_index_map_device")
+
+        best = tuple(o[:count] for o in out)
+        if not candidates:
+            call(None, (None,) * 3, 0)
+            return best
+        cand_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        call(cand_off, (None,) * 3, 0)  # the counting call: the per-pattern answer and cand_off are final after it
+        cap = int(total.value)
+        lists = (torch.empty(max(cap, 1), dtype=torch.int64, device=dev), torch.empty(max(cap, 1), dtype=torch.int64, device=dev),
+                 torch.empty(max(cap, 1), dtype=torch.uint8, device=dev))
+        if cap > 0:
+            call(cand_off, lists, cap)
+        return best + (cand_off,) + tuple(o[:cap] for o in lists)
+
     def locate(self, patterns, capacity: Optional[int] = None, base_offset: int = 0):
         """(offsets, positions, total) (bmx_index_locate_device): ``offsets`` int64 CUDA tensor of count + 1 entries, the
         exclusive prefix sum of the counts; positions[offsets[i] : offsets[i + 1]] = base_offset + p for every occurrence
@@ -1448,6 +1536,12 @@ def index_seeds(text, patterns, min_len: int, max_occ: int = 0):
     """The seeds of every pattern in ``text`` through a text index built for the call (bmx_index_seeds): (seed_off, qpos,
     len, lo, cnt), see Context.index_seeds."""
     return default_context().index_seeds(text, patterns, min_len, max_occ)
+
+
+def index_map(text, patterns, min_len: int, max_occ: int, k: int, candidates: bool = False):
+    """Where every pattern lies in ``text`` within k edits, through a text index built for the call (bmx_index_map):
+    (best_start, best_end, best_dist), see Context.index_map."""
+    return default_context().index_map(text, patterns, min_len, max_occ, k, candidates)
 
 
 def lcp_array(text) -> Tuple[np.ndarray, np.ndarray]:
