@@ -1,7 +1,8 @@
 // bmx_host_entries.cpp -- the host-buffer entries of the C ABI (include/bmx.h): host buffers in, host buffers out, over
 // the public device API.  Each checks its arguments (every BMX_ERR_ARG and BMX_ERR_DOMAIN before any HIP call: the CPU
-// suite calls these with ctx = NULL on a machine without a GPU), uploads, runs the device entry and downloads.  Plain
-// host C++: no kernel, one object for both libraries.
+// suite calls these with ctx = NULL on a machine without a GPU), uploads, runs the device entry and downloads.  HostCall
+// holds one call's context and device buffers; IndexCall adds what the five index entries open with.  Plain host C++: no
+// kernel, one object for both libraries.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -16,8 +17,8 @@ namespace {
 
 // One host-buffer call: the context (the caller's, or one on device 0 that lives as long as the call), the device buffers
 // the call hands out and the running return code.  upload() and alloc() do nothing once a step has failed; everything is
-// freed when the call leaves scope.  Handles that must go before the context (bmx_dict, bmx_index) are the entry's to
-// destroy, before this object.
+// freed when the call leaves scope.  A handle that must go before the context is the entry's to destroy, before this
+// object (bmx_dict), or a derived class's (IndexCall).
 class HostCall {
 public:
     int rc = BMX_OK;
@@ -79,6 +80,26 @@ private:
     bmx_ctx *ctx_;
     bool own_ctx_;
     std::vector<void *> bufs_;
+};
+
+// What the five index entries open with, behind their argument checks: the text, the query blob and its offsets on the
+// device and an index over the text (its own suffix array).  The index goes before the context does.
+class IndexCall : public HostCall {
+public:
+    bmx_index *ix = nullptr;
+    void *d_pat;
+    const uint64_t *d_off;
+
+    IndexCall(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat, uint64_t pat_bytes,
+              const uint64_t *pat_off, uint64_t count)
+        : HostCall(entry, ctx_in)
+    {
+        void *d_text = upload(text, n);
+        d_pat = upload(pat, pat_bytes);
+        d_off = upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+        if (rc == BMX_OK) rc = bmx_index_create_device(ctx(), d_text, n, nullptr, nullptr, &ix);
+    }
+    ~IndexCall() { bmx_index_destroy(ix); }
 };
 
 // table errors (a pattern outside the ASCII domain) before any device work
@@ -376,16 +397,10 @@ int bmx_index_count(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *p
     if (count == 0) return BMX_OK;
     const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
     if (qrc != BMX_OK) return qrc;
-    HostCall c("bmx_index_count", ctx_in);
-    bmx_index *ix = nullptr;
-    void *d_text = c.upload(text, n);
-    void *d_pat = c.upload(pat, pat_bytes);
-    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
+    IndexCall c("bmx_index_count", ctx_in, text, n, pat, pat_bytes, pat_off, count);
     uint32_t *d_cnt = c.alloc<uint32_t>(count * sizeof(uint32_t));
-    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
-    if (c.rc == BMX_OK) c.rc = bmx_index_count_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, nullptr, d_cnt, nullptr);
+    if (c.rc == BMX_OK) c.rc = bmx_index_count_device(c.ctx(), c.ix, c.d_pat, pat_bytes, c.d_off, count, nullptr, d_cnt, nullptr);
     if (c.rc == BMX_OK) c.download(cnt, d_cnt, count * sizeof(uint32_t), "the counts");
-    bmx_index_destroy(ix); // before the context
     return c.rc;
 }
 
@@ -399,24 +414,19 @@ int bmx_index_locate(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *
     if (count == 0) return BMX_OK;
     const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
     if (qrc != BMX_OK) return qrc;
-    HostCall c("bmx_index_locate", ctx_in);
-    bmx_index *ix = nullptr;
+    IndexCall c("bmx_index_locate", ctx_in, text, n, pat, pat_bytes, pat_off, count);
     uint64_t total = 0;
-    void *d_text = c.upload(text, n);
-    void *d_pat = c.upload(pat, pat_bytes);
-    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
     uint64_t *d_out_off = c.alloc<uint64_t>((count + 1) * sizeof(uint64_t));
     uint64_t *d_pos = capacity ? c.alloc<uint64_t>(capacity * sizeof(uint64_t)) : nullptr;
-    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
     if (c.rc == BMX_OK)
-        c.rc = bmx_index_locate_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, 0, d_out_off, d_pos, capacity, &total, nullptr);
+        c.rc = bmx_index_locate_device(c.ctx(), c.ix, c.d_pat, pat_bytes, c.d_off, count, 0, d_out_off, d_pos, capacity, &total,
+                                       nullptr);
     if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
         c.download(out_off, d_out_off, (count + 1) * sizeof(uint64_t), "the positions");
         // (behind the stored segments: unspecified, as in the device entry)
         c.download(pos, d_pos, std::min(total, capacity) * sizeof(uint64_t), "the positions");
         if (n_matches) *n_matches = total;
     }
-    bmx_index_destroy(ix); // before the context
     return c.rc;
 }
 
@@ -427,24 +437,19 @@ int bmx_index_match(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *p
     if (count == 0) return BMX_OK;
     const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
     if (qrc != BMX_OK) return qrc;
-    HostCall c("bmx_index_match", ctx_in);
-    bmx_index *ix = nullptr;
+    IndexCall c("bmx_index_match", ctx_in, text, n, pat, pat_bytes, pat_off, count);
     // (only the bytes inside the queries come back: the caller's entries outside them stay as they are)
     const uint64_t at = pat_off[0], used = pat_off[count] - at;
-    void *d_text = c.upload(text, n);
-    void *d_pat = c.upload(pat, pat_bytes);
-    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
     uint32_t *d_len = c.alloc<uint32_t>(pat_bytes * sizeof(uint32_t));
     uint32_t *d_lo = lo ? c.alloc<uint32_t>(pat_bytes * sizeof(uint32_t)) : nullptr;
     uint32_t *d_cnt = cnt ? c.alloc<uint32_t>(pat_bytes * sizeof(uint32_t)) : nullptr;
-    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
-    if (c.rc == BMX_OK) c.rc = bmx_index_match_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, d_len, d_lo, d_cnt, nullptr);
+    if (c.rc == BMX_OK)
+        c.rc = bmx_index_match_device(c.ctx(), c.ix, c.d_pat, pat_bytes, c.d_off, count, d_len, d_lo, d_cnt, nullptr);
     if (c.rc == BMX_OK) {
         c.download(len + at, d_len + at, used * sizeof(uint32_t), "the match lengths");
         if (lo) c.download(lo + at, d_lo + at, used * sizeof(uint32_t), "the interval starts");
         if (cnt) c.download(cnt + at, d_cnt + at, used * sizeof(uint32_t), "the interval sizes");
     }
-    bmx_index_destroy(ix); // before the context
     return c.rc;
 }
 
@@ -459,19 +464,14 @@ int bmx_index_seeds(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *p
     if (count == 0) return BMX_OK;
     const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
     if (qrc != BMX_OK) return qrc;
-    HostCall c("bmx_index_seeds", ctx_in);
-    bmx_index *ix = nullptr;
+    IndexCall c("bmx_index_seeds", ctx_in, text, n, pat, pat_bytes, pat_off, count);
     uint64_t total = 0;
     // (no more seeds than blob bytes: a larger capacity needs no larger device lists)
     const uint64_t dev_cap = std::min(capacity, pat_bytes);
-    void *d_text = c.upload(text, n);
-    void *d_pat = c.upload(pat, pat_bytes);
-    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
     uint64_t *d_seed_off = c.alloc<uint64_t>((count + 1) * sizeof(uint64_t));
     uint32_t *d_out = dev_cap ? c.alloc<uint32_t>(4 * dev_cap * sizeof(uint32_t)) : nullptr;
-    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
     if (c.rc == BMX_OK)
-        c.rc = bmx_index_seeds_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, min_len, max_occ, d_seed_off, d_out,
+        c.rc = bmx_index_seeds_device(c.ctx(), c.ix, c.d_pat, pat_bytes, c.d_off, count, min_len, max_occ, d_seed_off, d_out,
                                       d_out ? d_out + dev_cap : nullptr, d_out ? d_out + 2 * dev_cap : nullptr,
                                       d_out ? d_out + 3 * dev_cap : nullptr, dev_cap, &total, nullptr);
     if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
@@ -483,7 +483,6 @@ int bmx_index_seeds(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *p
         c.download(cnt, d_out + 3 * dev_cap, stored, "the seeds");
         if (n_seeds) *n_seeds = total;
     }
-    bmx_index_destroy(ix); // before the context
     return c.rc;
 }
 
@@ -500,22 +499,17 @@ int bmx_index_map(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat
     if (count == 0) return BMX_OK;
     const int qrc = bmx_index_queries_ok(pat, pat_bytes, pat_off, count);
     if (qrc != BMX_OK) return qrc;
-    HostCall c("bmx_index_map", ctx_in);
-    bmx_index *ix = nullptr;
+    IndexCall c("bmx_index_map", ctx_in, text, n, pat, pat_bytes, pat_off, count);
     uint64_t total = 0;
     // (a blob byte is at most one seed of at most max_occ occurrences, and no call has more than BMX_MAP_MAX_CANDIDATES:
     // a larger capacity needs no larger device lists, and one pass fills them)
     const uint64_t most = pat_bytes > BMX_MAP_MAX_CANDIDATES / max_occ ? BMX_MAP_MAX_CANDIDATES : pat_bytes * max_occ;
     const uint64_t dev_cap = std::min(capacity, most);
-    void *d_text = c.upload(text, n);
-    void *d_pat = c.upload(pat, pat_bytes);
-    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (count + 1) * sizeof(uint64_t));
     uint64_t *d_best = c.alloc<uint64_t>(2 * count * sizeof(uint64_t) + count);
     uint64_t *d_cand_off = cand_off ? c.alloc<uint64_t>((count + 1) * sizeof(uint64_t)) : nullptr;
     uint64_t *d_cand = dev_cap ? c.alloc<uint64_t>(2 * dev_cap * sizeof(uint64_t) + dev_cap) : nullptr;
-    if (c.rc == BMX_OK) c.rc = bmx_index_create_device(c.ctx(), d_text, n, nullptr, nullptr, &ix);
     if (c.rc == BMX_OK)
-        c.rc = bmx_index_map_device(c.ctx(), ix, d_pat, pat_bytes, d_off, count, min_len, max_occ, k, 0, d_best, d_best + count,
+        c.rc = bmx_index_map_device(c.ctx(), c.ix, c.d_pat, pat_bytes, c.d_off, count, min_len, max_occ, k, 0, d_best, d_best + count,
                                     reinterpret_cast<uint8_t *>(d_best + 2 * count), d_cand_off, d_cand,
                                     d_cand ? d_cand + dev_cap : nullptr,
                                     d_cand ? reinterpret_cast<uint8_t *>(d_cand + 2 * dev_cap) : nullptr, dev_cap, &total, nullptr);
@@ -530,7 +524,6 @@ int bmx_index_map(bmx_ctx *ctx_in, const char *text, uint64_t n, const void *pat
         c.download(cand_dist, d_cand + 2 * dev_cap, lists, "the candidates");
         if (n_candidates) *n_candidates = total;
     }
-    bmx_index_destroy(ix); // before the context
     return c.rc;
 }
 

@@ -11,10 +11,12 @@
 // LESS than the pattern unless it carries the virtual symbol and the pattern's next byte is below 96.  The suffixes
 // that have the pattern as a prefix are then one interval [lo, lo + cnt) of the array: the true occurrences.
 //
-// index_count_kernel: one query per lane, two binary searches (first suffix not below the pattern, first suffix above
-// it) with the common-prefix lengths of both bounds carried along, so that a probe starts comparing at the smaller of
-// the two (Manber and Myers); bytes are compared eight at a time as big-endian words with the sign bits flipped.  A
-// query of two or more bytes starts inside the directory's bucket of its first two bytes.  The path is a chain of
+// index_count_kernel: one query per lane, two binary searches (index_bound: first suffix not below the pattern, first
+// suffix above it) with the common-prefix lengths of both bounds carried along, so that a probe starts comparing at the
+// smaller of the two (Manber and Myers); bytes are compared eight at a time as big-endian words with the sign bits
+// flipped.  A query of two or more bytes starts inside the directory's bucket of its first two bytes (index_bucket).
+// The match and map kernels (bmx_index_match_kernel.h, bmx_index_map_kernel.h) search with the same pieces: the query
+// descriptor IndexQuery, index_bytes_ok, index_bucket, index_bound and index_query_of live here, once.  The path is a chain of
 // dependent random reads (array entry, then text words): it is bound by latency and by the number of lanes in flight.
 //
 // Memory safety: a text or pattern byte is fetched as part of the aligned 8-byte word that holds it; no word is read
@@ -35,7 +37,9 @@ constexpr uint32_t INDEX_DIR_ENTRIES = INDEX_DIR_SIDE * INDEX_DIR_SIDE;
 // would leave more than half of its lanes idle in its only step.
 constexpr uint32_t INDEX_FILL_SHORT = 32;
 
-struct IndexArgs {
+// What every kernel of the index reads: the text and its array, the query blob and its offsets, the directory and the
+// status words.  IndexArgs, IndexMatchArgs and IndexMapArgs begin with one and put their outputs behind it.
+struct IndexQuery {
     const uint8_t *text;
     uint32_t n;
     const int32_t *sa;
@@ -44,9 +48,13 @@ struct IndexArgs {
     const uint64_t *pat_off;
     uint64_t count;
     const uint32_t *dir_lo, *dir_cnt; // the directory (INDEX_DIR_ENTRIES each), or nullptr: every search is plain
-    uint32_t *lo;                     // may be nullptr
-    uint32_t *cnt;
     uint64_t *status; // [0]: offsets or lengths out of range, [1]: a pattern byte >= 0x80
+};
+
+struct IndexArgs {
+    IndexQuery q;
+    uint32_t *lo; // may be nullptr
+    uint32_t *cnt;
 };
 
 // base[at .. at + 8) as one big-endian word with every byte's sign bit flipped: unsigned order of two such words is
@@ -101,51 +109,84 @@ __device__ __forceinline__ uint32_t index_entry(const int32_t *sa, uint32_t j, u
     return p < n ? p : n - 1u;
 }
 
+// No byte of pat[at .. at + m) is 0x80 or above (flipped sign bits: such a byte shows as a clear top bit).
+__device__ __forceinline__ bool index_bytes_ok(const uint8_t *pat, uint64_t at, uint32_t m, uint64_t pat_bytes)
+{
+    for (uint32_t k = 0; k < m; k += 8) {
+        const uint32_t valid = m - k < 8u ? m - k : 8u;
+        const uint64_t w = index_load8(pat, at + k, pat_bytes);
+        if (~w & 0x8080808080808080ull & (~0ull << (8u * (8u - valid)))) return false;
+    }
+    return true;
+}
+
+// The directory's bucket [lo, hi) of the two bytes at pat[at]: every suffix in it shares them with the pattern.  false,
+// and lo and hi as they were: there is no directory, or the pattern has one byte.  What an empty bucket means is the
+// caller's to say.
+__device__ __forceinline__ bool index_bucket(const IndexQuery &q, uint64_t at, uint32_t m, uint32_t &lo, uint32_t &hi)
+{
+    if (!q.dir_lo || m < 2) return false;
+    const uint32_t b = (uint32_t)q.pat[at] * INDEX_DIR_SIDE + q.pat[at + 1];
+    lo = q.dir_lo[b];
+    hi = lo + q.dir_cnt[b];
+    return true;
+}
+
+// Bisection of [x, y) for pat[at .. at + m): x becomes the first suffix that is not below the pattern, or with UPPER the
+// first one above it.  lx, ly: in, bytes that the suffixes in front of x and from y on are known to share with the
+// pattern; out, the bytes that sa[x - 1] and sa[x] share with it (a bound that never moved keeps what came in).  A probe
+// starts comparing at the smaller of the two.
+template <bool UPPER>
+__device__ __forceinline__ void index_bound(const IndexQuery &q, uint64_t at, uint32_t m, uint32_t &x, uint32_t y, uint32_t &lx,
+                                            uint32_t &ly)
+{
+    while (x < y) {
+        const uint32_t mid = x + ((y - x) >> 1);
+        uint32_t l = lx < ly ? lx : ly;
+        const int c = index_compare(q.text, q.n, index_entry(q.sa, mid, q.n), q.pat, q.pat_bytes, at, m, l);
+        if (UPPER ? c <= 0 : c < 0) x = mid + 1, lx = l;
+        else y = mid, ly = l;
+    }
+}
+
+// The last query that starts at or before blob byte b (count >= 1; offsets that are not sorted give some query, which
+// the caller checks).
+__device__ __forceinline__ uint64_t index_query_of(const uint64_t *pat_off, uint64_t count, uint64_t b)
+{
+    uint64_t q = 0, qe = count;
+    while (qe - q > 1) {
+        const uint64_t mid = q + ((qe - q) >> 1);
+        if (pat_off[mid] <= b) q = mid;
+        else qe = mid;
+    }
+    return q;
+}
+
 __global__ __launch_bounds__(INDEX_BLOCK) void index_count_kernel(IndexArgs a)
 {
+    const IndexQuery &q = a.q;
     const uint64_t i = (uint64_t)blockIdx.x * INDEX_BLOCK + threadIdx.x;
-    if (i >= a.count) return;
-    const uint64_t o0 = a.pat_off[i], o1 = a.pat_off[i + 1];
-    if (o1 < o0 || o1 > a.pat_bytes || o1 == o0 || o1 - o0 > INDEX_MAX_PATTERN) {
-        a.status[0] = 1;
+    if (i >= q.count) return;
+    const uint64_t o0 = q.pat_off[i], o1 = q.pat_off[i + 1];
+    if (o1 < o0 || o1 > q.pat_bytes || o1 == o0 || o1 - o0 > INDEX_MAX_PATTERN) {
+        q.status[0] = 1;
         return;
     }
     const uint32_t m = (uint32_t)(o1 - o0);
-    for (uint32_t k = 0; k < m; k += 8) { // flipped sign bits: a byte >= 0x80 shows as a clear top bit
-        const uint32_t valid = m - k < 8u ? m - k : 8u;
-        const uint64_t w = index_load8(a.pat, o0 + k, a.pat_bytes);
-        if (~w & 0x8080808080808080ull & (~0ull << (8u * (8u - valid)))) {
-            a.status[1] = 1;
-            return;
-        }
+    if (!index_bytes_ok(q.pat, o0, m, q.pat_bytes)) {
+        q.status[1] = 1;
+        return;
     }
 
-    uint32_t lo = 0, hi = a.n, known = 0; // the interval that is searched; bytes every suffix in it shares with the pattern
-    if (a.dir_lo && m >= 2) {
-        const uint32_t b = (uint32_t)a.pat[o0] * INDEX_DIR_SIDE + a.pat[o0 + 1];
-        lo = a.dir_lo[b];
-        hi = lo + a.dir_cnt[b];
-        known = 2;
-    }
+    uint32_t lo = 0, hi = q.n; // the interval that is searched; `known` bytes every suffix in it shares with the pattern
+    const uint32_t known = index_bucket(q, o0, m, lo, hi) ? 2u : 0u;
     uint32_t first = lo, end = hi;
     if (!(known == 2 && (m == 2 || lo == hi))) { // (an empty bucket's start is the pattern's insertion point as well)
-        uint32_t x = lo, y = hi, lx = known, ly = known; // first suffix that is not below the pattern
-        while (x < y) {
-            const uint32_t mid = x + ((y - x) >> 1);
-            uint32_t l = lx < ly ? lx : ly;
-            const int c = index_compare(a.text, a.n, index_entry(a.sa, mid, a.n), a.pat, a.pat_bytes, o0, m, l);
-            if (c < 0) x = mid + 1, lx = l;
-            else y = mid, ly = l;
-        }
+        uint32_t x = lo, lx = known, ly = known;
+        index_bound<false>(q, o0, m, x, hi, lx, ly);
         first = x;
-        y = hi, lx = known, ly = known; // first suffix above it
-        while (x < y) {
-            const uint32_t mid = x + ((y - x) >> 1);
-            uint32_t l = lx < ly ? lx : ly;
-            const int c = index_compare(a.text, a.n, index_entry(a.sa, mid, a.n), a.pat, a.pat_bytes, o0, m, l);
-            if (c <= 0) x = mid + 1, lx = l;
-            else y = mid, ly = l;
-        }
+        lx = known, ly = known;
+        index_bound<true>(q, o0, m, x, hi, lx, ly);
         end = x;
     }
     if (a.lo) a.lo[i] = first;

@@ -7,7 +7,7 @@
 // scan of it (64-bit, bytes + 1 entries) is `scan`: the candidates in front of blob byte b.  So the candidates of query q
 // are [scan[off[q]], scan[off[q+1]]) and the total is scan[bytes].  index_map_fill_kernel: one lane per candidate c; the
 // lane finds its blob byte by a binary search of c over scan (the last b with scan[b] <= c has a non-zero count), its
-// query by the match kernel's search over the offsets, and writes (q, i, p = sa[lo[b] + c - scan[b]]).  No atomics: the
+// query by index_query_of over the offsets, and writes (q, i, p = sa[lo[b] + c - scan[b]]).  No atomics: the
 // list is in order of (query, seed, t) in every run.
 //
 // Verification (index_map_verify_kernel<W>): one candidate per lane.  d = p - i is the diagonal, the window is
@@ -78,14 +78,10 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_map_off_kernel(const uint64
     if (q == count) res[0] = s;
 }
 
+// q.status has a second meaning here, behind the match kernel's (whose two words are then 0: it has raised none).
+// [0]: a candidate that failed its checks, [1]: a start pass that disagrees with its verification.  The directory is not read.
 struct IndexMapArgs {
-    const uint8_t *text;
-    uint32_t n;
-    const int32_t *sa;
-    const uint8_t *pat;
-    uint64_t pat_bytes;
-    const uint64_t *pat_off;
-    uint64_t count;
+    IndexQuery q;
     const uint64_t *scan;      // bytes + 1 entries
     const uint32_t *qpos, *lo; // per blob byte
     uint64_t total;            // candidates
@@ -99,30 +95,24 @@ struct IndexMapArgs {
     uint64_t capacity;
     uint64_t *best_start, *best_end; // per query
     uint8_t *best_dist;
-    uint64_t *status; // [0]: a candidate that failed its checks, [1]: a start pass that disagrees with its verification
 };
 
 __global__ __launch_bounds__(INDEX_BLOCK) void index_map_fill_kernel(IndexMapArgs a)
 {
     const uint64_t c = (uint64_t)blockIdx.x * INDEX_BLOCK + threadIdx.x;
     if (c >= a.total) return;
-    uint64_t x = 0, y = a.pat_bytes; // the last b in [0, bytes) with scan[b] <= c (scan[0] == 0, scan[bytes] == total > c)
+    uint64_t x = 0, y = a.q.pat_bytes; // the last b in [0, bytes) with scan[b] <= c (scan[0] == 0, scan[bytes] == total > c)
     while (y - x > 1) {
         const uint64_t mid = x + ((y - x) >> 1);
         if (a.scan[mid] <= c) x = mid;
         else y = mid;
     }
     const uint64_t b = x;
-    uint64_t q = 0, qe = a.count; // the last query that starts at or before byte b
-    while (qe - q > 1) {
-        const uint64_t mid = q + ((qe - q) >> 1);
-        if (a.pat_off[mid] <= b) q = mid;
-        else qe = mid;
-    }
+    const uint64_t q = index_query_of(a.q.pat_off, a.q.count, b);
     const uint64_t j = (uint64_t)a.lo[b] + (c - a.scan[b]);
     a.cq[c] = (uint32_t)q;
     a.ci[c] = a.qpos[b];
-    a.cp[c] = index_entry(a.sa, j < a.n ? (uint32_t)j : a.n - 1u, a.n);
+    a.cp[c] = index_entry(a.q.sa, j < a.q.n ? (uint32_t)j : a.q.n - 1u, a.q.n);
 }
 
 // The query Q[0..m) into 16 W registers, in the layout ed_batch_eq32 reads: bit 64w + 32h + 8k + j of Eq belongs to
@@ -186,14 +176,14 @@ __device__ __forceinline__ MapCand map_candidate(const IndexMapArgs &a, uint64_t
     if (c >= a.total) return r;
     const uint64_t q = a.cq[c];
     const uint32_t i = a.ci[c], p = a.cp[c];
-    bool ok = q < a.count;
+    bool ok = q < a.q.count;
     uint64_t o0 = 0, o1 = 0;
     if (ok) {
-        o0 = a.pat_off[q], o1 = a.pat_off[q + 1];
-        ok = o1 > o0 && o1 <= a.pat_bytes && o1 - o0 <= 64u * W && (uint64_t)i < o1 - o0 && p < a.n;
+        o0 = a.q.pat_off[q], o1 = a.q.pat_off[q + 1];
+        ok = o1 > o0 && o1 <= a.q.pat_bytes && o1 - o0 <= 64u * W && (uint64_t)i < o1 - o0 && p < a.q.n;
     }
     if (!ok) {
-        a.status[0] = 1;
+        a.q.status[0] = 1;
         return r;
     }
     r.ok = true;
@@ -203,8 +193,8 @@ __device__ __forceinline__ MapCand map_candidate(const IndexMapArgs &a, uint64_t
     const int64_t d = (int64_t)p - (int64_t)i;
     const int64_t lo = d - (int64_t)a.k, hi = d + (int64_t)r.m + (int64_t)a.k;
     r.w0 = lo > 0 ? (uint32_t)lo : 0u;
-    r.w1 = hi < (int64_t)a.n ? (uint32_t)hi : a.n; // > w0: the window holds the seed's occurrence
-    r.Q = a.pat + o0;
+    r.w1 = hi < (int64_t)a.q.n ? (uint32_t)hi : a.q.n; // > w0: the window holds the seed's occurrence
+    r.Q = a.q.pat + o0;
     return r;
 }
 
@@ -243,7 +233,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_map_verify_kernel(const Ind
     uint32_t score = cd.m, best = 0xffffffffu, best_end = 0;
 
     // aligned 8-byte words of the window, from the word that holds w0 to the one that holds w1 - 1
-    const uintptr_t t0 = (uintptr_t)a.text;
+    const uintptr_t t0 = (uintptr_t)a.q.text;
     const uint64_t *words8 = reinterpret_cast<const uint64_t *>(t0 & ~(uintptr_t)7);
     const uint64_t first = t0 & 7u;
     uint64_t wi = (first + cd.w0) >> 3;
@@ -291,7 +281,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_map_start_kernel(const Inde
         uint32_t score = cd.m, len = 0;
         const uint32_t steps = cd.ok ? min(end - cd.w0 + 1u, cd.m + a.k) : 0u;
 
-        const uintptr_t t0 = (uintptr_t)a.text;
+        const uintptr_t t0 = (uintptr_t)a.q.text;
         const uint64_t *words8 = reinterpret_cast<const uint64_t *>(t0 & ~(uintptr_t)7);
         const uint64_t first = t0 & 7u;
         int64_t wi = cd.ok ? (int64_t)((first + end) >> 3) : 0;
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_map_start_kernel(const Inde
     if (!listed) return;
     uint32_t start = MAP_NO_POS32;
     if (cd.ok) {
-        if (best != dist) a.status[1] = 1;
+        if (best != dist) a.q.status[1] = 1;
         start = end - (best_len - 1u);
     }
     a.cstart[c] = start;
@@ -330,12 +320,12 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_map_start_kernel(const Inde
 __global__ __launch_bounds__(INDEX_BLOCK) void index_map_best_kernel(const IndexMapArgs a)
 {
     const uint64_t q = (uint64_t)blockIdx.x * INDEX_BLOCK + threadIdx.x;
-    if (q >= a.count) return;
+    if (q >= a.q.count) return;
     uint64_t c0 = 0, c1 = 0;
     if (a.total) { // (without a candidate the scan is not read: every query is unmapped)
-        const uint64_t o0 = a.pat_off[q], o1 = a.pat_off[q + 1];
-        c0 = a.scan[o0 < a.pat_bytes ? o0 : a.pat_bytes];
-        c1 = a.scan[o1 < a.pat_bytes ? o1 : a.pat_bytes];
+        const uint64_t o0 = a.q.pat_off[q], o1 = a.q.pat_off[q + 1];
+        c0 = a.scan[o0 < a.q.pat_bytes ? o0 : a.q.pat_bytes];
+        c1 = a.scan[o1 < a.q.pat_bytes ? o1 : a.q.pat_bytes];
         if (c1 > a.total) c1 = a.total;
     }
     uint32_t bd = MAP_NO_HIT, be = MAP_NO_POS32, bs = MAP_NO_POS32;

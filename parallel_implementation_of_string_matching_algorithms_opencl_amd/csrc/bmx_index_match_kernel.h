@@ -1,13 +1,15 @@
 // bmx_index_match_kernel.h -- kernels of the text index's matching statistics and seeds (bmx_index_match_device,
-// bmx_index_seeds_device, include/bmx.h), over the comparator, loads and directory of bmx_index_kernel.h.
+// bmx_index_seeds_device, include/bmx.h), over the query descriptor, comparator, loads, directory and bisection of
+// bmx_index_kernel.h.
 //
-// index_match_kernel: one lane per blob byte b.  The lane finds its query q (binary search of b over pat_off), checks
+// index_match_kernel: one lane per blob byte b.  The lane finds its query q (index_query_of: b over pat_off), checks
 // that q holds b, is at most INDEX_MAX_PATTERN bytes long and that every byte of the query's rest pat[b .. off[q+1]) is
 // below 0x80, and then answers for that rest, which it treats as a query of its own that ends where query q ends:
-//   1. the rest's insertion point x in the array, by the count kernel's first search (inside the directory bucket of
-//      the rest's first two bytes, common-prefix lengths of both bounds carried along).  When the search ends, the two
-//      lengths it carries are the common prefixes of the rest with sa[x - 1] and sa[x]; the longer one is the longest
-//      match `len` (tests/match_oracle.py holds that to brute force; the virtual symbol equals no query byte).
+//   1. the rest's insertion point x in the array, by the count kernel's first search (index_bound, inside the bucket
+//      index_bucket gives for the rest's first two bytes, common-prefix lengths of both bounds carried along).  When
+//      the search ends, the two lengths it carries are the common prefixes of the rest with sa[x - 1] and sa[x]; the
+//      longer one is the longest match `len` (tests/match_oracle.py holds that to brute force; the virtual symbol
+//      equals no query byte).
 //   2. the interval of the prefix rest[0 .. len): it holds x - 1 or x.  The neighbour whose common prefix is shorter
 //      than len is outside, so that bound is x with no further read; on the other side the lane gallops away from x
 //      (1, 2, 4, .. entries) and bisects the last step, comparing against the prefix only.  An interval of c entries
@@ -32,65 +34,43 @@ namespace bmx {
 constexpr uint32_t INDEX_NO_QUERY = 0xffffffffu; // workspace qpos of a blob byte that no lane answered for
 
 struct IndexMatchArgs {
-    const uint8_t *text;
-    uint32_t n;
-    const int32_t *sa;
-    const uint8_t *pat;
-    uint64_t pat_bytes;
-    const uint64_t *pat_off;
-    uint64_t count;
-    const uint32_t *dir_lo, *dir_cnt; // the directory, or nullptr: every search is plain
-    uint32_t *len;                    // per blob byte
-    uint32_t *lo, *cnt;               // per blob byte; may be nullptr
-    uint32_t *qpos;                   // per blob byte: its position inside its query (seeds), or nullptr
-    uint64_t *status;                 // [0]: offsets or lengths out of range, [1]: a pattern byte >= 0x80
+    IndexQuery q;
+    uint32_t *len;      // per blob byte
+    uint32_t *lo, *cnt; // per blob byte; may be nullptr
+    uint32_t *qpos;     // per blob byte: its position inside its query (seeds), or nullptr
 };
 
 __global__ __launch_bounds__(INDEX_BLOCK) void index_match_kernel(IndexMatchArgs a)
 {
+    const IndexQuery &q = a.q;
     const uint64_t t = (uint64_t)blockIdx.x * INDEX_BLOCK + threadIdx.x;
-    if (t < a.count) {
-        const uint64_t q0 = a.pat_off[t], q1 = a.pat_off[t + 1];
-        if (q1 < q0 || q1 > a.pat_bytes || q1 == q0 || q1 - q0 > INDEX_MAX_PATTERN) a.status[0] = 1;
+    if (t < q.count) {
+        const uint64_t q0 = q.pat_off[t], q1 = q.pat_off[t + 1];
+        if (q1 < q0 || q1 > q.pat_bytes || q1 == q0 || q1 - q0 > INDEX_MAX_PATTERN) q.status[0] = 1;
     }
-    if (t >= a.pat_bytes || t < a.pat_off[0] || t >= a.pat_off[a.count]) return; // outside every query: left untouched
+    if (t >= q.pat_bytes || t < q.pat_off[0] || t >= q.pat_off[q.count]) return; // outside every query: left untouched
 
-    uint64_t q = 0, qe = a.count; // the last query that starts at or before byte t
-    while (qe - q > 1) {
-        const uint64_t mid = q + ((qe - q) >> 1);
-        if (a.pat_off[mid] <= t) q = mid;
-        else qe = mid;
-    }
-    const uint64_t o0 = a.pat_off[q], o1 = a.pat_off[q + 1];
-    if (o0 > t || o1 <= t || o1 > a.pat_bytes || o1 - o0 > INDEX_MAX_PATTERN) { // (offsets that are not sorted end here)
-        a.status[0] = 1;
+    const uint64_t qi = index_query_of(q.pat_off, q.count, t);
+    const uint64_t o0 = q.pat_off[qi], o1 = q.pat_off[qi + 1];
+    if (o0 > t || o1 <= t || o1 > q.pat_bytes || o1 - o0 > INDEX_MAX_PATTERN) { // (offsets that are not sorted end here)
+        q.status[0] = 1;
         return;
     }
     uint32_t m = (uint32_t)(o1 - t); // the rest of the query: the match never runs into the next one
-    for (uint32_t k = 0; k < m; k += 8) {
-        const uint32_t valid = m - k < 8u ? m - k : 8u;
-        const uint64_t w = index_load8(a.pat, t + k, a.pat_bytes);
-        if (~w & 0x8080808080808080ull & (~0ull << (8u * (8u - valid)))) {
-            a.status[1] = 1;
-            return;
-        }
+    if (!index_bytes_ok(q.pat, t, m, q.pat_bytes)) {
+        q.status[1] = 1;
+        return;
     }
 
-    uint32_t lo0 = 0, hi0 = a.n, known = 0; // the interval that is searched; bytes every suffix in it shares with the rest
-    if (a.dir_lo && m >= 2) {
-        const uint32_t b = (uint32_t)a.pat[t] * INDEX_DIR_SIDE + a.pat[t + 1];
-        const uint32_t dl = a.dir_lo[b], dc = a.dir_cnt[b];
-        if (dc) lo0 = dl, hi0 = dl + dc, known = 2;
-        else m = 1; // the first two bytes occur nowhere: the match is 0 or 1 bytes long, the first byte's plain search says which
+    uint32_t lo0 = 0, hi0 = q.n, known = 0; // the interval that is searched; bytes every suffix in it shares with the rest
+    if (index_bucket(q, t, m, lo0, hi0)) {
+        // an empty bucket, the first two bytes occur nowhere: the match is 0 or 1 bytes long, and the first byte's plain
+        // search over the whole array says which
+        if (hi0 > lo0) known = 2;
+        else lo0 = 0, hi0 = q.n, m = 1;
     }
-    uint32_t x = lo0, y = hi0, lx = known, ly = known; // first suffix that is not below the rest
-    while (x < y) {
-        const uint32_t mid = x + ((y - x) >> 1);
-        uint32_t l = lx < ly ? lx : ly;
-        const int c = index_compare(a.text, a.n, index_entry(a.sa, mid, a.n), a.pat, a.pat_bytes, t, m, l);
-        if (c < 0) x = mid + 1, lx = l;
-        else y = mid, ly = l;
-    }
+    uint32_t x = lo0, lx = known, ly = known; // first suffix that is not below the rest
+    index_bound<false>(q, t, m, x, hi0, lx, ly);
     // lx, ly: the bytes sa[x - 1] and sa[x] share with the rest (a bound that never moved has its neighbour outside
     // the bucket, or none, and keeps `known`, which the other one reaches at least)
     const uint32_t len = lx > ly ? lx : ly;
@@ -104,7 +84,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_match_kernel(IndexMatchArgs
             while (b - f >= step) {
                 const uint32_t j = b - step;
                 uint32_t l = lf < lb ? lf : lb;
-                const int c = index_compare(a.text, a.n, index_entry(a.sa, j, a.n), a.pat, a.pat_bytes, t, len, l);
+                const int c = index_compare(q.text, q.n, index_entry(q.sa, j, q.n), q.pat, q.pat_bytes, t, len, l);
                 if (c < 0) {
                     f = j + 1u, lf = l;
                     break;
@@ -114,7 +94,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_match_kernel(IndexMatchArgs
             while (f < b) {
                 const uint32_t mid = f + ((b - f) >> 1);
                 uint32_t l = lf < lb ? lf : lb;
-                const int c = index_compare(a.text, a.n, index_entry(a.sa, mid, a.n), a.pat, a.pat_bytes, t, len, l);
+                const int c = index_compare(q.text, q.n, index_entry(q.sa, mid, q.n), q.pat, q.pat_bytes, t, len, l);
                 if (c < 0) f = mid + 1u, lf = l;
                 else b = mid, lb = l;
             }
@@ -125,7 +105,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_match_kernel(IndexMatchArgs
             while (b - f > step) {
                 const uint32_t j = f + step;
                 uint32_t l = lf < lb ? lf : lb;
-                const int c = index_compare(a.text, a.n, index_entry(a.sa, j, a.n), a.pat, a.pat_bytes, t, len, l);
+                const int c = index_compare(q.text, q.n, index_entry(q.sa, j, q.n), q.pat, q.pat_bytes, t, len, l);
                 if (c > 0) {
                     b = j, lb = l;
                     break;
@@ -135,7 +115,7 @@ __global__ __launch_bounds__(INDEX_BLOCK) void index_match_kernel(IndexMatchArgs
             while (b - f > 1u) {
                 const uint32_t mid = f + ((b - f) >> 1);
                 uint32_t l = lf < lb ? lf : lb;
-                const int c = index_compare(a.text, a.n, index_entry(a.sa, mid, a.n), a.pat, a.pat_bytes, t, len, l);
+                const int c = index_compare(q.text, q.n, index_entry(q.sa, mid, q.n), q.pat, q.pat_bytes, t, len, l);
                 if (c > 0) b = mid, lb = l;
                 else f = mid, lf = l;
             }

@@ -1,8 +1,8 @@
 """GPU suite for the text index (bmx_index_*, host.Index): count and locate against brute force (tests/index_oracle.py),
 against Context.search_device and Context.search_dict, at the smallest shapes at which each part can go wrong: every
 short query over the alphabet on small texts at three buffer alignments, the end-of-text rule of the builder's order,
-long common prefixes, the directory's edges, more queries than one workgroup, a caller's array and stream, capacities and
-every error the device entries report."""
+long common prefixes, the directory's edges, more queries than one workgroup, a caller's array and stream, capacities,
+every error the device entries report, and locate, seeds, map and match in alternation over the workspaces they share."""
 import ctypes as C
 import functools
 import os
@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 import index_oracle as io
+import map_oracle as mp
+import match_oracle as mo
 from conftest import ROOT
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import host
 
@@ -345,6 +347,96 @@ def test_device_entries_on_a_callers_stream_with_pending_work(entry, ctx):
     idx.close()
     del keep
     torch.cuda.empty_cache()
+
+
+# ---- locate, seeds, map and match in alternation on one context: the workspaces they share -----------------------------
+
+@functools.lru_cache(maxsize=None)
+def alternation_case():
+    """A text of 4,099 bytes on four letters and, in the order of the calls, what every call has to answer.  Intervals by
+    the rank of the occurrences (the interval of a match is exactly its set of occurrences, test_index_match_cpu.py)."""
+    rng = np.random.default_rng(0xA17E)
+    letters = b"acgt"
+    text = io.random_text(rng, 4099, letters)
+    sa = mp.lower_case_order(text)
+    rank = np.empty(len(text), np.int64)
+    rank[sa.astype(np.int64)] = np.arange(len(text))
+
+    def cut(m, edits):
+        at = int(rng.integers(0, len(text) - m))
+        read = bytearray(text[at:at + m])
+        for j in rng.integers(0, m, edits):
+            read[int(j)] = letters[int(rng.integers(0, 4))]
+        return bytes(read)
+
+    def located(queries):
+        occ = [io.occurrences(text, q) for q in queries]
+        return np.concatenate([[0], np.cumsum([o.size for o in occ])]), np.concatenate(occ)
+
+    def matched(queries):
+        """(len, lo, cnt) per blob byte of the packed queries."""
+        cols = []
+        for q in queries:
+            for i, l in enumerate(mo.matching_statistics(text, q)):
+                occ = io.occurrences(text, q[i:i + int(l)]) if l else np.zeros(0, np.int64)
+                r = rank[occ]
+                assert r.size == 0 or int(r.max() - r.min()) + 1 == r.size
+                cols.append((int(l), int(r.min()) if r.size else 0, r.size))
+        return [np.array(c, np.int64) for c in zip(*cols)]
+
+    def seeded(queries, min_len):
+        return mo.seeds_from_arrays(host.pack_strings(queries)[1], *matched(queries), min_len)
+
+    six = [text[100:106], text[2000:2006], b"acgtac"]
+    reads = [cut(128, 6) for _ in range(64)]
+    ones = [b"a", b"c", b"g", b"t"]
+    # exact, one substitution, a deletion and an insertion, random
+    r2 = bytearray(text[3000:3049])
+    del r2[10]
+    r2.insert(30, ord("a") if r2[30] != ord("a") else ord("c"))
+    maps = [text[500:548], cut(48, 1), bytes(r2[:48]), bytes(letters[int(j)] for j in rng.integers(0, 4, 48))]
+    five, one_read = [text[4000:4005]], [cut(64, 3)]
+    assert sum(len(r) for r in reads) == 8192 and all(len(r) == 48 for r in maps)
+    want = {"six": located(six), "reads": seeded(reads, 8), "ones": located(ones), "maps": mp.index_map(text, sa, maps, 8, 8, 2),
+            "five": matched(five), "one_read": seeded(one_read, 8)}
+    assert want["six"][0][-1] >= 2 and min(np.diff(want["ones"][0])) > 900 and want["reads"][0][-1] > 64
+    assert want["maps"][3][-1] >= 3 and sorted(want["maps"][2].tolist())[:3] == [0, 1, 2] and want["one_read"][0][-1] >= 1
+    return text, sa, {"six": six, "reads": reads, "ones": ones, "maps": maps, "five": five, "one_read": one_read}, want
+
+
+@pytest.mark.parametrize("stream", ["null", "side"])
+def test_locate_seeds_map_and_match_in_alternation(stream, ctx):
+    """One index, seven calls in a row: the per-position workspace holds sort keys, then the per-byte arrays of 8,192 blob
+    bytes, then larger keys, then map's arrays with the 64-bit scan behind them, then ever less; nothing stale is read."""
+    import contextlib
+
+    import torch
+
+    text, sa, q, want = alternation_case()
+    same = lambda got, w: np.array_equal(got.cpu().numpy().astype(np.uint64), np.asarray(w).astype(np.uint64))
+
+    def locate(name):
+        offsets, pos, total = idx.locate(q[name])
+        assert total == want[name][1].size and same(offsets, want[name][0]) and same(pos, want[name][1]), name
+
+    def seeds(name):
+        for g, w, what in zip(idx.seeds(q[name], 8), want[name], ("seed_off", "qpos", "len", "lo", "cnt")):
+            assert same(g, w), (name, what)
+
+    side = torch.cuda.Stream() if stream == "side" else None
+    assert side is None or side.cuda_stream != 0
+    with torch.cuda.stream(side) if side else contextlib.nullcontext():
+        with ctx.index(on_device(text, 0)) as idx:
+            assert np.array_equal(idx.sa.cpu().numpy(), sa)
+            locate("six")
+            seeds("reads")
+            locate("ones")
+            got = idx.map(q["maps"], 8, 8, 2, candidates=True)
+            w = want["maps"]
+            assert all(same(g, x) for g, x in zip(got, list(w[:3]) + [w[3]] + list(w[4:])))
+            assert all(same(g, x) for g, x in zip(idx.match(q["five"]), want["five"]))
+            seeds("one_read")
+            locate("six")
 
 
 def test_capacity(ctx):

@@ -83,7 +83,8 @@ def test_longest_match_is_the_larger_common_prefix_with_the_neighbours_of_the_in
     assert checked > 30000
 
 
-# ---- the lane of index_match_kernel, step for step (csrc/bmx_index_match_kernel.h) -------------------------------------
+# ---- the lane of index_match_kernel, step for step (csrc/bmx_index_match_kernel.h; its bucket and its first search are
+# ---- index_bucket and index_bound<false> of csrc/bmx_index_kernel.h, written out here) -----------------------------------
 
 def compare(t: bytes, p: int, pat: bytes, m: int, lcp: int):
     """index_compare: (-1 below / 0 the pattern is a prefix / +1 above, common bytes); the hint must be true."""
