@@ -445,6 +445,79 @@ int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t 
 int bmx_search_approx_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
                               int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
 
+/* ---- gapped pattern search: optional and counted classes, PROSITE --------------------------- */
+
+/* A class pattern whose parts sit at a variable distance: C-x(2,4)-C-x(3)-[LIVMFYWC]-x(8)-H-x(3,5)-H (the PROSITE
+ * zinc-finger signature), a primer pair with 10 to 20 bases between its halves, colou?r.  One pass over the text answers
+ * what otherwise takes one bmx_search_classes_device pass per combination of gap lengths.  The reference has no such
+ * program.  The matcher is Navarro and Raffinot's extended Shift-And restricted to BOUNDED repetition, one 32- or 64-bit
+ * word per lane, with the class search's geometry and ordered output (csrc/bmx_gaps_kernel.h).
+ *
+ * A gapped pattern is M positions, 1 <= M <= BMX_MAX_GAPS_PATTERN.  Position i has a class (BMX_CLASS_BYTES bytes, encoded
+ * exactly as for bmx_search_classes; an empty class is legal) and is OPTIONAL iff bit i of `optional` is set.  At least one
+ * position must be mandatory (a pattern that matches the empty string is BMX_ERR_ARG) and no bit at or above M may be set.
+ * A substring text[s..j] of length L >= 1 MATCHES iff there are positions i_0 < i_1 < ... < i_{L-1} that contain every
+ * mandatory position, with text[s + t] in class i_t for every t.
+ * Semantics: every END j in [lead, n) for which some s with 0 <= s <= j matches, each end once, ascending, reported as
+ * base_offset + j.  Ends, not starts, because several starts can share one end (the approximate search's convention).
+ * A match spans at most M bytes, so a shard passes a view that begins M - 1 bytes (clipped at 0) before its first end,
+ * with lead = that amount: the shards' lists then concatenate to the whole text's list.
+ * Two identities: with optional == 0 the list is bmx_search_classes_device's starts + M - 1; for any pattern it is the
+ * union of "starts + length - 1" over the fixed-length class patterns that the choices of optional positions give.
+ * Any byte values in text and classes; n < 2^40, any alignment of d_text.
+ * Capacity: the stored entries are the LOWEST `capacity` ends; *n_matches is the true total, and a larger total returns
+ * BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers where needed, M or `optional` out of range,
+ * lead > n, n too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer
+ * than its bound (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly
+ * ordered.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream.
+ * Out of scope: unbounded repetition (* and +), anchors, alternation, M > 64. */
+#define BMX_MAX_GAPS_PATTERN 64
+#define BMX_GAPS_PROSITE 4u /* (beside BMX_CLASS_ICASE and BMX_CLASS_IUPAC in the flags of bmx_compile_gaps) */
+/* Pure host code, no GPU.  *m is the number of positions after expansion, bit i of *optional says that position i is
+ * optional; classes has room for BMX_MAX_GAPS_PATTERN classes.
+ * Default syntax: the elements of bmx_compile_classes (. [...] [^...] \xHH \c, any other byte; BMX_CLASS_ICASE and
+ * BMX_CLASS_IUPAC as there), each optionally followed by ONE quantifier: ? or {a} or {a,b}, decimal, 0 <= a <= b, b >= 1.
+ * An element with {a,b} expands to a mandatory copies followed by b - a optional ones; ? is {0,1}.  \? \{ \* \+ are
+ * literals, and inside a set these four bytes are literals anyway.
+ * BMX_GAPS_PROSITE: elements separated by -; x is any byte, [ABC] a set, {ABC} a negated set (one or more bytes, taken
+ * literally: no ranges, no escapes), any other byte than - ] } ( ) < > . , is itself; (n) or (a,b) behind an element is
+ * its repetition, with the same bounds; one trailing . is ignored.  The anchors < and > are out of scope and return
+ * BMX_ERR_ARG, inside a set too.  BMX_CLASS_ICASE combines normally; BMX_CLASS_IUPAC with this flag is BMX_ERR_ARG.
+ * BMX_ERR_ARG: NULL arguments; a flag bit other than the three above; an unescaped * or +; {a,}; a quantifier with no element in front of it or right after
+ * another quantifier; b == 0, a > b, a malformed or unterminated {...} or (...); more than BMX_MAX_GAPS_PATTERN positions
+ * after expansion; no mandatory position; zero elements; an empty PROSITE element or set; every error of
+ * bmx_compile_classes (an unterminated set, a reversed range, a dangling \, bad hex).  The outputs are then untouched. */
+int bmx_compile_gaps(const char *expr, uint64_t expr_len, uint32_t flags,
+                     uint8_t *classes /* BMX_MAX_GAPS_PATTERN * BMX_CLASS_BYTES */, uint64_t *optional, int32_t *m);
+int bmx_search_gaps_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                           const uint8_t *classes, int32_t m, uint64_t optional, uint64_t *d_ends, uint64_t capacity,
+                           uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_gaps_device with lead = 0, download). */
+int bmx_search_gaps(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                    uint64_t optional, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the gapped-search kernel) of the last bmx_search_gaps_device on ctx; < 0 if none. */
+float bmx_last_gaps_ms(bmx_ctx *ctx);
+/* The START of a match for every end of a device-resident list, as bmx_search_gaps_device returns it for the same view,
+ * pattern and base_offset: d_starts[i] = base_offset + s with text[s..j_i] a match, d_ends[i] = base_offset + j_i.  By
+ * default s is the LARGEST such start (the shortest match), with BMX_GAPS_LONGEST the smallest s >= 0 of the view (the
+ * longest; a shard's halo of M - 1 bytes holds it).  One list entry per lane; the lane walks at most M bytes backwards
+ * from j.  Every end of the search is a true end of a match, so there is no selection of entries.
+ * Errors: NULL pointers where needed, a pattern or n out of range and unknown flag bits return BMX_ERR_ARG before any HIP
+ * call, with ctx = NULL too; count == 0 returns BMX_OK and launches nothing.  An entry outside
+ * [base_offset, base_offset + n) reads no byte and raises a status word, and so does an entry at which no match ends (a
+ * list of another pattern or text): the call then returns BMX_ERR_ARG and the outputs are unspecified.
+ * No byte outside the aligned 16-byte lines that hold text[0..n) is read, none below text[0]'s line.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising it. */
+#define BMX_GAPS_LONGEST 1u
+int bmx_gaps_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint8_t *classes, int32_t m,
+                           uint64_t optional, const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts,
+                           void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_gaps_device, bmx_gaps_starts_device (flags: BMX_GAPS_LONGEST or
+ * 0), download.  starts[i] belongs to ends[i]; capacity and *n_matches as for bmx_search_gaps.  ctx may be NULL. */
+int bmx_search_gaps_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                          uint64_t optional, uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity,
+                          uint64_t *n_matches);
+
 /* ---- match spans of the approximate search: (start, end, distance) ------------------------- */
 
 /* The approximate search reports ENDS, and every qualifying end, so one occurrence shows as a run of adjacent ends.

@@ -81,6 +81,16 @@ int bmx_internal_classes(void **state, int num_cu, const void *d_text, uint64_t 
                          hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_classes_free(void *state);
 float bmx_internal_classes_ms(const void *state);
+uint32_t bmx_internal_classes_piece_shift(uint64_t n, int32_t m, uint64_t resident_lanes); // log2 of the ends per lane
+// bmx_gaps.hip
+int bmx_internal_gaps(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                      const uint8_t *classes, int32_t m, uint64_t optional, uint64_t *d_ends, uint64_t capacity,
+                      uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_gaps_starts(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const uint8_t *classes,
+                             int32_t m, uint64_t optional, const uint64_t *d_ends, uint64_t count, uint32_t flags,
+                             uint64_t *d_starts, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_gaps_free(void *state);
+float bmx_internal_gaps_ms(const void *state);
 // bmx_ed_batch.hip
 int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
                           const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
@@ -160,6 +170,7 @@ struct bmx_ctx {
     void *sa = nullptr; // suffix array: workspace, pinned round counters, last ms and round counts (bmx_sa.hip)
     void *lcp = nullptr; // LCP array: workspace, status words, statistics partials, events, last ms and long pairs (bmx_lcp.hip)
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
+    void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
     void *spans = nullptr; // match spans: status words, tile counts of the selection, events (bmx_spans.hip)
@@ -195,6 +206,26 @@ inline bool bmx_approx_args_ok(uint64_t n, uint64_t lead, const void *pat, int32
 inline bool bmx_classes_args_ok(uint64_t n, const uint8_t *classes, int32_t m, const void *starts, uint64_t capacity)
 {
     return classes && m >= 1 && m <= BMX_MAX_CLASS_PATTERN && n < (1ull << 40) && (capacity == 0 || starts);
+}
+
+// gapped pattern search: the classes, and optional positions that lie inside the pattern and leave one mandatory
+inline bool bmx_gaps_pattern_ok(const uint8_t *classes, int32_t m, uint64_t optional)
+{
+    if (!classes || m < 1 || m > BMX_MAX_GAPS_PATTERN) return false;
+    const uint64_t all = m == 64 ? ~0ull : (1ull << m) - 1;
+    return (optional & ~all) == 0 && optional != all;
+}
+inline bool bmx_gaps_args_ok(uint64_t n, uint64_t lead, const uint8_t *classes, int32_t m, uint64_t optional, const void *ends,
+                             uint64_t capacity)
+{
+    return bmx_gaps_pattern_ok(classes, m, optional) && lead <= n && n < (1ull << 40) && (capacity == 0 || ends);
+}
+// ... and the starts of its matches
+inline bool bmx_gaps_starts_args_ok(uint64_t n, const uint8_t *classes, int32_t m, uint64_t optional, const uint64_t *ends,
+                                    uint64_t count, uint32_t flags, const uint64_t *starts)
+{
+    if (!bmx_gaps_pattern_ok(classes, m, optional) || n >= (1ull << 40) || (flags & ~BMX_GAPS_LONGEST)) return false;
+    return count == 0 || (ends && starts);
 }
 
 // match spans (pat: the string or the classes)

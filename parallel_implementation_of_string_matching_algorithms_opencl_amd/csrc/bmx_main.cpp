@@ -32,6 +32,13 @@
 //                             --icase folds the case of ASCII letters, --iupac reads R Y S W K M B D H V N as
 //                             nucleotide sets; prints the hit count, the first and last starts and the mean time.
 //                             With --approx K: the ends within K edits of the class pattern, printed as --approx does
+//   bmx_cli --gaps EXPR [--prosite] [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K] [--starts [--longest]]
+//                             gapped pattern search (no counterpart in the reference): EXPR is a class expression whose
+//                             elements may carry ? {a} {a,b} (bmx_compile_gaps), with --prosite the PROSITE form
+//                             C-x(2,4)-[LIVM]-{P}; prints the hit count, the first and last ends and the mean time as
+//                             --classes does for starts.  With --starts the start of every match as well
+//                             (bmx_search_gaps_spans: the largest one, with --longest the smallest), and --positions
+//                             then prints `start end` pairs
 //   bmx_cli --approx K --spans [--best] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--max-print K]
 //                             after what --approx prints: the span of every match (bmx_search_approx_spans), the total
 //                             and one `start end dist` line per span (at most --max-print of them); --best keeps one
@@ -139,7 +146,8 @@ int main(int argc, char **argv)
 {
     std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path, seeds_path, map_path;
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
-    bool have_classes = false;
+    bool have_classes = false, have_gaps = false, gaps_starts = false, gaps_longest = false;
+    std::string gaps_expr;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
     bool positions = false, spans = false, spans_best = false, with_lcp = false;
     uint64_t max_print = 32;
@@ -172,6 +180,10 @@ int main(int argc, char **argv)
         else if (a == "--min-len") min_len = (uint32_t)strtoul(need("--min-len"), nullptr, 10);
         else if (a == "--max-occ") max_occ = (uint32_t)strtoul(need("--max-occ"), nullptr, 10);
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
+        else if (a == "--gaps") gaps_expr = need("--gaps"), have_gaps = true;
+        else if (a == "--prosite") class_flags |= BMX_GAPS_PROSITE;
+        else if (a == "--starts") gaps_starts = true;
+        else if (a == "--longest") gaps_longest = true;
         else if (a == "--icase") class_flags |= BMX_CLASS_ICASE;
         else if (a == "--iupac") class_flags |= BMX_CLASS_IUPAC;
         else if (a == "--limit") limit = (uint32_t)strtoul(need("--limit"), nullptr, 10);
@@ -195,6 +207,15 @@ int main(int argc, char **argv)
     if (!map_path.empty()) seeds_path = map_path; // the same query file, read below
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
+        return 2;
+    }
+
+    if ((gaps_starts || (class_flags & BMX_GAPS_PROSITE)) && !have_gaps) {
+        fprintf(stderr, "--starts and --prosite need --gaps EXPR\n");
+        return 2;
+    }
+    if ((gaps_longest && !gaps_starts) || (have_gaps && (have_classes || approx_k >= 0))) {
+        fprintf(stderr, "--longest needs --starts; --gaps goes with neither --classes nor --approx\n");
         return 2;
     }
 
@@ -477,7 +498,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "cannot read text file %s\n", text_path.c_str());
         return 1;
     }
-    if (dict_path.empty() && !have_classes && !read_file(pat_path, pat)) { // (a dictionary search reads its own list, a class search its expression)
+    if (dict_path.empty() && !have_classes && !have_gaps && !read_file(pat_path, pat)) { // (a dictionary search reads its own list, a class search its expression)
         fprintf(stderr, "cannot read pattern file %s\n", pat_path.c_str());
         return 1;
     }
@@ -488,7 +509,15 @@ int main(int argc, char **argv)
         fprintf(stderr, "bad class expression %s\n", class_expr.c_str());
         return 1;
     }
-    if (have_classes)
+    uint64_t gaps_optional = 0;
+    if (have_gaps && bmx_compile_gaps(gaps_expr.data(), gaps_expr.size(), class_flags, classes.data(), &gaps_optional, &m) != BMX_OK) {
+        fprintf(stderr, "bad gapped pattern expression %s\n", gaps_expr.c_str());
+        return 1;
+    }
+    if (have_gaps)
+        printf("text %s: %llu bytes, gapped pattern %s: %d positions, %d of them optional\n", text_path.c_str(),
+               (unsigned long long)n, gaps_expr.c_str(), m, __builtin_popcountll(gaps_optional));
+    else if (have_classes)
         printf("text %s: %llu bytes, class expression %s: %d positions\n", text_path.c_str(), (unsigned long long)n,
                class_expr.c_str(), m);
     else if (dict_path.empty())
@@ -570,6 +599,66 @@ int main(int argc, char **argv)
             printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
         if (d_text) bmx_device_free(ctx, d_text);
         bmx_dict_destroy(dict);
+        bmx_ctx_destroy(ctx);
+        return 0;
+    }
+
+    if (have_gaps) {
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        void *d_text = nullptr;
+        uint64_t *d_ends = nullptr;
+        const uint64_t cap = n ? n : 1; // at most one hit per end
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap * sizeof(uint64_t), (void **)&d_ends);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "device setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        double total = 0.0, kernel_ms = 0.0;
+        uint64_t hits = 0;
+        for (int it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_search_gaps_device(ctx, d_text, n, 0, 0, classes.data(), m, gaps_optional, d_ends, cap, &hits, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_search_gaps_device failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_gaps_ms(ctx);
+        }
+        if (iters <= 0) { // no timed call has counted: a counting call
+            rc = bmx_search_gaps(ctx, text.data(), n, classes.data(), m, gaps_optional, nullptr, 0, &hits);
+            if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) hits = 0;
+        }
+        // the list itself through the host-buffer entry points: (text, pattern) -> ends, or -> (starts, ends)
+        std::vector<uint64_t> ends(hits ? hits : 1), starts(gaps_starts && hits ? hits : 1);
+        uint64_t got = 0;
+        rc = gaps_starts ? bmx_search_gaps_spans(ctx, text.data(), n, classes.data(), m, gaps_optional,
+                                                 gaps_longest ? BMX_GAPS_LONGEST : 0u, starts.data(), ends.data(), hits, &got)
+                         : bmx_search_gaps(ctx, text.data(), n, classes.data(), m, gaps_optional, ends.data(), hits, &got);
+        if (rc != BMX_OK || got != hits) {
+            fprintf(stderr, "%s failed: %d (%s), %llu hits against %llu\n", gaps_starts ? "bmx_search_gaps_spans" : "bmx_search_gaps",
+                    rc, bmx_last_error(), (unsigned long long)got, (unsigned long long)hits);
+            return 1;
+        }
+        printf("gapped matches: %llu\n", (unsigned long long)got);
+        if (got) {
+            printf("first end: %llu\n", (unsigned long long)ends[0]);
+            printf("last end: %llu\n", (unsigned long long)ends[got - 1]);
+        }
+        if (positions) {
+            for (uint64_t i = 0; i < got && i < max_print; ++i) {
+                if (gaps_starts) printf("Match at : %llu %llu\n", (unsigned long long)starts[i], (unsigned long long)ends[i]);
+                else printf("End at : %llu\n", (unsigned long long)ends[i]);
+            }
+            if (got > max_print) printf("... %llu more\n", (unsigned long long)(got - max_print));
+        }
+        if (iters > 0)
+            printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        bmx_device_free(ctx, d_ends);
+        bmx_device_free(ctx, d_text);
         bmx_ctx_destroy(ctx);
         return 0;
     }

@@ -105,6 +105,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_lcp_free(ctx->lcp);
     bmx_internal_approx_free(ctx->approx);
     bmx_internal_classes_free(ctx->classes);
+    bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
@@ -237,6 +238,31 @@ int bmx_search_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint
 }
 
 float bmx_last_classes_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_classes_ms(ctx->classes) : -1.0f; }
+
+// ---- gapped pattern search (bmx_gaps.hip; bmx_compile_gaps is bmx_gaps_compile.cpp) -------------
+int bmx_search_gaps_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                           const uint8_t *classes, int32_t m, uint64_t optional, uint64_t *d_ends, uint64_t capacity,
+                           uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_gaps_args_ok(n, lead, classes, m, optional, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_gaps(&ctx->gaps, ctx->num_cu, d_text, n, lead, base_offset, classes, m, optional, d_ends, capacity,
+                             n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_gaps_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_gaps_ms(ctx->gaps) : -1.0f; }
+
+int bmx_gaps_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint8_t *classes, int32_t m,
+                           uint64_t optional, const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts,
+                           void *stream_v)
+{
+    if (!bmx_gaps_starts_args_ok(n, classes, m, optional, d_ends, count, flags, d_starts)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_gaps_starts(&ctx->gaps, d_text, n, base_offset, classes, m, optional, d_ends, count, flags, d_starts,
+                                    (hipStream_t)stream_v, g_err, sizeof g_err);
+}
 
 // ---- match spans of the approximate search (bmx_spans.hip) --------------------------------------
 namespace {
@@ -460,7 +486,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->classes, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->classes, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }

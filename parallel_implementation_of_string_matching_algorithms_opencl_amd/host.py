@@ -38,6 +38,9 @@ MAX_CLASS_PATTERN = 64
 CLASS_BYTES = 32
 CLASS_ICASE = 1
 CLASS_IUPAC = 2
+MAX_GAPS_PATTERN = 64
+GAPS_PROSITE = 4  # a flag of compile_gaps, beside CLASS_ICASE and CLASS_IUPAC
+GAPS_LONGEST = 1  # a flag of gaps_starts_device
 SPANS_BEST = 1
 SPANS_BLOCK = 256  # list entries per workgroup of the starts kernel (csrc/bmx_spans_kernel.h)
 SPANS_TILE = 2048  # list entries per workgroup of the selection
@@ -136,6 +139,16 @@ SYMBOLS = [
     ("bmx_search_approx_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p,
                                                    C.c_void_p]),
+    ("bmx_compile_gaps", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, _u64p, _i32p]),
+    ("bmx_search_gaps_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
+                                         C.c_uint64, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_gaps", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p,
+                                  C.c_uint64, _u64p]),
+    ("bmx_search_gaps_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_gaps_ms", C.c_float, [C.c_void_p]),
+    ("bmx_gaps_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64,
+                                         C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("bmx_approx_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           _u64p, C.c_void_p]),
@@ -326,6 +339,27 @@ def _classes(classes_or_expr, flags: int = 0) -> np.ndarray:
     if arr.ndim != 2 or arr.shape[1] != CLASS_BYTES:
         raise ValueError("classes: a uint8 array of shape [m, 32]")
     return arr
+
+
+def compile_gaps(expr, flags: int = 0) -> Tuple[np.ndarray, int]:
+    """A gapped pattern expression (bmx_compile_gaps: the elements of compile_classes, each with an optional ``?``, ``{a}``
+    or ``{a,b}``; with GAPS_PROSITE the form ``C-x(2,4)-[LIVM]-{P}``) -> (classes uint8 [m, 32], optional): bit i of
+    ``optional`` says that position i may be skipped."""
+    e = _pat_bytes(expr)
+    buf = np.zeros((MAX_GAPS_PATTERN, CLASS_BYTES), dtype=np.uint8)
+    m = C.c_int32(0)
+    opt = C.c_uint64(0)
+    _check(lib().bmx_compile_gaps(e, len(e), int(flags), C.c_void_p(buf.ctypes.data), C.byref(opt), C.byref(m)),
+           "bmx_compile_gaps")
+    return buf[: int(m.value)].copy(), int(opt.value)
+
+
+def _gaps(expr_or_pair, flags: int = 0) -> Tuple[np.ndarray, int]:
+    """(classes [m, 32] uint8, optional) from an expression (str / bytes) or from such a pair, passed through."""
+    if isinstance(expr_or_pair, (str, bytes, bytearray)):
+        return compile_gaps(expr_or_pair, flags)
+    classes, optional = expr_or_pair
+    return _classes(classes), int(optional)
 
 
 class Context:
@@ -765,6 +799,95 @@ class Context:
 
     def last_classes_ms(self) -> float:
         return float(self._L.bmx_last_classes_ms(self._h))
+
+    # -- gapped pattern search: optional and counted classes, PROSITE ----------------------
+    def search_gaps_device(self, d_text, expr_or_pair, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
+                           base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
+        """Every end j in [lead, n) of the view ``d_text[0:n)`` at which a match of the gapped pattern ends, ascending,
+        reported as base_offset + j (bmx_search_gaps_device).  ``expr_or_pair``: an expression for compile_gaps(expr,
+        flags) or its result (classes [m, 32] uint8, optional).  ``out``: int64/uint64 CUDA tensor (allocated if None);
+        ``stream``: a torch.cuda.Stream (None: torch's current stream).  Returns (ends view, true total); the view holds
+        the lowest min(total, capacity) ends.  A capacity below the total is not an error here (the total says so)."""
+        import torch
+
+        cls, optional = _gaps(expr_or_pair, flags)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_gaps_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset,
+                                            C.c_void_p(cls.ctypes.data), cls.shape[0], optional, C.c_void_p(out.data_ptr()),
+                                            cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_gaps_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def search_gaps(self, text, expr_or_pair, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_gaps): ascending ends, uint64.  With ``capacity`` given and too small, raises
+        BmxError(ERR_CAPACITY); without it the list is always complete."""
+        cls, optional = _gaps(expr_or_pair, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_gaps(self._h, tptr, n, C.c_void_p(cls.ctypes.data), cls.shape[0], optional,
+                                         C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_gaps")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_gaps_spans(self, text, expr_or_pair, flags: int = 0, longest: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_gaps_spans): (starts uint64, ends uint64) of every match, ends ascending; each start
+        the largest one for its end, or with ``longest`` the smallest."""
+        cls, optional = _gaps(expr_or_pair, flags)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_gaps_spans(self._h, tptr, n, C.c_void_p(cls.ctypes.data), cls.shape[0], optional,
+                                               GAPS_LONGEST if longest else 0, C.c_void_p(starts.ctypes.data),
+                                               C.c_void_p(ends.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_gaps_spans")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy()
+
+    def gaps_starts_device(self, d_text, expr_or_pair, ends, *, longest: bool = False, flags: int = 0,
+                           n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """A start for every end of ``ends`` (int64 / uint64 CUDA tensor, as search_gaps_device returns it for the same
+        view, pattern and base_offset): the largest one, or with ``longest`` the smallest one of the view
+        (bmx_gaps_starts_device).  ``flags`` are the flags of compile_gaps where ``expr_or_pair`` is an expression.
+        Returns the starts, a tensor like ``ends``."""
+        import torch
+
+        cls, optional = _gaps(expr_or_pair, flags)
+        count = ends.numel()
+        if n is None:
+            n = d_text.numel()
+        if ends.element_size() != 8:
+            raise ValueError("ends: 8-byte entries")
+        starts = torch.empty(max(count, 1), dtype=ends.dtype, device=ends.device)
+        s = stream if stream is not None else torch.cuda.current_stream(ends.device)
+        rc = self._L.bmx_gaps_starts_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset,
+                                            C.c_void_p(cls.ctypes.data), cls.shape[0], optional, C.c_void_p(ends.data_ptr()),
+                                            count, GAPS_LONGEST if longest else 0, C.c_void_p(starts.data_ptr()),
+                                            C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_gaps_starts_device")
+        return starts[:count]
+
+    def last_gaps_ms(self) -> float:
+        return float(self._L.bmx_last_gaps_ms(self._h))
 
     # -- match spans of the approximate search: (start, end, distance) -------------------
     def approx_spans_device(self, d_text, pattern_or_classes, k: int, ends, dist=None, *, best: bool = False, flags: int = 0,
@@ -1509,6 +1632,13 @@ def search(text, pattern) -> np.ndarray:
 def search_classes(text, expr, flags: int = 0) -> np.ndarray:
     """(text, class expression) -> ascending starts of every window whose bytes belong to the classes (bmx_search_classes)."""
     return default_context().search_classes(text, expr, flags)
+
+
+def search_gaps(text, expr, flags: int = 0, spans: bool = False):
+    """(text, gapped pattern expression) -> ascending ends of every match (bmx_search_gaps); with ``spans`` the pair
+    (starts, ends), each start the largest one for its end (the shortest match)."""
+    ctx = default_context()
+    return ctx.search_gaps_spans(text, expr, flags) if spans else ctx.search_gaps(text, expr, flags)
 
 
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
