@@ -1,9 +1,9 @@
 // bmx_gaps.hip -- host side of the gapped pattern search (bmx_search_gaps_device, bmx_gaps_starts_device,
 // include/bmx.h): builds the Shift-And table and the four mask words of the extended recurrence from the classes and the
-// optional positions, picks the word width and the lane piece and launches bmx_gaps_kernel.h once inside an ordered-output
-// call (bmx_ordered_out.h); for the starts it builds the same for the reversed positions and launches one lane per list
-// entry.  The argument checks and the context are the shim's (bmx_shim.hip); everything here runs on a valid context with
-// valid arguments.  The shape is bmx_classes.hip's: the search kernel takes the same argument block, in end coordinates.
+// optional positions, picks the word width and the lane piece and launches bmx_gaps_kernel.h's policy through the tile
+// frame (bmx_tile_frame.h: state, geometry, the ordered-output call around the launch); for the starts it builds the same
+// for the reversed positions and launches one lane per list entry.  The argument checks and the context are the shim's
+// (bmx_shim.hip); everything here runs on a valid context with valid arguments.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,7 +15,7 @@
 #include "bmx_internal.h"
 
 static_assert(bmx::MAX_GAPS_PATTERN == BMX_MAX_GAPS_PATTERN, "header and kernel disagree");
-static_assert(sizeof(bmx::ApproxArgs) + sizeof(bmx::GapsMasks) <= 4096 && sizeof(bmx::GapsStartsArgs) <= 4096, "kernel arguments");
+static_assert(sizeof(bmx::TileArgs) + sizeof(bmx::GapsMasks) <= 4096 && sizeof(bmx::GapsStartsArgs) <= 4096, "kernel arguments");
 
 namespace {
 
@@ -23,12 +23,11 @@ constexpr const char *WHERE = "bmx_search_gaps_device";
 constexpr const char *WHERE_STARTS = "bmx_gaps_starts_device";
 
 struct GapsState {
-    bmx::OrderedOut oo; // (first: bmx_ordered_out.h)
-    int blocks_per_cu[2] = {0, 0}; // resident workgroups per CU of the 32- and the 64-bit kernel
+    bmx::TileState tile; // (first: bmx_tile_frame.h)
     uint64_t *d_ws = nullptr; // the starts pass: its status word ...
     uint64_t *h_ws = nullptr; // ... and the pinned copy of it
 };
-static_assert(offsetof(GapsState, oo) == 0, "ordered_set_seq");
+static_assert(offsetof(GapsState, tile) == 0, "tile_state, ordered_set_seq");
 
 // O, I, F, S for positions 0..m-1 with the optional ones in `optional`, shifted up by `up` bits.
 bmx::GapsMasks gaps_masks(uint64_t optional, int32_t m, uint32_t up)
@@ -48,78 +47,40 @@ bmx::GapsMasks gaps_masks(uint64_t optional, int32_t m, uint32_t up)
     return k;
 }
 
-// B[c]: bit i set iff c is in class i (reversed: in class m - 1 - i), shifted up by `up` bits.
-void gaps_table(const uint8_t *classes, int32_t m, uint32_t up, bool reversed, uint64_t peq[256])
-{
-    for (int32_t i = 0; i < m; ++i) {
-        const uint8_t *cls = classes + (size_t)(reversed ? m - 1 - i : i) * BMX_CLASS_BYTES;
-        for (uint32_t c = 0; c < 256; ++c)
-            if ((cls[c >> 3] >> (c & 7)) & 1u) peq[c] |= 1ull << (i + up);
-    }
-}
-
 } // namespace
 
 void bmx_internal_gaps_free(void *state_v)
 {
     GapsState *st = static_cast<GapsState *>(state_v);
     if (!st) return;
-    st->oo.free();
+    st->tile.oo.free();
     if (st->d_ws) (void)hipFree(st->d_ws);
     if (st->h_ws) (void)hipHostFree(st->h_ws);
     delete st;
 }
 
-float bmx_internal_gaps_ms(const void *state_v)
-{
-    const GapsState *st = static_cast<const GapsState *>(state_v);
-    return st ? st->oo.last_ms : -1.0f;
-}
+float bmx_internal_gaps_ms(const void *state_v) { return bmx::tile_last_ms(state_v); }
 
 int bmx_internal_gaps(void **state_v, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                       const uint8_t *classes, int32_t m, uint64_t optional, uint64_t *d_ends, uint64_t capacity,
                       uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen)
 {
-    if (!*state_v) *state_v = new GapsState();
-    GapsState *st = static_cast<GapsState *>(*state_v);
-    if (n_matches) *n_matches = 0;
-    st->oo.last_ms = 0.0f;
+    GapsState *st = bmx::tile_state<GapsState>(state_v, n_matches);
     if (lead >= n) return BMX_OK; // no end is owned (before anything is put on `stream`)
     const bool wide = m > 32;
-    void (*kernel)(const bmx::ApproxArgs, const bmx::GapsMasks) = wide ? bmx::gaps_kernel<true> : bmx::gaps_kernel<false>;
-    int &bpc = st->blocks_per_cu[wide ? 1 : 0];
-    if (bpc == 0) {
-        BMX_HIP(WHERE, hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, bmx::CLASSES_BLOCK, 0));
-        bpc = std::max(1, std::min(bpc, 8));
-    }
-
-    const uint64_t resident = (uint64_t)num_cu * (uint64_t)bpc * bmx::CLASSES_BLOCK;
-    const uint32_t ps = bmx_internal_classes_piece_shift(n - lead, m, resident);
-    const uint32_t tile_shift = ps + 8; // CLASSES_BLOCK lanes of 2^ps ends
-    const uint64_t addr = reinterpret_cast<uint64_t>(d_text);
-    bmx::ApproxArgs a;
+    void (*kernel)(const bmx::TileArgs, const bmx::GapsMasks) =
+        wide ? bmx::tile_kernel<bmx::ShiftAndPolicy<true, bmx::GapsStep<true>>, bmx::GapsMasks>
+             : bmx::tile_kernel<bmx::ShiftAndPolicy<false, bmx::GapsStep<false>>, bmx::GapsMasks>;
+    bmx::TileArgs a;
     std::memset(&a, 0, sizeof a);
-    a.text16 = reinterpret_cast<const uint8_t *>(addr & ~15ull);
-    a.first = addr & 15ull;
-    a.own_lo = lead + a.first;
-    a.own_hi = n + a.first;
-    a.out_bias = base_offset - a.first; // reported end = aligned end + out_bias
-    a.tile_begin = a.own_lo >> tile_shift;
-    a.n_tiles = ((a.own_hi + (1ull << tile_shift) - 1) >> tile_shift) - a.tile_begin;
-    a.out = capacity ? d_ends : nullptr;
-    a.cap = capacity;
     a.m = (uint32_t)m;
     a.warm = (uint32_t)m - 1;
-    a.p_shift = ps;
     const uint32_t up = (wide ? 64u : 32u) - (uint32_t)m; // bit m - 1 is the top bit of the lane's word
-    gaps_table(classes, m, up, false, a.peq);
+    bmx::tile_class_table(classes, m, up, false, a.peq);
     const bmx::GapsMasks k = gaps_masks(optional, m, up);
-
-    int rc = st->oo.begin(WHERE, stream, a, err, errlen);
-    if (rc != BMX_OK) return rc;
-    const uint64_t grid = std::min<uint64_t>(a.n_tiles, resident / bmx::CLASSES_BLOCK);
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(bmx::CLASSES_BLOCK), 0, stream, a, k);
-    return st->oo.finish(WHERE, grid, a.n_tiles, stream, capacity, n_matches, err, errlen);
+    const auto piece = [&](uint64_t resident) { return bmx_internal_classes_piece_shift(n - lead, m, resident); };
+    return bmx::tile_launch(&st->tile, WHERE, kernel, wide, num_cu, a, d_text, n, lead, base_offset, piece, d_ends, capacity, n_matches,
+                            stream, err, errlen, k);
 }
 
 // count >= 1: d_starts[i] for d_ends[i].
@@ -158,7 +119,7 @@ int bmx_internal_gaps_starts(void **state_v, const void *d_text, uint64_t n, uin
     uint64_t reversed = 0;
     for (int32_t i = 0; i < m; ++i)
         if ((optional >> (m - 1 - i)) & 1u) reversed |= 1ull << i;
-    gaps_table(classes, m, up, true, a.peq);
+    bmx::tile_class_table(classes, m, up, true, a.peq);
     a.k = gaps_masks(reversed, m, up);
     void (*kernel)(const bmx::GapsStartsArgs) = wide ? bmx::gaps_starts_kernel<uint64_t> : bmx::gaps_starts_kernel<uint32_t>;
     hipLaunchKernelGGL(kernel, dim3((uint32_t)n_blocks), dim3(bmx::GAPS_STARTS_BLOCK), 0, stream, a);

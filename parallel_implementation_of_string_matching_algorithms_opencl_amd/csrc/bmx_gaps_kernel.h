@@ -15,11 +15,11 @@
 // optional position above an active one, within the block only.  End j is a hit iff bit M - 1 of D is set.
 //
 // A match spans at most M bytes, so bit M - 1 depends on the last M bytes only and a lane that starts with D = 0 at least
-// M - 1 bytes before its first end is exact from there on.  Geometry, tile ticket, look-back, parking pool, second walk of
-// a dense tile and the pinned total are therefore the class kernel's (bmx_classes_kernel.h) with the
-// same argument block; the four mask words come as a second kernel argument.  As there, everything is shifted up so that
-// bit M - 1 is the TOP bit of the word (32 bits for M <= 32, two halves for 33..64), a chunk gathers its 16 B words and then
-// runs 16 steps with no branch, LDS atomic or store between them, and text comes in whole 128-byte lines per lane.
+// M - 1 bytes before its first end is exact from there on.  The tile loop, the ordered output and the argument block are
+// therefore bmx_tile_frame.h's and the lane's walk and the policy are the class search's (bmx_classes_kernel.h, DESIGN.md
+// s13, s20, s21) with the step below; the four mask words come as a second kernel argument.  As there, everything is
+// shifted up so that bit M - 1 is the TOP bit of the word (32 bits for M <= 32, two halves for 33..64), a chunk gathers its
+// 16 B words and then runs 16 steps with no branch, LDS atomic or store between them.
 //
 // Starts (gaps_starts_kernel): one list entry per lane.  The lane runs the same recurrence over the REVERSED positions
 // against text[j], text[j - 1], ... for at most M bytes, anchored: S enters at the first step only.  The top bit after L
@@ -61,7 +61,7 @@ __device__ __forceinline__ void gaps_step(const GapsMasks &k, ShiftAndState<WIDE
 
 // One 16-byte chunk: gather, then 16 steps.  Returns the hit bits, bit i = the step of byte i.
 template <bool WIDE>
-__device__ __forceinline__ uint32_t gaps_chunk(const uint32_t *tab, const GapsMasks &k, ShiftAndState<WIDE> &s, approx_u32x4 v)
+__device__ __forceinline__ uint32_t gaps_chunk(const uint32_t *tab, const GapsMasks &k, ShiftAndState<WIDE> &s, tile_u32x4 v)
 {
     uint32_t blo[16], bhi[16];
 #pragma unroll
@@ -90,7 +90,7 @@ __device__ __forceinline__ uint32_t gaps_chunk(const uint32_t *tab, const GapsMa
 // one may not: a shorter match that begins out there could end on one of the first ends.  One chunk per call, so a plain
 // loop: the bytes in front of the view are stepped with an empty B word, which leaves D = 0.
 template <bool WIDE>
-__device__ __forceinline__ uint32_t gaps_chunk_head(const uint32_t *tab, const GapsMasks &k, ShiftAndState<WIDE> &s, approx_u32x4 v,
+__device__ __forceinline__ uint32_t gaps_chunk_head(const uint32_t *tab, const GapsMasks &k, ShiftAndState<WIDE> &s, tile_u32x4 v,
                                                     uint32_t skip)
 {
     uint32_t hits = 0;
@@ -116,137 +116,17 @@ __device__ __forceinline__ uint32_t gaps_chunk_head(const uint32_t *tab, const G
     return hits;
 }
 
-// gaps_walk and gaps_kernel below are COPIES of classes_walk and classes_kernel (bmx_classes_kernel.h) that differ in the
-// step, the head chunk and the second kernel argument only: a fix to the parking, the second walk or the scan of the lane
-// counts there has to be made here too, and the other way round, until the two share one template.
-//
-// One lane: the ends [lo, hi) (aligned coordinates), after a warm-up of a.warm = M - 1 bytes (clipped at view byte 0),
-// line by line: classes_walk with the step above and the head chunk.  Returns the number of hits.  Every 16-byte load
-// holds at least one byte of the view: chunks lie between the one that holds the first warm-up byte and the one that
-// holds end hi - 1.  A warm-up that begins earlier inside the view is harmless (D = 0 there is a subset of the truth).
-template <bool WIDE, int PASS>
-__device__ __forceinline__ uint32_t gaps_walk(const ApproxArgs &a, const GapsMasks &k, const uint32_t *tab, uint64_t lo, uint64_t hi,
-                                              uint64_t tile0, uint64_t *stage, uint32_t *stage_n, uint64_t base)
-{
-    const uint64_t want = lo >= a.first + a.warm ? lo - a.warm : a.first;
-    const uint64_t origin = want & ~127ull;                  // the line of the first byte walked
-    const int32_t r_begin = (int32_t)((want & ~15ull) - origin); // everything below is relative to origin (< 2^12)
-    const int32_t r_lo = (int32_t)(lo - origin);
-    const int32_t r_hi = (int32_t)(hi - origin);
-    const approx_u32x4 *src = reinterpret_cast<const approx_u32x4 *>(a.text16) + (origin >> 4);
-    ShiftAndState<WIDE> s;
-    s.lo = s.hi = 0;
-    uint32_t cnt = 0;
-    for (int32_t line = 0; line < r_hi; line += 128, src += 8) {
-        approx_u32x4 v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int32_t r = line + 16 * q;
-            if (r >= r_begin && r < r_hi) v[q] = src[q];
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int32_t r = line + 16 * q;
-            if (r < r_begin || r >= r_hi) continue;
-            uint32_t hits;
-            if (q == 0 && (origin | (uint64_t)line) == 0 && a.first != 0) // (aligned byte 0: the one chunk with bytes in front)
-                hits = gaps_chunk_head<WIDE>(tab, k, s, v[0], (uint32_t)a.first);
-            else
-                hits = gaps_chunk<WIDE>(tab, k, s, v[q]);
-            const int32_t own_from = min(max(r_lo - r, 0), 16), own_to = min(r_hi - r, 16);
-            hits &= ((1u << own_to) - 1u) & ~((1u << own_from) - 1u);
-            if (hits == 0) continue; // the usual case, for the whole wave
-            const uint32_t ord0 = cnt;
-            const uint32_t pc = __builtin_popcount(hits);
-            cnt += pc;
-            if (PASS == APPROX_PARK) {
-                if (a.out == nullptr) continue;
-                uint32_t slot = atomicAdd(stage_n, pc);
-                const uint32_t pos0 = (uint32_t)(origin - tile0) + (uint32_t)r; // mod 2^32: origin may lie in front of the tile, a hit never
-                uint32_t ord = ord0;
-                for (uint32_t h = hits; h != 0; h &= h - 1u, ++slot, ++ord)
-                    if (slot < (uint32_t)CLASSES_STAGE)
-                        stage[slot] = (uint64_t)(pos0 + (uint32_t)__builtin_ctz(h)) | ((uint64_t)ord << 32);
-            } else {
-                uint64_t idx = base + ord0;
-                const uint64_t end0 = origin + (uint64_t)r + a.out_bias;
-                for (uint32_t h = hits; h != 0; h &= h - 1u, ++idx)
-                    if (idx < a.cap) a.out[idx] = end0 + (uint32_t)__builtin_ctz(h);
-            }
-        }
-    }
-    return cnt;
-}
-
+// The gapped search's step for the shared walk: the head chunk where bytes lie in front of the view, the unrolled one
+// everywhere else.  (A warm-up that begins earlier inside the view is harmless: D = 0 there is a subset of the truth.)
 template <bool WIDE>
-__global__ __launch_bounds__(CLASSES_BLOCK) void gaps_kernel(const ApproxArgs a, const GapsMasks k)
-{
-    __shared__ uint32_t tab[WIDE ? 512 : 256]; // B, bit M - 1 in the top bit (WIDE: {low, high} pairs)
-    __shared__ uint64_t stage[CLASSES_STAGE];
-    __shared__ uint32_t lane_base[CLASSES_BLOCK]; // hits per lane, then their exclusive scan
-    __shared__ uint32_t stage_n;
-    __shared__ uint64_t sh_tile, sh_prefix;
-    const uint32_t tid = threadIdx.x;
-    if (WIDE) {
-        tab[2 * tid] = (uint32_t)a.peq[tid]; // CLASSES_BLOCK == 256
-        tab[2 * tid + 1] = (uint32_t)(a.peq[tid] >> 32);
-    } else {
-        tab[tid] = (uint32_t)a.peq[tid];
+struct GapsStep {
+    const GapsMasks &k;
+    __device__ __forceinline__ GapsStep(const TileArgs &, const GapsMasks &masks) : k(masks) {}
+    __device__ __forceinline__ uint32_t chunk(const uint32_t *tab, ShiftAndState<WIDE> &s, tile_u32x4 v, uint32_t skip) const
+    {
+        return skip != 0 ? gaps_chunk_head<WIDE>(tab, k, s, v, skip) : gaps_chunk<WIDE>(tab, k, s, v);
     }
-    const uint32_t ps = a.p_shift;
-    for (;;) {
-        if (tid == 0) {
-            sh_tile = atomicAdd(a.ticket, 1ull) - a.ticket_base; // tiles in ascending order: every predecessor is owned
-            stage_n = 0;
-        }
-        __syncthreads(); // (also: tab, and the previous tile's last reads of the LDS are done)
-        const uint64_t t = sh_tile;
-        if (t >= a.n_tiles) break;
-        const uint64_t tile0 = (a.tile_begin + t) << (ps + 8);
-        const uint64_t lo = max(tile0 + ((uint64_t)tid << ps), a.own_lo);
-        const uint64_t hi = min(tile0 + ((uint64_t)(tid + 1) << ps), a.own_hi);
-        uint32_t cnt = 0;
-        if (lo < hi) cnt = gaps_walk<WIDE, APPROX_PARK>(a, k, tab, lo, hi, tile0, stage, &stage_n, 0);
-        lane_base[tid] = cnt;
-        __syncthreads();
-        if (tid < 64) { // wave 0: exclusive scan of the 256 lane counts, then the look-back
-            uint32_t v[4], sum = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = lane_base[4 * tid + q], sum += v[q];
-            uint32_t incl = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(incl, d);
-                if ((int)tid >= d) incl += o;
-            }
-            uint32_t run = incl - sum;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) lane_base[4 * tid + q] = run, run += v[q];
-            const uint64_t agg = (uint64_t)__shfl(incl, 63);
-            if (tid == 0) {
-                const uint64_t prefix = ordered_lookback(a, t, agg);
-                ordered_publish_total(a, t, prefix + agg);
-                sh_prefix = prefix;
-            }
-        }
-        __syncthreads();
-        const uint64_t prefix = sh_prefix;
-        const uint32_t parked = stage_n;
-        if (a.out != nullptr && prefix < a.cap) { // (a tile that starts at or past the capacity stores nothing)
-            if (parked <= (uint32_t)CLASSES_STAGE) {
-                for (uint32_t j = tid; j < parked; j += CLASSES_BLOCK) {
-                    const uint64_t e = stage[j];
-                    const uint32_t pos = (uint32_t)e;
-                    const uint64_t idx = prefix + lane_base[pos >> ps] + (uint32_t)(e >> 32);
-                    if (idx < a.cap) a.out[idx] = tile0 + pos + a.out_bias;
-                }
-            } else if (lo < hi) { // dense tile: walk it again, writing every hit to its slot
-                (void)gaps_walk<WIDE, APPROX_WRITE>(a, k, tab, lo, hi, tile0, stage, &stage_n, prefix + lane_base[tid]);
-            }
-        }
-        __syncthreads(); // the pool, the lane bases and stage_n are the next tile's
-    }
-}
+};
 
 struct GapsStartsArgs {
     const uint8_t *text16; // the 16-byte line that holds text[0]

@@ -1,10 +1,11 @@
-// bmx_ordered_out.h -- ordered output in one pass, shared by the approximate, the class-pattern and the dictionary
-// search: tiles are handed out in ascending order by an atomic ticket, every tile publishes its count in
-// a tagged status word and finds its exclusive prefix by decoupled look-back, the last tile writes the total to pinned
-// memory.  Device side: the status word and the look-back.  Host side: what a context keeps between calls for it and
-// the two halves of a call around the feature's own launch.
+// bmx_ordered_out.h -- ordered output in one pass, shared by the tile frame of the approximate, the
+// class-pattern and the gapped search (bmx_tile_frame.h) and by the dictionary search (bmx_dict_kernel.h): tiles are
+// handed out in ascending order by an atomic ticket, every tile publishes its count in a tagged status word and finds its
+// exclusive prefix by decoupled look-back, the last tile writes the total to pinned memory.  Device side: the status word
+// and the look-back.  Host side: what a context keeps between calls for it and the two halves of a call around the
+// feature's own launch.
 //
-// The argument block of a kernel that uses it (ApproxArgs, DictArgs) has the fields
+// The argument block of a kernel that uses it (TileArgs, DictArgs) has the fields
 //   uint64_t *status;            n_tiles tile words (tagged: no clearing between calls)
 //   unsigned long long *ticket;  monotonic across calls: this call's tickets start at ticket_base
 //   uint64_t ticket_base;

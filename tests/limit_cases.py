@@ -2,7 +2,7 @@
 built in numpy alone.  tests/test_limit_cases_cpu.py proves every per-tile count claimed here with the oracles, so the GPU
 tests may rely on "this tile holds 2049 hits" without a GPU having said so.
 
-Both kernels order their output tile by tile.  A tile parks its hits in an LDS pool of 2048 entries (APPROX_STAGE,
+Both kernels order their output tile by tile.  A tile parks its hits in an LDS pool of 2048 entries (TILE_STAGE,
 DICT_STAGE) and walks itself a second time when it has more.  Tiles are counted from the text pointer rounded down to
 16 bytes: view byte i has the aligned coordinate i + first, first = pointer mod 16.  For a text of 1 MiB or less
 
@@ -23,7 +23,7 @@ import numpy as np
 from approx_oracle import approx_ends
 from dict_oracle import dict_matches
 
-STAGE = 2048            # APPROX_STAGE == DICT_STAGE: hits a tile parks
+STAGE = 2048            # TILE_STAGE == DICT_STAGE: hits a tile parks
 DICT_TILE = 8192        # dictionary tile of a text <= 1 MiB
 MAX_TILE_TEXT = 1 << 20  # the tile sizes above hold up to here
 OFFSETS = (0, 1, 15)    # pointer offsets (mod 16) every tile case is rebuilt for
