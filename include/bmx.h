@@ -388,8 +388,28 @@ int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint6
  * device 0 is created and destroyed inside); ends / dist as above (dist may be NULL). */
 int bmx_search_approx(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *pat, int32_t m,
                       int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
-/* Device time (ms, HIP events around the approximate-search kernel) of the last call on ctx; < 0 if none. */
+/* Device time (ms, HIP events around the approximate-search kernel) of the last call on ctx, whichever of the entries of
+ * this section or of bmx_search_approx_classes* made it; < 0 if none. */
 float bmx_last_approx_ms(bmx_ctx *ctx);
+
+/* Patterns of up to 512 bytes: a sequencing read or a long motif, placed without an index.  The semantics are word for
+ * word those of bmx_search_approx_device -- every end j in [lead, n) with min over s of ED(pat, text[s..j]) <= k,
+ * ascending, that minimum in d_dist; the lead / base_offset contract with a view that begins m + k - 1 bytes early; the
+ * lowest `capacity` ends stored, the true total returned, BMX_ERR_CAPACITY above it; any byte values, any alignment of
+ * d_text, n < 2^40.  Domain: 1 <= m <= BMX_MAX_APPROX_LONG_PATTERN, 0 <= k < m and k <= BMX_MAX_APPROX_LONG_K (a
+ * distance stays one byte).  m <= BMX_MAX_APPROX_PATTERN is handed to bmx_search_approx_device and returns its lists;
+ * above it a lane carries Myers' column in ceil(m / 64) 64-bit words, run by a kernel of 2, 4 or 8 words
+ * (csrc/bmx_approx_long_kernel.h), so a call costs about that many times a one-word call.
+ * Argument errors return BMX_ERR_ARG before any HIP call.  One kernel launch on `stream`; the call returns after
+ * synchronising that stream; bmx_last_approx_ms times it. */
+#define BMX_MAX_APPROX_LONG_PATTERN 512
+#define BMX_MAX_APPROX_LONG_K 255
+int bmx_search_approx_long_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                  const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist /* may be NULL */,
+                                  uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out, as bmx_search_approx (ctx may be NULL; dist may be NULL). */
+int bmx_search_approx_long(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *pat, int32_t m,
+                           int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
 
 /* ---- class-pattern search: wildcards, sets, case folding, IUPAC codes ---------------------- */
 
@@ -572,7 +592,18 @@ int bmx_search_approx_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text,
 int bmx_search_approx_spans_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes,
                                     int32_t m, int32_t k, uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist,
                                     uint64_t capacity, uint64_t *n_spans);
-/* Device time (ms, HIP events around the spans kernels) of the last call on ctx; < 0 if none. */
+/* The same for the lists of bmx_search_approx_long_device: a string of up to BMX_MAX_APPROX_LONG_PATTERN bytes with
+ * k <= BMX_MAX_APPROX_LONG_K.  Definitions, outputs, BMX_SPANS_BEST, the three list checks and the synchronisation are
+ * those of bmx_approx_spans_device; above 64 bytes the starts kernel carries the reversed pattern's column in several
+ * words and walks at most m + k bytes back from every end. */
+int bmx_approx_long_spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, int32_t m,
+                                 int32_t k, const uint64_t *d_ends, const uint8_t *d_dist /* may be NULL if flags == 0 */,
+                                 uint64_t count, uint32_t flags, uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist,
+                                 uint64_t *n_spans, void *stream);
+int bmx_search_approx_long_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *pat, int32_t m,
+                                 int32_t k, uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
+                                 uint64_t *n_spans);
+/* Device time (ms, HIP events around the spans kernels) of the last call on ctx (the long entries included); < 0 if none. */
 float bmx_last_spans_ms(bmx_ctx *ctx);
 
 /* ---- dictionary search: many patterns in one pass ------------------------------------------ */

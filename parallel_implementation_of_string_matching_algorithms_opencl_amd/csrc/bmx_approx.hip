@@ -49,6 +49,6 @@ int bmx_internal_approx(void **state_v, int num_cu, const void *d_text, uint64_t
         bmx::tile_class_table(classes, m, 0, false, a.peq);
     }
     const auto piece = [&](uint64_t resident) { return bmx_internal_approx_piece_shift(n, m, k, resident); };
-    return bmx::tile_launch(st, "bmx_search_approx_device", kernel, wide, num_cu, a, d_text, n, lead, base_offset, piece, d_ends,
+    return bmx::tile_launch(st, "bmx_search_approx_device", kernel, wide ? 1 : 0, num_cu, a, d_text, n, lead, base_offset, piece, d_ends,
                             capacity, n_matches, stream, err, errlen);
 }

@@ -47,6 +47,6 @@ int bmx_internal_classes(void **state_v, int num_cu, const void *d_text, uint64_
     // B[c]: bit i set iff c is in class i, shifted up so that bit m - 1 is the top bit of the lane's word
     bmx::tile_class_table(classes, m, (wide ? 64u : 32u) - (uint32_t)m, false, a.peq);
     const auto piece = [&](uint64_t resident) { return bmx_internal_classes_piece_shift(n_ends, m, resident); };
-    return bmx::tile_launch(st, "bmx_search_classes_device", kernel, wide, num_cu, a, d_text, n_ends, lead,
+    return bmx::tile_launch(st, "bmx_search_classes_device", kernel, wide ? 1 : 0, num_cu, a, d_text, n_ends, lead,
                             base_offset - lead /* reported: the start */, piece, d_starts, capacity, n_matches, stream, err, errlen);
 }

@@ -79,7 +79,7 @@ int bmx_internal_gaps(void **state_v, int num_cu, const void *d_text, uint64_t n
     bmx::tile_class_table(classes, m, up, false, a.peq);
     const bmx::GapsMasks k = gaps_masks(optional, m, up);
     const auto piece = [&](uint64_t resident) { return bmx_internal_classes_piece_shift(n - lead, m, resident); };
-    return bmx::tile_launch(&st->tile, WHERE, kernel, wide, num_cu, a, d_text, n, lead, base_offset, piece, d_ends, capacity, n_matches,
+    return bmx::tile_launch(&st->tile, WHERE, kernel, wide ? 1 : 0, num_cu, a, d_text, n, lead, base_offset, piece, d_ends, capacity, n_matches,
                             stream, err, errlen, k);
 }
 

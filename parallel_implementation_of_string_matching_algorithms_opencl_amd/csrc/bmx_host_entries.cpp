@@ -232,11 +232,13 @@ int bmx_lcp_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out
 
 namespace {
 
-// the approximate search for a string (classes == NULL) or for classes (pat == NULL)
+// the approximate search for a string (classes == NULL) or for classes (pat == NULL); lng: the string's long entry
 int search_approx_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes,
-                       int32_t m, int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+                       int32_t m, int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches, bool lng = false)
 {
-    if (!bmx_approx_args_ok(n, 0, pat ? (const void *)pat : (const void *)classes, m, k, ends, capacity) || (n > 0 && !text))
+    const void *what = pat ? (const void *)pat : (const void *)classes;
+    if (!(lng ? bmx_approx_long_args_ok(n, 0, what, m, k, ends, capacity) : bmx_approx_args_ok(n, 0, what, m, k, ends, capacity)) ||
+        (n > 0 && !text))
         return BMX_ERR_ARG;
     if (n_matches) *n_matches = 0;
     if (n == 0) return BMX_OK;
@@ -247,7 +249,8 @@ int search_approx_host(const char *entry, bmx_ctx *ctx_in, const char *text, uin
     uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
     uint8_t *d_dist = dev_cap && dist ? c.alloc<uint8_t>(dev_cap) : nullptr;
     if (c.rc != BMX_OK) return c.rc;
-    c.rc = pat ? bmx_search_approx_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr)
+    c.rc = lng ? bmx_search_approx_long_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr)
+           : pat ? bmx_search_approx_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, dev_cap, &total, nullptr)
                : bmx_search_approx_classes_device(c.ctx(), d_text, n, 0, 0, classes, m, k, d_ends, d_dist, dev_cap, &total, nullptr);
     if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
     const uint64_t stored = std::min(total, dev_cap);
@@ -261,9 +264,10 @@ int search_approx_host(const char *entry, bmx_ctx *ctx_in, const char *text, uin
 // ... and its match spans
 int search_spans_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes,
                       int32_t m, int32_t k, uint32_t flags, uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity,
-                      uint64_t *n_spans)
+                      uint64_t *n_spans, bool lng = false)
 {
-    if (!bmx_approx_args_ok(n, 0, pat ? (const void *)pat : (const void *)classes, m, k, ends, capacity) ||
+    const void *what = pat ? (const void *)pat : (const void *)classes;
+    if (!(lng ? bmx_approx_long_args_ok(n, 0, what, m, k, ends, capacity) : bmx_approx_args_ok(n, 0, what, m, k, ends, capacity)) ||
         (flags & ~BMX_SPANS_BEST) || (capacity && !starts) || (n > 0 && !text))
         return BMX_ERR_ARG;
     if (n_spans) *n_spans = 0;
@@ -277,7 +281,8 @@ int search_spans_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint
         d_ends = cap ? c.alloc<uint64_t>(cap * sizeof(uint64_t)) : nullptr;
         d_dist = cap ? c.alloc<uint8_t>(cap) : nullptr;
         if (c.rc != BMX_OK) return;
-        c.rc = pat ? bmx_search_approx_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, cap, &total, nullptr)
+        c.rc = lng ? bmx_search_approx_long_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, cap, &total, nullptr)
+               : pat ? bmx_search_approx_device(c.ctx(), d_text, n, 0, 0, pat, m, k, d_ends, d_dist, cap, &total, nullptr)
                    : bmx_search_approx_classes_device(c.ctx(), d_text, n, 0, 0, classes, m, k, d_ends, d_dist, cap, &total, nullptr);
     };
     // counting only if `capacity` cannot hold a single end; else in one go if it holds them all
@@ -295,7 +300,9 @@ int search_spans_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint
         if (flags) d_sel_ends = c.alloc<uint64_t>(total * sizeof(uint64_t));
         if (flags) d_sel_dist = c.alloc<uint8_t>(total);
         if (c.rc == BMX_OK)
-            c.rc = pat ? bmx_approx_spans_device(c.ctx(), d_text, n, 0, pat, m, k, d_ends, d_dist, total, flags, d_starts, d_sel_ends,
+            c.rc = lng ? bmx_approx_long_spans_device(c.ctx(), d_text, n, 0, pat, m, k, d_ends, d_dist, total, flags, d_starts,
+                                                      d_sel_ends, d_sel_dist, &spans, nullptr)
+                   : pat ? bmx_approx_spans_device(c.ctx(), d_text, n, 0, pat, m, k, d_ends, d_dist, total, flags, d_starts, d_sel_ends,
                                                  d_sel_dist, &spans, nullptr)
                        : bmx_approx_spans_classes_device(c.ctx(), d_text, n, 0, classes, m, k, d_ends, d_dist, total, flags, d_starts,
                                                          d_sel_ends, d_sel_dist, &spans, nullptr);
@@ -321,6 +328,13 @@ int bmx_search_approx(bmx_ctx *ctx, const char *text, uint64_t n, const char *pa
     return search_approx_host("bmx_search_approx", ctx, text, n, pat, nullptr, m, k, ends, dist, capacity, n_matches);
 }
 
+int bmx_search_approx_long(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t *ends,
+                           uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_approx_host("bmx_search_approx_long", ctx, text, n, pat, nullptr, m, k, ends, dist, capacity, n_matches, true);
+}
+
 int bmx_search_approx_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
                               uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
 {
@@ -334,6 +348,14 @@ int bmx_search_approx_spans(bmx_ctx *ctx, const char *text, uint64_t n, const ch
     if (!pat) return BMX_ERR_ARG;
     return search_spans_host("bmx_search_approx_spans", ctx, text, n, pat, nullptr, m, k, flags, starts, ends, dist, capacity,
                              n_spans);
+}
+
+int bmx_search_approx_long_spans(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint32_t flags,
+                                 uint64_t *starts, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_spans)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_spans_host("bmx_search_approx_long_spans", ctx, text, n, pat, nullptr, m, k, flags, starts, ends, dist, capacity,
+                             n_spans, true);
 }
 
 int bmx_search_approx_spans_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,

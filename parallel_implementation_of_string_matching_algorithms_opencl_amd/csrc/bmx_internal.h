@@ -75,6 +75,13 @@ int bmx_internal_approx(void **state, int num_cu, const void *d_text, uint64_t n
                         uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_approx_free(void *state);
 float bmx_internal_approx_ms(const void *state);
+// bmx_approx_long.hip (64 < m <= BMX_MAX_APPROX_LONG_PATTERN)
+int bmx_internal_approx_long(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                             const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
+                             uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_approx_long_free(void *state);
+float bmx_internal_approx_long_ms(const void *state);
+uint32_t bmx_internal_approx_long_piece_shift(uint64_t n, int32_t m, int32_t k, uint64_t resident_lanes); // log2 of the ends per lane
 // bmx_classes.hip
 int bmx_internal_classes(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
                          const uint8_t *classes, int32_t m, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
@@ -172,6 +179,8 @@ struct bmx_ctx {
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
+    void *approx_long = nullptr; // ... for patterns of more than 64 bytes: the same kind of state, its own (bmx_approx_long.hip)
+    bool approx_last_long = false; // which of the two the last approximate search on this context used (bmx_last_approx_ms)
     void *ed_batch = nullptr; // batched edit distance: status words, fallback list, events (bmx_ed_batch.hip)
     void *spans = nullptr; // match spans: status words, tile counts of the selection, events (bmx_spans.hip)
     void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
@@ -200,6 +209,14 @@ inline bool bmx_approx_args_ok(uint64_t n, uint64_t lead, const void *pat, int32
 {
     return pat && m >= 1 && m <= BMX_MAX_APPROX_PATTERN && k >= 0 && k < m && lead <= n && n < (1ull << 40) &&
            (capacity == 0 || ends);
+}
+
+// ... for patterns of up to BMX_MAX_APPROX_LONG_PATTERN bytes (a string)
+inline bool bmx_approx_long_args_ok(uint64_t n, uint64_t lead, const void *pat, int32_t m, int32_t k, const void *ends,
+                                    uint64_t capacity)
+{
+    return pat && m >= 1 && m <= BMX_MAX_APPROX_LONG_PATTERN && k >= 0 && k < m && k <= BMX_MAX_APPROX_LONG_K && lead <= n &&
+           n < (1ull << 40) && (capacity == 0 || ends);
 }
 
 // class-pattern search
@@ -233,6 +250,17 @@ inline bool bmx_spans_args_ok(uint64_t n, const void *pat, int32_t m, int32_t k,
                               uint64_t count, uint32_t flags, const uint64_t *starts, const uint64_t *sel_ends)
 {
     if (!pat || m < 1 || m > BMX_MAX_APPROX_PATTERN || k < 0 || k >= m || n >= (1ull << 40) || (flags & ~BMX_SPANS_BEST)) return false;
+    if (count == 0) return true;
+    return ends && starts && (flags == 0 || (dist && sel_ends));
+}
+
+// ... for patterns of up to BMX_MAX_APPROX_LONG_PATTERN bytes (a string)
+inline bool bmx_spans_long_args_ok(uint64_t n, const void *pat, int32_t m, int32_t k, const uint64_t *ends, const uint8_t *dist,
+                                   uint64_t count, uint32_t flags, const uint64_t *starts, const uint64_t *sel_ends)
+{
+    if (!pat || m < 1 || m > BMX_MAX_APPROX_LONG_PATTERN || k < 0 || k >= m || k > BMX_MAX_APPROX_LONG_K || n >= (1ull << 40) ||
+        (flags & ~BMX_SPANS_BEST))
+        return false;
     if (count == 0) return true;
     return ends && starts && (flags == 0 || (dist && sel_ends));
 }

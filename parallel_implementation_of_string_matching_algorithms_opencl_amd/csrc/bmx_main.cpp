@@ -23,7 +23,8 @@
 //                             values follow the array's, and one more line gives the longest repeat (length and two
 //                             positions), the number of distinct substrings and the LCP kernels' time
 //   bmx_cli --approx K [--text F] [--pattern F] [--iters N] [--positions] [--max-print K]
-//                             approximate search (no counterpart in the reference): every end of a match
+//                             approximate search (no counterpart in the reference; a pattern of up to 512 bytes, through
+//                             bmx_search_approx_long*): every end of a match
 //                             with at most K edits, on the resident text; prints the hit count, the first
 //                             and last ends with their distances and the mean time
 //   bmx_cli --classes EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K]
@@ -734,11 +735,12 @@ int main(int argc, char **argv)
             auto t0 = std::chrono::steady_clock::now();
             rc = have_classes ? bmx_search_approx_classes_device(ctx, d_text, n, 0, 0, classes.data(), m, approx_k, d_ends, d_dist,
                                                                  cap, &hits, nullptr)
-                              : bmx_search_approx_device(ctx, d_text, n, 0, 0, pat.data(), m, approx_k, d_ends, d_dist, cap, &hits,
-                                                         nullptr);
+                              : bmx_search_approx_long_device(ctx, d_text, n, 0, 0, pat.data(), m, approx_k, d_ends, d_dist, cap,
+                                                              &hits, nullptr); // (any m up to 512; up to 64: the short entry's list)
             auto t1 = std::chrono::steady_clock::now();
             if (rc != BMX_OK) {
-                fprintf(stderr, "bmx_search_approx_device failed: %d (%s)\n", rc, bmx_last_error());
+                fprintf(stderr, "%s failed: %d (%s)\n", have_classes ? "bmx_search_approx_classes_device" : "bmx_search_approx_long_device",
+                        rc, bmx_last_error());
                 return 1;
             }
             total += std::chrono::duration<double>(t1 - t0).count();
@@ -751,9 +753,10 @@ int main(int argc, char **argv)
         if (have_classes)
             rc = bmx_search_approx_classes(ctx, text.data(), n, classes.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
         else
-            rc = bmx_search_approx(ctx, text.data(), n, pat.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
+            rc = bmx_search_approx_long(ctx, text.data(), n, pat.data(), m, approx_k, ends.data(), dist.data(), hits, &got);
         if (rc != BMX_OK || got != hits) {
-            fprintf(stderr, "bmx_search_approx failed: %d (%s), %llu hits against %llu\n", rc, bmx_last_error(),
+            fprintf(stderr, "%s failed: %d (%s), %llu hits against %llu\n",
+                    have_classes ? "bmx_search_approx_classes" : "bmx_search_approx_long", rc, bmx_last_error(),
                     (unsigned long long)got, (unsigned long long)hits);
             return 1;
         }
@@ -779,10 +782,11 @@ int main(int argc, char **argv)
                 rc = bmx_search_approx_spans_classes(ctx, text.data(), n, classes.data(), m, approx_k, flags, s_starts.data(),
                                                      s_ends.data(), s_dist.data(), room, &n_spans);
             else
-                rc = bmx_search_approx_spans(ctx, text.data(), n, pat.data(), m, approx_k, flags, s_starts.data(), s_ends.data(),
-                                             s_dist.data(), room, &n_spans);
+                rc = bmx_search_approx_long_spans(ctx, text.data(), n, pat.data(), m, approx_k, flags, s_starts.data(), s_ends.data(),
+                                                  s_dist.data(), room, &n_spans);
             if (rc != BMX_OK) {
-                fprintf(stderr, "bmx_search_approx_spans failed: %d (%s)\n", rc, bmx_last_error());
+                fprintf(stderr, "%s failed: %d (%s)\n", have_classes ? "bmx_search_approx_spans_classes" : "bmx_search_approx_long_spans",
+                        rc, bmx_last_error());
                 return 1;
             }
             printf("match spans%s: %llu  (spans kernels %.3f ms)\n", spans_best ? " (best)" : "", (unsigned long long)n_spans,

@@ -104,6 +104,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_sa_free(ctx->sa);
     bmx_internal_lcp_free(ctx->lcp);
     bmx_internal_approx_free(ctx->approx);
+    bmx_internal_approx_long_free(ctx->approx_long);
     bmx_internal_classes_free(ctx->classes);
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_ed_batch_free(ctx->ed_batch);
@@ -209,6 +210,7 @@ int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint6
 {
     if (!bmx_approx_args_ok(n, lead, pat, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->approx_last_long = false;
     return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, pat, nullptr, m, k, d_ends, d_dist,
                                capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
@@ -220,11 +222,31 @@ int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t 
 {
     if (!bmx_approx_args_ok(n, lead, classes, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->approx_last_long = false;
     return bmx_internal_approx(&ctx->approx, ctx->num_cu, d_text, n, lead, base_offset, nullptr, classes, m, k, d_ends, d_dist,
                                capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
-float bmx_last_approx_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_approx_ms(ctx->approx) : -1.0f; }
+// patterns of up to BMX_MAX_APPROX_LONG_PATTERN bytes: more than 64 take a column of several words (bmx_approx_long.hip),
+// the others the kernels above
+int bmx_search_approx_long_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                  const char *pat, int32_t m, int32_t k, uint64_t *d_ends, uint8_t *d_dist, uint64_t capacity,
+                                  uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_approx_long_args_ok(n, lead, pat, m, k, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    if (m <= BMX_MAX_APPROX_PATTERN)
+        return bmx_search_approx_device(ctx, d_text, n, lead, base_offset, pat, m, k, d_ends, d_dist, capacity, n_matches, stream_v);
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->approx_last_long = true;
+    return bmx_internal_approx_long(&ctx->approx_long, ctx->num_cu, d_text, n, lead, base_offset, pat, m, k, d_ends, d_dist,
+                                    capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_approx_ms(bmx_ctx *ctx)
+{
+    if (!ctx) return -1.0f;
+    return ctx->approx_last_long ? bmx_internal_approx_long_ms(ctx->approx_long) : bmx_internal_approx_ms(ctx->approx);
+}
 
 // ---- class-pattern search (bmx_classes.hip; bmx_compile_classes is bmx_classes_compile.cpp) -----
 int bmx_search_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
@@ -298,6 +320,24 @@ int bmx_approx_spans_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n
     if (!classes) return BMX_ERR_ARG;
     return spans_device(ctx, d_text, n, base_offset, nullptr, classes, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends,
                         d_sel_dist, n_spans, stream_v);
+}
+
+// a string of up to BMX_MAX_APPROX_LONG_PATTERN bytes (the list of bmx_search_approx_long_device): the same state, the same
+// selection, the starts by a column of several words where m > 64
+int bmx_approx_long_spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, int32_t m,
+                                 int32_t k, const uint64_t *d_ends, const uint8_t *d_dist, uint64_t count, uint32_t flags,
+                                 uint64_t *d_starts, uint64_t *d_sel_ends, uint8_t *d_sel_dist, uint64_t *n_spans, void *stream_v)
+{
+    if (!bmx_spans_long_args_ok(n, pat, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends)) return BMX_ERR_ARG;
+    if (m <= BMX_MAX_APPROX_PATTERN)
+        return bmx_approx_spans_device(ctx, d_text, n, base_offset, pat, m, k, d_ends, d_dist, count, flags, d_starts, d_sel_ends,
+                                       d_sel_dist, n_spans, stream_v);
+    if (n_spans) *n_spans = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_spans(&ctx->spans, d_text, n, base_offset, pat, nullptr, m, k, d_ends, d_dist, count, flags, d_starts,
+                              d_sel_ends, d_sel_dist, n_spans, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
 float bmx_last_spans_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_spans_ms(ctx->spans) : -1.0f; }
@@ -486,7 +526,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->classes, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }

@@ -23,12 +23,16 @@
 // The lane runs Myers' GLOBAL recurrence (bmx_ed_batch_kernel.h) of the REVERSED pattern against text[j], text[j-1], ...:
 // after L bytes the score is ED(pat, text[j-L+1..j]).  It tracks the minimum and the first L that attains it over
 // L = 1..min(j + 1, m + k).  Every lane takes the same ceil((m + k) / 8) chunks of 8 steps, steps past a lane's own bound
-// only stop counting, so waves stay converged.  Text comes as aligned 8-byte words, downwards in address, one word
+// only stop counting, so waves stay converged.  A pattern of more than 64 positions (bmx_approx_long_spans_device) takes
+// spans_starts_long_kernel: the same lane with a column of W words (bmx_myers_words.h), the reversed pattern a kernel
+// argument.  Text comes as aligned 8-byte words, downwards in address, one word
 // ahead; a word below text[0]'s 16-byte line is never loaded.  An entry whose end is outside the view reads no byte.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "bmx_myers_words.h"
 
 namespace bmx {
 
@@ -213,6 +217,63 @@ __global__ __launch_bounds__(SPANS_BLOCK) void spans_starts_kernel(const SpansAr
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             spans_step<W>(s, eq[t], hb);
+            ++len;
+            if (len <= steps && s.score < best) { // the first (smallest) length that attains the minimum
+                best = s.score;
+                best_len = len;
+            }
+        }
+    }
+    if (!valid) return;
+    if (best > a.k)
+        atomicOr((unsigned long long *)&a.ws[0], (unsigned long long)SPANS_BAD_MIN);
+    else if (a.dist && a.dist[i] != best)
+        atomicOr((unsigned long long *)&a.ws[0], (unsigned long long)SPANS_BAD_DIST);
+    a.starts[i] = e - (best_len - 1);
+}
+
+// The same for a pattern of 65 to 512 positions: a column of W words whose table the workgroup builds from `rev`, the
+// REVERSED pattern (a.peq is not used).  The global form: 1 enters word 0.
+template <int W>
+__global__ __launch_bounds__(SPANS_BLOCK) void spans_starts_long_kernel(const SpansArgs a, const LongPattern rev)
+{
+    __shared__ words_u64x2 tab[256 * W / 2];
+    const uint32_t tid = threadIdx.x;
+    words_fill<W>(tab, rev, a.m, tid); // SPANS_BLOCK == 256
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * SPANS_BLOCK + tid;
+    if (i >= a.count) return;
+
+    const uint64_t e = a.ends[i];
+    const uint64_t j = e - a.base;
+    const bool valid = e >= a.base && j < a.n;
+    uint32_t steps = 0, b = 0;
+    int64_t wi = -1; // index of the 8-byte word that holds text[j], counted from text16
+    if (valid) {
+        steps = (uint32_t)min(j + 1, (uint64_t)(a.m + a.k)); // the window is clipped at text[0]
+        const uint64_t q = a.first + j;
+        wi = (int64_t)(q >> 3);
+        b = (uint32_t)(q & 7);
+    } else {
+        atomicOr((unsigned long long *)&a.ws[0], (unsigned long long)SPANS_BAD_END); // no byte is read for this entry
+    }
+    const uint64_t *words = reinterpret_cast<const uint64_t *>(a.text16);
+    uint64_t hi = valid ? words[wi] : 0;                // text[j] is byte b of hi
+    uint64_t lo = valid && wi > 0 ? words[wi - 1] : 0;  // word 0 lies in text[0]'s line: nothing below it is loaded
+
+    const uint32_t lw = (a.m - 1) >> 6, hb = (a.m - 1) & 63, n_words = lw + 1;
+    WordsColumn<W> s;
+    words_init<W>(s, a.m);
+    uint32_t best = 0xFFFFFFFFu, best_len = 0, len = 0;
+    for (uint32_t c = 0; c < a.chunks; ++c) {
+        // the next 8 bytes downwards from text[j - 8c], the first of them in the top byte
+        const uint64_t cur = (hi << (8 * (7 - b))) | ((lo >> (8 * b)) >> 8);
+        hi = lo;
+        --wi;
+        lo = valid && wi > 0 ? words[wi - 1] : 0; // one word ahead of its use
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t byte = (uint32_t)(cur >> (8 * (7 - t))) & 0xFFu;
+            words_column<W>(s, tab + (size_t)byte * (W / 2), 1, lw, hb, n_words);
             ++len;
             if (len <= steps && s.score < best) { // the first (smallest) length that attains the minimum
                 best = s.score;

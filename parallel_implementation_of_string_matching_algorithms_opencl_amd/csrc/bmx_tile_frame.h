@@ -16,7 +16,8 @@
 //
 // A policy P has
 //   Elem, TAB             the LDS table: TAB elements of type Elem ...
-//   fill(tab, a, tid)     ... filled from a.peq by lane tid of TILE_BLOCK
+//   fill(tab, a, tid)     ... filled from a.peq by lane tid of TILE_BLOCK; a policy with FILL_TAKES_X = true builds its
+//                         table from the further arguments instead: fill(tab, a, tid, x...)
 //   walk<PASS>(a, tab, lo, hi, tile0, stage, stage_n, base, x...)
 //                         one lane over the ends [lo, hi): returns the number of hits.  TILE_PARK: every hit takes a slot
 //                         of the pool with atomicAdd(stage_n, ..) and, if the slot is below TILE_STAGE, parks
@@ -87,6 +88,12 @@ __device__ __forceinline__ uint32_t tile_scan_counts(uint32_t *lane_base, uint32
     return __shfl(incl, 63);
 }
 
+// P::FILL_TAKES_X, false for a policy that does not say
+template <typename P, typename = void>
+struct tile_fill_takes_x : std::false_type {};
+template <typename P>
+struct tile_fill_takes_x<P, typename std::enable_if<P::FILL_TAKES_X>::type> : std::true_type {};
+
 template <typename P, typename... X>
 __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, const X... x)
 {
@@ -96,7 +103,8 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, cons
     __shared__ uint32_t stage_n;
     __shared__ uint64_t sh_tile, sh_prefix;
     const uint32_t tid = threadIdx.x;
-    P::fill(tab, a, tid);
+    if constexpr (tile_fill_takes_x<P>::value) P::fill(tab, a, tid, x...);
+    else P::fill(tab, a, tid);
     const uint32_t ps = a.p_shift;
     for (;;) {
         if (tid == 0) {
@@ -148,7 +156,8 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, cons
 // What a context keeps between calls of one search.  A search that keeps more has it as the FIRST member of its state.
 struct TileState {
     OrderedOut oo; // (first: bmx_ordered_out.h)
-    int blocks_per_cu[2] = {0, 0}; // resident workgroups per CU of the 32- and the 64-bit kernel
+    int blocks_per_cu[3] = {0, 0, 0}; // resident workgroups per CU of the search's kernels, by slot (the 32- and the 64-bit
+                                      // one; the long approximate search: 2, 4 and 8 words)
 };
 static_assert(offsetof(TileState, oo) == 0, "ordered_set_seq");
 
@@ -185,16 +194,17 @@ inline void tile_class_table(const uint8_t *classes, int32_t m, uint32_t up, boo
     }
 }
 
-// One call of `kernel` (its 64-bit form: wide) over the ends [lead, n_ends) of the view at d_text, each reported as
+// One call of `kernel` (slot: which of the search's kernels it is, for the occupancy cache) over the ends [lead, n_ends)
+// of the view at d_text, each reported as
 // end + base_offset (a search that reports starts passes base_offset - lead).  piece(resident lanes) is the search's rule
 // for log2 of the ends per lane.  The caller has set a.m, a.k, a.warm, a.peq and a.dist in a block that is otherwise zero;
 // x... are the kernel's further arguments.
 template <typename K, typename Piece, typename... X>
-int tile_launch(TileState *st, const char *where, K kernel, bool wide, int num_cu, TileArgs &a, const void *d_text,
+int tile_launch(TileState *st, const char *where, K kernel, int slot, int num_cu, TileArgs &a, const void *d_text,
                 uint64_t n_ends, uint64_t lead, uint64_t base_offset, Piece piece, uint64_t *d_out, uint64_t capacity,
                 uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen, const X &...x)
 {
-    int &bpc = st->blocks_per_cu[wide ? 1 : 0];
+    int &bpc = st->blocks_per_cu[slot];
     if (bpc == 0) {
         BMX_HIP(where, hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, TILE_BLOCK, 0));
         bpc = std::max(1, std::min(bpc, 8));

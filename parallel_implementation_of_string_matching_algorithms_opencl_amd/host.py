@@ -34,6 +34,8 @@ EXP_LIB_PATH = os.path.join(_HERE, "lib", "libbmx_exp.so")
 MAX_PATTERN = 512
 MAX_MULTI = 8
 MAX_APPROX_PATTERN = 64
+MAX_APPROX_LONG_PATTERN = 512  # bmx_search_approx_long*: a column of several words per lane above 64 bytes
+MAX_APPROX_LONG_K = 255
 MAX_CLASS_PATTERN = 64
 CLASS_BYTES = 32
 CLASS_ICASE = 1
@@ -128,6 +130,10 @@ SYMBOLS = [
     ("bmx_search_approx", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_last_approx_ms", C.c_float, [C.c_void_p]),
+    ("bmx_search_approx_long_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p,
+                                                C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_approx_long", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_compile_classes", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, _i32p]),
     ("bmx_search_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                             C.c_int32, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
@@ -159,6 +165,11 @@ SYMBOLS = [
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_search_approx_spans_classes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32,
                                                   C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_approx_long_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, _u64p, C.c_void_p]),
+    ("bmx_search_approx_long_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_last_spans_ms", C.c_float, [C.c_void_p]),
     ("bmx_dict_create", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), _i32p, C.c_int32, C.POINTER(C.c_void_p)]),
     ("bmx_dict_destroy", None, [C.c_void_p]),
@@ -680,7 +691,8 @@ class Context:
     def search_approx_device(self, d_text, pattern, k: int, *, n: Optional[int] = None, lead: int = 0, base_offset: int = 0,
                              out=None, dist_out=None, capacity: Optional[int] = None):
         """Every end j in [lead, n) of the view ``d_text[0:n)`` with min over s of ED(pattern, text[s..j]) <= k, ascending,
-        reported as base_offset + j (bmx_search_approx_device).  ``out``: int64/uint64 CUDA tensor, ``dist_out``: uint8
+        reported as base_offset + j (bmx_search_approx_device; a pattern of more than 64 and up to 512 bytes goes through
+        bmx_search_approx_long_device).  ``out``: int64/uint64 CUDA tensor, ``dist_out``: uint8
         CUDA tensor (both allocated if None).  Returns (ends view, distances view, true total); the views hold the lowest
         min(total, capacity) ends.  A capacity below the total is not an error here (the total says so)."""
         import torch
@@ -696,29 +708,33 @@ class Context:
         cap = min(out.numel(), dist_out.numel()) if capacity is None else min(capacity, out.numel(), dist_out.numel())
         stream = C.c_void_p(torch.cuda.current_stream(d_text.device).cuda_stream)
         total = C.c_uint64(0)
-        rc = self._L.bmx_search_approx_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset, pat, len(pat),
-                                              int(k), C.c_void_p(out.data_ptr()), C.c_void_p(dist_out.data_ptr()), cap,
-                                              C.byref(total), stream)
-        self._chk(rc, "bmx_search_approx_device", allow=(ERR_CAPACITY,))
+        long = len(pat) > MAX_APPROX_PATTERN
+        fn = self._L.bmx_search_approx_long_device if long else self._L.bmx_search_approx_device
+        rc = fn(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset, pat, len(pat), int(k), C.c_void_p(out.data_ptr()),
+                C.c_void_p(dist_out.data_ptr()), cap, C.byref(total), stream)
+        self._chk(rc, "bmx_search_approx_long_device" if long else "bmx_search_approx_device", allow=(ERR_CAPACITY,))
         got = min(int(total.value), cap)
         return out[:got], dist_out[:got], int(total.value)
 
     def search_approx(self, text, pattern, k: int, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-        """Host buffers (bmx_search_approx): (ends uint64, distances uint8), ascending.  With ``capacity`` given and too
-        small, raises BmxError(ERR_CAPACITY); without it the list is always complete."""
+        """Host buffers (bmx_search_approx; bmx_search_approx_long for a pattern of more than 64 bytes): (ends uint64,
+        distances uint8), ascending.  With ``capacity`` given and too small, raises BmxError(ERR_CAPACITY); without it the
+        list is always complete."""
         pat = _pat_bytes(pattern)
+        long = len(pat) > MAX_APPROX_PATTERN
+        fn = self._L.bmx_search_approx_long if long else self._L.bmx_search_approx
         tptr, n, keep = _host_text(text)
         cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
         while True:
             ends = np.empty(max(cap, 1), dtype=np.uint64)
             dist = np.empty(max(cap, 1), dtype=np.uint8)
             total = C.c_uint64(0)
-            rc = self._L.bmx_search_approx(self._h, tptr, n, pat, len(pat), int(k), C.c_void_p(ends.ctypes.data),
-                                           C.c_void_p(dist.ctypes.data), cap, C.byref(total))
+            rc = fn(self._h, tptr, n, pat, len(pat), int(k), C.c_void_p(ends.ctypes.data), C.c_void_p(dist.ctypes.data), cap,
+                    C.byref(total))
             if rc == ERR_CAPACITY and capacity is None:
                 cap = int(total.value)
                 continue
-            self._chk(rc, "bmx_search_approx")
+            self._chk(rc, "bmx_search_approx_long" if long else "bmx_search_approx")
             del keep
             t = int(total.value)
             return ends[:t].copy(), dist[:t].copy()
@@ -919,12 +935,14 @@ class Context:
                 C.byref(total), s)
         if isinstance(pattern_or_classes, (str, bytes, bytearray)):
             pat = _pat_bytes(pattern_or_classes)
-            rc = self._L.bmx_approx_spans_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, pat, len(pat), *tail)
+            what = "bmx_approx_long_spans_device" if len(pat) > MAX_APPROX_PATTERN else "bmx_approx_spans_device"
+            rc = getattr(self._L, what)(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, pat, len(pat), *tail)
         else:
             cls = _classes(pattern_or_classes)
+            what = "bmx_approx_spans_device"  # (the name this check has always reported for both)
             rc = self._L.bmx_approx_spans_classes_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset,
                                                          C.c_void_p(cls.ctypes.data), cls.shape[0], *tail)
-        self._chk(rc, "bmx_approx_spans_device")
+        self._chk(rc, what)
         t = int(total.value)
         if best:
             return starts[:t], sel_ends[:t], sel_dist[:t], t
@@ -952,6 +970,9 @@ class Context:
         """Host buffers (bmx_search_approx_spans): (starts uint64, ends uint64, distances uint8) of every match of
         ``pattern`` within k edits, ascending; ``best``: one entry per occurrence, else every qualifying end."""
         pat = _pat_bytes(pattern)
+        if len(pat) > MAX_APPROX_PATTERN:  # up to 512 bytes
+            return self._search_spans_host(self._L.bmx_search_approx_long_spans, "bmx_search_approx_long_spans", text, pat, len(pat),
+                                           k, best)
         return self._search_spans_host(self._L.bmx_search_approx_spans, "bmx_search_approx_spans", text, pat, len(pat), k, best)
 
     def search_approx_spans_classes(self, text, classes_or_expr, k: int, flags: int = 0,
