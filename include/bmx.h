@@ -465,6 +465,47 @@ int bmx_search_approx_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t 
 int bmx_search_approx_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
                               int32_t k, uint64_t *ends, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
 
+/* ---- k-mismatch (Hamming) search: at most k substitutions, no insertions or deletions -------- */
+
+/* Where does a fixed-length pattern occur with at most k positions wrong: a barcode, an adapter or a primer site with a few
+ * mismatches, a peptide motif, a CRISPR guide of 20 bases with up to k mismatches next to a PAM such as NGG that must match
+ * exactly.  The approximate search answers a wider question (edits, every end of a run of ends); this one counts
+ * substitutions only and reports each window once, by its start.  The reference has no such program.  The matcher is
+ * Shift-Add (Baeza-Yates and Gonnet) with bit-sliced counters, two slices for k <= 3 and four for k <= 15, in one 32- or
+ * 64-bit word per slice and lane, over the class search's walk and ordered output (csrc/bmx_hamming_kernel.h).
+ *
+ * A pattern is m classes as in bmx_search_classes_device; the string form is m singleton classes.
+ * Semantics: every start p with p < n_own and p + m <= n at which d(p), the number of positions i in [0, m) with
+ * text[p + i] NOT in class i, is at most k and no position i with bit i of `must` set mismatches; ascending, each reported
+ * as base_offset + p, with d(p) in d_dist (one byte per entry, 0..k; d_dist may be NULL).  A class of every byte value
+ * never counts; an empty class always mismatches (it counts 1, or rules the window out if it is in `must`).  With k = 0
+ * the list is bmx_search_classes_device's, every distance is 0 and `must` has no effect.  Every hit's end p + m - 1 is
+ * among bmx_search_approx_classes_device's ends at the same k, with an edit distance <= d(p).
+ * Overlapping matches count; n_own >= n means all of the view.  These are bmx_search_device's conventions: a shard passes
+ * m - 1 halo bytes and the shards' lists concatenate to the whole text's list.  Any byte values in text and classes;
+ * 1 <= m <= BMX_MAX_HAMMING_PATTERN, 0 <= k < m, k <= BMX_MAX_HAMMING_K, no bit of `must` at or above m, n < 2^40, any
+ * alignment of d_text.
+ * Capacity: the stored entries are the LOWEST `capacity` starts; *n_matches is the true total, and a larger total returns
+ * BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers where needed, m, k or `must` out of range, n
+ * too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer than its bound
+ * (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly ordered.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream. */
+#define BMX_MAX_HAMMING_PATTERN 64
+#define BMX_MAX_HAMMING_K 15
+int bmx_search_hamming_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                              const char *pat, int32_t m, int32_t k, uint64_t must, uint64_t *d_starts,
+                              uint8_t *d_dist /* may be NULL */, uint64_t capacity, uint64_t *n_matches, void *stream);
+int bmx_search_hamming_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                                      const uint8_t *classes, int32_t m, int32_t k, uint64_t must, uint64_t *d_starts,
+                                      uint8_t *d_dist /* may be NULL */, uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, the device entry, download; dist may be NULL). */
+int bmx_search_hamming(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k,
+                       uint64_t must, uint64_t *starts, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
+int bmx_search_hamming_classes(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
+                               int32_t k, uint64_t must, uint64_t *starts, uint8_t *dist, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the k-mismatch kernel) of the last call on ctx; < 0 if none. */
+float bmx_last_hamming_ms(bmx_ctx *ctx);
+
 /* ---- gapped pattern search: optional and counted classes, PROSITE --------------------------- */
 
 /* A class pattern whose parts sit at a variable distance: C-x(2,4)-C-x(3)-[LIVMFYWC]-x(8)-H-x(3,5)-H (the PROSITE

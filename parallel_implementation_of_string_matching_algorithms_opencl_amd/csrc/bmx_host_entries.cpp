@@ -387,6 +387,56 @@ int bmx_search_classes(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint
     return c.rc;
 }
 
+} // extern "C"
+
+namespace {
+
+// the k-mismatch search for a string (classes == NULL) or for classes (pat == NULL)
+int search_hamming_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const char *pat, const uint8_t *classes,
+                        int32_t m, int32_t k, uint64_t must, uint64_t *starts, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    const void *what = pat ? (const void *)pat : (const void *)classes;
+    if (!bmx_hamming_args_ok(n, what, m, k, must, starts, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n < (uint64_t)m) return BMX_OK;
+    HostCall c(entry, ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n - (uint64_t)m + 1);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint8_t *d_dist = dev_cap && dist ? c.alloc<uint8_t>(dev_cap) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = pat ? bmx_search_hamming_device(c.ctx(), d_text, n, n, 0, pat, m, k, must, d_starts, d_dist, dev_cap, &total, nullptr)
+               : bmx_search_hamming_classes_device(c.ctx(), d_text, n, n, 0, classes, m, k, must, d_starts, d_dist, dev_cap, &total,
+                                                   nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "k-mismatch matches");
+    if (dist) c.download(dist, d_dist, stored, "k-mismatch matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int bmx_search_hamming(bmx_ctx *ctx, const char *text, uint64_t n, const char *pat, int32_t m, int32_t k, uint64_t must,
+                       uint64_t *starts, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!pat) return BMX_ERR_ARG;
+    return search_hamming_host("bmx_search_hamming", ctx, text, n, pat, nullptr, m, k, must, starts, dist, capacity, n_matches);
+}
+
+int bmx_search_hamming_classes(bmx_ctx *ctx, const char *text, uint64_t n, const uint8_t *classes, int32_t m, int32_t k,
+                               uint64_t must, uint64_t *starts, uint8_t *dist, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!classes) return BMX_ERR_ARG;
+    return search_hamming_host("bmx_search_hamming_classes", ctx, text, n, nullptr, classes, m, k, must, starts, dist, capacity,
+                               n_matches);
+}
+
 int bmx_search_gaps(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint8_t *classes, int32_t m, uint64_t optional,
                     uint64_t *ends, uint64_t capacity, uint64_t *n_matches)
 {

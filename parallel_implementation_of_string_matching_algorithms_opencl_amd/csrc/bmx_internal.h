@@ -89,6 +89,12 @@ int bmx_internal_classes(void **state, int num_cu, const void *d_text, uint64_t 
 void bmx_internal_classes_free(void *state);
 float bmx_internal_classes_ms(const void *state);
 uint32_t bmx_internal_classes_piece_shift(uint64_t n, int32_t m, uint64_t resident_lanes); // log2 of the ends per lane
+// bmx_hamming.hip (pat: the string, or NULL and the classes)
+int bmx_internal_hamming(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                         const char *pat, const uint8_t *classes, int32_t m, int32_t k, uint64_t must, uint64_t *d_starts,
+                         uint8_t *d_dist, uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_hamming_free(void *state);
+float bmx_internal_hamming_ms(const void *state);
 // bmx_gaps.hip
 int bmx_internal_gaps(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                       const uint8_t *classes, int32_t m, uint64_t optional, uint64_t *d_ends, uint64_t capacity,
@@ -177,6 +183,7 @@ struct bmx_ctx {
     void *sa = nullptr; // suffix array: workspace, pinned round counters, last ms and round counts (bmx_sa.hip)
     void *lcp = nullptr; // LCP array: workspace, status words, statistics partials, events, last ms and long pairs (bmx_lcp.hip)
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
+    void *hamming = nullptr; // k-mismatch search: the same again (bmx_hamming.hip)
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *approx_long = nullptr; // ... for patterns of more than 64 bytes: the same kind of state, its own (bmx_approx_long.hip)
@@ -223,6 +230,14 @@ inline bool bmx_approx_long_args_ok(uint64_t n, uint64_t lead, const void *pat, 
 inline bool bmx_classes_args_ok(uint64_t n, const uint8_t *classes, int32_t m, const void *starts, uint64_t capacity)
 {
     return classes && m >= 1 && m <= BMX_MAX_CLASS_PATTERN && n < (1ull << 40) && (capacity == 0 || starts);
+}
+
+// k-mismatch search (pat: the string or the classes): k below m and at most BMX_MAX_HAMMING_K, `must` inside the pattern
+inline bool bmx_hamming_args_ok(uint64_t n, const void *pat, int32_t m, int32_t k, uint64_t must, const void *starts, uint64_t capacity)
+{
+    if (!pat || m < 1 || m > BMX_MAX_HAMMING_PATTERN || k < 0 || k >= m || k > BMX_MAX_HAMMING_K) return false;
+    if (m < 64 && (must >> m) != 0) return false;
+    return n < (1ull << 40) && (capacity == 0 || starts);
 }
 
 // gapped pattern search: the classes, and optional positions that lie inside the pattern and leave one mandatory

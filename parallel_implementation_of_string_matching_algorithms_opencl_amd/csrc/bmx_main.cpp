@@ -33,6 +33,13 @@
 //                             --icase folds the case of ASCII letters, --iupac reads R Y S W K M B D H V N as
 //                             nucleotide sets; prints the hit count, the first and last starts and the mean time.
 //                             With --approx K: the ends within K edits of the class pattern, printed as --approx does
+//   bmx_cli --hamming K [--must A-B[,C-D...]] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--iters N]
+//           [--positions] [--max-print K]
+//                             k-mismatch search (no counterpart in the reference): every start of a window with at most
+//                             K substitutions against the pattern or the class expression (bmx_search_hamming*), none of
+//                             them at a position of --must (inclusive ranges of pattern positions, from 0; a single
+//                             position is A); prints the hit count, the first and last starts with their distances and
+//                             the mean time, and with --positions one `Start at : P (distance D)` line per hit
 //   bmx_cli --gaps EXPR [--prosite] [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K] [--starts [--longest]]
 //                             gapped pattern search (no counterpart in the reference): EXPR is a class expression whose
 //                             elements may carry ? {a} {a,b} (bmx_compile_gaps), with --prosite the PROSITE form
@@ -149,7 +156,8 @@ int main(int argc, char **argv)
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false, have_gaps = false, gaps_starts = false, gaps_longest = false;
     std::string gaps_expr;
-    int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1;
+    int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
+    std::string must_spec;
     bool positions = false, spans = false, spans_best = false, with_lcp = false;
     uint64_t max_print = 32;
     uint32_t min_len = 0, max_occ = 0;
@@ -171,6 +179,8 @@ int main(int argc, char **argv)
         else if (a == "--max-print") max_print = strtoull(need("--max-print"), nullptr, 10);
         else if (a == "--positions") positions = true;
         else if (a == "--approx") approx_k = atoi(need("--approx"));
+        else if (a == "--hamming") hamming_k = atoi(need("--hamming"));
+        else if (a == "--must") must_spec = need("--must");
         else if (a == "--spans") spans = true;
         else if (a == "--best") spans_best = true;
         else if (a == "--lcp") with_lcp = true;
@@ -209,6 +219,29 @@ int main(int argc, char **argv)
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
         return 2;
+    }
+
+    uint64_t must = 0;
+    if ((!must_spec.empty() && hamming_k < 0) || (hamming_k >= 0 && (approx_k >= 0 || have_gaps))) {
+        fprintf(stderr, "--must needs --hamming K; --hamming goes with neither --approx nor --gaps\n");
+        return 2;
+    }
+    for (const char *p = must_spec.c_str(); *p;) { // A-B[,C-D...]: inclusive ranges of positions
+        char *end = nullptr;
+        const unsigned long from = strtoul(p, &end, 10);
+        unsigned long to = from;
+        bool ok = end != p;
+        if (ok && *end == '-') {
+            p = end + 1;
+            to = strtoul(p, &end, 10);
+            ok = end != p;
+        }
+        if (!ok || to < from || to >= 64 || (*end != ',' && *end != 0) || (*end == ',' && end[1] == 0)) {
+            fprintf(stderr, "bad --must %s\n", must_spec.c_str());
+            return 2;
+        }
+        for (unsigned long i = from; i <= to; ++i) must |= 1ull << i;
+        p = *end ? end + 1 : end;
     }
 
     if ((gaps_starts || (class_flags & BMX_GAPS_PROSITE)) && !have_gaps) {
@@ -659,6 +692,70 @@ int main(int argc, char **argv)
         if (iters > 0)
             printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
         bmx_device_free(ctx, d_ends);
+        bmx_device_free(ctx, d_text);
+        bmx_ctx_destroy(ctx);
+        return 0;
+    }
+
+    if (hamming_k >= 0) {
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        void *d_text = nullptr;
+        uint64_t *d_starts = nullptr;
+        uint8_t *d_dist = nullptr;
+        const uint64_t cap = n ? n : 1; // at most one hit per start
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap * sizeof(uint64_t), (void **)&d_starts);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap, (void **)&d_dist);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "device setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        double total = 0.0, kernel_ms = 0.0;
+        uint64_t hits = 0;
+        for (int it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = have_classes ? bmx_search_hamming_classes_device(ctx, d_text, n, n, 0, classes.data(), m, hamming_k, must, d_starts,
+                                                                  d_dist, cap, &hits, nullptr)
+                              : bmx_search_hamming_device(ctx, d_text, n, n, 0, pat.data(), m, hamming_k, must, d_starts, d_dist, cap,
+                                                          &hits, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "%s failed: %d (%s)\n", have_classes ? "bmx_search_hamming_classes_device" : "bmx_search_hamming_device",
+                        rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_hamming_ms(ctx);
+        }
+        // the list itself through the host-buffer entry point (text, pattern, k, must) -> (starts, distances)
+        std::vector<uint64_t> starts(hits ? hits : 1);
+        std::vector<uint8_t> dist(hits ? hits : 1);
+        uint64_t got = 0;
+        if (have_classes)
+            rc = bmx_search_hamming_classes(ctx, text.data(), n, classes.data(), m, hamming_k, must, starts.data(), dist.data(), hits,
+                                            &got);
+        else
+            rc = bmx_search_hamming(ctx, text.data(), n, pat.data(), m, hamming_k, must, starts.data(), dist.data(), hits, &got);
+        if (rc != BMX_OK || got != hits) {
+            fprintf(stderr, "%s failed: %d (%s), %llu hits against %llu\n", have_classes ? "bmx_search_hamming_classes" : "bmx_search_hamming",
+                    rc, bmx_last_error(), (unsigned long long)got, (unsigned long long)hits);
+            return 1;
+        }
+        printf("k-mismatch matches (k = %d): %llu\n", hamming_k, (unsigned long long)hits);
+        if (hits) {
+            printf("first start: %llu (distance %d)\n", (unsigned long long)starts[0], dist[0]);
+            printf("last start: %llu (distance %d)\n", (unsigned long long)starts[hits - 1], dist[hits - 1]);
+        }
+        if (positions) {
+            for (uint64_t i = 0; i < hits && i < max_print; ++i)
+                printf("Start at : %llu (distance %d)\n", (unsigned long long)starts[i], dist[i]);
+            if (hits > max_print) printf("... %llu more\n", (unsigned long long)(hits - max_print));
+        }
+        if (iters > 0)
+            printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        bmx_device_free(ctx, d_dist);
+        bmx_device_free(ctx, d_starts);
         bmx_device_free(ctx, d_text);
         bmx_ctx_destroy(ctx);
         return 0;

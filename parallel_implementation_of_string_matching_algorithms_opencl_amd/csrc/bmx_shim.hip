@@ -106,6 +106,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_approx_free(ctx->approx);
     bmx_internal_approx_long_free(ctx->approx_long);
     bmx_internal_classes_free(ctx->classes);
+    bmx_internal_hamming_free(ctx->hamming);
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
@@ -260,6 +261,30 @@ int bmx_search_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint
 }
 
 float bmx_last_classes_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_classes_ms(ctx->classes) : -1.0f; }
+
+// ---- k-mismatch search (bmx_hamming.hip) --------------------------------------------------------
+int bmx_search_hamming_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset, const char *pat,
+                              int32_t m, int32_t k, uint64_t must, uint64_t *d_starts, uint8_t *d_dist, uint64_t capacity,
+                              uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_hamming_args_ok(n, pat, m, k, must, d_starts, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_hamming(&ctx->hamming, ctx->num_cu, d_text, n, n_own, base_offset, pat, nullptr, m, k, must, d_starts, d_dist,
+                                capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+// the same with a class per pattern position: only the kernel's table is built differently
+int bmx_search_hamming_classes_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t n_own, uint64_t base_offset,
+                                      const uint8_t *classes, int32_t m, int32_t k, uint64_t must, uint64_t *d_starts,
+                                      uint8_t *d_dist, uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_hamming_args_ok(n, classes, m, k, must, d_starts, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_hamming(&ctx->hamming, ctx->num_cu, d_text, n, n_own, base_offset, nullptr, classes, m, k, must, d_starts,
+                                d_dist, capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_hamming_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_hamming_ms(ctx->hamming) : -1.0f; }
 
 // ---- gapped pattern search (bmx_gaps.hip; bmx_compile_gaps is bmx_gaps_compile.cpp) -------------
 int bmx_search_gaps_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
@@ -526,7 +551,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }

@@ -1,6 +1,6 @@
-// bmx_tile_frame.h -- what the approximate, the class-pattern and the gapped search share: the argument
-// block, the tile loop of the kernel and the host side of a launch.  A search supplies its per-byte recurrence as a
-// policy; everything with an invariant across tiles or calls is here, once.
+// bmx_tile_frame.h -- what the approximate, the class-pattern, the gapped and the k-mismatch search share (DESIGN.md s9,
+// s21, s23): the argument block, the tile loop of the kernel and the host side of a launch.  A search supplies its
+// per-byte recurrence as a policy; everything with an invariant across tiles or calls is here, once.
 //
 // Geometry.  A workgroup of TILE_BLOCK lanes takes tiles of TILE_BLOCK * P end positions from an atomic ticket, in
 // ascending order.  Lane l owns the P ends [tile + l*P, tile + (l+1)*P) and first walks a.warm bytes in front of them
@@ -25,7 +25,8 @@
 //                         TILE_WRITE: hit number i of the lane goes to slot base + i if that is below a.cap.
 //   ordinal(e)            the ordinal in lane of the parked entry e
 //   also(a, idx, e)       what the entry stores at slot idx besides its position (the approximate search: the distance)
-// and x... are further by-value kernel arguments handed through to walk (the gapped search: its four mask words).
+// and x... are further by-value kernel arguments handed through to walk (the gapped search: its four mask words; the
+// k-mismatch search: its `must` mask and counter bias).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,7 +52,7 @@ struct TileArgs {
     uint64_t tile_begin;   // first tile index (aligned end / tile bytes)
     uint64_t n_tiles;
     uint64_t *out;         // positions, ascending (NULL: count only)
-    uint8_t *dist;         // approximate search: their distances (NULL: not wanted)
+    uint8_t *dist;         // approximate and k-mismatch search: their distances (NULL: not wanted)
     uint64_t cap;          // entries out / dist have room for
     uint64_t *status;      // n_tiles tile words (tagged: no clearing between calls)
     unsigned long long *ticket; // monotonic across calls: this call's tickets start at ticket_base
@@ -59,7 +60,7 @@ struct TileArgs {
     uint64_t *host_status; // pinned: [0] total, [1] give-up flag, [2] seq (written by the last tile)
     uint64_t seq;
     uint64_t tag;          // seq mod 2^22 (never 0)
-    uint32_t m, k, warm;   // pattern length, approximate search: edits; bytes walked in front of a lane's first end
+    uint32_t m, k, warm;   // pattern length, edits (k-mismatch search: mismatches); bytes walked in front of a lane's first end
     uint32_t p_shift;      // P = 1 << p_shift ends per lane
     uint64_t peq[256];     // the search's table, bit i for pattern position i (low word used when m <= 32)
 };
@@ -156,8 +157,9 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, cons
 // What a context keeps between calls of one search.  A search that keeps more has it as the FIRST member of its state.
 struct TileState {
     OrderedOut oo; // (first: bmx_ordered_out.h)
-    int blocks_per_cu[3] = {0, 0, 0}; // resident workgroups per CU of the search's kernels, by slot (the 32- and the 64-bit
-                                      // one; the long approximate search: 2, 4 and 8 words)
+    int blocks_per_cu[4] = {0, 0, 0, 0}; // resident workgroups per CU of the search's kernels, by slot (the 32- and the
+                                         // 64-bit one; the long approximate search: 2, 4 and 8 words; the k-mismatch search:
+                                         // two slices at 32 and 64 bits, then four)
 };
 static_assert(offsetof(TileState, oo) == 0, "ordered_set_seq");
 

@@ -40,6 +40,8 @@ MAX_CLASS_PATTERN = 64
 CLASS_BYTES = 32
 CLASS_ICASE = 1
 CLASS_IUPAC = 2
+MAX_HAMMING_PATTERN = 64
+MAX_HAMMING_K = 15
 MAX_GAPS_PATTERN = 64
 GAPS_PROSITE = 4  # a flag of compile_gaps, beside CLASS_ICASE and CLASS_IUPAC
 GAPS_LONGEST = 1  # a flag of gaps_starts_device
@@ -145,6 +147,16 @@ SYMBOLS = [
     ("bmx_search_approx_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p,
                                                    C.c_void_p]),
+    ("bmx_search_hamming_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32,
+                                            C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_hamming_classes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                    C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p,
+                                                    C.c_void_p]),
+    ("bmx_search_hamming", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_uint64,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_hamming_classes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_hamming_ms", C.c_float, [C.c_void_p]),
     ("bmx_compile_gaps", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, _u64p, _i32p]),
     ("bmx_search_gaps_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
                                          C.c_uint64, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
@@ -350,6 +362,23 @@ def _classes(classes_or_expr, flags: int = 0) -> np.ndarray:
     if arr.ndim != 2 or arr.shape[1] != CLASS_BYTES:
         raise ValueError("classes: a uint8 array of shape [m, 32]")
     return arr
+
+
+def _must_mask(must) -> int:
+    """The ``must`` argument of the k-mismatch search as a mask: None (no position), an int mask, or an iterable of
+    positions."""
+    if must is None:
+        return 0
+    if isinstance(must, (int, np.integer)):
+        if int(must) < 0 or int(must) >> 64:
+            raise ValueError("must: a mask of 64 bits")
+        return int(must)
+    mask = 0
+    for i in must:
+        if not 0 <= int(i) < 64:
+            raise ValueError("must: positions in [0, 64)")
+        mask |= 1 << int(i)
+    return mask
 
 
 def compile_gaps(expr, flags: int = 0) -> Tuple[np.ndarray, int]:
@@ -815,6 +844,81 @@ class Context:
 
     def last_classes_ms(self) -> float:
         return float(self._L.bmx_last_classes_ms(self._h))
+
+    # -- k-mismatch (Hamming) search: at most k substitutions -------------------------------
+    @staticmethod
+    def _hamming_pattern(pattern_or_classes, flags: int):
+        """(string bytes or None, classes array or None): str / bytes are a STRING, unless ``flags`` (CLASS_*) are given,
+        which make them an expression for compile_classes; a [m, 32] uint8 array is a class pattern."""
+        if isinstance(pattern_or_classes, (str, bytes, bytearray)) and not flags:
+            return _pat_bytes(pattern_or_classes), None
+        return None, _classes(pattern_or_classes, flags)
+
+    def search_hamming_device(self, d_text, pattern_or_classes, k: int, *, must=None, flags: int = 0, n: Optional[int] = None,
+                              n_own: Optional[int] = None, base_offset: int = 0, out=None, dist_out=None, stream=None):
+        """Every start p < n_own of the view ``d_text[0:n)`` at which at most k positions i have text[p + i] outside
+        position i of the pattern and none of them is in ``must`` (an int mask or an iterable of positions), ascending,
+        reported as base_offset + p (bmx_search_hamming[_classes]_device).  ``pattern_or_classes``: str / bytes are a
+        STRING, a [m, 32] uint8 array is a class pattern; with ``flags`` (CLASS_ICASE, CLASS_IUPAC) str / bytes are an
+        expression for compile_classes.  ``out``: int64/uint64 CUDA tensor, ``dist_out``: uint8 CUDA tensor (both allocated
+        if None); ``stream``: a torch.cuda.Stream (None: torch's current stream).  Returns (starts view, distances view,
+        true total); the views hold the lowest min(total, capacity) starts.  A capacity below the total is not an error
+        here (the total says so)."""
+        import torch
+
+        pat, cls = self._hamming_pattern(pattern_or_classes, flags)
+        if n is None:
+            n = d_text.numel()
+        if n_own is None:
+            n_own = n
+        if out is None:
+            out = torch.empty(1 << 16, dtype=torch.int64, device=d_text.device)
+        if dist_out is None:
+            dist_out = torch.empty(max(out.numel(), 1), dtype=torch.uint8, device=d_text.device)
+        cap = min(out.numel(), dist_out.numel())
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(d_text.device)).cuda_stream)
+        total = C.c_uint64(0)
+        head = (self._h, C.c_void_p(d_text.data_ptr()), n, n_own, base_offset)
+        tail = (int(k), _must_mask(must), C.c_void_p(out.data_ptr()), C.c_void_p(dist_out.data_ptr()), cap, C.byref(total), s)
+        if pat is not None:
+            what = "bmx_search_hamming_device"
+            rc = self._L.bmx_search_hamming_device(*head, pat, len(pat), *tail)
+        else:
+            what = "bmx_search_hamming_classes_device"
+            rc = self._L.bmx_search_hamming_classes_device(*head, C.c_void_p(cls.ctypes.data), cls.shape[0], *tail)
+        self._chk(rc, what, allow=(ERR_CAPACITY,))
+        got = min(int(total.value), cap)
+        return out[:got], dist_out[:got], int(total.value)
+
+    def search_hamming(self, text, pattern_or_classes, k: int, must=None, flags: int = 0,
+                       capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_hamming[_classes]): (starts uint64, distances uint8), ascending.  With ``capacity``
+        given and too small, raises BmxError(ERR_CAPACITY); without it the list is always complete."""
+        pat, cls = self._hamming_pattern(pattern_or_classes, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        mask = _must_mask(must)
+        while True:
+            starts = np.empty(max(cap, 1), dtype=np.uint64)
+            dist = np.empty(max(cap, 1), dtype=np.uint8)
+            total = C.c_uint64(0)
+            tail = (int(k), mask, C.c_void_p(starts.ctypes.data), C.c_void_p(dist.ctypes.data), cap, C.byref(total))
+            if pat is not None:
+                what = "bmx_search_hamming"
+                rc = self._L.bmx_search_hamming(self._h, tptr, n, pat, len(pat), *tail)
+            else:
+                what = "bmx_search_hamming_classes"
+                rc = self._L.bmx_search_hamming_classes(self._h, tptr, n, C.c_void_p(cls.ctypes.data), cls.shape[0], *tail)
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, what)
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), dist[:t].copy()
+
+    def last_hamming_ms(self) -> float:
+        return float(self._L.bmx_last_hamming_ms(self._h))
 
     # -- gapped pattern search: optional and counted classes, PROSITE ----------------------
     def search_gaps_device(self, d_text, expr_or_pair, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
@@ -1653,6 +1757,12 @@ def search(text, pattern) -> np.ndarray:
 def search_classes(text, expr, flags: int = 0) -> np.ndarray:
     """(text, class expression) -> ascending starts of every window whose bytes belong to the classes (bmx_search_classes)."""
     return default_context().search_classes(text, expr, flags)
+
+
+def search_hamming(text, pattern, k: int, must=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(text, pattern, k) -> (starts, distances): every window with at most k mismatches against the pattern, none of them
+    at a position of ``must`` (bmx_search_hamming)."""
+    return default_context().search_hamming(text, pattern, k, must)
 
 
 def search_gaps(text, expr, flags: int = 0, spans: bool = False):
