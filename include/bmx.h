@@ -899,6 +899,82 @@ float bmx_last_index_ms(bmx_ctx *ctx);
 /* Device time (ms) of the index's creation: the suffix array if it was built here, plus the directory. */
 float bmx_index_build_ms(const bmx_index *ix);
 
+/* ---- alignments: a CIGAR for every approximate match and mapped read ------- */
+
+/* What says HOW a pattern lies in a span that bmx_approx_spans_device or bmx_index_map_device reported: which bytes are
+ * equal, substituted, inserted or deleted.  The reference has no such program.
+ *
+ * Inputs.  The text is resident: d_text holds n bytes, text byte 0 is global position base_offset.  The patterns are one
+ * string column in the Arrow layout of bmx_edit_distance_batch_device (a byte blob plus pat_count + 1 non-decreasing
+ * uint64 offsets); bytes may have any value, each pattern has 1 .. BMX_ALIGN_MAX_PATTERN bytes.  Entry e aligns pattern
+ * pid[e] against the span text[s..j] with d_start[e] = base_offset + s and d_end[e] = base_offset + j, the end INCLUSIVE,
+ * as the spans and map entries report it.  With d_pid == NULL, pat_count is `count` (entry e takes pattern e) or 1 (every
+ * entry takes pattern 0), the a_count convention of the batched edit distance.  So best_start / best_end of
+ * bmx_index_map_device go in unchanged with pat_count == count, and the lists of bmx_approx_spans_device with
+ * pat_count == 1.
+ * Result.  D[i][t] = ED(pat[0..i), span[0..t)) is the plain unit-cost table, m the pattern's length, L the span's.
+ * d_dist[e] (d_dist may be NULL) = D[m][L], the GLOBAL distance of the whole pattern against the whole span.  The script
+ * is the walk from (m, L) back to (0, 0) that takes at each cell the first of these steps that keeps the value:
+ * diagonal ('=' if the two bytes are equal, else 'X'), up ('I': a pattern byte with no text byte), left ('D': a text byte
+ * with no pattern byte).  It is written from the start of the span to its end with equal neighbouring ops merged into
+ * runs, one op word per run: run length << 4 | code, the BAM encoding.  That puts gaps as far left as they can go, and it
+ * makes ONE script per span, so results compare bit for bit.  A script with d edits has at most 2d + 1 runs.
+ * abcd / abxd: 2=1X1=.  abcd / acd: 1=1I2=.  abcd / abccd: 2=1D2=.  AAA / AA: 1I2=.  GATTACA / GCATGCA: 1=2X1=1X2=.
+ * No alignment.  An entry with start == end == BMX_MAP_NO_POS (a read without a hit), with |L - m| > k (answered without
+ * reading a byte) or with D[m][L] > k gets dist = BMX_ALIGN_NONE and an empty script.  These are not errors.
+ * Output.  d_op_off (count + 1 entries) = the exclusive prefix sum of the runs per entry, always written in full, so
+ * d_op_off[count] == *n_ops == the true total; d_ops[d_op_off[e] .. d_op_off[e+1]) is entry e's script.  A total above a
+ * non-zero `capacity` returns BMX_ERR_CAPACITY; every entry whose segment ends at or below capacity is then stored
+ * complete and the rest of d_ops is unspecified (the rule of bmx_index_locate_device).  capacity 0 counts only (d_ops may
+ * be NULL).  The output is the same in every run: no atomics decide anything.
+ * Domain and errors.  0 <= k <= BMX_ALIGN_MAX_K, n < 2^40, any alignment of d_text.  NULL pointers where count > 0, k out
+ * of range and, with d_pid == NULL, a pat_count that is neither 1 nor count return BMX_ERR_ARG before any HIP call, with
+ * ctx == NULL too; count == 0 returns BMX_OK and launches nothing (*n_ops = 0).  The host entry checks offsets, lengths,
+ * pids and positions on the host.  The device entry checks them in the kernel: an entry with pid >= pat_count, offsets
+ * that decrease or end past pat_bytes, a pattern of 0 or more than BMX_ALIGN_MAX_PATTERN bytes, a position outside
+ * [base_offset, base_offset + n), end < start, or exactly one of the two positions equal to BMX_MAP_NO_POS reads neither
+ * pattern nor text and raises a status word; the call then returns BMX_ERR_ARG and the outputs are unspecified.
+ * No text byte is read except inside the aligned 8-byte words that hold the span.
+ * Method (csrc/bmx_align_kernel.h): one entry per lane; Myers' bit-parallel column in its global form over the span;
+ * every column leaves two bits per row in workspace (the diagonal step keeps the value; the bytes are equal, or else the
+ * up step keeps it); the same lane walks back from (m, L) on those bits alone, several columns per load; runs collected
+ * per entry, rocPRIM's exclusive scan, a fill pass.  The longest pattern M of the column picks the instance: a 32-bit
+ * word, or 1, 2, 4 or 8 64-bit words, w = 4, 8, 16, 32 or 64 bytes per column and plane.  A walk of at most k edits stays
+ * on rows |i - t| <= k; where that band is narrower than the words (M > 32, k <= 63 and b = 4 ceil((2k + 1) / 32) < w)
+ * only the band is stored, b bytes per column and plane.
+ * Workspace: per entry 8 ceil((M + k) / 8) columns x 2 min(w, b) bytes, plus 2k + 2 32-bit words.  It lives behind bmx_ctx
+ * like the other features', is grown on demand and kept.  A call that would need more than BMX_ALIGN_WORKSPACE_BYTES runs
+ * its entries in launches of as many whole waves as fit; the lists still come out as one.
+ * All device work goes on `stream`; the call waits for it once in between, to read the longest pattern, and once at the
+ * end.
+ *
+ * bmx_align: host buffers, base_offset as given.  Uploads text, column and lists, calls bmx_align_device with room for
+ * every possible run and downloads; `capacity` is the room in ops.
+ *
+ * Measured on one MI355X: DESIGN.md s24. */
+#define BMX_ALIGN_MAX_PATTERN 512
+#define BMX_ALIGN_MAX_K 254
+#define BMX_ALIGN_NONE 255u /* no alignment within k (== BMX_MAP_NO_HIT) */
+#define BMX_CIGAR_INS 1u    /* pattern byte with no text byte   (SAM I) */
+#define BMX_CIGAR_DEL 2u    /* text byte with no pattern byte   (SAM D) */
+#define BMX_CIGAR_EQ 7u     /* bytes equal                      (SAM =) */
+#define BMX_CIGAR_X 8u      /* bytes differ                     (SAM X) */
+#define BMX_ALIGN_WORKSPACE_BYTES (1ull << 30)
+int bmx_align_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const void *d_pat, uint64_t pat_bytes,
+                     const uint64_t *d_pat_off, uint64_t pat_count, const uint32_t *d_pid /* may be NULL */,
+                     const uint64_t *d_start, const uint64_t *d_end, uint64_t count, int32_t k, uint8_t *d_dist /* may be NULL */,
+                     uint64_t *d_op_off /* count + 1 */, uint32_t *d_ops, uint64_t capacity, uint64_t *n_ops, void *stream);
+int bmx_align(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, uint64_t base_offset, const void *pat,
+              uint64_t pat_bytes, const uint64_t *pat_off, uint64_t pat_count, const uint32_t *pid /* may be NULL */,
+              const uint64_t *start, const uint64_t *end, uint64_t count, int32_t k, uint8_t *dist /* may be NULL */,
+              uint64_t *op_off /* count + 1 */, uint32_t *ops, uint64_t capacity, uint64_t *n_ops);
+/* Device time (ms, HIP events around the reduction and around the launches) of the last bmx_align_device on ctx; < 0 if
+ * none. */
+float bmx_last_align_ms(bmx_ctx *ctx);
+/* Launches of the alignment kernel in the last bmx_align_device on ctx (more than 1: the entries did not fit the
+ * workspace at once); < 0 if none. */
+int64_t bmx_last_align_launches(bmx_ctx *ctx);
+
 /* ---- synthetic corpus, generated in HBM ---------------------- */
 
 /* d_dst[j] = byte (start + j) of the counter-based splitmix64 stream;

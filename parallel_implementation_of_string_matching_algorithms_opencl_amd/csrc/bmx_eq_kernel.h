@@ -9,7 +9,7 @@
 namespace bmx {
 
 // 32 flags: bit 8k + j = (byte k of p[j] == c), c4 = c in all four bytes.
-__device__ __forceinline__ uint32_t ed_batch_eq32(const uint32_t *p, uint32_t c4)
+__host__ __device__ __forceinline__ uint32_t ed_batch_eq32(const uint32_t *p, uint32_t c4)
 {
     uint32_t eq = 0;
 #pragma unroll
@@ -22,7 +22,7 @@ __device__ __forceinline__ uint32_t ed_batch_eq32(const uint32_t *p, uint32_t c4
 }
 
 template <typename W>
-__device__ __forceinline__ W ed_batch_eq(const uint32_t *p, uint32_t c4, W mask)
+__host__ __device__ __forceinline__ W ed_batch_eq(const uint32_t *p, uint32_t c4, W mask)
 {
     if (sizeof(W) == 4) return (W)ed_batch_eq32(p, c4) & mask;
     return (W)(((uint64_t)ed_batch_eq32(p + 8, c4) << 32) | ed_batch_eq32(p, c4)) & mask;

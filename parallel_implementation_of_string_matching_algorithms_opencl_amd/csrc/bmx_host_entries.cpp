@@ -228,6 +228,39 @@ int bmx_lcp_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out
     return c.rc;
 }
 
+int bmx_align(bmx_ctx *ctx_in, const char *text, uint64_t n, uint64_t base_offset, const void *pat, uint64_t pat_bytes,
+              const uint64_t *pat_off, uint64_t pat_count, const uint32_t *pid, const uint64_t *start, const uint64_t *end,
+              uint64_t count, int32_t k, uint8_t *dist, uint64_t *op_off, uint32_t *ops, uint64_t capacity, uint64_t *n_ops)
+{
+    if (!bmx_align_args_ok(text, n, pat, pat_off, pat_count, pid, start, end, count, k, op_off, ops, capacity)) return BMX_ERR_ARG;
+    if (n_ops) *n_ops = 0;
+    if (count == 0) return BMX_OK;
+    if (!bmx_align_entries_ok(n, base_offset, pat_bytes, pat_off, pat_count, pid, start, end, count)) return BMX_ERR_ARG;
+    HostCall c("bmx_align", ctx_in);
+    void *d_text = c.upload(text, n);
+    void *d_pat = c.upload(pat, pat_bytes);
+    const uint64_t *d_off = c.upload<uint64_t>(pat_off, (pat_count + 1) * sizeof(uint64_t));
+    const uint32_t *d_pid = pid ? c.upload<uint32_t>(pid, count * sizeof(uint32_t)) : nullptr;
+    const uint64_t *d_start = c.upload<uint64_t>(start, count * sizeof(uint64_t));
+    const uint64_t *d_end = c.upload<uint64_t>(end, count * sizeof(uint64_t));
+    // (no entry has more than 2k + 1 runs: a larger capacity needs no larger device list)
+    const uint64_t dev_cap = std::min(capacity, count * (2 * (uint64_t)k + 1));
+    uint64_t total = 0;
+    uint64_t *d_op_off = c.alloc<uint64_t>((count + 1) * sizeof(uint64_t));
+    uint32_t *d_ops = dev_cap ? c.alloc<uint32_t>(dev_cap * sizeof(uint32_t)) : nullptr;
+    uint8_t *d_dist = dist ? c.alloc<uint8_t>(count) : nullptr;
+    if (c.rc == BMX_OK)
+        c.rc = bmx_align_device(c.ctx(), d_text, n, base_offset, d_pat, pat_bytes, d_off, pat_count, d_pid, d_start, d_end, count, k,
+                                d_dist, d_op_off, d_ops, dev_cap, &total, nullptr);
+    if (c.rc == BMX_OK || c.rc == BMX_ERR_CAPACITY) {
+        if (dist) c.download(dist, d_dist, count, "the distances");
+        c.download(op_off, d_op_off, (count + 1) * sizeof(uint64_t), "the script offsets");
+        c.download(ops, d_ops, std::min(total, dev_cap) * sizeof(uint32_t), "the scripts");
+        if (n_ops) *n_ops = total;
+    }
+    return c.rc;
+}
+
 } // extern "C"
 
 namespace {

@@ -158,6 +158,15 @@ void bmx_internal_index_state_free(void *state);
 float bmx_internal_index_ms(const void *state);
 int64_t bmx_internal_index_map_candidates(const void *state);
 int bmx_internal_index_map_phases(const void *state, float out[5]);
+// bmx_align.hip (ws_cap: 0, or the workspace one launch may take -- libbmx_exp.so's knob)
+int bmx_internal_align(void **state, uint64_t ws_cap, const void *d_text, uint64_t n, uint64_t base_offset, const void *d_pat,
+                       uint64_t pat_bytes, const uint64_t *d_pat_off, uint64_t pat_count, const uint32_t *d_pid,
+                       const uint64_t *d_start, const uint64_t *d_end, uint64_t count, uint32_t k, uint8_t *d_dist,
+                       uint64_t *d_op_off, uint32_t *d_ops, uint64_t capacity, uint64_t *n_ops, hipStream_t stream, char *err,
+                       size_t errlen);
+void bmx_internal_align_free(void *state);
+float bmx_internal_align_ms(const void *state);
+int64_t bmx_internal_align_launches(const void *state);
 // bmx_lcp.hip
 int bmx_internal_lcp(void **state, const uint8_t *d_text, uint32_t n, const int32_t *d_sa, int32_t *d_lcp, hipStream_t stream,
                      char *err, size_t errlen);
@@ -192,6 +201,8 @@ struct bmx_ctx {
     void *spans = nullptr; // match spans: status words, tile counts of the selection, events (bmx_spans.hip)
     void *dict = nullptr;   // dictionary search: the same for its kernel (bmx_dict.hip)
     void *index = nullptr;  // text index: status words, events, workspace of count / locate (bmx_index.hip)
+    void *align = nullptr;  // alignments: status words, events, the launches' workspace (bmx_align.hip)
+    int align_ws_kib = 0;   // libbmx_exp.so: > 0: one launch of the alignments takes at most this much workspace (KiB)
 };
 
 // ---- argument checks: every argument error, before any HIP call (the CPU suite calls the entries with ctx = NULL) ----
@@ -278,6 +289,34 @@ inline bool bmx_spans_long_args_ok(uint64_t n, const void *pat, int32_t m, int32
         return false;
     if (count == 0) return true;
     return ends && starts && (flags == 0 || (dist && sel_ends));
+}
+
+// alignments: the column, the lists and the outputs where there is an entry, k, and which pattern an entry takes
+inline bool bmx_align_args_ok(const void *text, uint64_t n, const void *pat, const uint64_t *pat_off, uint64_t pat_count,
+                              const uint32_t *pid, const uint64_t *start, const uint64_t *end, uint64_t count, int32_t k,
+                              const uint64_t *op_off, const uint32_t *ops, uint64_t capacity)
+{
+    if (k < 0 || k > BMX_ALIGN_MAX_K || n >= (1ull << 40)) return false;
+    if (count == 0) return true;
+    if (!pid && pat_count != 1 && pat_count != count) return false;
+    return text && pat && pat_off && start && end && op_off && (capacity == 0 || ops);
+}
+// ... the host entry's entries: what the kernel calls a bad entry (csrc/bmx_align_kernel.h)
+inline bool bmx_align_entries_ok(uint64_t n, uint64_t base_offset, uint64_t pat_bytes, const uint64_t *pat_off, uint64_t pat_count,
+                                 const uint32_t *pid, const uint64_t *start, const uint64_t *end, uint64_t count)
+{
+    for (uint64_t p = 0; p < pat_count; ++p)
+        if (pat_off[p + 1] < pat_off[p] || pat_off[p + 1] > pat_bytes) return false;
+    for (uint64_t e = 0; e < count; ++e) {
+        const uint64_t s = start[e], j = end[e];
+        if (s == BMX_MAP_NO_POS && j == BMX_MAP_NO_POS) continue;
+        if (s == BMX_MAP_NO_POS || j == BMX_MAP_NO_POS || s < base_offset || j < s || j - base_offset >= n) return false;
+        const uint64_t p = pid ? pid[e] : pat_count == 1 ? 0 : e;
+        if (p >= pat_count) return false;
+        const uint64_t m = pat_off[p + 1] - pat_off[p];
+        if (m == 0 || m > BMX_ALIGN_MAX_PATTERN) return false;
+    }
+    return true;
 }
 
 // a dictionary's patterns: BMX_ERR_ARG for NULL arrays or a count or length out of range, BMX_ERR_DOMAIN for a byte >= 0x80

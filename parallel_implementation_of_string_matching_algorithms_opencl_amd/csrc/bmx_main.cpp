@@ -50,7 +50,9 @@
 //   bmx_cli --approx K --spans [--best] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--max-print K]
 //                             after what --approx prints: the span of every match (bmx_search_approx_spans), the total
 //                             and one `start end dist` line per span (at most --max-print of them); --best keeps one
-//                             span per occurrence (BMX_SPANS_BEST) instead of one per qualifying end
+//                             span per occurrence (BMX_SPANS_BEST) instead of one per qualifying end; with --cigar
+//                             (a string pattern only) each span line ends in one more column, the span's CIGAR
+//                             (bmx_align: = X I D runs)
 //   bmx_cli --dict F [--text F] [--iters N] [--positions] [--max-print K]
 //                             dictionary search (no counterpart in the reference): every occurrence of every
 //                             pattern of F, one per line as `grep -F -f` reads it (empty lines skipped), in
@@ -76,7 +78,8 @@
 //                             where every line of READS_FILE (empty lines skipped) lies in the text within K edits, by
 //                             extending its seeds of (L, N >= 1), through bmx_index_map; one line `query start end dist`
 //                             per read (`query - - -` for a read that maps nowhere) and a last line
-//                             `mapped M of COUNT, candidates TOTAL`; not together with --index-seeds
+//                             `mapped M of COUNT, candidates TOTAL`; not together with --index-seeds; with --cigar
+//                             each line of a mapped read ends in one more column, its CIGAR (bmx_align)
 //           [--gpus G]        also run the search over G GPUs from this one process: devices, RCCL
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
@@ -148,6 +151,27 @@ void split_lines(const std::string &text, std::string &blob, std::vector<uint64_
     }
 }
 
+// --cigar: the script of every span as a SAM CIGAR string (bmx_align; "" for an entry without an alignment)
+bool cigar_strings(bmx_ctx *ctx, const std::string &text, uint64_t base_offset, const void *pat, uint64_t pat_bytes,
+                   const uint64_t *pat_off, uint64_t pat_count, const std::vector<uint64_t> &start, const std::vector<uint64_t> &end,
+                   int k, std::vector<std::string> &out)
+{
+    const uint64_t count = start.size(), room = count * (2 * (uint64_t)k + 1);
+    std::vector<uint64_t> op_off(count + 1, 0);
+    std::vector<uint32_t> ops(room ? room : 1);
+    uint64_t total = 0;
+    const int rc = bmx_align(ctx, text.data(), text.size(), base_offset, pat, pat_bytes, pat_off, pat_count, nullptr, start.data(),
+                             end.data(), count, k, nullptr, op_off.data(), ops.data(), room, &total);
+    if (rc != BMX_OK) {
+        fprintf(stderr, "bmx_align failed: %d (%s)\n", rc, bmx_last_error());
+        return false;
+    }
+    out.assign(count, std::string());
+    for (uint64_t e = 0; e < count; ++e)
+        for (uint64_t j = op_off[e]; j < op_off[e + 1]; ++j) out[e] += std::to_string(ops[j] >> 4) + "MIDNSHP=X"[ops[j] & 15u];
+    return true;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -158,7 +182,7 @@ int main(int argc, char **argv)
     std::string gaps_expr;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
     std::string must_spec;
-    bool positions = false, spans = false, spans_best = false, with_lcp = false;
+    bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false;
     uint64_t max_print = 32;
     uint32_t min_len = 0, max_occ = 0;
     for (int i = 1; i < argc; ++i) {
@@ -183,6 +207,7 @@ int main(int argc, char **argv)
         else if (a == "--must") must_spec = need("--must");
         else if (a == "--spans") spans = true;
         else if (a == "--best") spans_best = true;
+        else if (a == "--cigar") cigar = true;
         else if (a == "--lcp") with_lcp = true;
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--index-count") index_path = need("--index-count");
@@ -218,6 +243,10 @@ int main(int argc, char **argv)
     if (!map_path.empty()) seeds_path = map_path; // the same query file, read below
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
+        return 2;
+    }
+    if (cigar && ((!spans && map_path.empty()) || have_classes)) {
+        fprintf(stderr, "--cigar needs --approx K --spans with a string pattern, or --index-map\n");
         return 2;
     }
 
@@ -294,12 +323,16 @@ int main(int argc, char **argv)
                 fprintf(stderr, "bmx_index_map failed: %d (%s)\n", rc, bmx_last_error());
                 return 1;
             }
+            std::vector<std::string> scripts;
+            if (cigar && !cigar_strings(ctx, text, 0, blob.data(), blob.size(), off.data(), count, start, end, approx_k, scripts)) return 1;
             for (uint64_t q = 0; q < count; ++q) {
                 if (dist[q] == BMX_MAP_NO_HIT) {
                     printf("%llu - - -\n", (unsigned long long)q);
                     continue;
                 }
-                printf("%llu %llu %llu %u\n", (unsigned long long)q, (unsigned long long)start[q], (unsigned long long)end[q], dist[q]);
+                printf("%llu %llu %llu %u", (unsigned long long)q, (unsigned long long)start[q], (unsigned long long)end[q], dist[q]);
+                if (cigar) printf(" %s", scripts[q].c_str());
+                printf("\n");
                 ++mapped;
             }
             printf("mapped %llu of %llu, candidates %llu\n", (unsigned long long)mapped, (unsigned long long)count,
@@ -888,8 +921,17 @@ int main(int argc, char **argv)
             }
             printf("match spans%s: %llu  (spans kernels %.3f ms)\n", spans_best ? " (best)" : "", (unsigned long long)n_spans,
                    n_spans ? bmx_last_spans_ms(ctx) : 0.0);
-            for (uint64_t i = 0; i < n_spans && i < max_print; ++i)
-                printf("%llu %llu %d\n", (unsigned long long)s_starts[i], (unsigned long long)s_ends[i], s_dist[i]);
+            std::vector<std::string> scripts;
+            if (cigar) {
+                const uint64_t one_off[2] = {0, (uint64_t)m};
+                s_starts.resize(n_spans), s_ends.resize(n_spans);
+                if (!cigar_strings(ctx, text, 0, pat.data(), (uint64_t)m, one_off, 1, s_starts, s_ends, approx_k, scripts)) return 1;
+            }
+            for (uint64_t i = 0; i < n_spans && i < max_print; ++i) {
+                printf("%llu %llu %d", (unsigned long long)s_starts[i], (unsigned long long)s_ends[i], s_dist[i]);
+                if (cigar) printf(" %s", scripts[i].c_str());
+                printf("\n");
+            }
             if (n_spans > max_print) printf("... %llu more\n", (unsigned long long)(n_spans - max_print));
         }
         bmx_device_free(ctx, d_dist);

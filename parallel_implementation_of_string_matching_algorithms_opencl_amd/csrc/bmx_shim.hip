@@ -112,6 +112,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
     bmx_internal_index_state_free(ctx->index);
+    bmx_internal_align_free(ctx->align);
     delete ctx;
 }
 
@@ -494,6 +495,27 @@ int bmx_last_index_map_phases(bmx_ctx *ctx, float out[5])
 
 float bmx_last_index_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_index_ms(ctx->index) : -1.0f; }
 
+// ---- alignments (bmx_align.hip) ------------------------------------------------------------------
+int bmx_align_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const void *d_pat, uint64_t pat_bytes,
+                     const uint64_t *d_pat_off, uint64_t pat_count, const uint32_t *d_pid, const uint64_t *d_start,
+                     const uint64_t *d_end, uint64_t count, int32_t k, uint8_t *d_dist, uint64_t *d_op_off, uint32_t *d_ops,
+                     uint64_t capacity, uint64_t *n_ops, void *stream_v)
+{
+    if (!bmx_align_args_ok(d_text, n, d_pat, d_pat_off, pat_count, d_pid, d_start, d_end, count, k, d_op_off, d_ops, capacity))
+        return BMX_ERR_ARG;
+    if (n_ops) *n_ops = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_align(&ctx->align, (uint64_t)(ctx->align_ws_kib > 0 ? ctx->align_ws_kib : 0) << 10, d_text, n, base_offset,
+                              d_pat, pat_bytes, d_pat_off, pat_count, d_pid, d_start, d_end, count, (uint32_t)k, d_dist, d_op_off,
+                              d_ops, capacity, n_ops, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_align_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_align_ms(ctx->align) : -1.0f; }
+
+int64_t bmx_last_align_launches(bmx_ctx *ctx) { return ctx ? bmx_internal_align_launches(ctx->align) : -1; }
+
 int bmx_device_alloc(bmx_ctx *ctx, uint64_t bytes, void **d_ptr_out)
 {
     if (!ctx || !d_ptr_out) return BMX_ERR_ARG;
@@ -550,6 +572,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "ed_stamp_block") ctx->ed_knobs.stamp_block = value;
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
+    else if (k == "align_ws_kib") ctx->align_ws_kib = value;
     else if (k == "ordered_seq" && value >= 0) {
         for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else return BMX_ERR_ARG;

@@ -57,6 +57,15 @@ MAP_MAX_K = 64  # most edits of Index.map (BMX_MAP_MAX_K)
 MAP_NO_HIT = 255  # distance of a candidate or a read without a hit (BMX_MAP_NO_HIT)
 MAP_NO_POS = 0xFFFFFFFFFFFFFFFF  # ... and its positions (BMX_MAP_NO_POS); -1 in the int64 tensors of Index.map
 MAP_MAX_CANDIDATES = 1 << 27
+ALIGN_MAX_PATTERN = 512  # longest pattern of Context.align (BMX_ALIGN_MAX_PATTERN)
+ALIGN_MAX_K = 254
+ALIGN_NONE = 255  # distance of an entry without an alignment within k (BMX_ALIGN_NONE == MAP_NO_HIT)
+ALIGN_WORKSPACE_BYTES = 1 << 30  # the workspace one launch of the alignments may take (BMX_ALIGN_WORKSPACE_BYTES)
+CIGAR_INS = 1  # op codes of the scripts, the BAM encoding: an op word is run length << 4 | code
+CIGAR_DEL = 2
+CIGAR_EQ = 7
+CIGAR_X = 8
+_CIGAR_CHARS = "MIDNSHP=X"
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -232,6 +241,14 @@ SYMBOLS = [
     ("bmx_last_index_map_phases", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("bmx_last_index_ms", C.c_float, [C.c_void_p]),
     ("bmx_index_build_ms", C.c_float, [C.c_void_p]),
+    ("bmx_align_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_align", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_uint64, _u64p]),
+    ("bmx_last_align_ms", C.c_float, [C.c_void_p]),
+    ("bmx_last_align_launches", C.c_int64, [C.c_void_p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     ("bmx_plant_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, _u64p,
                                    C.c_uint64, C.c_void_p]),
@@ -332,6 +349,32 @@ def pack_strings(strings) -> Tuple[np.ndarray, np.ndarray]:
     if items:
         off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
     return np.frombuffer(b"".join(items), dtype=np.uint8), off
+
+
+def cigar_strings(op_off, ops) -> list:
+    """The scripts of Context.align / align_device as SAM CIGAR strings, one per entry ("" for an entry without an
+    alignment): ``op_off`` count + 1 offsets, ``ops`` the op words (numpy arrays or tensors)."""
+    off = np.asarray(op_off.cpu() if hasattr(op_off, "cpu") else op_off).astype(np.int64)
+    words = np.asarray(ops.cpu() if hasattr(ops, "cpu") else ops).astype(np.int64)
+    if off.size and int(off[-1]) > words.size:
+        raise ValueError("ops holds fewer op words than op_off[-1]")
+    parts = [f"{int(w) >> 4}{_CIGAR_CHARS[int(w) & 15]}" for w in words[: int(off[-1]) if off.size else 0]]
+    return ["".join(parts[int(off[e]):int(off[e + 1])]) for e in range(max(off.size - 1, 0))]
+
+
+def _device_strings(patterns, dev):
+    """(blob tensor, offsets tensor, count) on ``dev``: a list of bytes / str or a (blob, offsets) numpy pair is uploaded,
+    a pair of CUDA tensors is passed through."""
+    import torch
+
+    if isinstance(patterns, tuple) and len(patterns) == 2 and hasattr(patterns[0], "data_ptr"):
+        d_blob, d_off = patterns
+        if d_blob.element_size() != 1 or d_off.element_size() != 8:
+            raise ValueError("patterns: a 1-byte blob and 8-byte offsets")
+        return d_blob, d_off, d_off.numel() - 1
+    blob, off = pack_strings(patterns)
+    d_blob = torch.from_numpy(blob.copy() if blob.size else np.zeros(1, np.uint8)).to(dev)
+    return d_blob[: blob.size], torch.from_numpy(off.astype(np.int64)).to(dev), off.size - 1
 
 
 def build_tables(pattern) -> Tuple[np.ndarray, np.ndarray]:
@@ -1070,14 +1113,20 @@ class Context:
             t = int(total.value)
             return starts[:t].copy(), ends[:t].copy(), dist[:t].copy()
 
-    def search_approx_spans(self, text, pattern, k: int, best: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def search_approx_spans(self, text, pattern, k: int, best: bool = True, cigar: bool = False):
         """Host buffers (bmx_search_approx_spans): (starts uint64, ends uint64, distances uint8) of every match of
-        ``pattern`` within k edits, ascending; ``best``: one entry per occurrence, else every qualifying end."""
+        ``pattern`` within k edits, ascending; ``best``: one entry per occurrence, else every qualifying end.  With
+        ``cigar`` a fourth element: the CIGAR string of every span (bmx_align)."""
         pat = _pat_bytes(pattern)
         if len(pat) > MAX_APPROX_PATTERN:  # up to 512 bytes
-            return self._search_spans_host(self._L.bmx_search_approx_long_spans, "bmx_search_approx_long_spans", text, pat, len(pat),
-                                           k, best)
-        return self._search_spans_host(self._L.bmx_search_approx_spans, "bmx_search_approx_spans", text, pat, len(pat), k, best)
+            res = self._search_spans_host(self._L.bmx_search_approx_long_spans, "bmx_search_approx_long_spans", text, pat, len(pat),
+                                          k, best)
+        else:
+            res = self._search_spans_host(self._L.bmx_search_approx_spans, "bmx_search_approx_spans", text, pat, len(pat), k, best)
+        if not cigar:
+            return res
+        _, op_off, ops = self.align(text, [pat], res[0], res[1], k)
+        return res + (cigar_strings(op_off, ops),)
 
     def search_approx_spans_classes(self, text, classes_or_expr, k: int, flags: int = 0,
                                     best: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -1089,6 +1138,101 @@ class Context:
 
     def last_spans_ms(self) -> float:
         return float(self._L.bmx_last_spans_ms(self._h))
+
+    # -- alignments: the edit script of every span ----------------------------------------
+    def align_device(self, d_text, patterns, starts, ends, k: int, pid=None, base_offset: int = 0,
+                     capacity: Optional[int] = None, out=None, stream=None):
+        """(dist, op_off, ops) (bmx_align_device): for entry e the global distance of its pattern against the span
+        text[starts[e] - base_offset .. ends[e] - base_offset] (the end inclusive, as approx_spans_device and Index.map
+        report it) and its canonical edit script.  ``dist`` uint8 (ALIGN_NONE: no alignment within k), ``op_off`` int64 of
+        count + 1 entries (the exclusive prefix sum of the runs per entry; op_off[-1] is the true total), ``ops`` int32 op
+        words (run length << 4 | CIGAR_*), entry e's at ops[op_off[e] : op_off[e + 1]]; cigar_strings makes strings of
+        them.  ``d_text``: a uint8 CUDA tensor; ``patterns``: a list of bytes / str, a (blob, offsets) numpy pair or such
+        a pair of CUDA tensors, one pattern per entry or ONE for all of them, unless ``pid`` (an int32 CUDA tensor) names
+        each entry's; ``starts`` / ``ends``: 8-byte CUDA tensors.  Without ``capacity`` the list is complete.  With a
+        capacity below the total every entry whose segment ends at or below it is stored; that is no error here
+        (op_off[-1] says so); capacity 0 counts only.  ``out``: three tensors to take the answer, used as given.
+        ``stream``: a torch.cuda.Stream (None: torch's current one)."""
+        import torch
+
+        dev = d_text.device
+        d_blob, d_off, pat_count = _device_strings(patterns, dev)
+        count = starts.numel()
+        if starts.element_size() != 8 or ends.element_size() != 8 or ends.numel() != count:
+            raise ValueError("starts, ends: 8-byte entries, as many of one as of the other")
+        if pid is not None and (pid.element_size() != 4 or pid.numel() < count):
+            raise ValueError("pid: 4-byte entries, one per entry")
+        most = count * (2 * int(k) + 1)
+        if out is not None:
+            dist, op_off, ops = out
+            if capacity is None:
+                capacity = ops.numel()
+        else:
+            dist = torch.empty(max(count, 1), dtype=torch.uint8, device=dev)
+            op_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+            ops = None
+        if dist.element_size() != 1 or op_off.element_size() != 8 or dist.numel() < count or op_off.numel() < count + 1:
+            raise ValueError("out: dist 1-byte entries (count), op_off 8-byte entries (count + 1), ops 4-byte entries")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(dev)).cuda_stream)
+        total = C.c_uint64(0)
+
+        def call(ops_t, cap):
+            rc = self._L.bmx_align_device(self._h, ptr(d_text), d_text.numel(), base_offset, ptr(d_blob), d_blob.numel(),
+                                          ptr(d_off), pat_count, ptr(pid), ptr(starts), ptr(ends), count, int(k), ptr(dist),
+                                          ptr(op_off), ptr(ops_t), cap, C.byref(total), s)
+            self._chk(rc, "bmx_align_device", allow=(ERR_CAPACITY,))
+
+        if capacity is None:
+            if most > (1 << 26):  # a counting call first rather than room for every possible run
+                call(None, 0)
+                most = int(total.value)
+            capacity = most
+        if ops is None:
+            ops = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+        if ops.element_size() != 4 or ops.numel() < capacity:
+            raise ValueError("ops: 4-byte entries, at least `capacity` of them")
+        call(ops if capacity > 0 else None, capacity)
+        return dist[:count], op_off[: count + 1], ops[: min(int(total.value), capacity)]
+
+    def align(self, text, patterns, starts, ends, k: int, pid=None, base_offset: int = 0):
+        """Host buffers (bmx_align): (dist uint8, op_off uint64, ops uint32) as align_device, complete.  ``starts`` /
+        ``ends``: sequences of positions (MAP_NO_POS for an entry without a hit)."""
+        tptr, n, keep = _host_text(text)
+        blob, off = pack_strings(patterns)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        ends = np.ascontiguousarray(ends, dtype=np.uint64)
+        count = starts.size
+        if ends.size != count:
+            raise ValueError("starts and ends: as many of one as of the other")
+        pid_arr = None if pid is None else np.ascontiguousarray(pid, dtype=np.uint32)
+        if pid_arr is not None and pid_arr.size != count:
+            raise ValueError("pid: one per entry")
+        dist = np.empty(max(count, 1), dtype=np.uint8)
+        op_off = np.zeros(count + 1, dtype=np.uint64)
+        cap = max(1, min(count * (2 * max(int(k), 0) + 1), 1 << 24))
+        while True:
+            ops = np.empty(cap, dtype=np.uint32)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_align(self._h, tptr, n, base_offset, C.c_void_p(blob.ctypes.data), blob.size,
+                                   C.c_void_p(off.ctypes.data), off.size - 1,
+                                   None if pid_arr is None else C.c_void_p(pid_arr.ctypes.data), C.c_void_p(starts.ctypes.data),
+                                   C.c_void_p(ends.ctypes.data), count, int(k), C.c_void_p(dist.ctypes.data),
+                                   C.c_void_p(op_off.ctypes.data), C.c_void_p(ops.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_align")
+            del keep
+            return dist[:count], op_off, ops[: int(total.value)].copy()
+
+    def last_align_ms(self) -> float:
+        return float(self._L.bmx_last_align_ms(self._h))
+
+    def last_align_launches(self) -> int:
+        """Launches of the alignment kernel in the last align_device on this context (> 1: the entries did not fit the
+        workspace at once); < 0 if none."""
+        return int(self._L.bmx_last_align_launches(self._h))
 
     # -- dictionary search: many patterns in one pass ----------------------------------
     def dictionary(self, patterns) -> "Dictionary":
@@ -1175,21 +1319,24 @@ class Context:
         del keep
         return (seed_off,) + tuple(o[:cap] for o in out)
 
-    def index_map(self, text, patterns, min_len: int, max_occ: int, k: int, candidates: bool = False):
+    def index_map(self, text, patterns, min_len: int, max_occ: int, k: int, candidates: bool = False, cigar: bool = False):
         """Host buffers: (best_start, best_end uint64, best_dist uint8), one entry per pattern: where the pattern lies in
         ``text`` within k edits (MAP_NO_POS, MAP_NO_POS, MAP_NO_HIT if nowhere), by extending its seeds of
         (min_len, max_occ).  That is one bmx_index_map.  With ``candidates`` also (cand_off uint64 of count + 1 entries,
         cand_start, cand_end uint64, cand_dist uint8): every seed occurrence's own answer, in order of (pattern, seed,
-        occurrence); the lists are sized by a counting call, so the index is built once here and Index.map makes both."""
+        occurrence); the lists are sized by a counting call, so the index is built once here and Index.map makes both.
+        With ``cigar`` one more element at the end: the CIGAR string of every pattern at its best position ("" for a
+        pattern that maps nowhere)."""
         if candidates:
             import torch
 
             d_text = torch.from_numpy(np.frombuffer(_host_text(text)[2], dtype=np.uint8).copy()).cuda(self.device)
             with self.index(d_text) as idx:
-                res = idx.map(patterns, min_len, max_occ, k, candidates=True)
-                res = tuple(o.cpu().numpy() for o in res)
+                res = idx.map(patterns, min_len, max_occ, k, candidates=True, cigar=cigar)
+                tail = (res[7],) if cigar else ()
+                res = tuple(o.cpu().numpy() for o in res[:7])
             return (res[0].view(np.uint64), res[1].view(np.uint64), res[2], res[3].view(np.uint64), res[4].view(np.uint64),
-                    res[5].view(np.uint64), res[6])
+                    res[5].view(np.uint64), res[6]) + tail
         tptr, n, keep = _host_text(text)
         blob, off = pack_strings(patterns)
         count = off.size - 1
@@ -1201,7 +1348,11 @@ class Context:
                                    C.byref(total))
         self._chk(rc, "bmx_index_map")
         del keep
-        return tuple(o[:count] for o in best)
+        res = tuple(o[:count] for o in best)
+        if not cigar:
+            return res
+        _, op_off, ops = self.align(text, (blob, off), res[0], res[1], k)
+        return res + (cigar_strings(op_off, ops),)
 
     def last_index_ms(self) -> float:
         return float(self._L.bmx_last_index_ms(self._h))
@@ -1556,14 +1707,17 @@ class Index:
         stored = min(int(total.value), capacity)
         return (seed_off,) + tuple(o[:stored] for o in out)
 
-    def map(self, patterns, min_len: int, max_occ: int, k: int, base_offset: int = 0, candidates: bool = False, out=None):
+    def map(self, patterns, min_len: int, max_occ: int, k: int, base_offset: int = 0, candidates: bool = False, out=None,
+            cigar: bool = False):
         """(best_start, best_end, best_dist) (bmx_index_map_device): where every pattern lies in the text within k edits,
         by extending its seeds of (min_len, max_occ >= 1): int64, int64 and uint8 CUDA tensors, one entry per pattern,
         positions as base_offset + p; a pattern that maps nowhere has MAP_NO_POS (-1 in int64) and MAP_NO_HIT.  With
         ``candidates`` four more: cand_off (int64, count + 1 entries, the exclusive prefix sum of the candidates per
         pattern; cand_off[-1] is the true total) and cand_start, cand_end, cand_dist, one entry per seed occurrence in
         order of (pattern, seed, occurrence), complete (a counting call first).  ``out``: three tensors to take the
-        per-pattern answer, used as given.  ``patterns`` as for count.  Runs on torch's current stream."""
+        per-pattern answer, used as given.  ``patterns`` as for count.  With ``cigar`` one more element at the end: the
+        CIGAR string of every pattern at its best position (Context.align_device; "" for a pattern that maps nowhere).
+        Runs on torch's current stream."""
         import torch
 
         d_blob, d_off, count = self._queries(patterns)
@@ -1582,9 +1736,16 @@ class Index:
             self._ctx._chk(rc, "bmx_index_map_device")
 
         best = tuple(o[:count] for o in out)
+
+        def scripts():
+            if not cigar:
+                return ()
+            _, op_off, ops = self._ctx.align_device(self._text, (d_blob, d_off), best[0], best[1], k, base_offset=base_offset)
+            return (cigar_strings(op_off, ops),)
+
         if not candidates:
             call(None, (None,) * 3, 0)
-            return best
+            return best + scripts()
         cand_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
         call(cand_off, (None,) * 3, 0)  # the counting call: the per-pattern answer and cand_off are final after it
         cap = int(total.value)
@@ -1592,7 +1753,7 @@ class Index:
                  torch.empty(max(cap, 1), dtype=torch.uint8, device=dev))
         if cap > 0:
             call(cand_off, lists, cap)
-        return best + (cand_off,) + tuple(o[:cap] for o in lists)
+        return best + (cand_off,) + tuple(o[:cap] for o in lists) + scripts()
 
     def locate(self, patterns, capacity: Optional[int] = None, base_offset: int = 0):
         """(offsets, positions, total) (bmx_index_locate_device): ``offsets`` int64 CUDA tensor of count + 1 entries, the
@@ -1777,10 +1938,16 @@ def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
     return default_context().search_approx(text, pattern, k)
 
 
-def search_approx_spans(text, pattern, k: int, best: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+def search_approx_spans(text, pattern, k: int, best: bool = True, cigar: bool = False):
     """(text, pattern, k) -> (starts, ends, distances): the span of every match with at most k edits, one per occurrence
-    with ``best`` (bmx_search_approx_spans)."""
-    return default_context().search_approx_spans(text, pattern, k, best)
+    with ``best`` (bmx_search_approx_spans); with ``cigar`` also the CIGAR string of every span."""
+    return default_context().search_approx_spans(text, pattern, k, best, cigar)
+
+
+def align(text, patterns, starts, ends, k: int, pid=None, base_offset: int = 0):
+    """(text, patterns, starts, ends, k) -> (dist, op_off, ops): the edit script of every span (bmx_align), see
+    Context.align; cigar_strings(op_off, ops) makes CIGAR strings of them."""
+    return default_context().align(text, patterns, starts, ends, k, pid, base_offset)
 
 
 def edit_distance_batch(a, b, limit: Optional[int] = None) -> np.ndarray:
@@ -1799,10 +1966,10 @@ def index_seeds(text, patterns, min_len: int, max_occ: int = 0):
     return default_context().index_seeds(text, patterns, min_len, max_occ)
 
 
-def index_map(text, patterns, min_len: int, max_occ: int, k: int, candidates: bool = False):
+def index_map(text, patterns, min_len: int, max_occ: int, k: int, candidates: bool = False, cigar: bool = False):
     """Where every pattern lies in ``text`` within k edits, through a text index built for the call (bmx_index_map):
     (best_start, best_end, best_dist), see Context.index_map."""
-    return default_context().index_map(text, patterns, min_len, max_occ, k, candidates)
+    return default_context().index_map(text, patterns, min_len, max_occ, k, candidates, cigar)
 
 
 def lcp_array(text) -> Tuple[np.ndarray, np.ndarray]:
