@@ -531,7 +531,8 @@ float bmx_last_hamming_ms(bmx_ctx *ctx);
  * lead > n, n too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer
  * than its bound (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly
  * ordered.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream.
- * Out of scope: unbounded repetition (* and +), anchors, alternation, M > 64. */
+ * Out of scope: unbounded repetition (* and +), anchors, M > 64; alternation and groups are not part of this search but of
+ * the regular-expression search below (bmx_compile_regex, bmx_search_regex_device). */
 #define BMX_MAX_GAPS_PATTERN 64
 #define BMX_GAPS_PROSITE 4u /* (beside BMX_CLASS_ICASE and BMX_CLASS_IUPAC in the flags of bmx_compile_gaps) */
 /* Pure host code, no GPU.  *m is the number of positions after expansion, bit i of *optional says that position i is
@@ -578,6 +579,87 @@ int bmx_gaps_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_
 int bmx_search_gaps_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint8_t *classes, int32_t m,
                           uint64_t optional, uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity,
                           uint64_t *n_matches);
+
+/* ---- regular-expression search: groups, alternation, counted repeats (star-free) ------------- */
+
+/* ATG([ACGT]{3}){2,4}(TAA|TAG|TGA), (ERROR|FATAL|PANIC): [0-9]{2,4}, ([0-9]{1,3}\.){3}[0-9]{1,3}: one pass over the text
+ * answers what otherwise takes one class or gapped pass per fixed-length variant and a merge of their lists.  The
+ * expressions are the STAR-FREE ones: a star-free expression has a longest match, so a lane's warm-up of a fixed number
+ * of bytes is exact and the geometry, the shard contract and the ordered output are the gapped search's.  The reference
+ * has no such program.  The matcher runs the Glushkov (position) automaton bit-parallel, one 32- or 64-bit word per
+ * lane: positions whose only successor is the next one move by a shift, the others through small tables in LDS
+ * (csrc/bmx_regex_kernel.h).
+ *
+ * The automaton is plain data.  Positions are numbered left to right; position i has a class (BMX_CLASS_BYTES bytes,
+ * encoded exactly as for bmx_search_classes; an empty class is legal, and so are positions that no match can use).
+ * A substring text[s..j] of length L >= 1 MATCHES iff there are positions i_0, .., i_{L-1} with i_0 in `first`,
+ * i_{t+1} in follow[i_t], i_{L-1} in `last` and text[s + t] in class i_t for every t.
+ * Valid: 1 <= m <= BMX_MAX_REGEX_POSITIONS; first and last non-zero; no bit at or above m in first, last or any
+ * follow[i]; follow[i] holds only bits j > i.  The automaton is then acyclic, a match visits a position at most once and
+ * max_len <= m.  The search entries recompute min_len and max_len from the sets and do not read the two fields;
+ * bmx_compile_regex fills them so that the caller knows its halo. */
+#define BMX_MAX_REGEX_POSITIONS 64
+typedef struct bmx_regex {
+    int32_t  m;                 /* positions, 1..64, numbered left to right after expansion */
+    int32_t  min_len, max_len;  /* shortest / longest match in bytes; filled by bmx_compile_regex */
+    uint64_t first;             /* bit i: a match may begin with position i */
+    uint64_t last;              /* bit i: a match may end with position i */
+    uint64_t follow[BMX_MAX_REGEX_POSITIONS];  /* bit j of follow[i]: position j may come right after i */
+    uint8_t  classes[BMX_MAX_REGEX_POSITIONS * BMX_CLASS_BYTES];  /* as for bmx_search_classes */
+} bmx_regex;
+/* Pure host code, no GPU.
+ *   alt    := concat ('|' concat)*        an empty alternative is allowed: (a|) is a?
+ *   concat := repeat*
+ *   repeat := atom quant?                 quant := '?' | '{a}' | '{a,b}'   decimal, 0 <= a <= b, b >= 1
+ *   atom   := element | '(' alt ')'
+ * An element is exactly one element of bmx_compile_classes (. [...] [^...] \xHH \c, any other byte; BMX_CLASS_ICASE and
+ * BMX_CLASS_IUPAC as there, and no other flag), so \( \) \| \? \{ \* \+ are literals and inside a set these bytes are
+ * literals anyway.  X{a,b} expands to a copies of X followed by b - a optional copies, for a group as for an element;
+ * first, last, follow and nullability come from the standard Glushkov recursion.  Groups do not capture.
+ * BMX_ERR_ARG, with *out untouched and a text in bmx_last_error: NULL arguments; an unknown flag bit; an unescaped * or +,
+ * or {a,} (unbounded repetition is out of scope); unbalanced ( or ); a quantifier with nothing in front of it or right
+ * after another quantifier (so (?: is an error); b == 0, a > b, a malformed or unterminated {...}; nesting deeper than 32;
+ * more than BMX_MAX_REGEX_POSITIONS positions after expansion, or zero; an expression that matches the empty string;
+ * every error of bmx_compile_classes. */
+int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out);
+/* Semantics: every END j in [lead, n) at which some match ends, each end once, ascending, reported as base_offset + j
+ * (ends, as in the gapped search: several starts can share one end).  A match spans at most max_len bytes, so a shard
+ * passes a view that begins max_len - 1 bytes (clipped at 0) before its first end, with lead = that amount: the shards'
+ * lists then concatenate to the whole text's list.
+ * Two identities: an expression without groups gives bmx_search_gaps_device's list; any expression gives the union of
+ * "starts + length - 1" over the fixed-length class patterns that its paths from `first` to `last` spell.
+ * Any byte values in text and classes; n < 2^40, any alignment of d_text.
+ * Capacity: the stored entries are the LOWEST `capacity` ends; *n_matches is the true total, and a larger total returns
+ * BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers where needed, an automaton that is not valid,
+ * lead > n, n too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer
+ * than its bound (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly
+ * ordered.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream.
+ * Out of scope: unbounded repetition (* + {a,}), anchors, back-references, capture groups, more than 64 positions. */
+int bmx_search_regex_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                            const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_regex_device with lead = 0, download). */
+int bmx_search_regex(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                     uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the regex-search kernel) of the last bmx_search_regex_device on ctx; < 0 if none. */
+float bmx_last_regex_ms(bmx_ctx *ctx);
+/* The START of a match for every end of a device-resident list, as bmx_search_regex_device returns it for the same view,
+ * automaton and base_offset: d_starts[i] = base_offset + s with text[s..j_i] a match, d_ends[i] = base_offset + j_i.  By
+ * default s is the LARGEST such start (the shortest match), with BMX_REGEX_LONGEST the smallest s >= 0 of the view (the
+ * longest; a shard's halo of max_len - 1 bytes holds it).  One list entry per lane; the lane runs the reversed automaton
+ * over at most max_len bytes backwards from j.
+ * Errors: NULL pointers where needed, an automaton that is not valid, n out of range and unknown flag bits return
+ * BMX_ERR_ARG before any HIP call, with ctx = NULL too; count == 0 returns BMX_OK and launches nothing.  An entry outside
+ * [base_offset, base_offset + n) reads no byte and raises a status word, and so does an entry at which no match ends (a
+ * list of another expression or text): the call then returns BMX_ERR_ARG and the outputs are unspecified.
+ * No byte outside the aligned 16-byte lines that hold text[0..n) is read, none below text[0]'s line.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising it. */
+#define BMX_REGEX_LONGEST 1u
+int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                            const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_regex_device, bmx_regex_starts_device (flags: BMX_REGEX_LONGEST or
+ * 0), download.  starts[i] belongs to ends[i]; capacity and *n_matches as for bmx_search_regex.  ctx may be NULL. */
+int bmx_search_regex_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re, uint32_t flags,
+                           uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
 
 /* ---- match spans of the approximate search: (start, end, distance) ------------------------- */
 

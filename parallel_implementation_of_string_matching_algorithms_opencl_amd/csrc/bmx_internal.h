@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "bmx.h"
+#include "bmx_regex_sets.h"
 
 // In a function with `char *err, size_t errlen` that returns a BMX_* code: `where` names the entry point.
 #define BMX_HIP(where, expr)                                                                      \
@@ -104,6 +105,15 @@ int bmx_internal_gaps_starts(void **state, const void *d_text, uint64_t n, uint6
                              uint64_t *d_starts, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_gaps_free(void *state);
 float bmx_internal_gaps_ms(const void *state);
+// bmx_regex.hip
+int bmx_internal_regex(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                       const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, hipStream_t stream,
+                       char *err, size_t errlen);
+int bmx_internal_regex_starts(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                              const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, hipStream_t stream,
+                              char *err, size_t errlen);
+void bmx_internal_regex_free(void *state);
+float bmx_internal_regex_ms(const void *state);
 // bmx_ed_batch.hip
 int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
                           const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
@@ -194,6 +204,7 @@ struct bmx_ctx {
     void *classes = nullptr; // class-pattern search: the same kind of state, its own (bmx_classes.hip)
     void *hamming = nullptr; // k-mismatch search: the same again (bmx_hamming.hip)
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
+    void *regex = nullptr; // regular-expression search: the same as the gapped search's, its own (bmx_regex.hip)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *approx_long = nullptr; // ... for patterns of more than 64 bytes: the same kind of state, its own (bmx_approx_long.hip)
     bool approx_last_long = false; // which of the two the last approximate search on this context used (bmx_last_approx_ms)
@@ -268,6 +279,20 @@ inline bool bmx_gaps_starts_args_ok(uint64_t n, const uint8_t *classes, int32_t 
                                     uint64_t count, uint32_t flags, const uint64_t *starts)
 {
     if (!bmx_gaps_pattern_ok(classes, m, optional) || n >= (1ull << 40) || (flags & ~BMX_GAPS_LONGEST)) return false;
+    return count == 0 || (ends && starts);
+}
+
+// regular-expression search: a valid automaton (bmx_regex_sets.h)
+inline bool bmx_regex_ok(const bmx_regex *re) { return re && bmx_regex_sets_ok(re->m, re->first, re->last, re->follow); }
+inline bool bmx_regex_args_ok(uint64_t n, uint64_t lead, const bmx_regex *re, const void *ends, uint64_t capacity)
+{
+    return bmx_regex_ok(re) && lead <= n && n < (1ull << 40) && (capacity == 0 || ends);
+}
+// ... and the starts of its matches
+inline bool bmx_regex_starts_args_ok(uint64_t n, const bmx_regex *re, const uint64_t *ends, uint64_t count, uint32_t flags,
+                                     const uint64_t *starts)
+{
+    if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
     return count == 0 || (ends && starts);
 }
 

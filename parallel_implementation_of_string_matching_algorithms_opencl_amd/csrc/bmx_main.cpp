@@ -47,6 +47,11 @@
 //                             --classes does for starts.  With --starts the start of every match as well
 //                             (bmx_search_gaps_spans: the largest one, with --longest the smallest), and --positions
 //                             then prints `start end` pairs
+//   bmx_cli --regex EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K] [--starts [--longest]]
+//                             regular-expression search (no counterpart in the reference): EXPR is a star-free regular
+//                             expression, the elements of --classes with groups ( ), alternation | and ? {a} {a,b} on
+//                             elements and groups (bmx_compile_regex); prints what --gaps prints, `regex matches: N` in
+//                             place of `gapped matches: N`.  It goes with none of --gaps, --classes, --approx, --hamming
 //   bmx_cli --approx K --spans [--best] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--max-print K]
 //                             after what --approx prints: the span of every match (bmx_search_approx_spans), the total
 //                             and one `start end dist` line per span (at most --max-print of them); --best keeps one
@@ -179,7 +184,8 @@ int main(int argc, char **argv)
     std::string text_path = "inputEd.txt", pat_path = "input1Search.txt", ed_a, ed_b, sa_path, dict_path, edb_a, edb_b, class_expr, index_path, seeds_path, map_path;
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false, have_gaps = false, gaps_starts = false, gaps_longest = false;
-    std::string gaps_expr;
+    std::string gaps_expr, regex_expr;
+    bool have_regex = false;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
     std::string must_spec;
     bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false;
@@ -217,6 +223,7 @@ int main(int argc, char **argv)
         else if (a == "--max-occ") max_occ = (uint32_t)strtoul(need("--max-occ"), nullptr, 10);
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
         else if (a == "--gaps") gaps_expr = need("--gaps"), have_gaps = true;
+        else if (a == "--regex") regex_expr = need("--regex"), have_regex = true;
         else if (a == "--prosite") class_flags |= BMX_GAPS_PROSITE;
         else if (a == "--starts") gaps_starts = true;
         else if (a == "--longest") gaps_longest = true;
@@ -273,8 +280,12 @@ int main(int argc, char **argv)
         p = *end ? end + 1 : end;
     }
 
-    if ((gaps_starts || (class_flags & BMX_GAPS_PROSITE)) && !have_gaps) {
-        fprintf(stderr, "--starts and --prosite need --gaps EXPR\n");
+    if (have_regex && (have_gaps || have_classes || approx_k >= 0 || hamming_k >= 0 || (class_flags & BMX_GAPS_PROSITE))) {
+        fprintf(stderr, "--regex goes with none of --gaps, --prosite, --classes, --approx, --hamming\n");
+        return 2;
+    }
+    if ((gaps_starts && !have_gaps && !have_regex) || ((class_flags & BMX_GAPS_PROSITE) && !have_gaps)) {
+        fprintf(stderr, "--starts needs --gaps EXPR or --regex EXPR, --prosite needs --gaps EXPR\n");
         return 2;
     }
     if ((gaps_longest && !gaps_starts) || (have_gaps && (have_classes || approx_k >= 0))) {
@@ -565,7 +576,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "cannot read text file %s\n", text_path.c_str());
         return 1;
     }
-    if (dict_path.empty() && !have_classes && !have_gaps && !read_file(pat_path, pat)) { // (a dictionary search reads its own list, a class search its expression)
+    if (dict_path.empty() && !have_classes && !have_gaps && !have_regex && !read_file(pat_path, pat)) { // (a dictionary search reads its own list, a class search its expression)
         fprintf(stderr, "cannot read pattern file %s\n", pat_path.c_str());
         return 1;
     }
@@ -580,6 +591,72 @@ int main(int argc, char **argv)
     if (have_gaps && bmx_compile_gaps(gaps_expr.data(), gaps_expr.size(), class_flags, classes.data(), &gaps_optional, &m) != BMX_OK) {
         fprintf(stderr, "bad gapped pattern expression %s\n", gaps_expr.c_str());
         return 1;
+    }
+    if (have_regex) {
+        bmx_regex re;
+        if (bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re) != BMX_OK) {
+            fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
+            return 1;
+        }
+        printf("text %s: %llu bytes, regular expression %s: %d positions, matches of %d to %d bytes\n", text_path.c_str(),
+               (unsigned long long)n, regex_expr.c_str(), re.m, re.min_len, re.max_len);
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        void *d_text = nullptr;
+        uint64_t *d_ends = nullptr;
+        const uint64_t cap = n ? n : 1; // at most one hit per end
+        if (rc == BMX_OK) rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+        if (rc == BMX_OK) rc = bmx_device_alloc(ctx, cap * sizeof(uint64_t), (void **)&d_ends);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "device setup failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        double total = 0.0, kernel_ms = 0.0;
+        uint64_t hits = 0;
+        for (int it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = bmx_search_regex_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr);
+            auto t1 = std::chrono::steady_clock::now();
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_search_regex_device failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            total += std::chrono::duration<double>(t1 - t0).count();
+            kernel_ms += bmx_last_regex_ms(ctx);
+        }
+        if (iters <= 0) { // no timed call has counted: a counting call
+            rc = bmx_search_regex(ctx, text.data(), n, &re, nullptr, 0, &hits);
+            if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) hits = 0;
+        }
+        // the list itself through the host-buffer entry points: (text, automaton) -> ends, or -> (starts, ends)
+        std::vector<uint64_t> ends(hits ? hits : 1), starts(gaps_starts && hits ? hits : 1);
+        uint64_t got = 0;
+        rc = gaps_starts ? bmx_search_regex_spans(ctx, text.data(), n, &re, gaps_longest ? BMX_REGEX_LONGEST : 0u, starts.data(),
+                                                  ends.data(), hits, &got)
+                         : bmx_search_regex(ctx, text.data(), n, &re, ends.data(), hits, &got);
+        if (rc != BMX_OK || got != hits) {
+            fprintf(stderr, "%s failed: %d (%s), %llu hits against %llu\n", gaps_starts ? "bmx_search_regex_spans" : "bmx_search_regex",
+                    rc, bmx_last_error(), (unsigned long long)got, (unsigned long long)hits);
+            return 1;
+        }
+        printf("regex matches: %llu\n", (unsigned long long)got);
+        if (got) {
+            printf("first end: %llu\n", (unsigned long long)ends[0]);
+            printf("last end: %llu\n", (unsigned long long)ends[got - 1]);
+        }
+        if (positions) {
+            for (uint64_t i = 0; i < got && i < max_print; ++i) {
+                if (gaps_starts) printf("Match at : %llu %llu\n", (unsigned long long)starts[i], (unsigned long long)ends[i]);
+                else printf("End at : %llu\n", (unsigned long long)ends[i]);
+            }
+            if (got > max_print) printf("... %llu more\n", (unsigned long long)(got - max_print));
+        }
+        if (iters > 0)
+            printf("Average time = %.6f s  (kernel %.3f ms)\n", total / iters, kernel_ms / iters);
+        bmx_device_free(ctx, d_ends);
+        bmx_device_free(ctx, d_text);
+        bmx_ctx_destroy(ctx);
+        return 0;
     }
     if (have_gaps)
         printf("text %s: %llu bytes, gapped pattern %s: %d positions, %d of them optional\n", text_path.c_str(),

@@ -108,6 +108,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_classes_free(ctx->classes);
     bmx_internal_hamming_free(ctx->hamming);
     bmx_internal_gaps_free(ctx->gaps);
+    bmx_internal_regex_free(ctx->regex);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
@@ -310,6 +311,29 @@ int bmx_gaps_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_gaps_starts(&ctx->gaps, d_text, n, base_offset, classes, m, optional, d_ends, count, flags, d_starts,
                                     (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+// ---- regular-expression search (bmx_regex.hip; bmx_compile_regex is bmx_regex_compile.cpp) ------
+int bmx_search_regex_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset, const bmx_regex *re,
+                            uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_regex_args_ok(n, lead, re, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex(&ctx->regex, ctx->num_cu, d_text, n, lead, base_offset, re, d_ends, capacity, n_matches,
+                              (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_ms(ctx->regex) : -1.0f; }
+
+int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                            const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, void *stream_v)
+{
+    if (!bmx_regex_starts_args_ok(n, re, d_ends, count, flags, d_starts)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_starts(&ctx->regex, d_text, n, base_offset, re, d_ends, count, flags, d_starts,
+                                     (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
 // ---- match spans of the approximate search (bmx_spans.hip) --------------------------------------
@@ -574,7 +598,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "align_ws_kib") ctx->align_ws_kib = value;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }

@@ -45,6 +45,8 @@ MAX_HAMMING_K = 15
 MAX_GAPS_PATTERN = 64
 GAPS_PROSITE = 4  # a flag of compile_gaps, beside CLASS_ICASE and CLASS_IUPAC
 GAPS_LONGEST = 1  # a flag of gaps_starts_device
+MAX_REGEX_POSITIONS = 64
+REGEX_LONGEST = 1  # a flag of regex_starts_device
 SPANS_BEST = 1
 SPANS_BLOCK = 256  # list entries per workgroup of the starts kernel (csrc/bmx_spans_kernel.h)
 SPANS_TILE = 2048  # list entries per workgroup of the selection
@@ -176,6 +178,15 @@ SYMBOLS = [
     ("bmx_last_gaps_ms", C.c_float, [C.c_void_p]),
     ("bmx_gaps_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64,
                                          C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_compile_regex", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("bmx_search_regex_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_regex", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, _u64p]),
+    ("bmx_last_regex_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.c_uint32, C.c_void_p, C.c_void_p]),
     ("bmx_approx_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           _u64p, C.c_void_p]),
@@ -443,6 +454,35 @@ def _gaps(expr_or_pair, flags: int = 0) -> Tuple[np.ndarray, int]:
         return compile_gaps(expr_or_pair, flags)
     classes, optional = expr_or_pair
     return _classes(classes), int(optional)
+
+
+class Regex(C.Structure):
+    """struct bmx_regex (include/bmx.h): the position automaton of a star-free regular expression, plain data.  Bit j of
+    ``follow[i]``: position j may come right after position i; ``classes``: 32 bytes per position, as compile_classes."""
+    _fields_ = [("m", C.c_int32), ("min_len", C.c_int32), ("max_len", C.c_int32), ("first", C.c_uint64), ("last", C.c_uint64),
+                ("follow", C.c_uint64 * MAX_REGEX_POSITIONS), ("classes", C.c_uint8 * (MAX_REGEX_POSITIONS * CLASS_BYTES))]
+
+    def class_array(self) -> np.ndarray:
+        """The classes of the m positions, uint8 [m, 32]."""
+        return np.frombuffer(bytes(self.classes), dtype=np.uint8).reshape(MAX_REGEX_POSITIONS, CLASS_BYTES)[: self.m].copy()
+
+
+def compile_regex(expr, flags: int = 0) -> Regex:
+    """A star-free regular expression (bmx_compile_regex: the elements of compile_classes, groups ``( )``, alternation
+    ``|`` and the quantifiers ``?``, ``{a}``, ``{a,b}`` on elements and on groups) -> its position automaton."""
+    e = _pat_bytes(expr)
+    out = Regex()
+    _check(lib().bmx_compile_regex(e, len(e), int(flags), C.byref(out)), "bmx_compile_regex")
+    return out
+
+
+def _regex(expr_or_regex, flags: int = 0) -> Regex:
+    """A Regex from an expression (str / bytes) or such a structure, passed through."""
+    if isinstance(expr_or_regex, (str, bytes, bytearray)):
+        return compile_regex(expr_or_regex, flags)
+    if not isinstance(expr_or_regex, Regex):
+        raise ValueError("expr_or_regex: an expression or a Regex")
+    return expr_or_regex
 
 
 class Context:
@@ -1051,6 +1091,90 @@ class Context:
 
     def last_gaps_ms(self) -> float:
         return float(self._L.bmx_last_gaps_ms(self._h))
+
+    # -- regular-expression search: groups, alternation, counted repeats (star-free) -------
+    def search_regex_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
+                            base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
+        """Every end j in [lead, n) of the view ``d_text[0:n)`` at which a match of the expression ends, ascending,
+        reported as base_offset + j (bmx_search_regex_device).  ``expr_or_regex``: an expression for compile_regex(expr,
+        flags) or its result.  ``out``, ``capacity``, ``stream`` and the return value (ends view, true total) are those
+        of search_gaps_device."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_regex_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset, C.byref(re_),
+                                             C.c_void_p(out.data_ptr()), cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_regex_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def search_regex(self, text, expr_or_regex, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex): ascending ends, uint64.  With ``capacity`` given and too small, raises
+        BmxError(ERR_CAPACITY); without it the list is always complete."""
+        re_ = _regex(expr_or_regex, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex(self._h, tptr, n, C.byref(re_), C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_regex_spans(self, text, expr_or_regex, flags: int = 0, longest: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_regex_spans): (starts uint64, ends uint64) of every match, ends ascending; each start
+        the largest one for its end, or with ``longest`` the smallest."""
+        re_ = _regex(expr_or_regex, flags)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_spans(self._h, tptr, n, C.byref(re_), REGEX_LONGEST if longest else 0,
+                                                C.c_void_p(starts.ctypes.data), C.c_void_p(ends.ctypes.data), cap,
+                                                C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_spans")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy()
+
+    def regex_starts_device(self, d_text, expr_or_regex, ends, *, longest: bool = False, flags: int = 0,
+                            n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """A start for every end of ``ends`` (int64 / uint64 CUDA tensor, as search_regex_device returns it for the same
+        view, expression and base_offset): the largest one, or with ``longest`` the smallest one of the view
+        (bmx_regex_starts_device).  Returns the starts, a tensor like ``ends``."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags)
+        count = ends.numel()
+        if n is None:
+            n = d_text.numel()
+        if ends.element_size() != 8:
+            raise ValueError("ends: 8-byte entries")
+        starts = torch.empty(max(count, 1), dtype=ends.dtype, device=ends.device)
+        s = stream if stream is not None else torch.cuda.current_stream(ends.device)
+        rc = self._L.bmx_regex_starts_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                             C.c_void_p(ends.data_ptr()), count, REGEX_LONGEST if longest else 0,
+                                             C.c_void_p(starts.data_ptr()), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_starts_device")
+        return starts[:count]
+
+    def last_regex_ms(self) -> float:
+        return float(self._L.bmx_last_regex_ms(self._h))
 
     # -- match spans of the approximate search: (start, end, distance) -------------------
     def approx_spans_device(self, d_text, pattern_or_classes, k: int, ends, dist=None, *, best: bool = False, flags: int = 0,
@@ -1931,6 +2055,13 @@ def search_gaps(text, expr, flags: int = 0, spans: bool = False):
     (starts, ends), each start the largest one for its end (the shortest match)."""
     ctx = default_context()
     return ctx.search_gaps_spans(text, expr, flags) if spans else ctx.search_gaps(text, expr, flags)
+
+
+def search_regex(text, expr, flags: int = 0, spans: bool = False, longest: bool = False):
+    """(text, star-free regular expression) -> ascending ends of every match (bmx_search_regex); with ``spans`` the pair
+    (starts, ends), each start the largest one for its end (the shortest match) or with ``longest`` the smallest."""
+    ctx = default_context()
+    return ctx.search_regex_spans(text, expr, flags, longest) if spans else ctx.search_regex(text, expr, flags)
 
 
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
