@@ -19,8 +19,23 @@ extern "C" {
  * array instead of their directory bucket: same answers, tools/index_rate.py measures the difference), "ordered_seq"
  * (>= 0: the sequence number of every ordered-output session the context already has -- approximate, class-pattern and
  * dictionary search; the next call takes the one after it, so (1 << 22) - 1 puts that call on the wrap of the status
- * words' 22-bit tag).  BMX_ERR_ARG for an unknown name and for a negative "ordered_seq". */
+ * words' 22-bit tag), "tile_piece_shift" and "tile_max_grid" (the launch geometry of the same sessions, the long
+ * approximate, k-mismatch, gapped and regex search included, from their next call on; tests reach with them, on texts an
+ * oracle can check in full, what only texts of GiB reach otherwise.  tile_piece_shift: 0 = the production rule, else 6..12 =
+ * log2 of the ends per lane in place of the rule's value; the dictionary search takes value - 6 for the log2 of the 8 KiB rounds
+ * per tile, at most 5 (256 KiB), so a context that has a dictionary session accepts at most 11.  tile_max_grid: 0 = off, else
+ * the most workgroups a call starts; tiles are handed out in ascending order and every started workgroup is resident, so
+ * any grid finishes.  Values are not checked against the pattern: a piece below ceil_log2(4 m) is a geometry the product
+ * never runs).  BMX_ERR_ARG for an unknown name, a negative "ordered_seq" or "tile_max_grid" and a "tile_piece_shift"
+ * outside those ranges. */
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
+
+/* What the last launch of one ordered-output session of the context ran with: out3 = {log2 of the ends per lane (the
+ * dictionary search: 6 + log2 of the rounds per tile), workgroups started, tiles}; zeros before the session's first launch.
+ * session: "approx" (also the approximate search over classes), "approx_long", "classes", "hamming", "gaps", "regex" or
+ * "dict".  Tests assert with it that the geometry they forced ("tile_piece_shift", "tile_max_grid") is the one that ran.
+ * BMX_ERR_ARG for another name. */
+int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3);
 
 /* Read-only sweep of n bytes at d_text (16-byte aligned) with plain global loads into registers, XOR-folded: no LDS,
  * no barrier, no tiles (csrc/bmx_probe_kernel.h).  unroll = loads in flight per lane (1, 2, 4, 8, 16), nt = cache

@@ -18,6 +18,9 @@
 static_assert(bmx::DICT_MAX == BMX_MAX_DICT, "header and kernel disagree");
 static_assert(bmx::DICT_ROUND == 1 << 13, "tile_shift assumes 8 KiB rounds");
 static_assert(sizeof(bmx::DictArgs) <= 4096, "kernel arguments");
+#ifdef BMX_EXPERIMENTS
+static_assert(6 + bmx::DICT_MAX_ROUNDS_SHIFT == bmx::ORDERED_DICT_MAX_PIECE_SHIFT, "what the knob tile_piece_shift accepts");
+#endif
 
 struct bmx_dict {
     const void *owner = nullptr; // the context it was built for
@@ -210,7 +213,10 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
     const uint64_t resident = (uint64_t)num_cu * (uint64_t)st->blocks_per_cu;
     const uint64_t rounds = (a.own_hi + bmx::DICT_ROUND - 1) / bmx::DICT_ROUND;
     const uint64_t per = rounds / std::max<uint64_t>(8 * resident, 1);
-    const uint32_t rs = std::min<uint32_t>(per ? 63 - __builtin_clzll(per) : 0, bmx::DICT_MAX_ROUNDS_SHIFT);
+    uint32_t rs = std::min<uint32_t>(per ? 63 - __builtin_clzll(per) : 0, bmx::DICT_MAX_ROUNDS_SHIFT);
+#ifdef BMX_EXPERIMENTS
+    if (st->oo.force_piece_shift) rs = st->oo.force_piece_shift - 6; // libbmx_exp.so's knob "tile_piece_shift" (6..11 here)
+#endif
     const uint32_t tile_shift = rs + 13;
     a.tile_begin = a.first >> tile_shift; // == 0
     a.n_tiles = ((a.own_hi + (1ull << tile_shift) - 1) >> tile_shift) - a.tile_begin;
@@ -231,7 +237,11 @@ int bmx_internal_dict_search(void **state_v, int num_cu, const bmx_dict *d, cons
     BMX_HIP(where, hipMemsetAsync(st->d_cand, 0, sizeof(unsigned long long), stream));
     int rc = st->oo.begin(where, stream, a, err, errlen);
     if (rc != BMX_OK) return rc;
-    const uint64_t grid = std::min<uint64_t>(a.n_tiles, resident);
+    uint64_t grid = std::min<uint64_t>(a.n_tiles, resident);
+#ifdef BMX_EXPERIMENTS
+    if (st->oo.force_max_grid) grid = std::min<uint64_t>(grid, st->oo.force_max_grid); // ... "tile_max_grid"
+    st->oo.last_piece_shift = rs + 6, st->oo.last_grid = grid, st->oo.last_tiles = a.n_tiles; // (bmx_exp_last_launch)
+#endif
     hipLaunchKernelGGL(bmx::dict_kernel, dim3((uint32_t)grid), dim3(bmx::DICT_BLOCK), 0, stream, a);
     st->launched = true;
     return st->oo.finish(where, grid, a.n_tiles, stream, capacity, n_matches, err, errlen);

@@ -97,6 +97,12 @@ struct OrderedOut {
     uint64_t seq = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = -1.0f;
+#ifdef BMX_EXPERIMENTS
+    uint32_t force_piece_shift = 0; // libbmx_exp.so's knob "tile_piece_shift": 0, or log2 of the ends per lane of every call
+    uint32_t force_max_grid = 0;    // ... "tile_max_grid": 0, or the most workgroups a call starts
+    uint32_t last_piece_shift = 0;  // what the last launch ran with (bmx_exp_last_launch): log2 of the ends per lane,
+    uint64_t last_grid = 0, last_tiles = 0; // its workgroups and its tiles
+#endif
 
     void free()
     {
@@ -182,5 +188,29 @@ inline void ordered_set_seq(void *state, uint64_t seq)
 {
     if (state) static_cast<OrderedOut *>(state)->seq = seq;
 }
+
+#ifdef BMX_EXPERIMENTS
+constexpr uint32_t ORDERED_DICT_MAX_PIECE_SHIFT = 11; // the dictionary search: 6 + DICT_MAX_ROUNDS_SHIFT (bmx_dict.hip asserts it)
+
+// ... "tile_piece_shift" and "tile_max_grid": the geometry of this session's calls from now on (0: the production rule's).
+// A small grid cannot stall the look-back: tickets go out in ascending order and a workgroup holds one tile at a time, so
+// every tile below a waiting one is held by a running workgroup or is published already.
+inline void ordered_set_piece_shift(void *state, uint32_t ps)
+{
+    if (state) static_cast<OrderedOut *>(state)->force_piece_shift = ps;
+}
+inline void ordered_set_max_grid(void *state, uint32_t grid)
+{
+    if (state) static_cast<OrderedOut *>(state)->force_max_grid = grid;
+}
+// ... bmx_exp_last_launch: {piece shift, workgroups, tiles} of the session's last launch (zeros before the first)
+inline void ordered_last_launch(const void *state, uint64_t out3[3])
+{
+    const OrderedOut *oo = static_cast<const OrderedOut *>(state);
+    out3[0] = oo ? oo->last_piece_shift : 0;
+    out3[1] = oo ? oo->last_grid : 0;
+    out3[2] = oo ? oo->last_tiles : 0;
+}
+#endif
 
 } // namespace bmx

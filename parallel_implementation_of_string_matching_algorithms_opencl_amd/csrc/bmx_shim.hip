@@ -599,7 +599,32 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "align_ws_kib") ctx->align_ws_kib = value;
     else if (k == "ordered_seq" && value >= 0) {
         for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+    } else if (k == "tile_piece_shift" && (value == 0 || (value >= 6 && value <= 12))) {
+        // the dictionary's tile is 2^(value - 6) rounds of 8 KiB and at most 256 KiB: a context with a dictionary session
+        // takes no 12
+        if ((uint32_t)value > bmx::ORDERED_DICT_MAX_PIECE_SHIFT && ctx->dict) return BMX_ERR_ARG;
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
+    } else if (k == "tile_max_grid" && value >= 0) {
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
     } else return BMX_ERR_ARG;
+    return BMX_OK;
+}
+
+// libbmx_exp.so only: what the last launch of one ordered-output session ran with (tests assert the geometry they forced)
+int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
+{
+    if (!ctx || !session || !out3) return BMX_ERR_ARG;
+    const std::string k(session);
+    const void *state = nullptr;
+    if (k == "approx") state = ctx->approx;
+    else if (k == "approx_long") state = ctx->approx_long;
+    else if (k == "classes") state = ctx->classes;
+    else if (k == "hamming") state = ctx->hamming;
+    else if (k == "gaps") state = ctx->gaps;
+    else if (k == "regex") state = ctx->regex;
+    else if (k == "dict") state = ctx->dict;
+    else return BMX_ERR_ARG;
+    bmx::ordered_last_launch(state, out3);
     return BMX_OK;
 }
 

@@ -212,7 +212,10 @@ int tile_launch(TileState *st, const char *where, K kernel, int slot, int num_cu
         bpc = std::max(1, std::min(bpc, 8));
     }
     const uint64_t resident = (uint64_t)num_cu * (uint64_t)bpc * TILE_BLOCK;
-    const uint32_t ps = piece(resident);
+    uint32_t ps = piece(resident);
+#ifdef BMX_EXPERIMENTS
+    if (st->oo.force_piece_shift) ps = st->oo.force_piece_shift; // libbmx_exp.so's knob "tile_piece_shift"
+#endif
     const uint32_t tile_shift = ps + 8; // TILE_BLOCK lanes of 2^ps ends
     const uint64_t addr = reinterpret_cast<uint64_t>(d_text);
     a.text16 = reinterpret_cast<const uint8_t *>(addr & ~15ull);
@@ -228,7 +231,11 @@ int tile_launch(TileState *st, const char *where, K kernel, int slot, int num_cu
 
     int rc = st->oo.begin(where, stream, a, err, errlen);
     if (rc != BMX_OK) return rc;
-    const uint64_t grid = std::min<uint64_t>(a.n_tiles, resident / TILE_BLOCK);
+    uint64_t grid = std::min<uint64_t>(a.n_tiles, resident / TILE_BLOCK);
+#ifdef BMX_EXPERIMENTS
+    if (st->oo.force_max_grid) grid = std::min<uint64_t>(grid, st->oo.force_max_grid); // ... "tile_max_grid"
+    st->oo.last_piece_shift = ps, st->oo.last_grid = grid, st->oo.last_tiles = a.n_tiles; // (bmx_exp_last_launch)
+#endif
     hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(TILE_BLOCK), 0, stream, a, x...);
     return st->oo.finish(where, grid, a.n_tiles, stream, capacity, n_matches, err, errlen);
 }

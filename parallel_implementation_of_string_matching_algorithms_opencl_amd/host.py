@@ -275,6 +275,7 @@ class BmxError(RuntimeError):
 # entry points only libbmx_exp.so exports
 EXP_SYMBOLS = [
     ("bmx_exp_set_knob", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    ("bmx_exp_last_launch", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]),
     ("bmx_probe_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.POINTER(C.c_float), C.c_void_p]),
     ("bmx_exp_ed_stamps", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -510,8 +511,15 @@ class Context:
 
     def set_knob(self, name: str, value: int):
         """libbmx_exp.so only (bmx_exp_set_knob): max_grid, no_dense, no_text_sample, multi_no_qgram, ed_lag, ed_group, ed_step_x,
-        ed_stamp_block, sa_flags."""
+        ed_stamp_block, sa_flags, index_no_dir, align_ws_kib, ordered_seq, tile_piece_shift, tile_max_grid (include/bmx_exp.h)."""
         self._chk(self._L.bmx_exp_set_knob(self._h, name.encode(), int(value)), "bmx_exp_set_knob")
+
+    def last_launch(self, session: str) -> Tuple[int, int, int]:
+        """libbmx_exp.so only (bmx_exp_last_launch): (piece shift, workgroups, tiles) of the last launch of the session
+        "approx", "approx_long", "classes", "hamming", "gaps", "regex" or "dict"."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self._L.bmx_exp_last_launch(self._h, session.encode(), out), "bmx_exp_last_launch")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def ed_stamps(self):
         """libbmx_exp.so only (bmx_exp_ed_stamps): cycle counts of one band of the last edit distance (ed variants 11, 12, 13), the

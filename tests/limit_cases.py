@@ -1,5 +1,6 @@
-"""Test helper: inputs for the thresholds of the approximate and the dictionary search (tests/test_gpu_search_limits.py),
-built in numpy alone.  tests/test_limit_cases_cpu.py proves every per-tile count claimed here with the oracles, so the GPU
+"""Test helper: inputs for the thresholds of the approximate and the dictionary search (tests/test_gpu_search_limits.py)
+and for every search over the tile frame at a chosen piece size and grid (tests/test_gpu_tile_geometry.py; below, from
+`Search` on), built in numpy alone.  tests/test_limit_cases_cpu.py proves every per-tile count claimed here with the oracles, so the GPU
 tests may rely on "this tile holds 2049 hits" without a GPU having said so.
 
 Both kernels order their output tile by tile.  A tile parks its hits in an LDS pool of 2048 entries (TILE_STAGE,
@@ -18,8 +19,14 @@ occurrence touches two of them, and the text's hits are the units' hits.
 from dataclasses import dataclass, field
 from typing import List, Sequence, Tuple
 
+import zlib
+
 import numpy as np
 
+import classes_oracle as co
+import gaps_oracle as go
+import hamming_oracle as ho
+import regex_oracle as ro
 from approx_oracle import approx_ends
 from dict_oracle import dict_matches
 
@@ -74,6 +81,8 @@ class TileCase:
     pat: bytes = b""                 # approximate search
     k: int = 0
     patterns: List[bytes] = field(default_factory=list)  # dictionary search
+    search: object = None            # a Search (tile frame at a chosen piece size)
+    ps: int = 0                      # ... and its piece shift: tile == 256 << ps
 
     def prefix(self, t: int) -> int:
         return int(sum(self.counts[:t]))
@@ -232,6 +241,285 @@ def dict_tile_cases(only: str = None):
         for li, counts in enumerate(dict_count_lists(variant)):
             for first in OFFSETS:
                 yield dict_tile_case(counts, variant, first, name=f"{variant} list {li} offset {first}")
+
+
+# ---- the searches over the tile frame at a chosen piece size and grid ---------------------------------------------------
+#
+# tests/test_gpu_tile_geometry.py forces the geometry of a launch through libbmx_exp.so's knobs "tile_piece_shift" and
+# "tile_max_grid": a tile is 256 << ps ends for a ps the production rule can give the pattern (Search.floor .. Search.cap),
+# and `grid` workgroups share the tiles.  A hit is counted in the tile of its END, whatever the search reports: the class
+# and the k-mismatch search report the start, end - (m - 1).
+
+@dataclass
+class Search:
+    """One search over the tile frame with its oracle.  kind: "classes", "approx_classes", "hamming", "gaps", "regex",
+    "approx" or "approx_long"; letters: the bytes a run is made of."""
+    kind: str
+    name: str
+    member: np.ndarray = None    # classes [m, 256] (classes, approx_classes, hamming, gaps)
+    k: int = 0                   # edits / mismatches
+    must: int = 0                # hamming
+    optional: int = 0            # gaps
+    rx: object = None            # regex: regex_oracle.Rx
+    pat: bytes = b""             # approx, approx_long
+    letters: bytes = b"ab"
+
+    @property
+    def m(self) -> int:
+        return self.rx.m if self.kind == "regex" else len(self.pat) if self.pat else len(self.member)
+
+    @property
+    def reach(self) -> int:
+        """No match is longer; two plants this far apart share no match, and the rule's floor is ceil_log2(4 reach)."""
+        if self.kind == "regex":
+            return self.rx.max_len
+        return self.m + (self.k if self.kind in ("approx", "approx_long", "approx_classes") else 0)
+
+    @property
+    def min_len(self) -> int:
+        """The shortest run of `letters` that holds a hit."""
+        if self.kind == "regex":
+            return self.rx.min_len
+        if self.kind == "gaps":
+            return self.m - bin(self.optional).count("1")
+        return self.m - self.k
+
+    @property
+    def floor(self) -> int:
+        """The smallest piece shift the production rule gives this pattern (bmx_internal_*_piece_shift)."""
+        return max(6, min(ceil_log2(4 * self.reach), self.cap))
+
+    @property
+    def cap(self) -> int:
+        return 12 if self.kind == "approx_long" else 11
+
+    @property
+    def report(self) -> int:
+        """reported position = end - report"""
+        return self.m - 1 if self.kind in ("classes", "hamming") else 0
+
+    def ends(self, text: bytes):
+        """(ends int64 ascending, distances int64 or None) by the search's own oracle."""
+        if self.kind == "classes":
+            return co.class_starts(text, self.member) + (self.m - 1), None
+        if self.kind == "approx_classes":
+            return co.class_approx_ends(text, self.member, self.k)
+        if self.kind == "hamming":
+            p, d = ho.hamming_starts(text, self.member, self.k, self.must)
+            return p + (self.m - 1), d
+        if self.kind == "gaps":
+            return go.gap_ends(text, self.member, self.optional), None
+        if self.kind == "regex":
+            return ro.ends_numpy(text, self.rx), None
+        return approx_ends(text, self.pat, self.k)
+
+    def run(self, length: int) -> bytes:
+        """`length` bytes of the search's letters (random among them, the same for every call)."""
+        rng = np.random.default_rng(zlib.crc32(self.name.encode()) + length)
+        return np.frombuffer(self.letters, np.uint8)[rng.integers(0, len(self.letters), length)].tobytes()
+
+    def unit(self, data: bytes) -> Unit:
+        """The hits of `data` between `reach` background bytes on either side, as ends relative to its first byte."""
+        pad = self.reach
+        bg = background(2 * pad, 0xB6).tobytes()
+        e, _ = self.ends(bg[:pad] + data + bg[pad:])
+        return Unit(data, e - pad)
+
+    def run_unit(self, hits: int) -> Unit:
+        """A run that holds `hits` hits at adjacent ends, or a few more where edits reach past its last byte."""
+        u = self.unit(self.run(self.min_len - 1 + hits))
+        assert hits <= u.count <= hits + self.k and np.all(np.diff(u.rel) == 1), (self.name, hits, u.count)
+        return u
+
+
+def _gaps(name, expr):
+    member, optional = go.parse(expr)
+    return Search("gaps", name, member=member, optional=optional)
+
+
+# Every kernel slot of the frame.  The Shift-And family matches runs of the letters a and b (the k-mismatch search: of
+# a alone, with position 0 in `must`, so that a run of L bytes holds L - (m - k) + 1 hits and its last k have the
+# distances 1..k); a run one byte longer holds one hit more, so a unit has any wanted count and a dense tile hits at
+# adjacent ends.  The gapped and the regex patterns have 1 to 3 ends per shortest plant.
+SEARCHES = {x.name: x for x in (
+    Search("approx", "approx32", pat=b"ab", k=1),
+    Search("approx", "approx64", pat=_DISTINCT33, k=1),
+    Search("approx_long", "approx_long2", pat=bytes(range(0x30, 0x30 + 65)), k=1),
+    Search("classes", "classes32", member=co.parse("[ab]" * 5)),
+    Search("classes", "classes64", member=co.parse("[ab]" * 64)),
+    Search("approx_classes", "approx_classes", member=co.parse("[aA][bB][cC][dD][eE][fF]"), k=1),
+    _gaps("gaps32", "[ab][cd]?[ab]{1,3}"),
+    _gaps("gaps64", "[ab]{30}[cd]?[ab]{1,3}"),
+    Search("hamming", "hamming32x2", member=co.singletons(b"a" * 8), k=2, must=1, letters=b"a"),
+    Search("hamming", "hamming32x4", member=co.singletons(b"a" * 12), k=6, must=1, letters=b"a"),
+    Search("hamming", "hamming64x2", member=co.singletons(b"a" * 40), k=3, must=1, letters=b"a"),
+    Search("hamming", "hamming64x4", member=co.singletons(b"a" * 40), k=9, must=1, letters=b"a"),
+    Search("regex", "regex32", rx=ro.parse("[ab][ab][ab]?")),
+    Search("regex", "regex64", rx=ro.parse("[ab]{33}[ab]?")),
+    Search("regex", "regex32nl", rx=ro.parse("([ab]|c[ab])[ab]{1,2}")),
+    Search("regex", "regex64nl", rx=ro.parse("([ab]|c[ab])[ab]{30}[ab]{1,2}")),
+)}
+# the long approximate search and the run search at k = 1 for the large pieces: runs of one letter
+SEARCHES["approx_run"] = Search("approx", "approx_run", pat=b"a" * 40, k=2, letters=b"a")
+SEARCHES["approx_long_run"] = Search("approx_long", "approx_long_run", pat=b"a" * 65, k=1, letters=b"a")
+
+GRIDS = (1, 2, 3)
+SEQUENCE_BOTH_WAYS = SEQUENCE + SEQUENCE[::-1]  # 14 tiles: dense then sparse and sparse then dense in every workgroup
+
+
+def tiles_per_workgroup_at_least(n_tiles: int, grid: int) -> int:
+    """Tiles go to the workgroups one ticket at a time, so how they spread is the scheduler's; but `grid` workgroups
+    that take n_tiles tiles between them leave one with at least the mean, rounded up."""
+    assert n_tiles >= 1 and grid >= 1
+    return -(-n_tiles // grid)
+
+
+def search_units(s: Search) -> List[Unit]:
+    """The units of a search's tile cases: for the distinct-byte approximate patterns the edited copies (1 or 3 ends
+    each), else runs of 1, 2, 3, 64 and 700 hits."""
+    if s.kind in ("approx", "approx_long", "approx_classes") and len(set(s.pat or b"abcdef")) > 2:
+        pat = s.pat or b"abcdef"
+        return [s.unit(p) for p in edited_copies(pat, s.k)]
+    if s.name == "approx32":
+        return [s.unit(p) for p in (b"ab", b"a", b"b")]
+    return [s.run_unit(c) for c in (1, 2, 3, 64, 700)]
+
+
+def geometry_counts(s: Search) -> List[int]:
+    """The run sparse / dense / sparse / full / dense / empty / one below, then backwards: 14 tiles, or as many of them
+    as 1 MiB holds at the search's floor (the long approximate search: 8 tiles of 128 KiB)."""
+    return SEQUENCE_BOTH_WAYS[:min(len(SEQUENCE_BOTH_WAYS), MAX_TILE_TEXT // (256 << s.floor))]
+
+
+def search_tile_case(s: Search, hits_per_tile: Sequence[int], ps: int, first: int = 0) -> TileCase:
+    """Tile t of 256 << ps ends (aligned coordinates) holds exactly hits_per_tile[t] hits of the search."""
+    assert s.floor <= ps <= s.cap, (s.name, ps)
+    units = search_units(s)
+    assert any(u.count == 1 for u in units), s.name
+    tile = 256 << ps
+    text = _lay_out(units, hits_per_tile, tile, first, s.reach, seed=zlib.crc32(s.name.encode()) % 100000 + first)
+    return TileCase(f"{s.name} ps={ps} offset {first}", text, tile, first, list(hits_per_tile), search=s, ps=ps)
+
+
+def geometry_cases(only: str = None):
+    """Every TileCase of the several-tiles-per-workgroup tests: each search at its floor, rebuilt for each pointer
+    offset."""
+    for name, s in SEARCHES.items():
+        if name.endswith("_run") or (only is not None and name != only):
+            continue
+        for first in OFFSETS:
+            yield search_tile_case(s, geometry_counts(s), s.floor, first)
+
+
+def dict_geometry_case(first: int) -> TileCase:
+    """The dictionary search's: two patterns at each planted position, 14 tiles of 8 KiB."""
+    return dict_tile_case(SEQUENCE_BOTH_WAYS, "two", first, name=f"dict two both ways offset {first}")
+
+
+def capacity_inside_second_dense(case: TileCase) -> int:
+    """A capacity that ends in the middle of the second tile with more hits than the pool."""
+    dense = [t for t, c in enumerate(case.counts) if c > STAGE]
+    assert len(dense) >= 2
+    return case.prefix(dense[1]) + case.counts[dense[1]] // 2
+
+
+# ---- large pieces: hits on tile and lane boundaries, a full lane, a dense tile beside an empty one ---------------------------
+
+BOUNDARY_OFFSET = 11
+# (search, piece shift): each of the four Shift-And searches at 9, 10 and 11, its kernel slots taking turns (only the
+# 32-bit k-mismatch slots run at all three or at two of them: an oracle run per case is the cost), m = 64 also at its floor
+# 8; the two approximate searches at their caps
+BOUNDARY_CASES = (
+    ("classes64", 8), ("classes64", 9), ("classes32", 10), ("classes64", 11),
+    ("gaps32", 9), ("gaps64", 10), ("gaps32", 11),
+    ("hamming64x4", 9), ("hamming32x2", 9), ("hamming32x2", 10), ("hamming32x4", 10), ("hamming64x2", 11), ("hamming32x4", 11),
+    ("regex32nl", 9), ("regex64", 10), ("regex32", 11), ("regex64nl", 11),
+    ("approx_run", 11), ("approx_long_run", 12),
+)
+BOUNDARY_LANES = (37, 101, 255)
+FULL_LANE = 100    # of tile 1, which is walked twice: its hits are written by the second walk
+PARKED_LANE = 150  # of tile 0, which stays below the pool: its hits go through the parked words, ordinal and all
+
+
+def parked_lane_hits(ps: int) -> int:
+    """Hits of the parked lane: the whole lane, or as many as leave tile 0 (with its boundary hits) inside the pool."""
+    return min(1 << ps, STAGE - 48)
+
+
+@dataclass
+class BoundaryCase:
+    name: str
+    search: Search
+    ps: int
+    first: int
+    text: bytes
+    spans: List[Tuple[int, int]]  # (start, length) of every plant, ascending
+
+    @property
+    def tile(self) -> int:
+        return 256 << self.ps
+
+    def windows(self) -> List[Tuple[int, int]]:
+        """The plants with `reach` bytes on either side, merged: every hit lies in one (plan_plants' argument)."""
+        out = []
+        for a, ln in self.spans:
+            lo, hi = max(a - self.search.reach, 0), min(a + ln + self.search.reach, len(self.text))
+            if out and lo <= out[-1][0] + out[-1][1]:
+                out[-1] = (out[-1][0], max(hi, out[-1][0] + out[-1][1]) - out[-1][0])
+            else:
+                out.append((lo, hi - lo))
+        return out
+
+    def ends_by_windows(self):
+        """The oracle on every window; the same lists as on the whole text (test_limit_cases_cpu.py), at a cost that
+        goes with the plants."""
+        es, ds = [], []
+        for lo, ln in self.windows():
+            e, d = self.search.ends(self.text[lo:lo + ln])
+            es.append(e + lo)
+            ds.append(d)
+        return np.concatenate(es), (None if ds[0] is None else np.concatenate(ds))
+
+
+def boundary_case(name: str, ps: int, first: int = BOUNDARY_OFFSET) -> BoundaryCase:
+    """Three tiles of 256 << ps ends and 5 bytes.  In aligned coordinates, with T the tile and P = 1 << ps the piece:
+    hits on both sides of the lane boundaries 37 P, 101 P and 255 P of tile 0 and of the tile boundary T; in lane 150 of
+    tile 0 a hit at each of the first min(P, 2000) ends, in a tile of 2048 hits or fewer, so that ordinals up to that
+    number less one are parked (and read back beside the distance, of which the run's last k hits have their own); in tile 1 nine
+    hits in the middle of every lane (more than the pool in all: the tile is walked twice) and every end of lane 100, with
+    the last end of lane 99 and the first of lane 101; the last ends of tile 1 up to 2 T - 1; tile 2 empty; the first end of
+    tile 3 and every one up to the text's last byte."""
+    s = SEARCHES[name]
+    assert s.floor <= ps <= s.cap, (name, ps)
+    T, P = 256 << ps, 1 << ps
+    n = 3 * T + 5
+    text = background(n, zlib.crc32(name.encode()) % 100000 + ps)
+    spans = []
+
+    def put(u: Unit, which: int, aligned_end: int):
+        """Unit u with its hit number `which` at the aligned end."""
+        at = aligned_end - first - int(u.rel[which])
+        assert at >= 0 and at + len(u.data) <= n and (not spans or at >= spans[-1][0] + spans[-1][1] + 1), (name, aligned_end)
+        text[at:at + len(u.data)] = np.frombuffer(u.data, np.uint8)
+        spans.append((at, len(u.data)))
+
+    three, nine, full = s.run_unit(3), s.run_unit(9), s.run_unit(P + 2)
+    for lane in BOUNDARY_LANES[:2]:
+        put(three, 1, lane * P)
+    put(s.run_unit(parked_lane_hits(ps) - s.k), 0, PARKED_LANE * P)  # (edits reach up to k ends past a run)
+    put(three, 1, BOUNDARY_LANES[2] * P)
+    put(three, 1, T)
+    for lane in range(2, 254):
+        if lane == FULL_LANE:
+            put(full, 0, T + lane * P - 1)
+        elif abs(lane - FULL_LANE) > 1:
+            put(nine, 0, T + lane * P + P // 2 - 4)
+    put(three, -1, 2 * T - 1)
+    # 5 + first hits, from the aligned end 3 T to the text's last byte (a k-mismatch window has to lie inside the text)
+    tail = s.run((s.m if s.kind == "hamming" else s.min_len) - 1 + 5 + first)
+    text[n - len(tail):] = np.frombuffer(tail, np.uint8)
+    spans.append((n - len(tail), len(tail)))
+    return BoundaryCase(f"{name} ps={ps}", s, ps, first, text.tobytes(), spans)
 
 
 # ---- planted texts for the large runs ---------------------------------------------------------------------------------

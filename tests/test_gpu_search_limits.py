@@ -9,8 +9,10 @@ around the plants, outside which no hit can lie (tests/limit_cases.py: plan_plan
 cases are proved on the CPU by tests/test_limit_cases_cpu.py; each case is REBUILT for every pointer offset, so the
 counts hold in the aligned coordinates the kernels cut their tiles in.
 
-Not covered: the wrap of the status words' 22-bit tag.  It takes 2^22 calls on one context; the host code clears the
-status array at the wrap (bmx_approx.hip, bmx_dict.hip) and nothing here loops four million calls to see it.
+The wrap of the status words' 22-bit tag takes 2^22 calls on one context; tests/test_gpu_streams.py
+(test_tag_wrap_clears_the_status_words) reaches it with libbmx_exp.so's knob "ordered_seq" for every search with ordered
+output.  The same searches with several tiles per workgroup, at large pieces and -- the class-pattern, gapped, k-mismatch
+and regular-expression search -- past 4 GiB: tests/test_gpu_tile_geometry.py.
 """
 import ctypes as C
 

@@ -430,8 +430,10 @@ def test_two_host_threads_each_with_its_own_context_and_streams(ctx, port):
 
 # ---- the wrap of the status words' 22-bit tag ----------------------------------------------------------------------------
 
-WRAP_N = 128 << 10  # 8 tiles of the approximate and the class-pattern search, 16 of the dictionary search
+WRAP_N = 128 << 10  # 8 tiles of the approximate, class-pattern, k-mismatch, gapped and regex search, 16 of the dictionary search
 WRAP_PATTERN = b"ACG"
+WRAP_LONG = b"GATTACAGATTACCAGGATCCAAGCTTGCATGCCTGCAGGTCGACTCTAGAGGATCCCCGGGTAC"  # 65 bytes: tiles of 128 KiB
+assert len(WRAP_LONG) == 65 and WRAP_LONG[30:31] == b"T"
 
 
 def _wrap_search(c, kind):
@@ -464,6 +466,59 @@ def _wrap_search(c, kind):
             assert total == want.size > 1000
             same(pos, want, "starts")
         return search, lambda: None
+    if kind == "approx_long":
+        def search(text):
+            # four tiles: the text four times over with copies of the pattern, half of them with byte 30 replaced, at
+            # places drawn from the text itself, so that the tiles' counts and prefixes differ from search to search
+            import zlib
+
+            rng = np.random.default_rng(zlib.crc32(text))
+            big = bytearray(text * 4)
+            at = int(rng.integers(0, 300))
+            while at + len(WRAP_LONG) <= len(big):
+                big[at:at + len(WRAP_LONG)] = WRAP_LONG if rng.integers(0, 2) else WRAP_LONG[:30] + b"A" + WRAP_LONG[31:]
+                at += len(WRAP_LONG) + int(rng.integers(100, 600))
+            big = bytes(big)
+            want_e, want_d = approx_ends(big, WRAP_LONG, 1)
+            e, d, total = c.search_approx_device(dev(big), WRAP_LONG, 1, capacity=len(text))
+            assert total == want_e.size > 1000 and set(want_d.tolist()) == {0, 1}
+            same(e, want_e, "ends"), same(d, want_d, "distances")
+        return search, lambda: None
+    if kind == "hamming":
+        import hamming_oracle as ho
+
+        member = co.singletons(WRAP_PATTERN)
+
+        def search(text):
+            want_s, want_d = ho.hamming_starts(text, member, 1)
+            pos, d, total = c.search_hamming_device(dev(text), co.pack(member), 1, out=torch.empty(len(text), dtype=torch.int64, device=f"cuda:{c.device}"))
+            assert total == want_s.size > 1000
+            same(pos, want_s, "starts"), same(d, want_d, "distances")
+        return search, lambda: None
+    if kind == "gaps":
+        import gaps_oracle as go
+
+        member, optional = go.parse("AC?G")
+
+        def search(text):
+            want = go.gap_ends(text, member, optional)
+            e, total = c.search_gaps_device(dev(text), (co.pack(member), optional), capacity=len(text))
+            assert total == want.size > 1000
+            same(e, want, "ends")
+        return search, lambda: None
+    if kind == "regex":
+        import regex_oracle as ro
+        from test_gpu_regex import _struct
+
+        rx = ro.parse("A(C|GT)G")
+
+        def search(text):
+            want = ro.ends_numpy(text, rx)
+            e, total = c.search_regex_device(dev(text), _struct(rx), capacity=len(text))
+            assert total == want.size > 1000
+            same(e, want, "ends")
+        return search, lambda: None
+    assert kind == "dict"
     d = c.dictionary([WRAP_PATTERN])
 
     def search(text):
@@ -474,7 +529,7 @@ def _wrap_search(c, kind):
     return search, d.close
 
 
-@pytest.mark.parametrize("kind", ["approx", "classes", "dict"])
+@pytest.mark.parametrize("kind", ["approx", "classes", "dict", "approx_long", "hamming", "gaps", "regex"])
 def test_tag_wrap_clears_the_status_words(exp_ctx, kind):
     """The status words of an ordered-output session carry the call's sequence number mod 2^22 and are cleared only when
     that tag wraps.  The first search leaves a tag-1 prefix in every word; "ordered_seq" then puts the next call on the

@@ -1,11 +1,15 @@
-"""CPU suite for tests/limit_cases.py: every per-tile count the GPU threshold tests (tests/test_gpu_search_limits.py) rely
-on, proved with the oracles alone -- the text of each case is searched by approx_ends / dict_matches, the hits are binned
-by tile in aligned coordinates and compared with what the case claims.  No call into the library is made here."""
+"""CPU suite for tests/limit_cases.py: every per-tile count the GPU threshold tests (tests/test_gpu_search_limits.py,
+tests/test_gpu_tile_geometry.py) rely on, proved with the oracles alone -- the text of each case is searched by the
+search's own oracle (approx_ends, dict_matches, class_starts, class_approx_ends, hamming_starts, gap_ends, ends_numpy), the
+hits are binned by tile in aligned coordinates and compared with what the case claims.  No call into the library is made
+here."""
 import numpy as np
+import pytest
 
 import limit_cases as lc
 from approx_oracle import approx_ends
 from dict_oracle import DictIndex, dict_matches
+import regex_oracle as ro
 
 
 def test_count_lists_cross_the_pool_on_both_sides():
@@ -102,3 +106,94 @@ def test_plan_plants_windows_hold_every_hit():
         wi.append(b)
     p, i = dict_matches(text, pats)
     assert np.array_equal(np.concatenate(wp), p) and np.array_equal(np.concatenate(wi), i)
+
+
+# ---- the tile frame at a chosen piece size and grid (tests/test_gpu_tile_geometry.py) ----------------------------------
+
+def test_searches_cover_every_kernel_slot_and_stay_inside_the_rule():
+    kinds = {}
+    for name, s in lc.SEARCHES.items():
+        kinds.setdefault(s.kind, []).append(s)
+        assert 6 <= s.floor <= s.cap and 1 <= s.min_len <= s.reach, name
+        if s.member is not None:
+            assert not s.member[:, 0x80:].any(), name  # no class holds a background byte
+    assert {s.m > 32 for s in kinds["classes"]} == {False, True} == {s.m > 32 for s in kinds["gaps"]}
+    assert {s.m > 32 for s in kinds["approx"]} == {False, True} and 64 < lc.SEARCHES["approx_long2"].m <= 128
+    assert {(s.m > 32, s.k > 3) for s in kinds["hamming"]} == {(w, f) for w in (False, True) for f in (False, True)}
+    assert {(s.rx.m > 32, ro.split(s.rx)[1] != 0) for s in kinds["regex"]} == {(w, f) for w in (False, True) for f in (False, True)}
+    assert [lc.SEARCHES[n].floor for n in ("classes32", "classes64", "gaps64", "hamming64x4", "regex64nl", "approx64", "approx_long2")] == \
+        [6, 8, 8, 8, 8, 8, 9]
+
+
+def test_tiles_per_workgroup():
+    assert [lc.tiles_per_workgroup_at_least(14, g) for g in (1, 2, 3, 14, 15)] == [14, 7, 5, 1, 1]
+    assert lc.tiles_per_workgroup_at_least(8, 3) == 3 and lc.tiles_per_workgroup_at_least(4, 2) == 2
+
+
+@pytest.mark.parametrize("name", [n for n in lc.SEARCHES if not n.endswith("_run")])
+def test_geometry_cases_hold_their_counts(name):
+    """Per-tile counts of the several-tiles-per-workgroup cases, at the three pointer offsets; every grid the GPU test
+    uses leaves some workgroup at least two tiles, a grid of one all of them."""
+    s = lc.SEARCHES[name]
+    ran = 0
+    for case in lc.geometry_cases(name):
+        n_tiles = len(case.counts)
+        assert case.tile == 256 << s.floor and 8 <= n_tiles <= 16 and n_tiles * case.tile <= lc.MAX_TILE_TEXT
+        assert len(case.text) == n_tiles * case.tile - case.first
+        assert case.counts == lc.SEQUENCE_BOTH_WAYS[:n_tiles] and set(lc.SEQUENCE) <= set(case.counts)
+        ends, dists = s.ends(case.text)
+        assert lc.bin_by_tile(ends, case.tile, case.first, n_tiles) == case.counts, case.name
+        if s.k:
+            assert len(set(dists.tolist())) > 1, case.name
+        for grid in lc.GRIDS:
+            least = lc.tiles_per_workgroup_at_least(n_tiles, grid)
+            assert least >= 2 and (grid != 1 or least == n_tiles)
+        cut = lc.capacity_inside_second_dense(case)
+        dense = [t for t, c in enumerate(case.counts) if c > lc.STAGE][1]
+        assert case.prefix(dense) < cut < case.prefix(dense + 1)
+        ran += 1
+    assert ran == len(lc.OFFSETS)
+
+
+def test_dict_geometry_cases_hold_their_counts():
+    for first in lc.OFFSETS:
+        case = lc.dict_geometry_case(first)
+        pos, _ = dict_matches(case.text, case.patterns)
+        assert lc.bin_by_tile(pos, case.tile, first, len(case.counts)) == case.counts == lc.SEQUENCE_BOTH_WAYS
+        assert all(lc.tiles_per_workgroup_at_least(len(case.counts), g) >= 2 for g in lc.GRIDS)
+
+
+@pytest.mark.parametrize("name,ps", lc.BOUNDARY_CASES)
+def test_boundary_cases_have_what_they_claim(name, ps):
+    """The large-piece cases: a piece shift the rule can give the pattern, hits on both sides of the lane and tile
+    boundaries, a lane whose every end is a hit (its ordinals reach 2^ps - 1), a tile of more hits than the pool with hits
+    in (nearly) every lane, an empty tile behind it, hits up to the text's last byte; for the k-mismatch search three
+    distances or more in the dense tile.  The windows around the plants give the whole text's list."""
+    case = lc.boundary_case(name, ps)
+    s, T, P, first = case.search, case.tile, 1 << ps, case.first
+    assert s.floor <= ps <= s.cap and len(case.text) == 3 * T + 5 and first == lc.BOUNDARY_OFFSET
+    ends, dists = case.ends_by_windows()
+    if ps <= 11:  # (the whole text where its oracle takes a second or so: all but the 3 MiB of the long approximate search)
+        whole_e, whole_d = s.ends(case.text)
+        assert np.array_equal(whole_e, ends) and (dists is None or np.array_equal(whole_d, dists))
+    aligned = ends + first
+    have = set(aligned.tolist())
+    for lane in lc.BOUNDARY_LANES:
+        assert {lane * P - 1, lane * P} <= have, (case.name, lane)
+    assert {T - 1, T, 2 * T - 1, 3 * T, len(case.text) - 1 + first} <= have and 2 * T not in have
+    lane0 = T + lc.FULL_LANE * P
+    assert set(range(lane0 - 1, lane0 + P + 1)) <= have
+    counts = lc.bin_by_tile(ends, T, first, 4)
+    # a tile that is parked (no more hits than the pool) has a lane with min(P, 2000) hits: the ordinals the read-out of
+    # the pool takes from the parked words go up to that; for the searches with distances the lane has two or more
+    lane_p = lc.PARKED_LANE * P
+    in_lane = (aligned >= lane_p) & (aligned < lane_p + P)
+    assert counts[0] <= lc.STAGE and lc.parked_lane_hits(ps) - s.k <= int(in_lane.sum()) <= P, (counts[0], int(in_lane.sum()))
+    if s.k:
+        assert np.unique(dists[in_lane]).size >= 2, case.name
+    assert lc.parked_lane_hits(ps) - s.k + 10 <= counts[0] <= lc.STAGE and counts[1] > lc.STAGE + P and counts[2] == 0 and counts[3] == 5 + first, counts
+    in_dense = (aligned >= T) & (aligned < 2 * T)
+    assert np.unique((aligned[in_dense] - T) // P).size >= 250
+    if s.kind == "hamming":
+        assert np.unique(dists[in_dense]).size >= 3
+    assert lc.tiles_per_workgroup_at_least(4, 2) >= 2
