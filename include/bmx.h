@@ -661,6 +661,66 @@ int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64
 int bmx_search_regex_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re, uint32_t flags,
                            uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
 
+/* ---- regular-expression search with unbounded repetition: * + {a,} ------------------------- */
+
+/* ERROR.*timeout, [0-9]+\.[0-9]+, ATG([ACGT]{3})+(TAA|TAG|TGA), [A-Za-z_][A-Za-z0-9_]*\(: the same automaton struct and
+ * the same per-byte step as above, with a cycle in follow[].  A cycle means there is no longest match, so no fixed
+ * warm-up makes a lane exact; the entries below are exact all the same, for every valid automaton and every text
+ * (csrc/bmx_regex_star_kernel.h).  The star-free entries above are unchanged and still refuse a cycle.
+ *
+ * max_len of an automaton with a cycle among the positions a match can use. */
+#define BMX_REGEX_UNBOUNDED (-1)
+/* bmx_compile_regex's grammar with  quant := '?' | '*' | '+' | '{a}' | '{a,}' | '{a,b}'.  X+ adds follow[l] |= first(X)
+ * for every l in last(X) (the Glushkov rule, for a group as for an element); X* is (X+)?; X{a,} is a - 1 copies of X
+ * followed by X+ (a == 0: X*).  Every other rule and every other error of bmx_compile_regex holds: an expression that
+ * matches the empty string (a*, (ab)*) is an error, so are more than 64 positions, nesting deeper than 32 and a
+ * quantifier right after another one; *out is untouched on error; the text in bmx_last_error begins with
+ * "bmx_compile_regex_star: ".  For an expression without * + {a,} the output equals bmx_compile_regex's byte for byte.
+ * min_len is the shortest match; max_len the longest, or BMX_REGEX_UNBOUNDED.  Pure host code, no GPU. */
+int bmx_compile_regex_star(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out);
+/* Valid for the entries below: 1 <= m <= BMX_MAX_REGEX_POSITIONS; first and last non-zero; no bit at or above m in first,
+ * last or any follow[i].  follow[i] may hold ANY bit below m, i itself included.  min_len and max_len are not read.
+ *
+ * Semantics: every END j in [lead, n) at which some text[s..j] with 0 <= s OF THE VIEW matches, each end once, ascending,
+ * reported as base_offset + j.  The list is exact: there is no approximation and no "unresolved" error.  An automaton
+ * without a cycle gives bmx_search_regex_device's list.
+ * Sharding: a match may begin anywhere, so there is no halo that makes shards' lists concatenate to the whole text's.
+ * What a caller CAN conclude from a shard whose view begins at text byte v: every reported end is an end of the whole
+ * text's list, and the ends it misses are those whose every match begins before v.  With a view that begins at text
+ * byte 0 and lead = the shard's first end, the shard's list is that slice of the whole text's list (at the price of
+ * reading the text in front).  A state carried from one shard into the next is not offered.
+ * Capacity, *n_matches, the argument errors before any HIP call (with ctx = NULL too), n < 2^40, any alignment and
+ * BMX_ERR_HIP in place of a partly ordered list: as for bmx_search_regex_device.
+ * One kernel launch in the common case: a lane warms up in front of its first end from the empty and from the full set
+ * of positions at once and is exact if the two meet.  If some lane's do not, the call repeats the search exactly with
+ * three more passes over the text (the state at every piece boundary as a linear map, a sweep over those, the search
+ * from the swept states); its workspace, 40 bytes per piece plus 8 per stored column, is allocated on the first such
+ * call and kept with the context.  The call returns after synchronising `stream`. */
+int bmx_search_regex_star_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                 const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_regex_star_device with lead = 0, download). */
+int bmx_search_regex_star(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                          uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms) of the last bmx_search_regex_star_device on ctx: the one launch, or, where the call repeated the
+ * search, from the first launch to the end of the last; < 0 if none. */
+float bmx_last_regex_star_ms(bmx_ctx *ctx);
+/* The START of a match of at most `window` bytes for every end of a device-resident list: the largest such start (the
+ * shortest match), with BMX_REGEX_LONGEST the smallest one that is still within `window` bytes of the end and within the
+ * view.  1 <= window <= BMX_MAX_REGEX_STAR_WINDOW.  An end at which no match that short ends gets UINT64_MAX and is not
+ * an error: a longer one may exist.  The bound is explicit because with .* the longest start is the text's first byte.
+ * Errors as for bmx_regex_starts_device, with the validity rule above and window out of range among the argument
+ * errors; an end outside the view raises the status word, and so does an end without a match within `window` if the
+ * automaton has no cycle and its longest match fits the window, so that no longer one can exist (BMX_ERR_ARG, outputs
+ * unspecified).  Where some end has no match a second small kernel writes the sentinels. */
+#define BMX_MAX_REGEX_STAR_WINDOW 65536u
+int bmx_regex_star_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                 const uint64_t *d_ends, uint64_t count, uint32_t window, uint32_t flags, uint64_t *d_starts,
+                                 void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_regex_star_device, bmx_regex_star_starts_device, download. */
+int bmx_search_regex_star_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                uint32_t window, uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity,
+                                uint64_t *n_matches);
+
 /* ---- match spans of the approximate search: (start, end, distance) ------------------------- */
 
 /* The approximate search reports ENDS, and every qualifying end, so one occurrence shows as a run of adjacent ends.

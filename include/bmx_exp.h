@@ -26,8 +26,13 @@ extern "C" {
  * per tile, at most 5 (256 KiB), so a context that has a dictionary session accepts at most 11.  tile_max_grid: 0 = off, else
  * the most workgroups a call starts; tiles are handed out in ascending order and every started workgroup is resident, so
  * any grid finishes.  Values are not checked against the pattern: a piece below ceil_log2(4 m) is a geometry the product
- * never runs).  BMX_ERR_ARG for an unknown name, a negative "ordered_seq" or "tile_max_grid" and a "tile_piece_shift"
- * outside those ranges. */
+ * never runs).  The regex search with unbounded repetition takes the two geometry knobs too, and has three of its own, kept
+ * in the context so that they hold from its first call: "regex_star_force_slow" (non-zero: the exact slow path runs behind
+ * the first launch even when nothing is tainted), "regex_star_piece_shift" (0, or 4..12: log2 of the ends per lane of THAT
+ * search, in front of "tile_piece_shift"; 4 and 5 make chains of pieces that cross tiles and workgroups on texts of a few
+ * KiB) and "regex_star_warm" (0 = the rule, else the bytes of the pair warm-up, a multiple of 16 up to 65,536).
+ * BMX_ERR_ARG for an unknown name, a negative "ordered_seq" or "tile_max_grid" and a "tile_piece_shift",
+ * "regex_star_piece_shift" or "regex_star_warm" outside those ranges. */
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
 
 /* What the last launch of one ordered-output session of the context ran with: out3 = {log2 of the ends per lane (the
@@ -36,6 +41,13 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
  * "dict".  Tests assert with it that the geometry they forced ("tile_piece_shift", "tile_max_grid") is the one that ran.
  * BMX_ERR_ARG for another name. */
 int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3);
+
+/* What the last bmx_search_regex_star_device of the context did: out10 = {waves of the first launch that held a lane whose
+ * two bounds did not meet (0: the call was untainted), 1 if the slow path ran, log2 of the ends per lane, bytes of the pair
+ * warm-up, pieces and stored columns of the slow path, then microseconds of the first launch, of R1 (bounds, scan,
+ * columns), of the sweep and of R2}; zeros before the first call and for a call that launched nothing.
+ * "bmx_exp_last_launch" knows the session as "regex_star". */
+int bmx_exp_regex_star_last(bmx_ctx *ctx, uint64_t *out10);
 
 /* Read-only sweep of n bytes at d_text (16-byte aligned) with plain global loads into registers, XOR-folded: no LDS,
  * no barrier, no tiles (csrc/bmx_probe_kernel.h).  unroll = loads in flight per lane (1, 2, 4, 8, 16), nt = cache

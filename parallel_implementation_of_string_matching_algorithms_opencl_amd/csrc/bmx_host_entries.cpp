@@ -564,6 +564,53 @@ int bmx_search_regex_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const 
     return c.rc;
 }
 
+int bmx_search_regex_star(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint64_t *ends, uint64_t capacity,
+                          uint64_t *n_matches)
+{
+    if (!bmx_regex_star_args_ok(n, 0, re, ends, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_star", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_star_device(c.ctx(), d_text, n, 0, 0, re, d_ends, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(ends, d_ends, std::min(total, dev_cap) * sizeof(uint64_t), "regex matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+int bmx_search_regex_star_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint32_t window, uint32_t flags,
+                                uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_regex_star_args_ok(n, 0, re, ends, capacity) || (capacity > 0 && !starts) || (n > 0 && !text) ||
+        (flags & ~BMX_REGEX_LONGEST) || window < 1 || window > BMX_MAX_REGEX_STAR_WINDOW)
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_star_spans", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_star_device(c.ctx(), d_text, n, 0, 0, re, d_ends, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    const int src = bmx_regex_star_starts_device(c.ctx(), d_text, n, 0, re, d_ends, stored, window, flags, d_starts, nullptr);
+    if (src != BMX_OK) return src;
+    c.download(ends, d_ends, stored * sizeof(uint64_t), "regex matches");
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "regex matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
 int bmx_dict_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *const *pats, const int32_t *ms, int32_t K,
                     uint64_t *pos, uint32_t *pid, uint64_t capacity, uint64_t *n_matches)
 {

@@ -110,10 +110,27 @@ int bmx_internal_regex(void **state, int num_cu, const void *d_text, uint64_t n,
                        const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, hipStream_t stream,
                        char *err, size_t errlen);
 int bmx_internal_regex_starts(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
-                              const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, hipStream_t stream,
-                              char *err, size_t errlen);
+                              const uint64_t *d_ends, uint64_t count, uint32_t window, uint32_t flags, uint64_t *d_starts,
+                              uint64_t *bad_out, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_regex_free(void *state);
 float bmx_internal_regex_ms(const void *state);
+constexpr uint64_t BMX_REGEX_STARTS_NO_MATCH = 2; // *bad_out: some end had no match (csrc/bmx_regex_kernel.h, REGEX_BAD_START)
+// bmx_regex_star.hip.  What (libbmx_exp.so) bmx_exp_set_knob sets:
+struct bmx_regex_star_knobs {
+    int piece_shift = 0;     // 0, or log2 of the ends per lane (4..12; the shared "tile_piece_shift" begins at 6)
+    int warm = 0;            // 0, or the bytes of the pair warm-up (a multiple of 16)
+    bool force_slow = false; // the exact slow path runs behind the first launch even when nothing is tainted
+};
+int bmx_internal_regex_star(void **state, int num_cu, const bmx_regex_star_knobs *knobs, const void *d_text, uint64_t n,
+                            uint64_t lead, uint64_t base_offset, const bmx_regex *re, uint64_t *d_ends, uint64_t capacity,
+                            uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_regex_star_starts_fix(const void *d_text, uint64_t base_offset, const bmx_regex *re, const uint64_t *d_ends,
+                                       uint64_t count, uint64_t *d_starts, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_regex_star_free(void *state);
+float bmx_internal_regex_star_ms(const void *state);
+void bmx_internal_regex_star_last(const void *state, uint64_t out10[10]); // libbmx_exp.so only
+uint32_t bmx_internal_regex_star_piece_shift(uint64_t n, uint64_t resident_lanes); // log2 of the ends per lane
+uint32_t bmx_internal_regex_star_warm(uint32_t piece_shift);                       // bytes of the pair warm-up
 // bmx_ed_batch.hip
 int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
                           const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
@@ -205,6 +222,8 @@ struct bmx_ctx {
     void *hamming = nullptr; // k-mismatch search: the same again (bmx_hamming.hip)
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *regex = nullptr; // regular-expression search: the same as the gapped search's, its own (bmx_regex.hip)
+    void *regex_star = nullptr; // ... with unbounded repetition: the same, the taint words and the slow path's workspace (bmx_regex_star.hip)
+    bmx_regex_star_knobs regex_star_knobs;
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *approx_long = nullptr; // ... for patterns of more than 64 bytes: the same kind of state, its own (bmx_approx_long.hip)
     bool approx_last_long = false; // which of the two the last approximate search on this context used (bmx_last_approx_ms)
@@ -293,6 +312,20 @@ inline bool bmx_regex_starts_args_ok(uint64_t n, const bmx_regex *re, const uint
                                      const uint64_t *starts)
 {
     if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
+    return count == 0 || (ends && starts);
+}
+
+// ... with unbounded repetition: follow[] may hold any bit below m
+inline bool bmx_regex_star_ok(const bmx_regex *re) { return re && bmx_regex_star_sets_ok(re->m, re->first, re->last, re->follow); }
+inline bool bmx_regex_star_args_ok(uint64_t n, uint64_t lead, const bmx_regex *re, const void *ends, uint64_t capacity)
+{
+    return bmx_regex_star_ok(re) && lead <= n && n < (1ull << 40) && (capacity == 0 || ends);
+}
+inline bool bmx_regex_star_starts_args_ok(uint64_t n, const bmx_regex *re, const uint64_t *ends, uint64_t count, uint32_t window,
+                                          uint32_t flags, const uint64_t *starts)
+{
+    if (!bmx_regex_star_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
+    if (window < 1 || window > BMX_MAX_REGEX_STAR_WINDOW) return false;
     return count == 0 || (ends && starts);
 }
 

@@ -52,6 +52,13 @@
 //                             expression, the elements of --classes with groups ( ), alternation | and ? {a} {a,b} on
 //                             elements and groups (bmx_compile_regex); prints what --gaps prints, `regex matches: N` in
 //                             place of `gapped matches: N`.  It goes with none of --gaps, --classes, --approx, --hamming
+//   bmx_cli --regex-star EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K]
+//           [--starts --window N [--longest]]
+//                             the same with unbounded repetition: EXPR may use * + {a,} (bmx_compile_regex_star,
+//                             bmx_search_regex_star*); a match of no fixed longest length prints `matches of A or more
+//                             bytes`.  --starts needs --window N (1..65536): the start of the shortest (--longest: the
+//                             longest) match of at most N bytes, 18446744073709551615 where there is none.  It goes with
+//                             none of --regex, --gaps, --classes, --approx, --hamming
 //   bmx_cli --approx K --spans [--best] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--max-print K]
 //                             after what --approx prints: the span of every match (bmx_search_approx_spans), the total
 //                             and one `start end dist` line per span (at most --max-print of them); --best keeps one
@@ -185,7 +192,8 @@ int main(int argc, char **argv)
     uint32_t limit = BMX_ED_NO_LIMIT, class_flags = 0;
     bool have_classes = false, have_gaps = false, gaps_starts = false, gaps_longest = false;
     std::string gaps_expr, regex_expr;
-    bool have_regex = false;
+    bool have_regex = false, regex_star = false, regex_both = false;
+    uint32_t star_window = 0;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
     std::string must_spec;
     bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false;
@@ -223,7 +231,9 @@ int main(int argc, char **argv)
         else if (a == "--max-occ") max_occ = (uint32_t)strtoul(need("--max-occ"), nullptr, 10);
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
         else if (a == "--gaps") gaps_expr = need("--gaps"), have_gaps = true;
-        else if (a == "--regex") regex_expr = need("--regex"), have_regex = true;
+        else if (a == "--regex") regex_both = have_regex, regex_expr = need("--regex"), have_regex = true;
+        else if (a == "--regex-star") regex_both = have_regex, regex_expr = need("--regex-star"), have_regex = regex_star = true;
+        else if (a == "--window") star_window = (uint32_t)strtoul(need("--window"), nullptr, 10);
         else if (a == "--prosite") class_flags |= BMX_GAPS_PROSITE;
         else if (a == "--starts") gaps_starts = true;
         else if (a == "--longest") gaps_longest = true;
@@ -282,6 +292,11 @@ int main(int argc, char **argv)
 
     if (have_regex && (have_gaps || have_classes || approx_k >= 0 || hamming_k >= 0 || (class_flags & BMX_GAPS_PROSITE))) {
         fprintf(stderr, "--regex goes with none of --gaps, --prosite, --classes, --approx, --hamming\n");
+        return 2;
+    }
+    if (regex_both || (regex_star && gaps_starts && (star_window < 1 || star_window > BMX_MAX_REGEX_STAR_WINDOW)) ||
+        (star_window != 0 && !(regex_star && gaps_starts))) {
+        fprintf(stderr, "--regex-star goes without --regex; its --starts needs --window N with 1 <= N <= 65536, and --window goes with nothing else\n");
         return 2;
     }
     if ((gaps_starts && !have_gaps && !have_regex) || ((class_flags & BMX_GAPS_PROSITE) && !have_gaps)) {
@@ -594,12 +609,17 @@ int main(int argc, char **argv)
     }
     if (have_regex) {
         bmx_regex re;
-        if (bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re) != BMX_OK) {
+        if ((regex_star ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
+                        : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
             fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
             return 1;
         }
-        printf("text %s: %llu bytes, regular expression %s: %d positions, matches of %d to %d bytes\n", text_path.c_str(),
-               (unsigned long long)n, regex_expr.c_str(), re.m, re.min_len, re.max_len);
+        if (re.max_len == BMX_REGEX_UNBOUNDED)
+            printf("text %s: %llu bytes, regular expression %s: %d positions, matches of %d or more bytes\n", text_path.c_str(),
+                   (unsigned long long)n, regex_expr.c_str(), re.m, re.min_len);
+        else
+            printf("text %s: %llu bytes, regular expression %s: %d positions, matches of %d to %d bytes\n", text_path.c_str(),
+                   (unsigned long long)n, regex_expr.c_str(), re.m, re.min_len, re.max_len);
         bmx_ctx *ctx = nullptr;
         int rc = bmx_ctx_create(device, &ctx);
         void *d_text = nullptr;
@@ -615,25 +635,32 @@ int main(int argc, char **argv)
         uint64_t hits = 0;
         for (int it = 0; it < iters; ++it) {
             auto t0 = std::chrono::steady_clock::now();
-            rc = bmx_search_regex_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr);
+            rc = regex_star ? bmx_search_regex_star_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr)
+                            : bmx_search_regex_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr);
             auto t1 = std::chrono::steady_clock::now();
             if (rc != BMX_OK) {
                 fprintf(stderr, "bmx_search_regex_device failed: %d (%s)\n", rc, bmx_last_error());
                 return 1;
             }
             total += std::chrono::duration<double>(t1 - t0).count();
-            kernel_ms += bmx_last_regex_ms(ctx);
+            kernel_ms += regex_star ? bmx_last_regex_star_ms(ctx) : bmx_last_regex_ms(ctx);
         }
         if (iters <= 0) { // no timed call has counted: a counting call
-            rc = bmx_search_regex(ctx, text.data(), n, &re, nullptr, 0, &hits);
+            rc = regex_star ? bmx_search_regex_star(ctx, text.data(), n, &re, nullptr, 0, &hits)
+                            : bmx_search_regex(ctx, text.data(), n, &re, nullptr, 0, &hits);
             if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) hits = 0;
         }
         // the list itself through the host-buffer entry points: (text, automaton) -> ends, or -> (starts, ends)
         std::vector<uint64_t> ends(hits ? hits : 1), starts(gaps_starts && hits ? hits : 1);
         uint64_t got = 0;
-        rc = gaps_starts ? bmx_search_regex_spans(ctx, text.data(), n, &re, gaps_longest ? BMX_REGEX_LONGEST : 0u, starts.data(),
-                                                  ends.data(), hits, &got)
-                         : bmx_search_regex(ctx, text.data(), n, &re, ends.data(), hits, &got);
+        const uint32_t span_flags = gaps_longest ? BMX_REGEX_LONGEST : 0u;
+        if (regex_star)
+            rc = gaps_starts ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, star_window, span_flags, starts.data(), ends.data(),
+                                                           hits, &got)
+                             : bmx_search_regex_star(ctx, text.data(), n, &re, ends.data(), hits, &got);
+        else
+            rc = gaps_starts ? bmx_search_regex_spans(ctx, text.data(), n, &re, span_flags, starts.data(), ends.data(), hits, &got)
+                             : bmx_search_regex(ctx, text.data(), n, &re, ends.data(), hits, &got);
         if (rc != BMX_OK || got != hits) {
             fprintf(stderr, "%s failed: %d (%s), %llu hits against %llu\n", gaps_starts ? "bmx_search_regex_spans" : "bmx_search_regex",
                     rc, bmx_last_error(), (unsigned long long)got, (unsigned long long)hits);

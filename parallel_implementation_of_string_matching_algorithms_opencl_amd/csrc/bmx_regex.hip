@@ -90,10 +90,13 @@ int bmx_internal_regex(void **state_v, int num_cu, const void *d_text, uint64_t 
                             n_matches, stream, err, errlen, k);
 }
 
-// count >= 1: d_starts[i] for d_ends[i].
+// count >= 1: d_starts[i] for d_ends[i].  window == 0: the automaton is acyclic and a lane walks max_len bytes; else it
+// walks `window` bytes of an automaton that may have a cycle (the transposed follow[] goes into the same tables).
+// bad_out != NULL: the status bits go there and only an end outside the view is an error here (the caller decides about
+// the ends without a match).
 int bmx_internal_regex_starts(void **state_v, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
-                              const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, hipStream_t stream,
-                              char *err, size_t errlen)
+                              const uint64_t *d_ends, uint64_t count, uint32_t window, uint32_t flags, uint64_t *d_starts,
+                              uint64_t *bad_out, hipStream_t stream, char *err, size_t errlen)
 {
     if (!*state_v) *state_v = new RegexState();
     RegexState *st = static_cast<RegexState *>(*state_v);
@@ -108,7 +111,8 @@ int bmx_internal_regex_starts(void **state_v, const void *d_text, uint64_t n, ui
 
     const int32_t m = re->m;
     int32_t min_len = 0, max_len = 0;
-    bmx_regex_lengths(m, re->first, re->last, re->follow, &min_len, &max_len);
+    if (window == 0) bmx_regex_lengths(m, re->first, re->last, re->follow, &min_len, &max_len);
+    else max_len = (int32_t)window;
     const uint64_t addr = reinterpret_cast<uint64_t>(d_text);
     bmx::RegexStartsArgs a;
     std::memset(&a, 0, sizeof a);
@@ -141,7 +145,11 @@ int bmx_internal_regex_starts(void **state_v, const void *d_text, uint64_t n, ui
     BMX_HIP(WHERE_STARTS, hipMemcpyAsync(st->h_ws, st->d_ws, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     BMX_HIP(WHERE_STARTS, hipStreamSynchronize(stream));
 
-    const uint64_t bad = st->h_ws[0];
+    uint64_t bad = st->h_ws[0];
+    if (bad_out) {
+        *bad_out = bad;
+        bad &= bmx::REGEX_BAD_END;
+    }
     if (bad != 0) {
         snprintf(err, errlen, "bmx_regex_starts_device: %s%s", bad & bmx::REGEX_BAD_END ? "an end outside the view; " : "",
                  bad & bmx::REGEX_BAD_START ? "an end at which no match of this expression ends; " : "");

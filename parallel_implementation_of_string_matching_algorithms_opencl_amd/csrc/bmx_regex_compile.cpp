@@ -1,9 +1,11 @@
-// bmx_regex_compile.cpp -- bmx_compile_regex (include/bmx.h): a star-free regular expression to its Glushkov (position)
-// automaton, struct bmx_regex (pure C++, no GPU).  No counterpart in the reference.
+// bmx_regex_compile.cpp -- bmx_compile_regex and bmx_compile_regex_star (include/bmx.h): a regular expression to its
+// Glushkov (position) automaton, struct bmx_regex (pure C++, no GPU).  No counterpart in the reference.  One parser
+// behind a switch (Compiler::star): the first entry takes the star-free expressions, the second also * + {a,}.
 //
 //     alt    := concat ('|' concat)*        an empty alternative is allowed: (a|) is a?
 //     concat := repeat*
 //     repeat := atom quant?                 quant := '?' | '{a}' | '{a,b}'   decimal, 0 <= a <= b, b >= 1
+//                                           (star: also '*' | '+' | '{a,}')
 //     atom   := element | '(' alt ')'
 // An element is exactly one element of bmx_compile_classes; this file only finds where it ends and hands it over, as
 // bmx_gaps_compile.cpp does, so the grammars cannot drift apart.  The expression is first parsed into a tree (every
@@ -13,6 +15,8 @@
 // last positions of what stands left to the first positions of what stands right of it, and nothing else makes a link.
 // A subtree without an element is the empty string whatever its counts say, so it is never expanded more than once and
 // every other expansion step makes a position: the work is bounded by the 64 positions, not by the counts.
+// With the switch: X+ links every last position of X to the first positions of X (the one rule that makes follow[] point
+// downward or at itself), X* is (X+)? and X{a,} is a - 1 copies of X followed by X+ (a == 0: X*).
 #include "bmx.h"
 
 #include <cstdio>
@@ -27,6 +31,7 @@ namespace {
 
 constexpr uint64_t NPOS = ~0ull;
 constexpr int MAX_DEPTH = 32;
+constexpr int UNBOUNDED = -1;
 
 // Behind a backslash at e[p - 1]: one past the escape, or NPOS where the expression ends first.
 uint64_t skip_escape(const uint8_t *e, uint64_t len, uint64_t p)
@@ -71,7 +76,7 @@ bool number(const uint8_t *e, uint64_t len, uint64_t &at, int &value)
 enum Kind { ELEM, CAT, ALT, REP };
 struct Node {
     Kind kind;
-    int a = 1, b = 1;          // REP
+    int a = 1, b = 1;          // REP (b == UNBOUNDED: no upper count)
     bool has_element = false;  // some element stands below it
     std::vector<int> kids;     // CAT, ALT: any number; REP: one
     uint8_t cls[BMX_CLASS_BYTES]; // ELEM
@@ -86,6 +91,7 @@ struct Compiler {
     const uint8_t *e;
     uint64_t len;
     uint32_t flags;
+    bool star = false; // the grammar of bmx_compile_regex_star
     uint64_t at = 0;
     const char *why = nullptr;
     std::vector<Node> nodes;
@@ -110,7 +116,12 @@ struct Compiler {
         b = a;
         if (at < len && e[at] == ',') {
             ++at;
-            if (at < len && e[at] == '}') return fail("{a,}: unbounded repetition is out of scope");
+            if (at < len && e[at] == '}') {
+                if (!star) return fail("{a,}: unbounded repetition is out of scope");
+                ++at;
+                b = UNBOUNDED;
+                return true;
+            }
             if (!number(e, len, at, b)) return fail("a malformed {...}");
         }
         if (at >= len || e[at] != '}') return fail("a malformed or unterminated {...}");
@@ -122,8 +133,8 @@ struct Compiler {
     bool parse_repeat(int depth, int &out)
     {
         const unsigned c = e[at];
-        if (c == '*' || c == '+') return fail("* and +: unbounded repetition is out of scope");
-        if (c == '?' || c == '{') return fail("a quantifier with nothing in front of it");
+        if (!star && (c == '*' || c == '+')) return fail("* and +: unbounded repetition is out of scope");
+        if (c == '?' || c == '{' || c == '*' || c == '+') return fail("a quantifier with nothing in front of it");
         int atom;
         if (c == '(') {
             if (depth + 1 > MAX_DEPTH) return fail("groups nested deeper than 32");
@@ -152,12 +163,16 @@ struct Compiler {
             ++at;
             if (!counts(a, b)) return false;
         } else if (e[at] == '*' || e[at] == '+') {
-            return fail("* and +: unbounded repetition is out of scope");
+            if (!star) return fail("* and +: unbounded repetition is out of scope");
+            a = e[at] == '*' ? 0 : 1;
+            b = UNBOUNDED;
+            ++at;
         } else {
             return true;
         }
         if (at < len && (e[at] == '?' || e[at] == '{')) return fail("a quantifier right after another quantifier");
-        if (at < len && (e[at] == '*' || e[at] == '+')) return fail("* and +: unbounded repetition is out of scope");
+        if (at < len && (e[at] == '*' || e[at] == '+'))
+            return fail(star ? "a quantifier right after another quantifier" : "* and +: unbounded repetition is out of scope");
         out = make(REP);
         nodes[out].a = a, nodes[out].b = b;
         nodes[out].has_element = nodes[atom].has_element;
@@ -227,6 +242,19 @@ struct Compiler {
             return true;
         }
         case REP:
+            if (nodes[id].b == UNBOUNDED) { // X{a,}: max(a, 1) copies, the last one looped; a == 0 makes that one optional
+                const int copies = nodes[id].a > 1 ? nodes[id].a : 1;
+                for (int i = 0; i < copies; ++i) {
+                    Frag g;
+                    if (!expand(nodes[id].kids[0], g)) return false;
+                    if (i == copies - 1) {
+                        for (uint64_t l = g.last; l != 0; l &= l - 1) re.follow[__builtin_ctzll(l)] |= g.first;
+                        if (nodes[id].a == 0) g.nullable = true;
+                    }
+                    out = cat(out, g, re.follow);
+                }
+                return true;
+            }
             for (int i = 0; i < nodes[id].b; ++i) { // (every copy makes a position, so 65 copies at the most)
                 Frag g;
                 if (!expand(nodes[id].kids[0], g)) return false;
@@ -241,21 +269,26 @@ struct Compiler {
 
 } // namespace
 
-extern "C" int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+namespace {
+
+int compile(const char *where, bool star, const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
 {
     char text[160];
     if (!expr || !out) {
-        bmx_internal_set_error("bmx_compile_regex: a NULL argument");
+        snprintf(text, sizeof text, "%s: a NULL argument", where);
+        bmx_internal_set_error(text);
         return BMX_ERR_ARG;
     }
     if (flags & ~(BMX_CLASS_ICASE | BMX_CLASS_IUPAC)) {
-        bmx_internal_set_error("bmx_compile_regex: an unknown flag bit");
+        snprintf(text, sizeof text, "%s: an unknown flag bit", where);
+        bmx_internal_set_error(text);
         return BMX_ERR_ARG;
     }
     Compiler c;
     c.e = reinterpret_cast<const uint8_t *>(expr);
     c.len = expr_len;
     c.flags = flags;
+    c.star = star;
     std::memset(&c.re, 0, sizeof c.re);
     int root = 0;
     Frag f = {true, 0, 0};
@@ -265,13 +298,26 @@ extern "C" int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t f
     if (ok && c.re.m == 0) ok = c.fail("zero positions");
     if (ok && f.nullable) ok = c.fail("the expression matches the empty string");
     if (!ok) {
-        snprintf(text, sizeof text, "bmx_compile_regex: %s", c.why ? c.why : "a bad expression");
+        snprintf(text, sizeof text, "%s: %s", where, c.why ? c.why : "a bad expression");
         bmx_internal_set_error(text);
         return BMX_ERR_ARG;
     }
     c.re.first = f.first;
     c.re.last = f.last;
-    bmx_regex_lengths(c.re.m, c.re.first, c.re.last, c.re.follow, &c.re.min_len, &c.re.max_len);
+    if (star) bmx_regex_star_lengths(c.re.m, c.re.first, c.re.last, c.re.follow, &c.re.min_len, &c.re.max_len, nullptr);
+    else bmx_regex_lengths(c.re.m, c.re.first, c.re.last, c.re.follow, &c.re.min_len, &c.re.max_len);
     *out = c.re;
     return BMX_OK;
+}
+
+} // namespace
+
+extern "C" int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+{
+    return compile("bmx_compile_regex", false, expr, expr_len, flags, out);
+}
+
+extern "C" int bmx_compile_regex_star(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+{
+    return compile("bmx_compile_regex_star", true, expr, expr_len, flags, out);
 }

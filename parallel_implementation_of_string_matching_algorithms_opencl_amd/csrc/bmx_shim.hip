@@ -109,6 +109,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_hamming_free(ctx->hamming);
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_regex_free(ctx->regex);
+    bmx_internal_regex_star_free(ctx->regex_star);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
@@ -332,8 +333,43 @@ int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64
     if (count == 0) return BMX_OK;
     if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
     HIPCHK(hipSetDevice(ctx->device));
-    return bmx_internal_regex_starts(&ctx->regex, d_text, n, base_offset, re, d_ends, count, flags, d_starts,
+    return bmx_internal_regex_starts(&ctx->regex, d_text, n, base_offset, re, d_ends, count, 0, flags, d_starts, nullptr,
                                      (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+// ---- regular-expression search with unbounded repetition (bmx_regex_star.hip; bmx_compile_regex_star is
+// bmx_regex_compile.cpp) ------
+int bmx_search_regex_star_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                 const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_regex_star_args_ok(n, lead, re, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_star(&ctx->regex_star, ctx->num_cu, &ctx->regex_star_knobs, d_text, n, lead, base_offset, re, d_ends,
+                                   capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_star_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_star_ms(ctx->regex_star) : -1.0f; }
+
+int bmx_regex_star_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                 const uint64_t *d_ends, uint64_t count, uint32_t window, uint32_t flags, uint64_t *d_starts,
+                                 void *stream_v)
+{
+    if (!bmx_regex_star_starts_args_ok(n, re, d_ends, count, window, flags, d_starts)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    uint64_t bad = 0;
+    const int rc = bmx_internal_regex_starts(&ctx->regex, d_text, n, base_offset, re, d_ends, count, window, flags, d_starts, &bad,
+                                             (hipStream_t)stream_v, g_err, sizeof g_err);
+    if (rc != BMX_OK || !(bad & BMX_REGEX_STARTS_NO_MATCH)) return rc;
+    int32_t min_len = 0, max_len = 0;
+    bmx_regex_star_lengths(re->m, re->first, re->last, re->follow, &min_len, &max_len, nullptr);
+    if (max_len != BMX_REGEX_UNBOUNDED && (max_len <= 0 || (uint32_t)max_len <= window)) { // no longer match can exist
+        set_err("bmx_regex_star_starts_device: an end at which no match of this expression ends");
+        return BMX_ERR_ARG;
+    }
+    return bmx_internal_regex_star_starts_fix(d_text, base_offset, re, d_ends, count, d_starts, (hipStream_t)stream_v, g_err,
+                                              sizeof g_err);
 }
 
 // ---- match spans of the approximate search (bmx_spans.hip) --------------------------------------
@@ -597,15 +633,18 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "align_ws_kib") ctx->align_ws_kib = value;
+    else if (k == "regex_star_force_slow") ctx->regex_star_knobs.force_slow = value != 0;
+    else if (k == "regex_star_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_star_knobs.piece_shift = value;
+    else if (k == "regex_star_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_knobs.warm = value;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_star, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else if (k == "tile_piece_shift" && (value == 0 || (value >= 6 && value <= 12))) {
         // the dictionary's tile is 2^(value - 6) rounds of 8 KiB and at most 256 KiB: a context with a dictionary session
         // takes no 12
         if ((uint32_t)value > bmx::ORDERED_DICT_MAX_PIECE_SHIFT && ctx->dict) return BMX_ERR_ARG;
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_star, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
     } else if (k == "tile_max_grid" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_star, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }
@@ -622,9 +661,18 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "hamming") state = ctx->hamming;
     else if (k == "gaps") state = ctx->gaps;
     else if (k == "regex") state = ctx->regex;
+    else if (k == "regex_star") state = ctx->regex_star;
     else if (k == "dict") state = ctx->dict;
     else return BMX_ERR_ARG;
     bmx::ordered_last_launch(state, out3);
+    return BMX_OK;
+}
+
+// libbmx_exp.so only: what the last bmx_search_regex_star_device of the context did (include/bmx_exp.h)
+int bmx_exp_regex_star_last(bmx_ctx *ctx, uint64_t *out10)
+{
+    if (!ctx || !out10) return BMX_ERR_ARG;
+    bmx_internal_regex_star_last(ctx->regex_star, out10);
     return BMX_OK;
 }
 

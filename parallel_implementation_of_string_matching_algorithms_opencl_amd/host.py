@@ -47,6 +47,8 @@ GAPS_PROSITE = 4  # a flag of compile_gaps, beside CLASS_ICASE and CLASS_IUPAC
 GAPS_LONGEST = 1  # a flag of gaps_starts_device
 MAX_REGEX_POSITIONS = 64
 REGEX_LONGEST = 1  # a flag of regex_starts_device
+REGEX_UNBOUNDED = -1  # Regex.max_len of an automaton with a cycle (compile_regex_star)
+MAX_REGEX_STAR_WINDOW = 65536  # regex_star_starts_device
 SPANS_BEST = 1
 SPANS_BLOCK = 256  # list entries per workgroup of the starts kernel (csrc/bmx_spans_kernel.h)
 SPANS_TILE = 2048  # list entries per workgroup of the selection
@@ -187,6 +189,15 @@ SYMBOLS = [
     ("bmx_last_regex_ms", C.c_float, [C.c_void_p]),
     ("bmx_regex_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_compile_regex_star", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("bmx_search_regex_star_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_regex_star", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_star_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_regex_star_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_star_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("bmx_approx_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           _u64p, C.c_void_p]),
@@ -276,6 +287,7 @@ class BmxError(RuntimeError):
 EXP_SYMBOLS = [
     ("bmx_exp_set_knob", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("bmx_exp_last_launch", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    ("bmx_exp_regex_star_last", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("bmx_probe_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.POINTER(C.c_float), C.c_void_p]),
     ("bmx_exp_ed_stamps", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -477,10 +489,19 @@ def compile_regex(expr, flags: int = 0) -> Regex:
     return out
 
 
-def _regex(expr_or_regex, flags: int = 0) -> Regex:
+def compile_regex_star(expr, flags: int = 0) -> Regex:
+    """A regular expression with unbounded repetition (bmx_compile_regex_star: compile_regex's grammar and ``*``, ``+``,
+    ``{a,}``) -> its position automaton; ``max_len`` is REGEX_UNBOUNDED where it has a cycle."""
+    e = _pat_bytes(expr)
+    out = Regex()
+    _check(lib().bmx_compile_regex_star(e, len(e), int(flags), C.byref(out)), "bmx_compile_regex_star")
+    return out
+
+
+def _regex(expr_or_regex, flags: int = 0, star: bool = False) -> Regex:
     """A Regex from an expression (str / bytes) or such a structure, passed through."""
     if isinstance(expr_or_regex, (str, bytes, bytearray)):
-        return compile_regex(expr_or_regex, flags)
+        return compile_regex_star(expr_or_regex, flags) if star else compile_regex(expr_or_regex, flags)
     if not isinstance(expr_or_regex, Regex):
         raise ValueError("expr_or_regex: an expression or a Regex")
     return expr_or_regex
@@ -516,10 +537,17 @@ class Context:
 
     def last_launch(self, session: str) -> Tuple[int, int, int]:
         """libbmx_exp.so only (bmx_exp_last_launch): (piece shift, workgroups, tiles) of the last launch of the session
-        "approx", "approx_long", "classes", "hamming", "gaps", "regex" or "dict"."""
+        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_star" or "dict"."""
         out = (C.c_uint64 * 3)()
         self._chk(self._L.bmx_exp_last_launch(self._h, session.encode(), out), "bmx_exp_last_launch")
         return int(out[0]), int(out[1]), int(out[2])
+
+    def regex_star_last(self) -> dict:
+        """libbmx_exp.so only (bmx_exp_regex_star_last): what the last search_regex_star_device did."""
+        out = (C.c_uint64 * 10)()
+        self._chk(self._L.bmx_exp_regex_star_last(self._h, out), "bmx_exp_regex_star_last")
+        keys = ["tainted", "slow", "piece_shift", "warm", "pieces", "columns", "first_us", "r1_us", "sweep_us", "r2_us"]
+        return dict(zip(keys, [int(v) for v in out]))
 
     def ed_stamps(self):
         """libbmx_exp.so only (bmx_exp_ed_stamps): cycle counts of one band of the last edit distance (ed variants 11, 12, 13), the
@@ -1183,6 +1211,92 @@ class Context:
 
     def last_regex_ms(self) -> float:
         return float(self._L.bmx_last_regex_ms(self._h))
+
+    # -- regular-expression search with unbounded repetition: * + {a,} -------------------
+    def search_regex_star_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
+                                 base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
+        """Every end j in [lead, n) of the view ``d_text[0:n)`` at which a match that begins inside the view ends, ascending
+        and exact, reported as base_offset + j (bmx_search_regex_star_device).  ``expr_or_regex``: an expression for
+        compile_regex_star(expr, flags) or a Regex, which may have a cycle.  The other arguments and the return value
+        (ends view, true total) are those of search_regex_device."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags, star=True)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_regex_star_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset, C.byref(re_),
+                                                  C.c_void_p(out.data_ptr()), cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_regex_star_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def search_regex_star(self, text, expr_or_regex, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex_star): ascending ends, uint64.  With ``capacity`` given and too small, raises
+        BmxError(ERR_CAPACITY); without it the list is always complete."""
+        re_ = _regex(expr_or_regex, flags, star=True)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_star(self._h, tptr, n, C.byref(re_), C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_star")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_regex_star_spans(self, text, expr_or_regex, flags: int = 0, longest: bool = False,
+                                window: int = 4096) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_regex_star_spans): (starts uint64, ends uint64), ends ascending; each start that of the
+        shortest match of at most ``window`` bytes for its end, with ``longest`` of the longest such, and UINT64_MAX where
+        no match that short ends there."""
+        re_ = _regex(expr_or_regex, flags, star=True)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_star_spans(self._h, tptr, n, C.byref(re_), int(window), REGEX_LONGEST if longest else 0,
+                                                     C.c_void_p(starts.ctypes.data), C.c_void_p(ends.ctypes.data), cap,
+                                                     C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_star_spans")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy()
+
+    def regex_star_starts_device(self, d_text, expr_or_regex, ends, *, window: int = 4096, longest: bool = False, flags: int = 0,
+                                 n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """A start for every end of ``ends`` (int64 / uint64 CUDA tensor, as search_regex_star_device returns it for the same
+        view, expression and base_offset) among the matches of at most ``window`` bytes: the largest one, or with
+        ``longest`` the smallest; all ones (-1 as int64) where there is none (bmx_regex_star_starts_device)."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags, star=True)
+        count = ends.numel()
+        if n is None:
+            n = d_text.numel()
+        if ends.element_size() != 8:
+            raise ValueError("ends: 8-byte entries")
+        starts = torch.empty(max(count, 1), dtype=ends.dtype, device=ends.device)
+        s = stream if stream is not None else torch.cuda.current_stream(ends.device)
+        rc = self._L.bmx_regex_star_starts_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                                  C.c_void_p(ends.data_ptr()), count, int(window), REGEX_LONGEST if longest else 0,
+                                                  C.c_void_p(starts.data_ptr()), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_star_starts_device")
+        return starts[:count]
+
+    def last_regex_star_ms(self) -> float:
+        return float(self._L.bmx_last_regex_star_ms(self._h))
 
     # -- match spans of the approximate search: (start, end, distance) -------------------
     def approx_spans_device(self, d_text, pattern_or_classes, k: int, ends, dist=None, *, best: bool = False, flags: int = 0,
@@ -2070,6 +2184,14 @@ def search_regex(text, expr, flags: int = 0, spans: bool = False, longest: bool 
     (starts, ends), each start the largest one for its end (the shortest match) or with ``longest`` the smallest."""
     ctx = default_context()
     return ctx.search_regex_spans(text, expr, flags, longest) if spans else ctx.search_regex(text, expr, flags)
+
+
+def search_regex_star(text, expr, flags: int = 0, spans: bool = False, longest: bool = False, window: int = 4096):
+    """(text, regular expression with * + {a,}) -> ascending ends of every match (bmx_search_regex_star); with ``spans`` the
+    pair (starts, ends), each start that of the shortest match of at most ``window`` bytes for its end, or with
+    ``longest`` of the longest such (UINT64_MAX where there is none)."""
+    ctx = default_context()
+    return ctx.search_regex_star_spans(text, expr, flags, longest, window) if spans else ctx.search_regex_star(text, expr, flags)
 
 
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
