@@ -3,6 +3,9 @@ and for every search over the tile frame at a chosen piece size and grid (tests/
 `Search` on), built in numpy alone.  tests/test_limit_cases_cpu.py proves every per-tile count claimed here with the oracles, so the GPU
 tests may rely on "this tile holds 2049 hits" without a GPU having said so.
 
+The star search (bmx_search_regex_star_device) has its searches (STAR_SEARCHES: a family that never taints a call and one
+that always does), its warm-up edge cases and its 4 GiB patterns here too, for tests/test_gpu_regex_star_limits.py.
+
 Both kernels order their output tile by tile.  A tile parks its hits in an LDS pool of 2048 entries (TILE_STAGE,
 DICT_STAGE) and walks itself a second time when it has more.  Tiles are counted from the text pointer rounded down to
 16 bytes: view byte i has the aligned coordinate i + first, first = pointer mod 16.  For a text of 1 MiB or less
@@ -27,6 +30,7 @@ import classes_oracle as co
 import gaps_oracle as go
 import hamming_oracle as ho
 import regex_oracle as ro
+import regex_star_oracle as so
 from approx_oracle import approx_ends
 from dict_oracle import dict_matches
 
@@ -88,10 +92,10 @@ class TileCase:
         return int(sum(self.counts[:t]))
 
 
-def _lay_out(units: Sequence[Unit], counts: Sequence[int], tile: int, first: int, gap: int, seed: int) -> bytes:
+def _lay_out(units: Sequence[Unit], counts: Sequence[int], tile: int, first: int, gap: int, seed: int, keep: int = 0) -> bytes:
     """A text of len(counts) tiles (aligned coordinates; the view starts at `first`) in which tile t holds exactly
     counts[t] hits, all from `units`.  In a tile the first unit sits as far left and the last as far right as the tile
-    allows (hits at both edges), the others evenly between."""
+    allows (hits at both edges), the others evenly between.  The first `keep` bytes of the view stay free (background)."""
     n = len(counts) * tile - first
     assert 0 < n <= MAX_TILE_TEXT, n
     text = background(n, seed)
@@ -101,7 +105,7 @@ def _lay_out(units: Sequence[Unit], counts: Sequence[int], tile: int, first: int
             by_count.setdefault(u.count, []).append(u)
     sizes = sorted(by_count, reverse=True)
     turn = 0
-    cursor = 0
+    cursor = keep
     for t, need in enumerate(counts):
         lo, hi = max(t * tile - first, 0), (t + 1) * tile - first
         chosen = []
@@ -253,32 +257,40 @@ def dict_tile_cases(only: str = None):
 @dataclass
 class Search:
     """One search over the tile frame with its oracle.  kind: "classes", "approx_classes", "hamming", "gaps", "regex",
-    "approx" or "approx_long"; letters: the bytes a run is made of."""
+    "regex_star", "approx" or "approx_long"; letters: the bytes a run is made of."""
     kind: str
     name: str
     member: np.ndarray = None    # classes [m, 256] (classes, approx_classes, hamming, gaps)
     k: int = 0                   # edits / mismatches
     must: int = 0                # hamming
     optional: int = 0            # gaps
-    rx: object = None            # regex: regex_oracle.Rx
+    rx: object = None            # regex: regex_oracle.Rx; regex_star: regex_star_oracle.StarRx
     pat: bytes = b""             # approx, approx_long
     letters: bytes = b"ab"
+    prefix: bytes = b""          # regex_star, natural taint: what the text begins with (and every hit's match)
 
     @property
     def m(self) -> int:
-        return self.rx.m if self.kind == "regex" else len(self.pat) if self.pat else len(self.member)
+        return self.rx.m if self.kind in ("regex", "regex_star") else len(self.pat) if self.pat else len(self.member)
 
     @property
     def reach(self) -> int:
-        """No match is longer; two plants this far apart share no match, and the rule's floor is ceil_log2(4 reach)."""
+        """No match is longer; two plants this far apart share no match, and the rule's floor is ceil_log2(4 reach).  The
+        star search has no longest match: a background byte between two plants empties the state of a pattern none of
+        whose classes holds one (test_limit_cases_cpu.py), and behind `prefix` it leaves the state the prefix alone
+        leaves, so 1."""
+        if self.kind == "regex_star":
+            return 1
         if self.kind == "regex":
             return self.rx.max_len
         return self.m + (self.k if self.kind in ("approx", "approx_long", "approx_classes") else 0)
 
     @property
     def min_len(self) -> int:
-        """The shortest run of `letters` that holds a hit."""
-        if self.kind == "regex":
+        """The shortest run of `letters` that holds a hit (behind `prefix`: every letter is one)."""
+        if self.kind == "regex_star" and self.prefix:
+            return 1
+        if self.kind in ("regex", "regex_star"):
             return self.rx.min_len
         if self.kind == "gaps":
             return self.m - bin(self.optional).count("1")
@@ -287,11 +299,13 @@ class Search:
     @property
     def floor(self) -> int:
         """The smallest piece shift the production rule gives this pattern (bmx_internal_*_piece_shift)."""
+        if self.kind == "regex_star":
+            return 8  # (MIN_PIECE_SHIFT of bmx_regex_star.hip: the pattern has no say)
         return max(6, min(ceil_log2(4 * self.reach), self.cap))
 
     @property
     def cap(self) -> int:
-        return 12 if self.kind == "approx_long" else 11
+        return 12 if self.kind in ("approx_long", "regex_star") else 11
 
     @property
     def report(self) -> int:
@@ -311,7 +325,15 @@ class Search:
             return go.gap_ends(text, self.member, self.optional), None
         if self.kind == "regex":
             return ro.ends_numpy(text, self.rx), None
+        if self.kind == "regex_star":
+            return so.ends_numpy(text, self.rx), None
         return approx_ends(text, self.pat, self.k)
+
+    def ends_behind_prefix(self, stretch: bytes):
+        """The hits of a stretch of text that lies somewhere behind `prefix` (relative to the stretch): the oracle on
+        the prefix and the stretch.  Without a prefix: ends()."""
+        e, d = self.ends(self.prefix + stretch)
+        return e - len(self.prefix), d
 
     def run(self, length: int) -> bytes:
         """`length` bytes of the search's letters (random among them, the same for every call)."""
@@ -322,7 +344,7 @@ class Search:
         """The hits of `data` between `reach` background bytes on either side, as ends relative to its first byte."""
         pad = self.reach
         bg = background(2 * pad, 0xB6).tobytes()
-        e, _ = self.ends(bg[:pad] + data + bg[pad:])
+        e, _ = self.ends_behind_prefix(bg[:pad] + data + bg[pad:])
         return Unit(data, e - pad)
 
     def run_unit(self, hits: int) -> Unit:
@@ -363,6 +385,37 @@ SEARCHES = {x.name: x for x in (
 SEARCHES["approx_run"] = Search("approx", "approx_run", pat=b"a" * 40, k=2, letters=b"a")
 SEARCHES["approx_long_run"] = Search("approx_long", "approx_long_run", pat=b"a" * 65, k=1, letters=b"a")
 
+# The star search (bmx_search_regex_star_device; tests/test_gpu_regex_star_limits.py), every kernel slot of its two
+# launches.  First family: no lane's pair warm-up ends with two different bounds (a letter or two, or one background
+# byte, and they meet), so the call is the first launch alone unless the slow path is forced: a cycle at 32 and at 64
+# bits (a self-loop is an irregular position), and the star-free automata of regex32, regex64 and regex32nl through the
+# star entry (the slots without irregular positions, and the acyclic irregular one).  Second family, NATURAL TAINT:
+# c.*[ab] on a text whose byte 0 is the only c.  The upper bound holds the `.` for ever and the lower bound never has it,
+# so every lane whose warm-up does not begin at view byte 0 is tainted, the first launch reports (nearly) nothing and the
+# slow path's columns carry the `.` from piece to piece; the hits are the letters, as for [ab]+.
+STAR_SEARCHES = {x.name: x for x in (
+    Search("regex_star", "star32", rx=so.parse("[ab]+")),
+    Search("regex_star", "star64", rx=so.parse("(q{33})?[ab]+")),
+    Search("regex_star", "star_regex32", rx=so.parse("[ab][ab][ab]?")),
+    Search("regex_star", "star_regex64", rx=so.parse("[ab]{33}[ab]?")),
+    Search("regex_star", "star_regex32nl", rx=so.parse("([ab]|c[ab])[ab]{1,2}")),
+    Search("regex_star", "taint32", rx=so.parse("c.*[ab]"), prefix=b"c"),
+    Search("regex_star", "taint64", rx=so.parse("(q{33})?c.*[ab]"), prefix=b"c"),
+)}
+STAR_FAST = [n for n, s in STAR_SEARCHES.items() if not s.prefix]
+STAR_TAINT = [n for n, s in STAR_SEARCHES.items() if s.prefix]
+STAR_COUNT_OFFSET = 15  # the pointer offset of the count-list cases (the geometry cases run at all of OFFSETS)
+
+
+def search_named(name: str) -> Search:
+    return SEARCHES[name] if name in SEARCHES else STAR_SEARCHES[name]
+
+
+def star_warm(ps: int) -> int:
+    """bmx_internal_regex_star_warm: a sixteenth of the piece, at least 64 bytes."""
+    return max(64, (1 << ps) >> 4)
+
+
 GRIDS = (1, 2, 3)
 SEQUENCE_BOTH_WAYS = SEQUENCE + SEQUENCE[::-1]  # 14 tiles: dense then sparse and sparse then dense in every workgroup
 
@@ -397,7 +450,8 @@ def search_tile_case(s: Search, hits_per_tile: Sequence[int], ps: int, first: in
     units = search_units(s)
     assert any(u.count == 1 for u in units), s.name
     tile = 256 << ps
-    text = _lay_out(units, hits_per_tile, tile, first, s.reach, seed=zlib.crc32(s.name.encode()) % 100000 + first)
+    text = _lay_out(units, hits_per_tile, tile, first, s.reach, seed=zlib.crc32(s.name.encode()) % 100000 + first, keep=len(s.prefix))
+    text = s.prefix + text[len(s.prefix):]
     return TileCase(f"{s.name} ps={ps} offset {first}", text, tile, first, list(hits_per_tile), search=s, ps=ps)
 
 
@@ -409,6 +463,19 @@ def geometry_cases(only: str = None):
             continue
         for first in OFFSETS:
             yield search_tile_case(s, geometry_counts(s), s.floor, first)
+
+
+def star_geometry_cases(name: str):
+    """The same fourteen tiles of 64 KiB (the star search's smallest piece) for a star search, at each pointer offset."""
+    s = STAR_SEARCHES[name]
+    for first in OFFSETS:
+        yield search_tile_case(s, SEQUENCE_BOTH_WAYS, s.floor, first)
+
+
+def star_count_case(name: str, which: int) -> TileCase:
+    """COUNT_LISTS[which] (every per-tile count 2040..2056 around the pool, 0, 1, 4096) in tiles of 64 KiB."""
+    s = STAR_SEARCHES[name]
+    return search_tile_case(s, COUNT_LISTS[which], s.floor, STAR_COUNT_OFFSET)
 
 
 def dict_geometry_case(first: int) -> TileCase:
@@ -436,6 +503,13 @@ BOUNDARY_CASES = (
     ("regex32nl", 9), ("regex64", 10), ("regex32", 11), ("regex64nl", 11),
     ("approx_run", 11), ("approx_long_run", 12),
 )
+# the star search at 9..12, its slots taking turns: first family (run on the fast path and with the slow path forced),
+# then natural taint
+STAR_BOUNDARY_CASES = (
+    ("star32", 9), ("star_regex64", 9), ("star64", 10), ("star_regex32nl", 10), ("star_regex32", 11), ("star64", 11),
+    ("star32", 12), ("star_regex64", 12), ("star_regex32nl", 12),
+)
+STAR_TAINT_BOUNDARY_CASES = (("taint32", 9), ("taint64", 10), ("taint64", 11), ("taint32", 12))
 BOUNDARY_LANES = (37, 101, 255)
 FULL_LANE = 100    # of tile 1, which is walked twice: its hits are written by the second walk
 PARKED_LANE = 150  # of tile 0, which stays below the pool: its hits go through the parked words, ordinal and all
@@ -475,7 +549,8 @@ class BoundaryCase:
         goes with the plants."""
         es, ds = [], []
         for lo, ln in self.windows():
-            e, d = self.search.ends(self.text[lo:lo + ln])
+            stretch = self.text[lo:lo + ln]
+            e, d = self.search.ends(stretch) if lo == 0 else self.search.ends_behind_prefix(stretch)
             es.append(e + lo)
             ds.append(d)
         return np.concatenate(es), (None if ds[0] is None else np.concatenate(ds))
@@ -489,7 +564,7 @@ def boundary_case(name: str, ps: int, first: int = BOUNDARY_OFFSET) -> BoundaryC
     hits in the middle of every lane (more than the pool in all: the tile is walked twice) and every end of lane 100, with
     the last end of lane 99 and the first of lane 101; the last ends of tile 1 up to 2 T - 1; tile 2 empty; the first end of
     tile 3 and every one up to the text's last byte."""
-    s = SEARCHES[name]
+    s = search_named(name)
     assert s.floor <= ps <= s.cap, (name, ps)
     T, P = 256 << ps, 1 << ps
     n = 3 * T + 5
@@ -519,6 +594,8 @@ def boundary_case(name: str, ps: int, first: int = BOUNDARY_OFFSET) -> BoundaryC
     tail = s.run((s.m if s.kind == "hamming" else s.min_len) - 1 + 5 + first)
     text[n - len(tail):] = np.frombuffer(tail, np.uint8)
     spans.append((n - len(tail), len(tail)))
+    assert spans[0][0] > len(s.prefix)
+    text[:len(s.prefix)] = np.frombuffer(s.prefix, np.uint8)  # (the star search's natural taint: the one c, at view byte 0)
     return BoundaryCase(f"{name} ps={ps}", s, ps, first, text.tobytes(), spans)
 
 
@@ -573,3 +650,84 @@ def host_planted_text(plan: PlantPlan, seed: int) -> bytes:
     t = background(plan.n, seed)
     t[plan.idx] = plan.val
     return t.tobytes()
+
+
+# ---- the star search: the edge of the pair warm-up -------------------------------------------------------------------------
+#
+# c[ab]*d on background with ONE run c, letters, d.  The loop keeps the upper bound alive on the letters and the lower
+# bound has it only behind the c, so the lane that owns the d is exact if and only if its warm-up holds the c -- or begins
+# at view byte 0 by rule.  Every other lane's warm-up ends on a background byte or holds the c too.
+
+STAR_EDGE = Search("regex_star", "edge", rx=so.parse("c[ab]*d"))
+
+
+@dataclass
+class WarmEdgeCase:
+    name: str
+    text: bytes
+    first: int
+    ps: int
+    warm: int
+    lead: int
+    tainted_waves: int  # what the first launch must count (so.fast_taint agrees: test_limit_cases_cpu.py)
+    d_at: int           # the one hit (view coordinates)
+
+
+def _edge_text(n: int, first: int, c_aligned: int, d_aligned: int, seed: int) -> bytes:
+    text = background(n, seed)
+    c, d = c_aligned - first, d_aligned - first
+    assert 0 <= c < d < n
+    rng = np.random.default_rng(seed + 1)
+    text[c + 1:d] = np.frombuffer(b"ab", np.uint8)[rng.integers(0, 2, d - c - 1)]
+    text[c], text[d] = ord("c"), ord("d")
+    return text.tobytes()
+
+
+def warm_edge_cases(ps: int, first: int, warm: int = None):
+    """Pieces of 2^ps ends, the view `first` bytes into its 16-byte line, a warm-up of `warm` bytes (default: the rule's).
+    First the lane at the aligned boundary S (lane 3 of tile 1 at ps 8, of tile 0 above) with its d at S + 7 and the c
+    at S - dist: inside the warm-up by one chunk (warm - 16), on its first chunk (its last and its first byte: warm - 15 + 14
+    = warm - 1, warm), in the chunk in front (warm + 1, warm + 16).  Then a lead that puts the first lane's start16 at
+    warm - 16, warm (both begin at view byte 0 by rule: exact whatever lies there) and warm + 16 (the warm-up begins at
+    chunk 1), with the c at view byte 0."""
+    warm = star_warm(ps) if warm is None else warm
+    S = ((256 + 3) << ps) if ps == 8 else (3 << ps)
+    seed = 7000 + 100 * ps + first
+    for dist in (warm - 16, warm - 1, warm, warm + 1, warm + 16):
+        if dist >= 1:
+            text = _edge_text(S + (2 << ps) - first, first, S - dist, S + 7, seed + dist)
+            yield WarmEdgeCase(f"ps={ps} offset {first} warm {warm}: c {dist} in front of start16", text, first, ps, warm, 0,
+                               int(dist > warm), S + 7 - first)
+    for start16 in (warm - 16, warm, warm + 16):
+        if start16 >= 16:
+            lo = start16 + 3
+            text = _edge_text(max(2 << ps, start16 + (1 << ps)) - first, first, first, lo + 4, seed + 50 + start16)
+            yield WarmEdgeCase(f"ps={ps} offset {first} warm {warm}: first lane's start16 {start16}, c at view byte 0", text, first,
+                               ps, warm, lo - first, int(start16 > warm), lo + 4 - first)
+
+
+# ---- the star search past 2^32: plants on ACGT -----------------------------------------------------------------------------
+
+STAR_BIG = so.parse("(wx|y)z+[ef]")   # plant letters only: the bounds meet at the first ACGT byte
+STAR_BIG_TAINT = so.parse("q.*[ef]")  # one q in front: no lane's bounds meet, one chain of pieces spans the text
+STAR_BIG_REACH = 16
+
+
+def star_big_instance(rng) -> bytes:
+    """A string STAR_BIG matches, of at most 32 bytes (a path cut short there matches nothing; it is a plant all the same)."""
+    buf = np.full(32, ord("z"), np.uint8)
+    end = so.plant_path(rng, buf, STAR_BIG, 0)
+    return buf[:end].tobytes()
+
+
+def row_of_windows(text_of, windows):
+    """(row, row_at, text_at): the windows laid end to end (text_of(lo, length) -> bytes), where window i begins in the
+    row, and where in the text."""
+    row = b"".join(text_of(lo, ln) for lo, ln in windows)
+    return row, np.cumsum([0] + [ln for _, ln in windows]), np.array([lo for lo, _ in windows], np.int64)
+
+
+def row_to_text(row_pos, row_at, text_at):
+    row_pos = np.asarray(row_pos, np.int64)
+    w = np.searchsorted(row_at, row_pos, side="right") - 1
+    return row_pos - row_at[w] + text_at[w]

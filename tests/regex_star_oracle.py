@@ -2,7 +2,9 @@
 bmx_compile_regex_star and of the bmx_search_regex_star* entries in include/bmx.h, not from the C code: regex_oracle's
 grammar with the three quantifiers ``*``, ``+`` and ``{a,}``, the Glushkov sets with cycles, a matcher that carries position
 sets, the answers for larger texts, a translation to Python's ``re`` with a brute force over it, a generator of random
-expressions, and the identity the slow path of csrc/bmx_regex_star_kernel.h rests on, restated on Python ints.
+expressions, the identity the slow path of csrc/bmx_regex_star_kernel.h rests on, restated on Python ints, and a model of
+the first launch on the tile frame's geometry (``fast_taint``: which lanes end their pair warm-up with two different
+bounds, how many waves hold one, and the lower-bound list such a launch reports).
 
 An automaton is a ``StarRx``: regex_oracle's ``Rx`` whose ``follow`` may point anywhere; ``max_len`` is UNBOUNDED where a
 cycle lies among the positions a match can use.
@@ -370,40 +372,50 @@ def run(text, rx: StarRx, entry: int, seed: bool) -> int:
     return D
 
 
-def pair_bounds(text, rx: StarRx, piece: int):
-    """(e, u) per piece of ``piece`` bytes: e_l the state in front of piece l from the pair walk's lower bound (over piece
-    l - 1 from the empty set; piece 0 and piece 1 are exact), u_l = f_l & ~e_l with f_l the upper bound (from every
+# The kernels cut pieces and tiles in ALIGNED coordinates: view byte i is aligned byte i + first, first = pointer mod 16,
+# and the ``first`` bytes in front of the view are stepped with an empty class word, which leaves the empty state.
+
+def run_aligned(text: bytes, rx: StarRx, first: int, a: int, b: int, entry: int, seed: bool) -> int:
+    """The state behind the aligned bytes [a, b) (clipped to the text's end) entered with ``entry``."""
+    D = entry
+    for i in range(a, min(b, len(text) + first)):
+        D = rx.step(D, text[i - first], seed) if i >= first else 0
+    return D
+
+
+def pair_bounds(text, rx: StarRx, piece: int, first: int = 0):
+    """(e, u) per piece of ``piece`` aligned bytes: e_l the state in front of piece l from the pair walk's lower bound (over
+    piece l - 1 from the empty set; piece 0 and piece 1 are exact), u_l = f_l & ~e_l with f_l the upper bound (from every
     position)."""
     t = bytes(text)
-    full = (1 << rx.m) - 1
-    n_pieces = (len(t) + piece - 1) // piece
+    full = getattr(rx, "all", (1 << rx.m) - 1)  # (masked(): the useful positions)
+    n_pieces = (len(t) + first + piece - 1) // piece
     e, u = [], []
     for l in range(n_pieces):
         if l == 0:
             e.append(0), u.append(0)
             continue
-        prev = t[(l - 1) * piece:l * piece]
-        lo = run(prev, rx, 0, True)
-        hi = run(prev, rx, 0 if l == 1 else full, True)
+        lo = run_aligned(t, rx, first, (l - 1) * piece, l * piece, 0, True)
+        hi = run_aligned(t, rx, first, (l - 1) * piece, l * piece, 0 if l == 1 else full, True)
         e.append(lo), u.append(hi & ~lo)
     return e, u
 
 
-def columns(text, rx: StarRx, piece: int, e, u):
+def columns(text, rx: StarRx, piece: int, e, u, first: int = 0):
     """(base, cols) per piece: base_l the state behind piece l entered with e_l, cols_l[r] the unseeded run of the piece
     from the r-th position of u_l."""
     t = bytes(text)
     base, cols = [], []
     for l in range(len(e)):
-        seg = t[l * piece:(l + 1) * piece]
-        base.append(run(seg, rx, e[l], True))
-        cols.append([run(seg, rx, 1 << p, False) for p in bits(u[l])])
+        base.append(run_aligned(t, rx, first, l * piece, (l + 1) * piece, e[l], True))
+        cols.append([run_aligned(t, rx, first, l * piece, (l + 1) * piece, 1 << p, False) for p in bits(u[l])])
     return base, cols
 
 
-def sweep(e, u, base, cols):
+def sweep(e, u, base, cols, use_columns: bool = True):
     """The true state in front of every piece: a piece with u == 0 knows it (e), the others get it from the piece before:
-    truth(l + 1) = base_l | OR over the positions of truth(l) & u_l of their column."""
+    truth(l + 1) = base_l | OR over the positions of truth(l) & u_l of their column.  ``use_columns`` False leaves the
+    column term out (what a sweep that carried ``base`` alone would give: a lower bound again)."""
     entry = [0] * len(e)
     for l in range(len(e)):
         if u[l] == 0:
@@ -411,8 +423,102 @@ def sweep(e, u, base, cols):
         else:
             k = l - 1
             nxt = base[k]
-            rank = {p: r for r, p in enumerate(bits(u[k]))}
-            for p in bits(entry[k] & u[k]):
-                nxt |= cols[k][rank[p]]
+            if use_columns:
+                rank = {p: r for r, p in enumerate(bits(u[k]))}
+                for p in bits(entry[k] & u[k]):
+                    nxt |= cols[k][rank[p]]
             entry[l] = nxt
     return entry
+
+
+# ---- the tile frame's geometry and a model of the first launch ---------------------------------------------------------
+
+def masked(rx: StarRx) -> StarRx:
+    """The automaton the host hands the kernels: only the positions a match can use (the others are taken out of the
+    classes, of first, last and follow[]); its ``all`` is where the upper bound starts."""
+    use = useful(rx.m, rx.first, rx.last, rx.follow)
+    member = rx.member.copy()
+    for i in range(rx.m):
+        if not (use >> i) & 1:
+            member[i] = False
+    k = StarRx(member, rx.first & use, rx.last & use, [f & use if (use >> i) & 1 else 0 for i, f in enumerate(rx.follow)])
+    k.all = use
+    return k
+
+
+def tile_lanes(n: int, first: int, lead: int, ps: int):
+    """(tile, lane, lo, hi) for every lane that owns ends, in aligned coordinates, as bmx_tile_frame.h cuts them: tiles of
+    256 << ps ends counted from aligned byte 0, lane l of a tile the 1 << ps ends from tile0 + (l << ps), both clipped to
+    [lead + first, n + first)."""
+    own_lo, own_hi = lead + first, n + first
+    shift = ps + 8
+    for tile in range(own_lo >> shift, (own_hi + (1 << shift) - 1) >> shift):
+        tile0 = tile << shift
+        for lane in range(256):
+            lo, hi = max(tile0 + (lane << ps), own_lo), min(tile0 + ((lane + 1) << ps), own_hi)
+            if lo < hi:
+                yield tile, lane, lo, hi
+
+
+class FastTaint:
+    """What fast_taint returns: ``lanes`` the (tile, lane) pairs whose two bounds did not meet, ``waves`` the number of
+    (tile, 64 consecutive lanes) that hold one (regex_star_last()["tainted"]), ``ends`` the list the launch reports (every
+    lane walked from its lower bound; view coordinates, ascending, int64)."""
+
+    def __init__(self, lanes, waves, ends):
+        self.lanes, self.waves, self.ends = lanes, waves, ends
+
+
+def fast_taint(text, rx: StarRx, first: int, lead: int, ps: int, warm: int, walk: bool = True) -> FastTaint:
+    """RegexStarPolicy<.., ENTRY = false>::walk on the tile frame's geometry: a lane with the owned ends [lo, hi) runs the
+    lower state e (from the empty set) and the upper state f (from every useful position) over the aligned bytes
+    [start16 - warm, start16), start16 = lo & ~15; a warm-up that would begin at or in front of aligned byte 0
+    (start16 <= warm) begins there with e = f = 0.  The lane is tainted where e != f; either way it reports the ends of
+    the walk from e.  ``walk`` False: the warm-ups alone (``ends`` stays empty)."""
+    t = bytes(text)
+    k = masked(rx)
+    last = k.last
+    lanes, waves, ends = [], set(), []
+    for tile, lane, lo, hi in tile_lanes(len(t), first, lead, ps):
+        start16 = lo & ~15
+        e, f, a = (0, 0, 0) if start16 <= warm else (0, k.all, start16 - warm)
+        for i in range(a, start16):
+            if i < first:
+                e = f = 0
+            elif e == f:  # (met: they stay equal)
+                e = f = k.step(e, t[i - first])
+            else:
+                e, f = k.step(e, t[i - first]), k.step(f, t[i - first])
+        if e != f:
+            lanes.append((tile, lane))
+            waves.add((tile, lane >> 6))
+        D = e
+        for i in range(start16, hi if walk else start16):
+            D = k.step(D, t[i - first]) if i >= first else 0
+            if i >= lo and D & last:
+                ends.append(i - first)
+    return FastTaint(lanes, len(waves), np.array(ends, np.int64))
+
+
+def entry_ends(text, rx: StarRx, first: int, lead: int, ps: int, entry) -> np.ndarray:
+    """RegexStarPolicy<.., ENTRY = true>::walk: every lane starts at the first byte of the aligned piece that holds its
+    first owned end, in the state ``entry`` gives for that piece."""
+    t = bytes(text)
+    ends = []
+    for _, _, lo, hi in tile_lanes(len(t), first, lead, ps):
+        piece = lo >> ps
+        D = entry[piece]
+        for i in range(piece << ps, hi):
+            D = rx.step(D, t[i - first]) if i >= first else 0
+            if i >= lo and D & rx.last:
+                ends.append(i - first)
+    return np.array(ends, np.int64)
+
+
+def slow_ends(text, rx: StarRx, first: int, lead: int, ps: int, use_columns: bool = True) -> np.ndarray:
+    """The slow path's list: pair bounds, columns and sweep over the aligned pieces from piece 0 (what lies in front of
+    ``lead`` counts), then the walk from the swept states."""
+    k = masked(rx)
+    e, u = pair_bounds(text, k, 1 << ps, first)
+    base, cols = columns(text, k, 1 << ps, e, u, first)
+    return entry_ends(text, k, first, lead, ps, sweep(e, u, base, cols, use_columns))

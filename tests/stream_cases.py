@@ -21,6 +21,8 @@ Sizes (those the oracles already handle in the GPU suite; ordering bugs need a p
                 oracle on the plants (reach 0)
     ed          9,000 x 7,000 and 3,000 x 2,500 over four letters              port.edit_distance
     sa          300,000 and 100,000 over a..d                                  port.suffix_array
+    regex_star  256 KiB + 9 of ACGT, N[ACGT]*G: one text that taints the call (slow path) and one that does not, each the
+                other's decoy                                                  regex_star_oracle.ends_numpy
 """
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -28,6 +30,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 import limit_cases as lc
+import regex_star_oracle as so
 from approx_oracle import approx_ends
 from dict_oracle import DictIndex, dict_matches
 from parallel_implementation_of_string_matching_algorithms_opencl_amd import corpus
@@ -59,6 +62,7 @@ class StreamCase:
     pat: bytes = b""
     k: int = 0
     patterns: List[bytes] = field(default_factory=list)
+    expr: str = ""                              # regex_star: the expression
     windows: Optional[Tuple[list, list]] = None  # (real, decoy): (start, length) windows that hold every hit
     _want: dict = field(default_factory=dict)
 
@@ -81,6 +85,8 @@ class StreamCase:
             return [[port.edit_distance(ops[0], ops[1])]]
         if self.kind == "sa":
             return [port.suffix_array(ops[0])]
+        if self.kind == "regex_star":
+            return [so.ends_numpy(ops[0].tobytes(), so.parse(self.expr))]
         text = ops[0].tobytes()
         wins = None if self.windows is None else self.windows[0 if which == "real" else 1]
         if self.kind == "approx":
@@ -214,6 +220,29 @@ def ed_case(seed: int, la: int = 9000, lb: int = 7000) -> StreamCase:
 def sa_case(seed: int, n: int = 300_000) -> StreamCase:
     real, decoy = _pair(lambda rng: (rng.integers(0, 4, n) + 97).astype(np.uint8), seed)
     return StreamCase(f"sa n={n}", "sa", (real,), (decoy,))
+
+
+# ---- the star search: a tainted and an untainted text under one expression ------------------------------------------------
+
+STAR_EXPR = "N[ACGT]*G"
+STAR_N = (256 << 10) + 9  # five tiles of 64 KiB at the rule's piece (2^8 ends, a warm-up of 64 bytes)
+
+
+def regex_star_cases(seed: int = 0x57A) -> List[StreamCase]:
+    """[real tainted / decoy untainted, the other way round] for bmx_search_regex_star_device.  Tainted: ACGT with one N
+    near the front -- the loop lives through every warm-up in the upper bound and in no lower one, so the call takes the
+    slow path (memset, three kernels, a scan, a copy and four events on the caller's stream), and every G behind the N is
+    a hit.  Untainted: the same kind of text with a '-' in every 32nd place, which ends the loop in both bounds, and an N
+    in every 100th; the call is the first launch alone.  tests/test_stream_cases_cpu.py proves both predictions with
+    so.fast_taint and that the two answers differ."""
+    rng = np.random.default_rng(seed)
+    tainted = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, STAR_N)].copy()
+    tainted[7] = ord("N")
+    clean = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, STAR_N)].copy()
+    clean[50::100] = ord("N")
+    clean[31::32] = ord("-")
+    return [StreamCase("star: real tainted, decoy untainted", "regex_star", (tainted,), (clean,), expr=STAR_EXPR),
+            StreamCase("star: real untainted, decoy tainted", "regex_star", (clean,), (tainted,), expr=STAR_EXPR)]
 
 
 # ---- the synthetic corpus produced on the stream (bmx_gen_text_device + bmx_plant_device) ------------------------------

@@ -159,6 +159,10 @@ def call(ctx, L):
         pos, pid, total = L.dictionary.search_device(L.buf[0], out=L.out, pid_out=L.aux)
         assert total == pos.numel(), ("BMX_ERR_CAPACITY", total)
         res = [pos, pid]
+    elif c.kind == "regex_star":
+        ends, total = ctx.search_regex_star_device(L.buf[0], c.expr, out=L.out)
+        assert total == ends.numel(), ("BMX_ERR_CAPACITY", total)
+        res = [ends]
     elif c.kind == "ed":
         return [np.array([ctx.edit_distance_device(L.buf[0], L.buf[1])], np.int64)]
     else:
@@ -262,7 +266,46 @@ def test_input_still_being_generated_on_the_stream(ctx, port):
         assert np.array_equal(L.buf[0].cpu().numpy(), planted.real[0])
 
 
+@pytest.mark.parametrize("which", [0, 1], ids=["real tainted, decoy untainted", "real untainted, decoy tainted"])
+def test_regex_star_input_still_being_produced_on_the_stream(which, exp_ctx, port):
+    """bmx_search_regex_star_device while the copy of the real text is outstanding.  Real tainted: the slow path's own
+    memset, kernels, scan, copy and events must all wait behind the caller's stream; a first launch that read the decoy
+    would not even be tainted.  Real untainted: a first launch that read the decoy would take the slow path."""
+    import torch
+
+    L = Loaded(sc.regex_star_cases()[which], port, start_with="decoy")
+    s = side_stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        delay(s)
+        L.produce()
+        pending = Pending(s)
+        pending.assert_outstanding("search_regex_star_device")
+        got = call(exp_ctx, L)
+    check(got, L, L.case.name)
+    last = exp_ctx.regex_star_last()
+    assert last["slow"] == int(which == 0) and (last["tainted"] > 0) == (which == 0), last
+    assert bool((L.out[L.want[0].size:] == -1).all())
+
+
 # ---- (b) output consumed on the stream -------------------------------------------------------------------------------------
+
+def test_output_of_the_regex_star_slow_path_consumed_on_the_stream(exp_ctx, port):
+    """One tainted call on the side stream behind the delay; a clone enqueued right behind it, with no synchronisation
+    by the caller in between, sees the slow path's list."""
+    import torch
+
+    L = Loaded(sc.regex_star_cases()[0], port, start_with="real")
+    s = side_stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        delay(s)
+        ends, total = exp_ctx.search_regex_star_device(L.buf[0], L.case.expr, out=L.out)
+        taken = L.out[:total].clone()
+    s.synchronize()
+    check([taken.cpu().numpy()], L, "clone behind search_regex_star_device")
+    assert exp_ctx.regex_star_last()["slow"] == 1
+
 
 def test_output_of_search_device_consumed_on_the_stream(ctx, port):
     """search_device polls a status word, it does not synchronise the stream: a clone enqueued right behind it sees the
@@ -518,6 +561,29 @@ def _wrap_search(c, kind):
             assert total == want.size > 1000
             same(e, want, "ends")
         return search, lambda: None
+    if kind in ("regex_star", "regex_star_slow"):
+        import regex_star_oracle as so
+        from test_gpu_regex import _struct
+
+        # fast: the loop C+ dies in every warm-up of a random ACGT text (the model says so for these texts).  slow: an N
+        # in place 7 and N.*ACG -- no lane's lower bound has the `.`, every upper bound keeps it: the call takes two
+        # sequence numbers, the first launch's and R2's
+        slow = kind == "regex_star_slow"
+        rx = so.parse("N.*ACG" if slow else "AC+G")
+
+        def search(text):
+            text = text * 4  # eight tiles of 64 KiB: a star piece is 2^8 ends at the least
+            if slow:
+                text = text[:7] + b"N" + text[8:]
+            want = so.ends_numpy(text, rx)
+            waves = so.fast_taint(text, rx, 0, 0, 8, 64, walk=False).waves
+            assert (waves > 0) == slow
+            e, total = c.search_regex_star_device(dev(text), _struct(rx), capacity=len(text))
+            assert total == want.size > 1000
+            same(e, want, "ends")
+            last = c.regex_star_last()
+            assert last["slow"] == int(slow) and last["tainted"] == waves and last["piece_shift"] == 8, last
+        return search, lambda: None
     assert kind == "dict"
     d = c.dictionary([WRAP_PATTERN])
 
@@ -529,12 +595,14 @@ def _wrap_search(c, kind):
     return search, d.close
 
 
-@pytest.mark.parametrize("kind", ["approx", "classes", "dict", "approx_long", "hamming", "gaps", "regex"])
+@pytest.mark.parametrize("kind", ["approx", "classes", "dict", "approx_long", "hamming", "gaps", "regex", "regex_star", "regex_star_slow"])
 def test_tag_wrap_clears_the_status_words(exp_ctx, kind):
     """The status words of an ordered-output session carry the call's sequence number mod 2^22 and are cleared only when
     that tag wraps.  The first search leaves a tag-1 prefix in every word; "ordered_seq" then puts the next call on the
     wrap, so it takes tag 1 again: without the clear its tiles would read the first search's prefixes as their
-    predecessors' (a wrong list, or BMX_ERR_HIP from the bounded wait -- never a hang)."""
+    predecessors' (a wrong list, or BMX_ERR_HIP from the bounded wait -- never a hang).  A tainted call of the star search
+    takes two sequence numbers: from 2^22 - 1 the wrap falls on its first launch, from 2^22 - 2 on R2, whose tiles would
+    then read what the searches before left under the tags 1 and 2."""
     rng = np.random.default_rng(0x7A6)
     texts = [np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, WRAP_N)].tobytes() for _ in range(3)]
     search, close = _wrap_search(exp_ctx, kind)
@@ -542,8 +610,9 @@ def test_tag_wrap_clears_the_status_words(exp_ctx, kind):
         search(texts[0])
         with pytest.raises(host.BmxError):  # (BMX_ERR_ARG, as for an unknown name)
             exp_ctx.set_knob("ordered_seq", -1)
-        exp_ctx.set_knob("ordered_seq", (1 << 22) - 1)
-        search(texts[1])
-        search(texts[2])
+        for seq in ((1 << 22) - 1,) + (((1 << 22) - 2,) if kind == "regex_star_slow" else ()):
+            exp_ctx.set_knob("ordered_seq", seq)
+            search(texts[1])
+            search(texts[2])
     finally:
         close()

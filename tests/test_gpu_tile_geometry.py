@@ -41,9 +41,10 @@ def _raw(ctx, s: lc.Search, d_text, out, dist, cap, base=0):
     if s.kind in ("approx", "approx_long"):
         fn = L.bmx_search_approx_long_device if s.kind == "approx_long" else L.bmx_search_approx_device
         rc = fn(h, text, n, 0, base, s.pat, len(s.pat), s.k, *tail_d)
-    elif s.kind == "regex":
+    elif s.kind in ("regex", "regex_star"):
         re_ = _struct(s.rx)
-        rc = L.bmx_search_regex_device(h, text, n, 0, base, C.byref(re_), *tail)
+        fn = L.bmx_search_regex_star_device if s.kind == "regex_star" else L.bmx_search_regex_device
+        rc = fn(h, text, n, 0, base, C.byref(re_), *tail)
     else:
         cls = co.pack(s.member)
         cp = C.c_void_p(cls.ctypes.data)

@@ -10,6 +10,7 @@ import limit_cases as lc
 from approx_oracle import approx_ends
 from dict_oracle import DictIndex, dict_matches
 import regex_oracle as ro
+import regex_star_oracle as so
 
 
 def test_count_lists_cross_the_pool_on_both_sides():
@@ -197,3 +198,191 @@ def test_boundary_cases_have_what_they_claim(name, ps):
     if s.kind == "hamming":
         assert np.unique(dists[in_dense]).size >= 3
     assert lc.tiles_per_workgroup_at_least(4, 2) >= 2
+
+
+# ---- the star search (tests/test_gpu_regex_star_limits.py) -------------------------------------------------------------
+
+def _states_behind(s, entry):
+    """Every state the search's automaton can be in behind `entry` on a text of the search's letters and background bytes,
+    and the set of those it is in right behind a background byte."""
+    alphabet = list(s.letters) + list(range(0x80, 0x100))
+    seen, frontier, behind_background = {entry}, [entry], set()
+    while frontier:
+        D = frontier.pop()
+        for c in alphabet:
+            D2 = s.rx.step(D, c)
+            if c >= 0x80:
+                behind_background.add(D2)
+            if D2 not in seen:
+                seen.add(D2)
+                frontier.append(D2)
+    return seen, behind_background
+
+
+def test_star_searches_cover_every_slot_and_a_background_byte_resets_them():
+    """floor 8, cap 12 (bmx_regex_star.hip), every kernel slot, and what reach == 1 rests on: no class of the first family
+    holds a background byte, so one such byte empties the state; behind the second family's prefix one background byte
+    leaves one and the same state, the one it leaves right behind the prefix (so the oracle on a window that begins with
+    a background byte, run behind a copy of the prefix, is the oracle on the whole text)."""
+    slots = set()
+    for name, s in lc.STAR_SEARCHES.items():
+        assert (s.kind, s.floor, s.cap, s.reach) == ("regex_star", 8, 12, 1), name
+        k = so.masked(s.rx)
+        assert k.all == (1 << s.m) - 1, name  # (every position is useful: the kernels see the automaton as it is)
+        irregular = any(f and f != 1 << (i + 1) for i, f in enumerate(k.follow))
+        slots.add((bool(s.prefix), s.m > 32, irregular, s.rx.max_len == so.UNBOUNDED))
+        entry = so.run(s.prefix, s.rx, 0, True)
+        seen, behind_background = _states_behind(s, entry)
+        if not s.prefix:
+            assert not s.rx.member[:, 0x80:].any(), name
+            assert behind_background == {0}, name
+        else:
+            assert s.prefix == b"c" and s.min_len == 1 and not set(s.prefix) & set(s.letters)
+            assert behind_background == {s.rx.step(entry, 0x80)} and 0 not in seen, name
+        for hits in (1, 2, 3, 9, 64, 700):  # a run of L letters: L hits (less min_len - 1) at adjacent ends
+            assert s.run_unit(hits).count == hits, (name, hits)
+    assert slots == {(False, False, True, True), (False, True, True, True), (False, False, False, False), (False, True, False, False),
+                     (False, False, True, False), (True, False, True, True), (True, True, True, True)}
+    assert [lc.star_warm(ps) for ps in (4, 8, 9, 10, 11, 12)] == [64, 64, 64, 64, 128, 256]
+
+
+def _star_proof(s, text, first, ps, ends):
+    """The taint a case claims, at its piece and the rule's warm-up.  First family: no lane's bounds differ.  Natural
+    taint: the first launch's waves are (all but the first few) tainted, its list misses true ends, and so does a slow
+    path that carried `base` alone from piece to piece -- the case runs the column term."""
+    warm = lc.star_warm(ps)
+    if not s.prefix:
+        model = so.fast_taint(text, s.rx, first, 0, ps, warm, walk=False)
+        assert model.waves == 0 and not model.lanes
+        return 0
+    assert text[:1] == s.prefix and text.count(s.prefix) == 1
+    letters = np.nonzero(np.isin(np.frombuffer(text, np.uint8), list(s.letters)))[0]
+    assert np.array_equal(ends, letters)  # the hits are the letters, as for [ab]+
+    model = so.fast_taint(text, s.rx, first, 0, ps, warm)
+    n_waves = len({(t, l >> 6) for t, l, _, _ in so.tile_lanes(len(text), first, 0, ps)})
+    assert n_waves - 1 <= model.waves <= n_waves and len(model.lanes) >= n_waves * 64 - (warm >> ps) - 66
+    assert model.ends.size < ends.size // 4 and np.isin(model.ends, ends).all()
+    k = so.masked(s.rx)
+    e, u = so.pair_bounds(text, k, 1 << ps, first)
+    base, cols = so.columns(text, k, 1 << ps, e, u, first)
+    assert sum(1 for x in u if x) >= len(u) - 2 and sum(len(c) for c in cols) >= len(u) - 2
+    without = so.entry_ends(text, k, first, 0, ps, so.sweep(e, u, base, cols, use_columns=False))
+    assert without.size < ends.size // 4 and np.isin(without, ends).all()
+    if len(text) <= 1 << 20:  # (and with the columns it is the truth)
+        assert np.array_equal(so.entry_ends(text, k, first, 0, ps, so.sweep(e, u, base, cols)), ends)
+    return model.waves
+
+
+def _star_tile_case_proof(case):
+    s, n_tiles = case.search, len(case.counts)
+    assert case.tile == 256 << 8 == 256 << case.ps and len(case.text) == n_tiles * case.tile - case.first <= lc.MAX_TILE_TEXT
+    ends, _ = s.ends(case.text)
+    assert lc.bin_by_tile(ends, case.tile, case.first, n_tiles) == case.counts, case.name
+    _star_proof(s, case.text, case.first, case.ps, ends)
+
+
+@pytest.mark.parametrize("name", list(lc.STAR_SEARCHES))
+def test_star_geometry_cases_hold_their_counts_and_their_taint(name):
+    ran = 0
+    for case in lc.star_geometry_cases(name):
+        assert case.counts == lc.SEQUENCE_BOTH_WAYS
+        _star_tile_case_proof(case)
+        assert all(lc.tiles_per_workgroup_at_least(len(case.counts), g) >= 2 for g in lc.GRIDS)
+        dense = [t for t, c in enumerate(case.counts) if c > lc.STAGE][1]
+        assert case.prefix(dense) < lc.capacity_inside_second_dense(case) < case.prefix(dense + 1)
+        ran += 1
+    assert ran == len(lc.OFFSETS)
+
+
+@pytest.mark.parametrize("name,which", [(n, w) for n in ("star32", "taint32") for w in (0, 1)])
+def test_star_count_cases_hold_their_counts_and_their_taint(name, which):
+    case = lc.star_count_case(name, which)
+    assert case.counts == lc.COUNT_LISTS[which] and case.first == lc.STAR_COUNT_OFFSET
+    _star_tile_case_proof(case)
+
+
+@pytest.mark.parametrize("name,ps", lc.STAR_BOUNDARY_CASES + lc.STAR_TAINT_BOUNDARY_CASES)
+def test_star_boundary_cases_have_what_they_claim(name, ps):
+    """test_boundary_cases_have_what_they_claim for the star search at pieces of 2^9 .. 2^12 ends, the window argument on
+    the whole text at every size, and the taint each case claims."""
+    case = lc.boundary_case(name, ps)
+    s, T, P, first = case.search, case.tile, 1 << ps, case.first
+    assert 9 <= ps <= s.cap and len(case.text) == 3 * T + 5 and first == lc.BOUNDARY_OFFSET
+    ends, _ = case.ends_by_windows()
+    whole, _ = s.ends(case.text)
+    assert np.array_equal(whole, ends)
+    aligned = ends + first
+    have = set(aligned.tolist())
+    for lane in lc.BOUNDARY_LANES:
+        assert {lane * P - 1, lane * P} <= have, (case.name, lane)
+    assert {T - 1, T, 2 * T - 1, 3 * T, len(case.text) - 1 + first} <= have and 2 * T not in have
+    lane0 = T + lc.FULL_LANE * P
+    assert set(range(lane0 - 1, lane0 + P + 1)) <= have  # (32 lines of the walk's loop at ps 12, every end a hit)
+    counts = lc.bin_by_tile(ends, T, first, 4)
+    lane_p = lc.PARKED_LANE * P
+    in_lane = (aligned >= lane_p) & (aligned < lane_p + P)
+    assert int(in_lane.sum()) == lc.parked_lane_hits(ps) == min(P, 2000)  # ordinals up to that less one are parked
+    assert lc.parked_lane_hits(ps) + 10 <= counts[0] <= lc.STAGE and counts[1] > lc.STAGE + P and counts[2] == 0 and counts[3] == 5 + first, counts
+    in_dense = (aligned >= T) & (aligned < 2 * T)
+    assert np.unique((aligned[in_dense] - T) // P).size >= 250
+    assert {n for n, _ in lc.STAR_BOUNDARY_CASES} == set(lc.STAR_FAST) and {n for n, _ in lc.STAR_TAINT_BOUNDARY_CASES} == set(lc.STAR_TAINT)
+    assert {p for _, p in lc.STAR_BOUNDARY_CASES} == {9, 10, 11, 12} == {p for _, p in lc.STAR_TAINT_BOUNDARY_CASES}
+    _star_proof(s, case.text, first, ps, ends)
+
+
+WARM_EDGE_SETS = [(ps, first, None) for ps in (8, 12) for first in (0, 5, 15)] + [(8, 5, 16), (8, 5, 4096)]
+
+
+@pytest.mark.parametrize("ps,first,warm", WARM_EDGE_SETS)
+def test_warm_edge_cases_straddle_the_edge(ps, first, warm):
+    """The placements of tests/test_gpu_regex_star_limits.py around the pair warm-up's edge: the model of the first
+    launch counts one tainted wave exactly where the c lies in front of the owning lane's warm-up and that warm-up does
+    not begin at view byte 0, none otherwise; either way the one hit is the d."""
+    seen = []
+    for case in lc.warm_edge_cases(ps, first, warm):
+        assert case.warm == (lc.star_warm(ps) if warm is None else warm)
+        want = so.ends_numpy(case.text, lc.STAR_EDGE.rx)
+        assert want.tolist() == [case.d_at] and case.lead <= case.d_at, case.name
+        model = so.fast_taint(case.text, lc.STAR_EDGE.rx, first, case.lead, ps, case.warm)
+        assert model.waves == case.tainted_waves == len(model.lanes), case.name
+        assert model.ends.tolist() == ([] if model.waves else [case.d_at]), case.name  # a tainted lane's list misses the hit
+        assert np.array_equal(so.slow_ends(case.text, lc.STAR_EDGE.rx, first, case.lead, ps), want), case.name
+        seen.append(case.tainted_waves)
+    assert seen.count(0) >= 3 and seen.count(1) >= 3 and len(seen) == (6 if warm == 16 else 8), seen
+
+
+def test_star_row_of_windows_gives_the_whole_texts_list():
+    """The 4 GiB test's argument on 300,000 bytes: plants of STAR_BIG's letters (and one q in front) on ACGT, the oracle on
+    the plants' windows laid end to end, mapped back, is the oracle on the whole text -- for STAR_BIG, whose state an
+    ACGT byte empties, and for STAR_BIG_TAINT, whose `.` holds through any run, long or short."""
+    rng = np.random.default_rng(0x57A9)
+    n = 300000
+    text = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n)].copy()
+    centre = 150000
+    cluster, at = [], centre - 40
+    while at < centre + 40:
+        inst = lc.star_big_instance(rng)
+        cluster.append((at, inst))
+        at += len(inst)
+    offs = lc.spread_offsets(0, n, 60, 64, rng, keep_clear=[(centre - 40, at)])
+    last = lc.star_big_instance(rng)
+    plants = [(5, b"q")] + cluster + [(p, lc.star_big_instance(rng)) for p in offs if p + 64 < n - 100] + [(n - len(last), last)]
+    plan = lc.plan_plants(n, plants, lc.STAR_BIG_REACH)
+    text[plan.idx] = plan.val
+    text = text.tobytes()
+    row, row_at, text_at = lc.row_of_windows(lambda lo, ln: text[lo:lo + ln], plan.windows)
+    assert len(row) < n // 20
+    for rx in (lc.STAR_BIG, lc.STAR_BIG_TAINT):
+        whole = so.ends_numpy(text, rx)
+        assert whole.size > 40 and int(whole[-1]) == n - 1
+        assert np.array_equal(lc.row_to_text(so.ends_numpy(row, rx), row_at, text_at), whole)
+    assert not lc.STAR_BIG.member[:, list(b"ACGT")].any()  # (no class of the untainted pattern holds a background letter)
+    for longest in (False, True):  # the starts within a window of 64 bytes, for STAR_BIG
+        whole = so.ends_numpy(text, lc.STAR_BIG)
+        row_e = so.ends_numpy(row, lc.STAR_BIG)
+        row_s = so.starts_numpy(row, lc.STAR_BIG, row_e, 64, longest)
+        assert np.array_equal(lc.row_to_text(row_s.astype(np.int64), row_at, text_at),
+                              so.starts_numpy(text, lc.STAR_BIG, whole, 64, longest).astype(np.int64))
+    # the tainted pattern is tainted: on ACGT alone the upper bound keeps the `.`, the lower one has nothing
+    k = so.masked(lc.STAR_BIG_TAINT)
+    assert so.run(b"ACGT" * 64, k, k.all, True) != so.run(b"ACGT" * 64, k, 0, True) == 0

@@ -338,6 +338,69 @@ def test_slow_path_identity_on_python_ints():
     assert unsure > 1000 and chained > 500, (unsure, chained)
 
 
+def test_slow_path_identity_with_a_lead_and_an_unaligned_view():
+    """The same identity in the kernels' aligned coordinates: the view begins ``first`` = 0..15 bytes into piece 0 (those
+    bytes leave the empty state), the bounds, columns and sweep run from aligned piece 0 whatever ``lead`` is, and the
+    walk from the swept states reports the true ends from ``lead`` on -- its first lane entering in the middle of a
+    piece."""
+    rng = np.random.default_rng(0x57A7)
+    unsure = inside = 0
+    for case in range(240):
+        symbols = np.arange(97, 97 + 2 + case % 2)
+        expr, rx = so.random_regex(rng, symbols, (8, 16, 40)[case % 3], cyclic=True)
+        n = int(rng.integers(1, 1500 if case % 8 == 0 else 300))
+        text = rng.choice(symbols, n).astype(np.uint8).tobytes()
+        first, ps = case % 16, (0, 2, 4)[case // 16 % 3]
+        truth = [0] + so.states(text, rx)
+        k = so.masked(rx)
+        e, u = so.pair_bounds(text, k, 1 << ps, first)
+        base_, cols_ = so.columns(text, k, 1 << ps, e, u, first)
+        entry = so.sweep(e, u, base_, cols_)
+        assert len(e) == ((n + first - 1) >> ps) + 1
+        assert entry == [truth[max((l << ps) - first, 0)] & k.all for l in range(len(e))], (expr, text, first, ps)
+        unsure += sum(1 for x in u if x)
+        want = so.ends_numpy(text, rx)
+        for lead in sorted({0, 1, n - 1, n, int(rng.integers(0, n + 1)), min(n, max(0, (1 << ps) * int(rng.integers(0, 9)) - first))}):
+            got = so.slow_ends(text, rx, first, lead, ps)
+            assert np.array_equal(got, want[want >= lead]), (expr, text, first, ps, lead)
+            inside += (lead + first) % (1 << ps) != 0
+    assert unsure > 1000 and inside > 300, (unsure, inside)
+
+
+def test_fast_taint_model_reports_a_lower_bound_and_the_truth_when_untainted():
+    """so.fast_taint on random expressions and small geometries: the list of the first launch is a subset of the true
+    list, and the true list where no lane is tainted; tainted or not, the slow path's model gives the true list."""
+    rng = np.random.default_rng(0x57A8)
+    tainted = clean = short = 0
+    for case in range(300):
+        symbols = np.arange(97, 97 + 2 + case % 3)
+        expr, rx = so.random_regex(rng, symbols, (8, 16, 40)[case % 3], cyclic=None if case % 5 else False)
+        ps = (4, 5, 6)[case % 3]
+        n = int(rng.integers(1, (600 << ps) // 4))
+        text = rng.choice(symbols, n).astype(np.uint8)
+        for _ in range(4):
+            so.plant_path(rng, text, rx, int(rng.integers(0, n)), stop=0.1)
+        text = text.tobytes()
+        first, lead, warm = case % 16, (0, int(rng.integers(0, n + 1)))[case % 2], (0, 16, 32, 64, 4096)[case % 5]
+        want = so.ends_numpy(text, rx)
+        want = want[want >= lead]
+        m = so.fast_taint(text, rx, first, lead, ps, warm)
+        assert np.all(np.diff(m.ends) > 0) and np.isin(m.ends, want).all(), (expr, first, lead, ps, warm)
+        assert (m.waves == 0) == (not m.lanes) and m.waves <= len(m.lanes)
+        assert m.waves == len({(t, l >> 6) for t, l in m.lanes})
+        if not m.lanes:
+            assert np.array_equal(m.ends, want), (expr, first, lead, ps, warm)
+            clean += 1
+        else:
+            tainted += 1
+            short += m.ends.size < want.size
+        if (n + first - 1) & ~15 <= warm:  # every warm-up begins at view byte 0: exact by rule
+            assert not m.lanes
+        if case % 3 == 0:
+            assert np.array_equal(so.slow_ends(text, rx, first, lead, ps), want), (expr, first, lead, ps)
+    assert tainted >= 60 and clean >= 60 and short >= 10, (tainted, clean, short)
+
+
 def test_library_exports_regex_star_symbols(built):
     L = C.CDLL(host.LIB_PATH)
     X = C.CDLL(host.EXP_LIB_PATH)

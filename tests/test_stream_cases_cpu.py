@@ -67,6 +67,26 @@ def test_sequence_cases_decoy_answers_differ_for_both_threads(port):
             assert not sc.same(answers[0][key], answers[1][key]), key
 
 
+def test_regex_star_cases_differ_and_taint_as_claimed(port):
+    """The star search's two cases: the decoy's answer differs, and at the rule's geometry for this size (pieces of 2^8
+    ends, a warm-up of 64 bytes, an aligned buffer) the model of the first launch taints the one text in (nearly) every
+    wave and the other in none."""
+    import regex_star_oracle as so
+
+    cases = sc.regex_star_cases()
+    assert [c.kind for c in cases] == ["regex_star", "regex_star"]
+    rx = so.parse(sc.STAR_EXPR)
+    waves = []
+    for case in cases:
+        real, decoy = _differs(case, port)
+        assert real[0].size > 5000 and decoy[0].size > 5000
+        waves.append(so.fast_taint(case.real[0].tobytes(), rx, 0, 0, 8, 64, walk=False).waves)
+    n_waves = -(-sc.STAR_N // (64 << 8))
+    assert waves[0] >= n_waves - 1 and waves[1] == 0, (waves, n_waves)
+    assert np.array_equal(cases[0].real[0], cases[1].decoy[0]) and np.array_equal(cases[0].decoy[0], cases[1].real[0])
+    assert 5 * (256 << 8) > sc.STAR_N > 4 * (256 << 8)  # five tiles: the slow path's kernels run several workgroups' worth of pieces
+
+
 def test_large_cases_windows_hold_every_hit():
     a = sc.approx_big_case(0xA11CE)
     for which, text in (("real", a.real[0]), ("decoy", a.decoy[0])):
