@@ -20,12 +20,48 @@
 // Eq words, one against many (a_count == 1, query of 1..ED_BATCH_WORD bytes): ONE 256-word Peq in LDS, built by the
 // workgroup from the query; a chunk's 16 words are gathered before its steps, and every lane walks its own b[i]
 // whatever its length.
+//
+// BMX_ED_BATCH_PIECES_ONLY (tests/ed_batch_check.hip): a --cuda-host-only build gets the lane functions (ed_batch_step,
+// ed_batch_load_pattern, ed_batch_walk) as host code, with host stand-ins for the two device builtins, and no kernel.
+// Without the switch the macros below are the builtins and the qualifiers themselves: the device build is unchanged.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bmx_eq_kernel.h"
+
+#ifdef BMX_ED_BATCH_PIECES_ONLY
+#define BMX_ED_BATCH_LANE static inline
+// v_perm_b32(hi, lo, sel): byte i of the result is chosen by byte i of sel: 0..3 that byte of lo, 4..7 of hi, 8..11 the
+// sign (bit 15 / 31) of lo / hi spread over the byte, 12 zero, 13 and above 0xff.
+static inline uint32_t bmx_ed_batch_host_perm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+    const uint64_t src = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t s = (sel >> (8 * i)) & 0xffu;
+        uint32_t b;
+        if (s < 8) b = (uint32_t)(src >> (8 * s)) & 0xffu;
+        else if (s < 12) b = ((src >> (16 * (s - 8) + 15)) & 1) ? 0xffu : 0u;
+        else b = s == 12 ? 0u : 0xffu;
+        r |= b << (8 * i);
+    }
+    return r;
+}
+// v_bfe_u32: `width` bits of src from bit `offset` (both taken modulo 32)
+static inline uint32_t bmx_ed_batch_host_ubfe(uint32_t src, uint32_t offset, uint32_t width)
+{
+    offset &= 31u, width &= 31u;
+    return width == 0 ? 0u : (src >> offset) & (0xffffffffu >> (32u - width));
+}
+#define BMX_ED_BATCH_PERM(hi, lo, sel) bmx_ed_batch_host_perm(hi, lo, sel)
+#define BMX_ED_BATCH_UBFE(src, offset, width) bmx_ed_batch_host_ubfe(src, offset, width)
+#else
+#define BMX_ED_BATCH_LANE __device__ __forceinline__
+#define BMX_ED_BATCH_PERM(hi, lo, sel) __builtin_amdgcn_perm(hi, lo, sel)
+#define BMX_ED_BATCH_UBFE(src, offset, width) __builtin_amdgcn_ubfe(src, offset, width)
+#endif
 
 namespace bmx {
 
@@ -56,7 +92,7 @@ struct EdBatchState {
 };
 
 template <typename W>
-__device__ __forceinline__ void ed_batch_step(EdBatchState<W> &s, W eq, uint32_t hb)
+BMX_ED_BATCH_LANE void ed_batch_step(EdBatchState<W> &s, W eq, uint32_t hb)
 {
     const W xv = eq | s.mv;
     const W xh = (((eq & s.pv) + s.pv) ^ s.pv) | eq;
@@ -72,10 +108,12 @@ __device__ __forceinline__ void ed_batch_step(EdBatchState<W> &s, W eq, uint32_t
 // The pattern into its registers: byte 8k + j of a 32-byte half -> byte k of register j.  The bytes come in 16-byte loads
 // at the pattern's own alignment (one to four global_load_dwordx4 per pair) and a 4 x 4 byte transpose (v_perm_b32, 16 per
 // half) puts them in place.  A load may run past the pattern into the next string of the blob: those bytes only reach
-// Eq bits at or above m, which the mask clears.  It never runs past the blob (`end`): the blob's last pattern, and only
-// it, takes its last chunk byte by byte.
+// Eq bits at or above m, which the mask clears.  It never runs past the blob (`end`): a chunk that would end past
+// `end` comes byte by byte, its bytes below m only.  That is any pattern whose last chunk starts fewer than 16 bytes before
+// the blob's end (the blob's last pattern, and those before it that are as close), and only a pattern's LAST chunk: an
+// earlier chunk holds 16 pattern bytes, all inside the blob.
 template <int ND>
-__device__ __forceinline__ void ed_batch_load_pattern(uint32_t *p, const uint8_t *P, uint32_t m, const uint8_t *end)
+BMX_ED_BATCH_LANE void ed_batch_load_pattern(uint32_t *p, const uint8_t *P, uint32_t m, const uint8_t *end)
 {
     uint32_t d[ND];
 #pragma unroll
@@ -99,12 +137,12 @@ __device__ __forceinline__ void ed_batch_load_pattern(uint32_t *p, const uint8_t
         for (int q = 0; q < 2; ++q) { // registers 4q .. 4q + 3 take the bytes of dwords q, 2 + q, 4 + q, 6 + q
             const uint32_t x0 = d[8 * h + q], x1 = d[8 * h + 2 + q], x2 = d[8 * h + 4 + q], x3 = d[8 * h + 6 + q];
             // v_perm_b32(hi, lo, sel): selector byte 0..3 takes that byte of lo, 4..7 of hi
-            const uint32_t t0 = __builtin_amdgcn_perm(x1, x0, 0x05010400u), t1 = __builtin_amdgcn_perm(x1, x0, 0x07030602u);
-            const uint32_t u0 = __builtin_amdgcn_perm(x3, x2, 0x05010400u), u1 = __builtin_amdgcn_perm(x3, x2, 0x07030602u);
-            p[8 * h + 4 * q + 0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u);
-            p[8 * h + 4 * q + 1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
-            p[8 * h + 4 * q + 2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u);
-            p[8 * h + 4 * q + 3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
+            const uint32_t t0 = BMX_ED_BATCH_PERM(x1, x0, 0x05010400u), t1 = BMX_ED_BATCH_PERM(x1, x0, 0x07030602u);
+            const uint32_t u0 = BMX_ED_BATCH_PERM(x3, x2, 0x05010400u), u1 = BMX_ED_BATCH_PERM(x3, x2, 0x07030602u);
+            p[8 * h + 4 * q + 0] = BMX_ED_BATCH_PERM(u0, t0, 0x05040100u);
+            p[8 * h + 4 * q + 1] = BMX_ED_BATCH_PERM(u0, t0, 0x07060302u);
+            p[8 * h + 4 * q + 2] = BMX_ED_BATCH_PERM(u1, t1, 0x05040100u);
+            p[8 * h + 4 * q + 3] = BMX_ED_BATCH_PERM(u1, t1, 0x07060302u);
         }
 }
 
@@ -112,8 +150,8 @@ __device__ __forceinline__ void ed_batch_load_pattern(uint32_t *p, const uint8_t
 // from P), else from P in registers (P_end: the end of P's blob).  Reads T[0..n) only: full 16-byte chunks of T, then its
 // last bytes singly.
 template <typename W, bool SHARED>
-__device__ __forceinline__ uint32_t ed_batch_walk(const uint8_t *P, uint32_t m, const uint8_t *P_end, const uint8_t *T, uint32_t n,
-                                                  const uint64_t *peq)
+BMX_ED_BATCH_LANE uint32_t ed_batch_walk(const uint8_t *P, uint32_t m, const uint8_t *P_end, const uint8_t *T, uint32_t n,
+                                         const uint64_t *peq)
 {
     constexpr int ND = sizeof(W) == 4 ? 8 : 16;
     uint32_t p[ND];
@@ -132,9 +170,9 @@ __device__ __forceinline__ uint32_t ed_batch_walk(const uint8_t *P, uint32_t m, 
 #pragma unroll
         for (int i = 0; i < 16; ++i) { // all of the chunk's Eq words first
             if (SHARED) {
-                eq[i] = (W)peq[__builtin_amdgcn_ubfe(v[i >> 2], 8 * (i & 3), 8)];
+                eq[i] = (W)peq[BMX_ED_BATCH_UBFE(v[i >> 2], 8 * (i & 3), 8)];
             } else {
-                const uint32_t c4 = __builtin_amdgcn_perm(v[i >> 2], v[i >> 2], 0x01010101u * (uint32_t)(i & 3));
+                const uint32_t c4 = BMX_ED_BATCH_PERM(v[i >> 2], v[i >> 2], 0x01010101u * (uint32_t)(i & 3));
                 eq[i] = ed_batch_eq<W>(p, c4, mask);
             }
         }
@@ -148,6 +186,8 @@ __device__ __forceinline__ uint32_t ed_batch_walk(const uint8_t *P, uint32_t m, 
     }
     return s.score;
 }
+
+#ifndef BMX_ED_BATCH_PIECES_ONLY // (tests/ed_batch_check.hip builds for the host alone: the pieces above, no kernel)
 
 __global__ __launch_bounds__(ED_BATCH_BLOCK) void ed_batch_kernel(const EdBatchArgs a)
 {
@@ -227,5 +267,7 @@ __global__ void ed_batch_scatter_kernel(const uint64_t *list, const uint32_t *va
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) dist[list[j * ED_BATCH_LIST_WORDS]] = vals[j];
 }
+
+#endif // BMX_ED_BATCH_PIECES_ONLY
 
 } // namespace bmx
