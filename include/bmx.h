@@ -1117,6 +1117,70 @@ float bmx_last_align_ms(bmx_ctx *ctx);
  * workspace at once); < 0 if none. */
 int64_t bmx_last_align_launches(bmx_ctx *ctx);
 
+/* ---- row-wise results: lines of a text, the row of each match, the matching rows ---- */
+
+/* Every search returns byte offsets into one text.  These three post-passes turn such lists into rows -- the lines of a
+ * log (grep -n, -c, -v) or the strings of a column (str.contains, str.count) -- on device-resident lists, with no atomics
+ * on the output and no sort.  The reference has no such program.
+ *
+ * Rows.  rows + 1 ascending uint64_t offsets off[0..rows], in the coordinates of the match lists (base_offset included).
+ * Row r is the byte range [off[r], off[r+1]).  Empty rows are legal where the caller supplies the offsets.  Bytes below
+ * off[0] or at or above off[rows] belong to no row.
+ * Split at a delimiter byte d.  off[0] = base_offset, off[i] = base_offset + (position of the i-th d) + 1, off[rows] =
+ * base_offset + n.  A row therefore holds its terminating delimiter as its last byte, a text that ends with d has no
+ * extra empty row behind it (wc -l), n = 0 gives rows = 0 and the single entry off[0], and
+ * rows = (#d) + (n > 0 && text[n-1] != d).
+ * Row of a match [s, e] (e the last byte, as the searches report ends): the r with off[r] <= s and e < off[r+1], or
+ * BMX_ROW_NONE where there is none: the match straddles a boundary or lies outside all rows.
+ * Consequence.  The searches report every end once and the starts post-passes default to the LARGEST start of an end.
+ * Some match that ends at e lies inside a row iff that largest start is >= off[r], so "ends + default starts" gives exact
+ * per-row semantics.  `.` matches every byte value, the delimiter included; a match that lies inside a row can hold the
+ * delimiter only as its last byte, and one that runs across a line break gets BMX_ROW_NONE.  On lines write [^\x0a]* for
+ * .* (\x0a is the grammars' escape for the newline; it also keeps the star search on its one-launch path).
+ *
+ * bmx_rows_split_device: one pass over the n bytes at d_text (any alignment, any byte value as delim, n < 2^40), the
+ * offsets written in order.  `capacity` counts entries of d_off; the call needs rows + 1.  A smaller non-zero capacity
+ * stores the lowest `capacity` entries and returns BMX_ERR_CAPACITY, capacity 0 only counts and returns BMX_OK; *n_rows
+ * is the true number either way.  *longest (may be NULL) is the longest row in bytes; where the offsets do not all go to
+ * the caller it costs a second pass into workspace.  No byte is read outside the aligned 16-byte lines that hold the text.
+ * bmx_rows_of_device: d_row[i] = the row of match i, one of three input forms: both lists and len == 0; only d_starts and
+ * len >= 1 (e = s + len - 1: the exact, class and Hamming lists with len = m); only d_ends and len >= 1 (s = e - len + 1,
+ * an end below len - 1 gives NONE).  A start of UINT64_MAX (the star search's "no match within the window") and an end
+ * below its start give NONE.  Lists in any order are answered correctly; ascending ends, which every search returns, are
+ * the fast case.  count == 0 returns BMX_OK and launches nothing.
+ * bmx_rows_matching_device: from a list of row ids that is non-decreasing once BMX_ROW_NONE entries are skipped, the
+ * distinct rows, ascending, in d_rows_out and (d_counts_out may be NULL) each one's number of list entries.  With
+ * BMX_ROWS_INVERT the rows of [0, rows) that have NO entry; d_counts_out must then be NULL.  More rows than `capacity`
+ * returns BMX_ERR_CAPACITY with the lowest `capacity` stored, *n_out the true number (capacity 0 counts only).  A list that
+ * decreases, or an id >= rows other than BMX_ROW_NONE, raises a status word: BMX_ERR_ARG, outputs unspecified.
+ * All three: NULL pointers where one is needed, contradictory list / len combinations, n too large and unknown flags
+ * return BMX_ERR_ARG before any HIP call, with ctx == NULL too.  Every launch, copy and memset goes on `stream`; the call
+ * returns after synchronising it.  Workspace is kept with the context.
+ * bmx_rows_split: host buffers, base_offset 0.
+ * Method (csrc/bmx_rows_kernel.h): the split compares whole 16-byte loads against the splatted delimiter, a wave reads one
+ * contiguous KiB per load, the ordered output of the one-pass searches (decoupled look-back); one match per lane, each
+ * wave's search bounded by the rows of its smallest and largest end; per-tile summaries, their carries and a fill.
+ * Measured on one MI355X: DESIGN.md s28. */
+#define BMX_ROW_NONE UINT64_MAX
+#define BMX_ROWS_INVERT 1u
+int bmx_rows_split_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, uint8_t delim, uint64_t *d_off,
+                          uint64_t capacity, uint64_t *n_rows, uint64_t *longest /* may be NULL */, void *stream);
+int bmx_rows_of_device(bmx_ctx *ctx, const uint64_t *d_off, uint64_t rows, const uint64_t *d_starts /* or NULL */,
+                       const uint64_t *d_ends /* or NULL */, uint64_t len, uint64_t count, uint64_t *d_row, void *stream);
+int bmx_rows_matching_device(bmx_ctx *ctx, const uint64_t *d_row, uint64_t count, uint64_t rows, uint32_t flags,
+                             uint64_t *d_rows_out, uint64_t *d_counts_out /* may be NULL */, uint64_t capacity, uint64_t *n_out,
+                             void *stream);
+/* Device time (ms, HIP events) of the last of the three device calls on ctx; < 0 if none. */
+float bmx_last_rows_ms(bmx_ctx *ctx);
+int bmx_rows_split(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, uint8_t delim, uint64_t *off,
+                   uint64_t capacity, uint64_t *n_rows, uint64_t *longest /* may be NULL */);
+/* bmx_rows_of, bmx_rows_matching: host buffers in, host buffers out (the driver's --lines works on the host searches'
+ * lists): upload, the device entry, download.  The same arguments, checks and return codes. */
+int bmx_rows_of(bmx_ctx *ctx /* NULL: device 0 */, const uint64_t *off, uint64_t rows, const uint64_t *starts /* or NULL */,
+                const uint64_t *ends /* or NULL */, uint64_t len, uint64_t count, uint64_t *row);
+int bmx_rows_matching(bmx_ctx *ctx /* NULL: device 0 */, const uint64_t *row, uint64_t count, uint64_t rows, uint32_t flags,
+                      uint64_t *rows_out, uint64_t *counts_out /* may be NULL */, uint64_t capacity, uint64_t *n_out);
+
 /* ---- synthetic corpus, generated in HBM ---------------------- */
 
 /* d_dst[j] = byte (start + j) of the counter-based splitmix64 stream;

@@ -39,6 +39,9 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
  * dictionary search: 6 + log2 of the rounds per tile), workgroups started, tiles}; zeros before the session's first launch.
  * session: "approx" (also the approximate search over classes), "approx_long", "classes", "hamming", "gaps", "regex" or
  * "dict".  Tests assert with it that the geometry they forced ("tile_piece_shift", "tile_max_grid") is the one that ran.
+ * "rows": the last bmx_rows_split_device, out3 = {log2 of the bytes of a tile, workgroups started, tiles}; a workgroup is
+ * eight waves, each with an eighth of the tile, read in batches of eight rounds of 1 KiB (the first entry is there
+ * before any split).
  * BMX_ERR_ARG for another name. */
 int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3);
 

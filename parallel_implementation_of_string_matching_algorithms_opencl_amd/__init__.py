@@ -12,9 +12,9 @@ AnupBS28/PARALLEL_IMPLEMENTATION_OF_STRING_MATCHING_ALGORITHMS_OPENCL (its
 from . import corpus, host, shard  # noqa: F401
 from .host import (BmxError, CLASS_ICASE, CLASS_IUPAC, Context, Dictionary, GAPS_LONGEST, GAPS_PROSITE, Index,  # noqa: F401
                    MAX_CLASS_PATTERN, MAX_GAPS_PATTERN, MAX_HAMMING_K, MAX_HAMMING_PATTERN, MAX_REGEX_POSITIONS, MAX_REGEX_STAR_WINDOW, REGEX_LONGEST,
-                   REGEX_UNBOUNDED, Regex,
+                   REGEX_UNBOUNDED, ROW_NONE, ROWS_INVERT, Regex, Rows,
                    align, build_tables, cigar_strings, compile_classes, compile_gaps, compile_regex, compile_regex_star, edit_distance_batch,
-                   index_count, index_map, index_seeds, lcp_array, longest_repeat, search, search_approx, search_classes,
+                   grep, index_count, index_map, index_seeds, lcp_array, longest_repeat, rows_split, search, search_approx, search_classes,
                    search_dict, search_gaps, search_hamming, search_ranges, search_regex, search_regex_star)
 
 __version__ = "0.1.0"

@@ -214,6 +214,66 @@ int bmx_suffix_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_
     return c.rc;
 }
 
+int bmx_rows_split(bmx_ctx *ctx_in, const char *text, uint64_t n, uint8_t delim, uint64_t *off, uint64_t capacity, uint64_t *n_rows,
+                   uint64_t *longest)
+{
+    if (!bmx_rows_split_args_ok(text, n, off, capacity)) return BMX_ERR_ARG;
+    if (n_rows) *n_rows = 0;
+    if (longest) *longest = 0;
+    if (n == 0) { // no row, the single entry off[0]: no device is touched
+        if (capacity) off[0] = 0;
+        return BMX_OK;
+    }
+    HostCall c("bmx_rows_split", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n + 1); // (no text has more than n rows)
+    uint64_t rows = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_off = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_rows_split_device(c.ctx(), d_text, n, 0, delim, d_off, dev_cap, &rows, longest, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(off, d_off, std::min(rows + 1, dev_cap) * sizeof(uint64_t), "row offsets");
+    if (n_rows) *n_rows = rows;
+    return c.rc;
+}
+
+int bmx_rows_of(bmx_ctx *ctx_in, const uint64_t *off, uint64_t rows, const uint64_t *starts, const uint64_t *ends, uint64_t len,
+                uint64_t count, uint64_t *row)
+{
+    if (!bmx_rows_of_args_ok(off, starts, ends, len, count, row)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    HostCall c("bmx_rows_of", ctx_in);
+    const uint64_t *d_off = c.upload<uint64_t>(off, (rows + 1) * sizeof(uint64_t));
+    const uint64_t *d_starts = starts ? c.upload<uint64_t>(starts, count * sizeof(uint64_t)) : nullptr;
+    const uint64_t *d_ends = ends ? c.upload<uint64_t>(ends, count * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_row = c.alloc<uint64_t>(count * sizeof(uint64_t));
+    if (c.rc == BMX_OK) c.rc = bmx_rows_of_device(c.ctx(), d_off, rows, d_starts, d_ends, len, count, d_row, nullptr);
+    if (c.rc == BMX_OK) c.download(row, d_row, count * sizeof(uint64_t), "row ids");
+    return c.rc;
+}
+
+int bmx_rows_matching(bmx_ctx *ctx_in, const uint64_t *row, uint64_t count, uint64_t rows, uint32_t flags, uint64_t *rows_out,
+                      uint64_t *counts_out, uint64_t capacity, uint64_t *n_out)
+{
+    if (!bmx_rows_matching_args_ok(row, count, flags, rows_out, counts_out, capacity)) return BMX_ERR_ARG;
+    if (n_out) *n_out = 0;
+    HostCall c("bmx_rows_matching", ctx_in);
+    // (no list has more distinct rows than entries, no text more absent rows than rows)
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, (flags & BMX_ROWS_INVERT) ? rows : std::min(count, rows));
+    uint64_t total = 0;
+    const uint64_t *d_row = count ? c.upload<uint64_t>(row, count * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_out = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_counts = dev_cap && counts_out ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_rows_matching_device(c.ctx(), d_row, count, rows, flags, d_out, d_counts, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(rows_out, d_out, std::min(total, dev_cap) * sizeof(uint64_t), "matching rows");
+    if (d_counts) c.download(counts_out, d_counts, std::min(total, dev_cap) * sizeof(uint64_t), "their counts");
+    if (n_out) *n_out = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
 int bmx_lcp_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out, int32_t *lcp_out)
 {
     if (!bmx_lcp_args_ok(text, n, lcp_out)) return BMX_ERR_ARG;

@@ -202,6 +202,18 @@ int bmx_internal_lcp_stats(void **state, const int32_t *d_lcp, uint32_t n, uint3
 void bmx_internal_lcp_free(void *state);
 float bmx_internal_lcp_ms(const void *state);
 int64_t bmx_internal_lcp_long_pairs(const void *state);
+// bmx_rows.hip
+int bmx_internal_rows_split(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t base_offset, uint8_t delim,
+                            uint64_t *d_off, uint64_t capacity, uint64_t *n_rows, uint64_t *longest, hipStream_t stream, char *err,
+                            size_t errlen);
+int bmx_internal_rows_of(void **state, const uint64_t *d_off, uint64_t rows, const uint64_t *d_starts, const uint64_t *d_ends,
+                         uint64_t len, uint64_t count, uint64_t *d_row, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_rows_matching(void **state, const uint64_t *d_row, uint64_t count, uint64_t rows, uint32_t flags,
+                               uint64_t *d_rows_out, uint64_t *d_counts_out, uint64_t capacity, uint64_t *n_out, hipStream_t stream,
+                               char *err, size_t errlen);
+void bmx_internal_rows_free(void *state);
+float bmx_internal_rows_ms(const void *state);
+void bmx_internal_rows_last(const void *state, uint64_t out3[3]); // libbmx_exp.so only
 
 // ---- the context: the device, the switches and one opaque state per feature (made on first use and owned by the
 // feature's file; the exact search's eagerly) ----
@@ -233,6 +245,7 @@ struct bmx_ctx {
     void *index = nullptr;  // text index: status words, events, workspace of count / locate (bmx_index.hip)
     void *align = nullptr;  // alignments: status words, events, the launches' workspace (bmx_align.hip)
     int align_ws_kib = 0;   // libbmx_exp.so: > 0: one launch of the alignments takes at most this much workspace (KiB)
+    void *rows = nullptr;   // row-wise results: the split's ordered output, status words, events, workspace (bmx_rows.hip)
 };
 
 // ---- argument checks: every argument error, before any HIP call (the CPU suite calls the entries with ctx = NULL) ----
@@ -375,6 +388,27 @@ inline bool bmx_align_entries_ok(uint64_t n, uint64_t base_offset, uint64_t pat_
         if (m == 0 || m > BMX_ALIGN_MAX_PATTERN) return false;
     }
     return true;
+}
+
+// row-wise results: the split (text: host or device) ...
+inline bool bmx_rows_split_args_ok(const void *text, uint64_t n, const uint64_t *off, uint64_t capacity)
+{
+    return (n == 0 || text) && n < (1ull << 40) && (capacity == 0 || off);
+}
+// ... the row of every match: exactly one of {both lists, len == 0}, {starts, len >= 1}, {ends, len >= 1}
+inline bool bmx_rows_of_args_ok(const uint64_t *off, const uint64_t *starts, const uint64_t *ends, uint64_t len, uint64_t count,
+                                const uint64_t *row)
+{
+    if (count == 0) return true;
+    if (!off || !row || (!starts && !ends)) return false;
+    return (starts && ends) ? len == 0 : len >= 1;
+}
+// ... and the matching rows: no counts of rows that have none
+inline bool bmx_rows_matching_args_ok(const uint64_t *row, uint64_t count, uint32_t flags, const uint64_t *rows_out,
+                                      const uint64_t *counts_out, uint64_t capacity)
+{
+    if ((flags & ~BMX_ROWS_INVERT) || ((flags & BMX_ROWS_INVERT) && counts_out)) return false;
+    return (count == 0 || row) && (capacity == 0 || rows_out);
 }
 
 // a dictionary's patterns: BMX_ERR_ARG for NULL arrays or a count or length out of range, BMX_ERR_DOMAIN for a byte >= 0x80

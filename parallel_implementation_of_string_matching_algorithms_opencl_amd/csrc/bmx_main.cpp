@@ -196,7 +196,7 @@ int main(int argc, char **argv)
     uint32_t star_window = 0;
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
     std::string must_spec;
-    bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false;
+    bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false, lines_mode = false, lines_invert = false;
     uint64_t max_print = 32;
     uint32_t min_len = 0, max_occ = 0;
     for (int i = 1; i < argc; ++i) {
@@ -223,6 +223,8 @@ int main(int argc, char **argv)
         else if (a == "--best") spans_best = true;
         else if (a == "--cigar") cigar = true;
         else if (a == "--lcp") with_lcp = true;
+        else if (a == "--lines") lines_mode = true;
+        else if (a == "--invert") lines_invert = true;
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--index-count") index_path = need("--index-count");
         else if (a == "--index-seeds") seeds_path = need("--index-seeds");
@@ -305,6 +307,13 @@ int main(int argc, char **argv)
     }
     if ((gaps_longest && !gaps_starts) || (have_gaps && (have_classes || approx_k >= 0))) {
         fprintf(stderr, "--longest needs --starts; --gaps goes with neither --classes nor --approx\n");
+        return 2;
+    }
+
+    if ((lines_invert && !lines_mode) ||
+        (lines_mode && (hamming_k >= 0 || spans || gaps_starts || positions || ranges > 0 || gpus > 0 || !dict_path.empty() ||
+                        !index_path.empty() || !seeds_path.empty() || !sa_path.empty() || !ed_a.empty() || !edb_a.empty()))) {
+        fprintf(stderr, "--invert needs --lines; --lines goes with --pattern, --classes, --gaps, --regex, --regex-star and --approx K only\n");
         return 2;
     }
 
@@ -606,6 +615,82 @@ int main(int argc, char **argv)
     if (have_gaps && bmx_compile_gaps(gaps_expr.data(), gaps_expr.size(), class_flags, classes.data(), &gaps_optional, &m) != BMX_OK) {
         fprintf(stderr, "bad gapped pattern expression %s\n", gaps_expr.c_str());
         return 1;
+    }
+    if (lines_mode) { // the rows of the text that hold a match (or, --invert, none): row<TAB>count, 0-based
+        bmx_ctx *ctx = nullptr;
+        int rc = bmx_ctx_create(device, &ctx);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "no device %d: %d (%s)\n", device, rc, bmx_last_error());
+            return 1;
+        }
+        std::vector<uint64_t> off(n + 1);
+        uint64_t rows = 0, longest = 0, hits = 0, len = 0;
+        rc = bmx_rows_split(ctx, text.data(), n, '\n', off.data(), off.size(), &rows, &longest);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "bmx_rows_split failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        // every match as (start, end): the searches that report ends with the starts of their default rule
+        const uint64_t room = n ? n : 1;
+        std::vector<uint64_t> starts(room), ends(room);
+        std::vector<uint8_t> dist(approx_k >= 0 ? room : 1);
+        const char *what = "bmx_search";
+        if (have_regex) {
+            bmx_regex re;
+            if ((regex_star ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
+                            : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
+                fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
+                return 1;
+            }
+            // (the star search: a match longer than the longest row lies in no row)
+            const uint32_t window = (uint32_t)std::min<uint64_t>(BMX_MAX_REGEX_STAR_WINDOW, std::max<uint64_t>(longest, 1));
+            what = regex_star ? "bmx_search_regex_star_spans" : "bmx_search_regex_spans";
+            rc = regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, 0, starts.data(), ends.data(), room, &hits)
+                            : bmx_search_regex_spans(ctx, text.data(), n, &re, 0, starts.data(), ends.data(), room, &hits);
+        } else if (have_gaps) {
+            what = "bmx_search_gaps_spans";
+            rc = bmx_search_gaps_spans(ctx, text.data(), n, classes.data(), m, gaps_optional, 0, starts.data(), ends.data(), room, &hits);
+        } else if (approx_k >= 0) {
+            what = "bmx_search_approx_spans";
+            if (have_classes)
+                rc = bmx_search_approx_spans_classes(ctx, text.data(), n, classes.data(), m, approx_k, 0, starts.data(), ends.data(),
+                                                     dist.data(), room, &hits);
+            else if (m > BMX_MAX_APPROX_PATTERN)
+                rc = bmx_search_approx_long_spans(ctx, text.data(), n, pat.data(), m, approx_k, 0, starts.data(), ends.data(), dist.data(),
+                                                  room, &hits);
+            else
+                rc = bmx_search_approx_spans(ctx, text.data(), n, pat.data(), m, approx_k, 0, starts.data(), ends.data(), dist.data(), room,
+                                             &hits);
+        } else if (have_classes) {
+            what = "bmx_search_classes";
+            len = (uint64_t)m;
+            rc = bmx_search_classes(ctx, text.data(), n, classes.data(), m, starts.data(), room, &hits);
+        } else {
+            len = (uint64_t)m;
+            rc = bmx_search(ctx, text.data(), n, pat.data(), m, starts.data(), room, &hits);
+        }
+        if (rc != BMX_OK) {
+            fprintf(stderr, "%s failed: %d (%s)\n", what, rc, bmx_last_error());
+            return 1;
+        }
+        std::vector<uint64_t> row(hits ? hits : 1), out(rows ? rows : 1), counts(rows ? rows : 1);
+        uint64_t n_out = 0;
+        rc = bmx_rows_of(ctx, off.data(), rows, starts.data(), len ? nullptr : ends.data(), len, hits, row.data());
+        if (rc == BMX_OK)
+            rc = bmx_rows_matching(ctx, row.data(), hits, rows, lines_invert ? BMX_ROWS_INVERT : 0u, out.data(),
+                                   lines_invert ? nullptr : counts.data(), rows, &n_out);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "bmx_rows_of / bmx_rows_matching failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        for (uint64_t i = 0; i < n_out && i < max_print; ++i) {
+            if (lines_invert) printf("%llu\n", (unsigned long long)out[i]);
+            else printf("%llu\t%llu\n", (unsigned long long)out[i], (unsigned long long)counts[i]);
+        }
+        printf("lines %s: %llu of %llu (%llu matches, longest line %llu bytes)\n", lines_invert ? "without a match" : "with a match",
+               (unsigned long long)n_out, (unsigned long long)rows, (unsigned long long)hits, (unsigned long long)longest);
+        bmx_ctx_destroy(ctx);
+        return 0;
     }
     if (have_regex) {
         bmx_regex re;

@@ -115,6 +115,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_dict_state_free(ctx->dict);
     bmx_internal_index_state_free(ctx->index);
     bmx_internal_align_free(ctx->align);
+    bmx_internal_rows_free(ctx->rows);
     delete ctx;
 }
 
@@ -206,6 +207,37 @@ int bmx_lcp_stats_device(bmx_ctx *ctx, const int32_t *d_lcp, uint64_t n, uint32_
 
 float bmx_last_lcp_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_lcp_ms(ctx->lcp) : -1.0f; }
 int64_t bmx_last_lcp_long_pairs(bmx_ctx *ctx) { return ctx ? bmx_internal_lcp_long_pairs(ctx->lcp) : -1; }
+
+// ---- row-wise results (bmx_rows.hip) -------------------------------------------------------------
+int bmx_rows_split_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, uint8_t delim, uint64_t *d_off,
+                          uint64_t capacity, uint64_t *n_rows, uint64_t *longest, void *stream_v)
+{
+    if (!bmx_rows_split_args_ok(d_text, n, d_off, capacity) || !ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_rows_split(&ctx->rows, ctx->num_cu, d_text, n, base_offset, delim, d_off, capacity, n_rows, longest,
+                                   (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_rows_of_device(bmx_ctx *ctx, const uint64_t *d_off, uint64_t rows, const uint64_t *d_starts, const uint64_t *d_ends,
+                       uint64_t len, uint64_t count, uint64_t *d_row, void *stream_v)
+{
+    if (!bmx_rows_of_args_ok(d_off, d_starts, d_ends, len, count, d_row)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_rows_of(&ctx->rows, d_off, rows, d_starts, d_ends, len, count, d_row, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_rows_matching_device(bmx_ctx *ctx, const uint64_t *d_row, uint64_t count, uint64_t rows, uint32_t flags, uint64_t *d_rows_out,
+                             uint64_t *d_counts_out, uint64_t capacity, uint64_t *n_out, void *stream_v)
+{
+    if (!bmx_rows_matching_args_ok(d_row, count, flags, d_rows_out, d_counts_out, capacity) || !ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_rows_matching(&ctx->rows, d_row, count, rows, flags, d_rows_out, d_counts_out, capacity, n_out,
+                                      (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_rows_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_rows_ms(ctx->rows) : -1.0f; }
 
 // ---- approximate search (bmx_approx.hip) -------------------------------------------------------
 int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
@@ -663,7 +695,10 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "regex") state = ctx->regex;
     else if (k == "regex_star") state = ctx->regex_star;
     else if (k == "dict") state = ctx->dict;
-    else return BMX_ERR_ARG;
+    else if (k == "rows") { // (its own state: the tile is fixed, so out3[0] is log2 of its bytes)
+        bmx_internal_rows_last(ctx->rows, out3);
+        return BMX_OK;
+    } else return BMX_ERR_ARG;
     bmx::ordered_last_launch(state, out3);
     return BMX_OK;
 }

@@ -70,6 +70,8 @@ CIGAR_DEL = 2
 CIGAR_EQ = 7
 CIGAR_X = 8
 _CIGAR_CHARS = "MIDNSHP=X"
+ROW_NONE = 0xFFFFFFFFFFFFFFFF  # the row of a match that lies in no row (BMX_ROW_NONE); -1 in the int64 tensors of Rows.of
+ROWS_INVERT = 1  # Rows.matching: the rows without an entry (BMX_ROWS_INVERT)
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -271,6 +273,17 @@ SYMBOLS = [
                             C.c_uint64, _u64p]),
     ("bmx_last_align_ms", C.c_float, [C.c_void_p]),
     ("bmx_last_align_launches", C.c_int64, [C.c_void_p]),
+    ("bmx_rows_split_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, _u64p,
+                                        _u64p, C.c_void_p]),
+    ("bmx_rows_of_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                     C.c_void_p]),
+    ("bmx_rows_matching_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_last_rows_ms", C.c_float, [C.c_void_p]),
+    ("bmx_rows_split", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, _u64p, _u64p]),
+    ("bmx_rows_of", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    ("bmx_rows_matching", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                    _u64p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     ("bmx_plant_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, _u64p,
                                    C.c_uint64, C.c_void_p]),
@@ -537,7 +550,8 @@ class Context:
 
     def last_launch(self, session: str) -> Tuple[int, int, int]:
         """libbmx_exp.so only (bmx_exp_last_launch): (piece shift, workgroups, tiles) of the last launch of the session
-        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_star" or "dict"."""
+        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_star" or "dict"; "rows": (log2 of the bytes
+        of a tile, workgroups, tiles) of the last rows_split_device."""
         out = (C.c_uint64 * 3)()
         self._chk(self._L.bmx_exp_last_launch(self._h, session.encode(), out), "bmx_exp_last_launch")
         return int(out[0]), int(out[1]), int(out[2])
@@ -1687,6 +1701,98 @@ class Context:
         """Pairs of the last lcp_array_device whose common prefix exceeded LCP_LANE_BYTES."""
         return int(self._L.bmx_last_lcp_long_pairs(self._h))
 
+    # -- row-wise results: lines of a text, the row of each match, the matching rows ------
+    def rows_split_device(self, d_text, delim: int = 10, n: Optional[int] = None, base_offset: int = 0, *, out=None,
+                          capacity: Optional[int] = None, stream=None) -> "Rows":
+        """The rows of the view ``d_text[0:n)`` split at the byte ``delim`` (bmx_rows_split_device): a Rows over count + 1
+        ascending offsets, offsets[0] = base_offset, a row holding its terminating delimiter as its last byte, no extra
+        empty row behind a final delimiter.  ``out``: int64/uint64 CUDA tensor for the offsets (allocated if None, for
+        ``capacity`` entries or a guess); where it is too small the call runs once more with the exact size, unless
+        ``capacity`` was given: then BmxError(ERR_CAPACITY).  ``stream``: a torch.cuda.Stream (None: torch's current one)."""
+        import torch
+
+        if n is None:
+            n = d_text.numel()
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(d_text.device)).cuda_stream)
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else max(1 << 12, n // 64 + 2), 1), dtype=torch.int64,
+                              device=d_text.device)
+        while True:
+            cap = out.numel() if capacity is None else min(capacity, out.numel())
+            rows, longest = C.c_uint64(0), C.c_uint64(0)
+            rc = self._L.bmx_rows_split_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, int(delim) & 0xFF,
+                                               C.c_void_p(out.data_ptr()), cap, C.byref(rows), C.byref(longest), s)
+            if rc == ERR_CAPACITY and capacity is None:
+                out = torch.empty(int(rows.value) + 1, dtype=out.dtype, device=d_text.device)
+                continue
+            self._chk(rc, "bmx_rows_split_device")
+            return Rows(self, out[: int(rows.value) + 1], int(longest.value))
+
+    def rows(self, offsets) -> "Rows":
+        """A Rows over a caller's offsets: an int64/uint64 CUDA tensor of rows + 1 ascending entries, in the coordinates of
+        the match lists (the offsets of a string column, say; empty rows are legal)."""
+        if offsets.element_size() != 8 or offsets.numel() < 1:
+            raise ValueError("offsets: at least one 8-byte entry")
+        return Rows(self, offsets)
+
+    def grep_device(self, d_text, expr, kind: str = "regex", rows: Optional["Rows"] = None, delim: int = 10, invert: bool = False,
+                    flags: int = 0, k: int = 0, window: Optional[int] = None):
+        """The rows of the resident text ``d_text`` that hold a match of ``expr``, ascending, and each one's number of
+        matches: (rows, counts) as int64 CUDA tensors (grep -n / -c); with ``invert`` the rows that hold none and None
+        (grep -v).  ``kind``: exact | classes | hamming | gaps | regex | regex_star | approx, the search that reads ``expr``
+        (``flags`` are its compile flags, ``k`` the mismatches or edits of hamming and approx).  ``rows``: a Rows in the
+        view's coordinates (base_offset 0), or None for the lines of the text split at ``delim``.  Runs the existing search,
+        for the kinds that report ends the existing starts post-pass with its default flags (the largest start of an
+        end, so a row holds a match that ends at e iff it holds this one), then Rows.of and Rows.matching.  A match that
+        runs across a row boundary counts for no row; `.` matches the delimiter too, so write ``[^\\x0a]*`` for ``.*`` on
+        lines.  regex_star: the starts come from a window of min(MAX_REGEX_STAR_WINDOW, rows.longest) bytes (or ``window``);
+        an end whose shortest match is longer than the window is not attributed to any row."""
+        import torch
+
+        if rows is None:
+            rows = self.rows_split_device(d_text, delim)
+
+        def complete(call):  # call(out) -> (list, ..., total): once more with room for all where the first guess was short
+            res = call(None)
+            if res[-1] > res[0].numel():
+                res = call(torch.empty(res[-1], dtype=torch.int64, device=d_text.device))
+            return res
+
+        if kind == "exact":
+            starts, _ = complete(lambda out: self.search_device(d_text, expr, out=out))
+            ids = rows.of(starts=starts, length=len(_pat_bytes(expr)))
+        elif kind == "classes":
+            cls = _classes(expr, flags)
+            starts, _ = complete(lambda out: self.search_classes_device(d_text, cls, out=out))
+            ids = rows.of(starts=starts, length=cls.shape[0])
+        elif kind == "hamming":
+            pat, cls = self._hamming_pattern(expr, flags)
+            starts, _, _ = complete(lambda out: self.search_hamming_device(d_text, expr, k, flags=flags, out=out))
+            ids = rows.of(starts=starts, length=len(pat) if pat is not None else cls.shape[0])
+        elif kind == "gaps":
+            pair = _gaps(expr, flags)
+            ends, _ = complete(lambda out: self.search_gaps_device(d_text, pair, out=out))
+            ids = rows.of(starts=self.gaps_starts_device(d_text, pair, ends), ends=ends)
+        elif kind == "regex":
+            re_ = _regex(expr, flags)
+            ends, _ = complete(lambda out: self.search_regex_device(d_text, re_, out=out))
+            ids = rows.of(starts=self.regex_starts_device(d_text, re_, ends), ends=ends)
+        elif kind == "regex_star":
+            re_ = _regex(expr, flags, star=True)
+            ends, _ = complete(lambda out: self.search_regex_star_device(d_text, re_, out=out))
+            w = window if window is not None else min(MAX_REGEX_STAR_WINDOW, max(rows.longest, 1))
+            ids = rows.of(starts=self.regex_star_starts_device(d_text, re_, ends, window=w), ends=ends)
+        elif kind == "approx":
+            ends, dist, _ = complete(lambda out: self.search_approx_device(d_text, expr, k, out=out))
+            starts = self.approx_spans_device(d_text, expr, k, ends, dist)[0]
+            ids = rows.of(starts=starts, ends=ends)
+        else:
+            raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_star | approx")
+        return rows.matching(ids, invert=invert)
+
+    def last_rows_ms(self) -> float:
+        return float(self._L.bmx_last_rows_ms(self._h))
+
     # -- synthetic corpus in HBM ------------------------------------------
     def gen_text(self, d_dst, start: int, seed: int, kind: int = 0, length: Optional[int] = None):
         import torch
@@ -1705,6 +1811,69 @@ class Context:
         stream = C.c_void_p(torch.cuda.current_stream(d_dst.device).cuda_stream)
         self._chk(self._L.bmx_plant_device(self._h, C.c_void_p(d_dst.data_ptr()), start, length, pat, len(pat),
                                       off.ctypes.data_as(_u64p), off.size, stream), "bmx_plant_device")
+
+
+class Rows:
+    """The rows of a text or of a string column on one context's device: ``offsets`` (count + 1 ascending entries, an
+    int64/uint64 CUDA tensor; row r is the byte range [offsets[r], offsets[r + 1])), ``count`` and ``longest``, the longest
+    row in bytes.  Context.rows_split_device and Context.rows make one."""
+
+    def __init__(self, ctx: "Context", offsets, longest: Optional[int] = None):
+        self._ctx = ctx
+        self.offsets = offsets
+        self.count = offsets.numel() - 1
+        self._longest = longest
+
+    @property
+    def longest(self) -> int:
+        if self._longest is None:
+            self._longest = int((self.offsets[1:] - self.offsets[:-1]).max().item()) if self.count > 0 else 0
+        return self._longest
+
+    def of(self, starts=None, ends=None, length: int = 0, *, stream=None):
+        """The row of every match (bmx_rows_of_device), an int64 tensor, -1 (ROW_NONE) for a match that lies in no row or
+        runs across a boundary: ``starts`` and ``ends`` (the last byte of a match, as the searches report it), or one of
+        them and the ``length`` of every match.  CUDA tensors of 8-byte entries in the coordinates of the offsets."""
+        import torch
+
+        lst = starts if starts is not None else ends
+        if lst is None:
+            raise ValueError("starts, ends or both")
+        for t in (starts, ends):
+            if t is not None and (t.element_size() != 8 or t.numel() != lst.numel()):
+                raise ValueError("starts, ends: 8-byte entries, as many of one as of the other")
+        count = lst.numel()
+        row = torch.empty(max(count, 1), dtype=torch.int64, device=self.offsets.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.offsets.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self._ctx._L.bmx_rows_of_device(self._ctx._h, ptr(self.offsets), self.count, ptr(starts), ptr(ends), int(length),
+                                             count, ptr(row), C.c_void_p(s.cuda_stream))
+        self._ctx._chk(rc, "bmx_rows_of_device")
+        return row[:count]
+
+    def matching(self, row_ids, invert: bool = False, *, counts: bool = True, capacity: Optional[int] = None, stream=None):
+        """(rows, counts): the distinct rows of ``row_ids`` (as Rows.of returns them for a list with ascending ends), ascending,
+        and each one's number of entries (None with ``counts`` False); with ``invert`` (rows, None), the rows that have no
+        entry (bmx_rows_matching_device).  int64 CUDA tensors.  ``capacity``: room for that many rows (default: for all
+        there can be); fewer than there are raises BmxError(ERR_CAPACITY)."""
+        import torch
+
+        if row_ids.element_size() != 8:
+            raise ValueError("row_ids: 8-byte entries")
+        count = row_ids.numel()
+        dev = self.offsets.device
+        cap = capacity if capacity is not None else (self.count if invert else min(count, self.count))
+        out = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        cnt = torch.empty(max(cap, 1), dtype=torch.int64, device=dev) if counts and not invert else None
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        total = C.c_uint64(0)
+        rc = self._ctx._L.bmx_rows_matching_device(self._ctx._h, C.c_void_p(row_ids.data_ptr()), count, self.count,
+                                                   ROWS_INVERT if invert else 0, C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(cnt.data_ptr()) if cnt is not None else None, cap, C.byref(total),
+                                                   C.c_void_p(s.cuda_stream))
+        self._ctx._chk(rc, "bmx_rows_matching_device")
+        t = int(total.value)
+        return out[:t], (cnt[:t] if cnt is not None else None)
 
 
 def _dict_arrays(patterns):
@@ -2192,6 +2361,38 @@ def search_regex_star(text, expr, flags: int = 0, spans: bool = False, longest: 
     ``longest`` of the longest such (UINT64_MAX where there is none)."""
     ctx = default_context()
     return ctx.search_regex_star_spans(text, expr, flags, longest, window) if spans else ctx.search_regex_star(text, expr, flags)
+
+
+def rows_split(text, delim: int = 10) -> Tuple[np.ndarray, int]:
+    """(text, delimiter byte) -> (offsets uint64, longest row): the rows of a host text (bmx_rows_split); offsets has
+    rows + 1 entries."""
+    L = lib()
+    tptr, n, keep = _host_text(text)
+    cap = max(1 << 12, n // 64 + 2)
+    while True:
+        off = np.empty(cap, dtype=np.uint64)
+        rows, longest = C.c_uint64(0), C.c_uint64(0)
+        rc = L.bmx_rows_split(default_context()._h if n else None, tptr, n, int(delim) & 0xFF, C.c_void_p(off.ctypes.data), cap,
+                              C.byref(rows), C.byref(longest))
+        if rc == ERR_CAPACITY:
+            cap = int(rows.value) + 1
+            continue
+        _check(rc, "bmx_rows_split")
+        del keep
+        return off[: int(rows.value) + 1].copy(), int(longest.value)
+
+
+def grep(text, expr, **kw) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """(text, expression) -> (rows, counts) as int64 arrays: the lines of a host text that hold a match and each one's number
+    of matches, or with ``invert=True`` the lines that hold none and None.  The keywords are Context.grep_device's."""
+    import torch
+
+    ctx = default_context()
+    _, _, keep = _host_text(text)
+    buf = np.frombuffer(keep, dtype=np.uint8) if isinstance(keep, bytes) else keep.reshape(-1)
+    d_text = torch.from_numpy(buf.copy()).cuda()
+    rows, counts = ctx.grep_device(d_text, expr, **kw)
+    return rows.cpu().numpy(), (counts.cpu().numpy() if counts is not None else None)
 
 
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
