@@ -1181,6 +1181,79 @@ int bmx_rows_of(bmx_ctx *ctx /* NULL: device 0 */, const uint64_t *off, uint64_t
 int bmx_rows_matching(bmx_ctx *ctx /* NULL: device 0 */, const uint64_t *row, uint64_t count, uint64_t rows, uint32_t flags,
                       uint64_t *rows_out, uint64_t *counts_out /* may be NULL */, uint64_t capacity, uint64_t *n_out);
 
+/* ---- non-overlapping match selection, replace and extract on device lists ---- */
+
+/* The searches report every end of a match, so their occurrences overlap: `aa` in `aaaa` gives three.  These post-passes
+ * pick "the non-overlapping matches, left to right" from such a list (re.finditer, bytes.count), and replace the spans
+ * picked by a literal (re.sub, sed s/x/y/g, str.replace) or copy them out as a string column (grep -o, re.findall).
+ *
+ * Spans.  [s, e], e the last byte, in the three input forms of bmx_rows_of_device: both lists and len == 0; only d_starts
+ * and len >= 1; only d_ends and len >= 1.  The selection SKIPS an entry -- never takes it, never an error -- whose start
+ * (or end) is UINT64_MAX, whose end is below its start or below len - 1, or for which d_row (may be NULL; what
+ * bmx_rows_of_device returned for the same entries) holds BMX_ROW_NONE: so a match across a line break stays out of a
+ * per-line replace.
+ *
+ * bmx_spans_select_device, flags 0 (disjoint).  Walk the list in its order and take an entry iff its start is greater
+ * than the end of the last entry taken; the first entry that is not skipped is taken.  The list must satisfy
+ * s[i] <= e[j] for all non-skipped i < j: non-decreasing ends (every search's list) do, non-decreasing starts (the
+ * dictionary search's) do as well.  A violation raises a status word: BMX_ERR_ARG, outputs unspecified.  For
+ * non-decreasing ends this is earliest-end-first, the largest possible set of pairwise disjoint matches; for lists of one
+ * length (exact, class, Hamming) it is exactly what re.finditer / bytes.count give.  For variable-length expressions with
+ * the default (largest) starts it selects LEFTMOST-SHORTEST matches: `[0-9]+` selects single digits.  POSIX
+ * leftmost-longest needs the longest match per start, a search over the reversed text, which is not part of the library;
+ * the rule covers such a list, which is sorted by start.
+ * BMX_SELECT_MERGE.  Needs non-decreasing ends (else BMX_ERR_ARG).  The output is the connected regions of the union of the
+ * spans, ascending: a region begins at entry j iff the smallest start among entries j.. exceeds the largest end among
+ * entries ..j-1, and runs from that smallest start to the last end before the next cut.  Overlapping spans merge,
+ * abutting spans do not.  With LONGEST starts (the smallest start of every end) the regions are the bytes that belong to
+ * at least one match: `[0-9]+` yields the maximal digit runs, the redaction semantics.
+ * d_index_out (may be NULL): the list index of every entry taken, with MERGE of every region's first entry.
+ *
+ * bmx_replace_device.  d_starts / d_ends / len: `count` ascending, pairwise disjoint spans inside
+ * [base_offset, base_offset + n) (a selection's output is one).  d_out receives the n bytes at d_text with every span's
+ * bytes replaced by the repl_len bytes at `repl` (host memory, 0 <= repl_len <= BMX_MAX_REPLACEMENT, no back-references):
+ * n' = n - sum(span lengths) + count * repl_len bytes.  Spans that are not ascending and disjoint, or that reach outside
+ * the view, raise a status word: BMX_ERR_ARG.  d_out must not overlap d_text (BMX_ERR_ARG).
+ * bmx_extract_device.  The same spans; d_blob receives their bytes one after the other and d_off the count + 1 offsets into
+ * it (always all of them): the column layout of bmx_edit_distance_batch and bmx_index_*.
+ *
+ * Capacity (entries for the selection, bytes for the other two): the true size always goes to *n_out; capacity 0 only
+ * counts and returns BMX_OK; a smaller non-zero capacity stores the lowest `capacity` entries or bytes and returns
+ * BMX_ERR_CAPACITY.  BMX_ERR_ARG before any HIP call, with ctx == NULL too: NULL where a pointer is needed, contradictory
+ * list / len combinations, unknown flags, n >= 2^40, count >= 2^32, repl_len > BMX_MAX_REPLACEMENT.  count == 0 launches
+ * nothing: the selection returns 0 entries, replace copies the text, extract writes the single offset 0.  Every launch,
+ * copy and memset goes on `stream`, and the call returns after synchronising it; workspace stays with the context.  No
+ * byte is read outside the aligned 16-byte lines that hold text[0..n).
+ * Method (csrc/bmx_subst_kernel.h): with key = s + 1 (0: skipped) and PM its prefix maximum, the list is in order iff
+ * PM[j-1] <= e[j] + 1, and the entry taken after j is the first i with PM[i] > e[j] + 1; the chain of these successors is
+ * resolved by pointer jumping in tiles of T entries, level by level (no lane follows more than T pointers per level, the
+ * levels grow with log_T count), then marked top down, counted and filled in order.  Replace and extract are one kernel
+ * driven by the output: a lane owns aligned 16-byte lines of it, finds its piece by a search the wave bounds, and where the
+ * line lies in one piece of text reads two aligned source lines, funnel-shifts them and stores 16 bytes.
+ * bmx_last_subst_ms: HIP events around the launches of the last of the three; < 0 if none. */
+#define BMX_SELECT_MERGE 1u
+#define BMX_MAX_REPLACEMENT 65536u
+int bmx_spans_select_device(bmx_ctx *ctx, const uint64_t *d_starts /* or NULL */, const uint64_t *d_ends /* or NULL */,
+                            uint64_t len, uint64_t count, const uint64_t *d_row /* may be NULL */, uint32_t flags,
+                            uint64_t *d_starts_out, uint64_t *d_ends_out, uint64_t *d_index_out /* may be NULL */,
+                            uint64_t capacity, uint64_t *n_out, void *stream);
+int bmx_replace_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_starts,
+                       const uint64_t *d_ends, uint64_t len, uint64_t count, const void *repl /* host */, uint64_t repl_len,
+                       void *d_out, uint64_t capacity /* bytes */, uint64_t *n_out, void *stream);
+int bmx_extract_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_starts,
+                       const uint64_t *d_ends, uint64_t len, uint64_t count, void *d_blob, uint64_t capacity /* bytes */,
+                       uint64_t *d_off /* count + 1 */, uint64_t *n_out, void *stream);
+float bmx_last_subst_ms(bmx_ctx *ctx);
+/* host buffers in, host buffers out, base_offset 0: upload, the device entry, download.  The same arguments, checks and
+ * return codes (an output that overlaps the text is BMX_ERR_ARG here too). */
+int bmx_spans_select(bmx_ctx *ctx /* NULL: device 0 */, const uint64_t *starts /* or NULL */, const uint64_t *ends /* or NULL */,
+                     uint64_t len, uint64_t count, const uint64_t *row /* may be NULL */, uint32_t flags, uint64_t *starts_out,
+                     uint64_t *ends_out, uint64_t *index_out /* may be NULL */, uint64_t capacity, uint64_t *n_out);
+int bmx_replace(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint64_t *starts, const uint64_t *ends,
+                uint64_t len, uint64_t count, const void *repl, uint64_t repl_len, void *out, uint64_t capacity, uint64_t *n_out);
+int bmx_extract(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint64_t *starts, const uint64_t *ends,
+                uint64_t len, uint64_t count, void *blob, uint64_t capacity, uint64_t *off /* count + 1 */, uint64_t *n_out);
+
 /* ---- synthetic corpus, generated in HBM ---------------------- */
 
 /* d_dst[j] = byte (start + j) of the counter-based splitmix64 stream;

@@ -31,7 +31,9 @@ extern "C" {
  * the first launch even when nothing is tainted), "regex_star_piece_shift" (0, or 4..12: log2 of the ends per lane of THAT
  * search, in front of "tile_piece_shift"; 4 and 5 make chains of pieces that cross tiles and workgroups on texts of a few
  * KiB) and "regex_star_warm" (0 = the rule, else the bytes of the pair warm-up, a multiple of 16 up to 65,536).
- * BMX_ERR_ARG for an unknown name, a negative "ordered_seq" or "tile_max_grid" and a "tile_piece_shift",
+ * "select_tile_shift": 0 = the production tile of bmx_spans_select_device (T = 2^8 entries), else 3..8 = log2 T, from the
+ * context's next selection on: lists of a few hundred entries then reach three levels of its pointer jumping.
+ * BMX_ERR_ARG for an unknown name, a "select_tile_shift" outside that range, a negative "ordered_seq" or "tile_max_grid" and a "tile_piece_shift",
  * "regex_star_piece_shift" or "regex_star_warm" outside those ranges. */
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
 
@@ -42,6 +44,8 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
  * "rows": the last bmx_rows_split_device, out3 = {log2 of the bytes of a tile, workgroups started, tiles}; a workgroup is
  * eight waves, each with an eighth of the tile, read in batches of eight rounds of 1 KiB (the first entry is there
  * before any split).
+ * "select": the last bmx_spans_select_device, out3 = {log2 T, levels of pointer jumping (0: at most T entries, or
+ * BMX_SELECT_MERGE), tiles of T entries}.
  * BMX_ERR_ARG for another name. */
 int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3);
 

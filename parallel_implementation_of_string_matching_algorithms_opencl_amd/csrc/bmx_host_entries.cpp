@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "bmx.h"
@@ -272,6 +273,83 @@ int bmx_rows_matching(bmx_ctx *ctx_in, const uint64_t *row, uint64_t count, uint
     if (n_out) *n_out = total;
     if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
     return c.rc;
+}
+
+int bmx_spans_select(bmx_ctx *ctx_in, const uint64_t *starts, const uint64_t *ends, uint64_t len, uint64_t count, const uint64_t *row,
+                     uint32_t flags, uint64_t *starts_out, uint64_t *ends_out, uint64_t *index_out, uint64_t capacity, uint64_t *n_out)
+{
+    if (!bmx_select_args_ok(starts, ends, len, count, flags, starts_out, ends_out, capacity, n_out)) return BMX_ERR_ARG;
+    *n_out = 0;
+    if (count == 0) return BMX_OK;
+    HostCall c("bmx_spans_select", ctx_in);
+    const uint64_t dev_cap = std::min(capacity, count); // (no list has more entries taken than entries)
+    const uint64_t *d_starts = starts ? c.upload<uint64_t>(starts, count * sizeof(uint64_t)) : nullptr;
+    const uint64_t *d_ends = ends ? c.upload<uint64_t>(ends, count * sizeof(uint64_t)) : nullptr;
+    const uint64_t *d_row = row ? c.upload<uint64_t>(row, count * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_so = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_eo = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_io = dev_cap && index_out ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    uint64_t total = 0;
+    c.rc = bmx_spans_select_device(c.ctx(), d_starts, d_ends, len, count, d_row, flags, d_so, d_eo, d_io, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap) * sizeof(uint64_t);
+    c.download(starts_out, d_so, stored, "the starts taken");
+    c.download(ends_out, d_eo, stored, "the ends taken");
+    if (d_io) c.download(index_out, d_io, stored, "their indices");
+    *n_out = total;
+    return c.rc;
+}
+
+namespace {
+// replace (off == NULL) and extract over host buffers
+int subst_copy_host(const char *entry, bmx_ctx *ctx_in, const char *text, uint64_t n, const uint64_t *starts, const uint64_t *ends,
+                    uint64_t len, uint64_t count, const void *repl, uint64_t repl_len, void *out, uint64_t capacity, uint64_t *off,
+                    uint64_t *n_out)
+{
+    const bool extract = off != nullptr;
+    *n_out = 0;
+    if (count == 0) { // no span: the text itself, or the single offset 0; no device is touched
+        if (extract) {
+            off[0] = 0;
+            return BMX_OK;
+        }
+        *n_out = n;
+        if (capacity) memcpy(out, text, std::min(n, capacity));
+        return capacity && n > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+    }
+    HostCall c(entry, ctx_in);
+    const uint64_t most = extract ? n : n + count * repl_len; // (spans inside the text: no output is longer)
+    const uint64_t dev_cap = std::min(capacity, most);
+    void *d_text = n ? c.upload(text, n) : nullptr;
+    const uint64_t *d_starts = starts ? c.upload<uint64_t>(starts, count * sizeof(uint64_t)) : nullptr;
+    const uint64_t *d_ends = ends ? c.upload<uint64_t>(ends, count * sizeof(uint64_t)) : nullptr;
+    void *d_out = dev_cap ? c.alloc(dev_cap) : nullptr;
+    uint64_t *d_off = extract ? c.alloc<uint64_t>((count + 1) * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    uint64_t total = 0;
+    if (extract) c.rc = bmx_extract_device(c.ctx(), d_text, n, 0, d_starts, d_ends, len, count, d_out, dev_cap, d_off, &total, nullptr);
+    else c.rc = bmx_replace_device(c.ctx(), d_text, n, 0, d_starts, d_ends, len, count, repl, repl_len, d_out, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(out, d_out, std::min(total, dev_cap), "the output");
+    if (extract) c.download(off, d_off, (count + 1) * sizeof(uint64_t), "the offsets");
+    *n_out = total;
+    return c.rc;
+}
+} // namespace
+
+int bmx_replace(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint64_t *starts, const uint64_t *ends, uint64_t len, uint64_t count,
+                const void *repl, uint64_t repl_len, void *out, uint64_t capacity, uint64_t *n_out)
+{
+    if (!bmx_subst_copy_args_ok(text, n, starts, ends, len, count, repl, repl_len, out, capacity, false, nullptr, n_out)) return BMX_ERR_ARG;
+    return subst_copy_host("bmx_replace", ctx_in, text, n, starts, ends, len, count, repl, repl_len, out, capacity, nullptr, n_out);
+}
+
+int bmx_extract(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint64_t *starts, const uint64_t *ends, uint64_t len, uint64_t count,
+                void *blob, uint64_t capacity, uint64_t *off, uint64_t *n_out)
+{
+    if (!bmx_subst_copy_args_ok(text, n, starts, ends, len, count, nullptr, 0, blob, capacity, true, off, n_out)) return BMX_ERR_ARG;
+    return subst_copy_host("bmx_extract", ctx_in, text, n, starts, ends, len, count, nullptr, 0, blob, capacity, off, n_out);
 }
 
 int bmx_lcp_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out, int32_t *lcp_out)

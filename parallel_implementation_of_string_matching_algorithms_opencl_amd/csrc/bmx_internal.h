@@ -214,6 +214,16 @@ int bmx_internal_rows_matching(void **state, const uint64_t *d_row, uint64_t cou
 void bmx_internal_rows_free(void *state);
 float bmx_internal_rows_ms(const void *state);
 void bmx_internal_rows_last(const void *state, uint64_t out3[3]); // libbmx_exp.so only
+// bmx_subst.hip (tile_shift: 0, or log2 of the selection's tile -- libbmx_exp.so's knob; the copy: d_off NULL = replace)
+int bmx_internal_select(void **state, int tile_shift, const uint64_t *d_starts, const uint64_t *d_ends, uint64_t len, uint64_t count,
+                        const uint64_t *d_row, uint32_t flags, uint64_t *d_starts_out, uint64_t *d_ends_out, uint64_t *d_index_out,
+                        uint64_t capacity, uint64_t *n_out, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_subst_copy(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_starts,
+                            const uint64_t *d_ends, uint64_t len, uint64_t count, const void *repl, uint64_t repl_len, void *d_out,
+                            uint64_t capacity, uint64_t *d_off, uint64_t *n_out, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_subst_free(void *state);
+float bmx_internal_subst_ms(const void *state);
+void bmx_internal_subst_last(const void *state, uint64_t out3[3]); // libbmx_exp.so only
 
 // ---- the context: the device, the switches and one opaque state per feature (made on first use and owned by the
 // feature's file; the exact search's eagerly) ----
@@ -246,6 +256,8 @@ struct bmx_ctx {
     void *align = nullptr;  // alignments: status words, events, the launches' workspace (bmx_align.hip)
     int align_ws_kib = 0;   // libbmx_exp.so: > 0: one launch of the alignments takes at most this much workspace (KiB)
     void *rows = nullptr;   // row-wise results: the split's ordered output, status words, events, workspace (bmx_rows.hip)
+    void *subst = nullptr;  // selection, replace, extract: status words, events, workspace, the replacement (bmx_subst.hip)
+    int select_tile_shift = 0; // libbmx_exp.so: 0, or log2 of the selection's tile (3..8) in place of the production one
 };
 
 // ---- argument checks: every argument error, before any HIP call (the CPU suite calls the entries with ctx = NULL) ----
@@ -409,6 +421,36 @@ inline bool bmx_rows_matching_args_ok(const uint64_t *row, uint64_t count, uint3
 {
     if ((flags & ~BMX_ROWS_INVERT) || ((flags & BMX_ROWS_INVERT) && counts_out)) return false;
     return (count == 0 || row) && (capacity == 0 || rows_out);
+}
+
+// selection, replace and extract: a list in one of the three forms of bmx_rows_of_device
+inline bool bmx_span_list_ok(const uint64_t *starts, const uint64_t *ends, uint64_t len, uint64_t count)
+{
+    if (count >= (1ull << 32)) return false;
+    if (count == 0) return true;
+    if (!starts && !ends) return false;
+    return (starts && ends) ? len == 0 : len >= 1;
+}
+inline bool bmx_select_args_ok(const uint64_t *starts, const uint64_t *ends, uint64_t len, uint64_t count, uint32_t flags,
+                               const uint64_t *starts_out, const uint64_t *ends_out, uint64_t capacity, const uint64_t *n_out)
+{
+    if ((flags & ~BMX_SELECT_MERGE) || !n_out) return false;
+    return bmx_span_list_ok(starts, ends, len, count) && (capacity == 0 || (starts_out && ends_out));
+}
+// ... the copy (text and out: host or device; off: the offsets of an extract, NULL for a replace).  A device output must
+// not overlap the text.
+inline bool bmx_subst_copy_args_ok(const void *text, uint64_t n, const uint64_t *starts, const uint64_t *ends, uint64_t len,
+                                   uint64_t count, const void *repl, uint64_t repl_len, const void *out, uint64_t capacity,
+                                   bool extract, const uint64_t *off, const uint64_t *n_out)
+{
+    if ((n > 0 && !text) || n >= (1ull << 40) || !n_out || (capacity > 0 && !out) || (extract && !off)) return false;
+    if (repl_len > BMX_MAX_REPLACEMENT || (repl_len > 0 && !repl)) return false;
+    if (!bmx_span_list_ok(starts, ends, len, count)) return false;
+    if (n > 0 && capacity > 0) {
+        const uintptr_t t = reinterpret_cast<uintptr_t>(text), o = reinterpret_cast<uintptr_t>(out);
+        if (t < o + capacity && o < t + n) return false;
+    }
+    return true;
 }
 
 // a dictionary's patterns: BMX_ERR_ARG for NULL arrays or a count or length out of range, BMX_ERR_DOMAIN for a byte >= 0x80

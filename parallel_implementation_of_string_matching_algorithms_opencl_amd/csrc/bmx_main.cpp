@@ -96,6 +96,13 @@
 //                             communicators and the text set up once (bmx_multi_*), `iters` searches on
 //                             the resident shards, each list checked against the one-GPU list; then once
 //                             through the host-buffer entry point bmx_search_multi
+//   bmx_cli (--replace STR | --only-matching) [--merge] [--lines] [--out F] [--max-print K] with --pattern, --classes,
+//           --gaps, --regex, --regex-star or --approx K
+//                             the non-overlapping matches, left to right (bmx_spans_select; --merge: the regions of the
+//                             union of the longest match of every end), replaced by STR (bmx_replace: the new text on
+//                             stdout or in F, a total line on stderr: sed s/x/STR/g) or printed one per line
+//                             (bmx_extract, at most --max-print of them: grep -o); with --lines a match that crosses a
+//                             line break is left alone
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -197,6 +204,8 @@ int main(int argc, char **argv)
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
     std::string must_spec;
     bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false, lines_mode = false, lines_invert = false;
+    bool have_replace = false, only_matching = false, select_merge = false; // --replace STR, --only-matching, --merge, --out F
+    std::string replace_str, out_path;
     uint64_t max_print = 32;
     uint32_t min_len = 0, max_occ = 0;
     for (int i = 1; i < argc; ++i) {
@@ -224,6 +233,10 @@ int main(int argc, char **argv)
         else if (a == "--cigar") cigar = true;
         else if (a == "--lcp") with_lcp = true;
         else if (a == "--lines") lines_mode = true;
+        else if (a == "--replace") have_replace = true, replace_str = need("--replace");
+        else if (a == "--only-matching") only_matching = true;
+        else if (a == "--merge") select_merge = true;
+        else if (a == "--out") out_path = need("--out");
         else if (a == "--invert") lines_invert = true;
         else if (a == "--dict") dict_path = need("--dict");
         else if (a == "--index-count") index_path = need("--index-count");
@@ -310,10 +323,16 @@ int main(int argc, char **argv)
         return 2;
     }
 
+    const bool subst_mode = have_replace || only_matching;
+    if ((have_replace && only_matching) || ((select_merge || !out_path.empty()) && !subst_mode) || (subst_mode && lines_invert) ||
+        replace_str.size() > BMX_MAX_REPLACEMENT) {
+        fprintf(stderr, "--replace STR (at most 65536 bytes) or --only-matching, not both; --merge and --out F go with one of them, --invert with neither\n");
+        return 2;
+    }
     if ((lines_invert && !lines_mode) ||
-        (lines_mode && (hamming_k >= 0 || spans || gaps_starts || positions || ranges > 0 || gpus > 0 || !dict_path.empty() ||
+        ((lines_mode || subst_mode) && (hamming_k >= 0 || spans || gaps_starts || positions || ranges > 0 || gpus > 0 || !dict_path.empty() ||
                         !index_path.empty() || !seeds_path.empty() || !sa_path.empty() || !ed_a.empty() || !edb_a.empty()))) {
-        fprintf(stderr, "--invert needs --lines; --lines goes with --pattern, --classes, --gaps, --regex, --regex-star and --approx K only\n");
+        fprintf(stderr, "--invert needs --lines; --lines, --replace and --only-matching go with --pattern, --classes, --gaps, --regex, --regex-star and --approx K only\n");
         return 2;
     }
 
@@ -616,7 +635,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "bad gapped pattern expression %s\n", gaps_expr.c_str());
         return 1;
     }
-    if (lines_mode) { // the rows of the text that hold a match (or, --invert, none): row<TAB>count, 0-based
+    // --lines: the rows of the text that hold a match (or, --invert, none): row<TAB>count, 0-based.  --replace STR and
+    // --only-matching: the non-overlapping matches (--merge: the regions of their union, from the longest match of every end)
+    // replaced by STR, or one per line; with --lines a match that crosses a line break is left alone.
+    if (lines_mode || subst_mode) {
         bmx_ctx *ctx = nullptr;
         int rc = bmx_ctx_create(device, &ctx);
         if (rc != BMX_OK) {
@@ -624,8 +646,11 @@ int main(int argc, char **argv)
             return 1;
         }
         std::vector<uint64_t> off(n + 1);
-        uint64_t rows = 0, longest = 0, hits = 0, len = 0;
-        rc = bmx_rows_split(ctx, text.data(), n, '\n', off.data(), off.size(), &rows, &longest);
+        uint64_t rows = 0, longest = 4096, hits = 0, len = 0;
+        const uint32_t longest_flag = select_merge ? 1u : 0u; // BMX_GAPS_LONGEST == BMX_REGEX_LONGEST: the smallest start of every end
+        static_assert(BMX_GAPS_LONGEST == 1u && BMX_REGEX_LONGEST == 1u, "one flag for both starts passes");
+        if (!lines_mode) off.resize(1);
+        rc = lines_mode ? bmx_rows_split(ctx, text.data(), n, '\n', off.data(), off.size(), &rows, &longest) : BMX_OK;
         if (rc != BMX_OK) {
             fprintf(stderr, "bmx_rows_split failed: %d (%s)\n", rc, bmx_last_error());
             return 1;
@@ -645,11 +670,11 @@ int main(int argc, char **argv)
             // (the star search: a match longer than the longest row lies in no row)
             const uint32_t window = (uint32_t)std::min<uint64_t>(BMX_MAX_REGEX_STAR_WINDOW, std::max<uint64_t>(longest, 1));
             what = regex_star ? "bmx_search_regex_star_spans" : "bmx_search_regex_spans";
-            rc = regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, 0, starts.data(), ends.data(), room, &hits)
-                            : bmx_search_regex_spans(ctx, text.data(), n, &re, 0, starts.data(), ends.data(), room, &hits);
+            rc = regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, longest_flag, starts.data(), ends.data(), room, &hits)
+                            : bmx_search_regex_spans(ctx, text.data(), n, &re, longest_flag, starts.data(), ends.data(), room, &hits);
         } else if (have_gaps) {
             what = "bmx_search_gaps_spans";
-            rc = bmx_search_gaps_spans(ctx, text.data(), n, classes.data(), m, gaps_optional, 0, starts.data(), ends.data(), room, &hits);
+            rc = bmx_search_gaps_spans(ctx, text.data(), n, classes.data(), m, gaps_optional, longest_flag, starts.data(), ends.data(), room, &hits);
         } else if (approx_k >= 0) {
             what = "bmx_search_approx_spans";
             if (have_classes)
@@ -675,6 +700,49 @@ int main(int argc, char **argv)
         }
         std::vector<uint64_t> row(hits ? hits : 1), out(rows ? rows : 1), counts(rows ? rows : 1);
         uint64_t n_out = 0;
+        if (subst_mode) {
+            if (lines_mode && (rc = bmx_rows_of(ctx, off.data(), rows, starts.data(), len ? nullptr : ends.data(), len, hits, row.data())) != BMX_OK) {
+                fprintf(stderr, "bmx_rows_of failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            std::vector<uint64_t> sel_s(hits ? hits : 1), sel_e(hits ? hits : 1), blob_off(hits + 1);
+            uint64_t taken = 0, n_new = 0;
+            rc = bmx_spans_select(ctx, starts.data(), len ? nullptr : ends.data(), len, hits, lines_mode ? row.data() : nullptr,
+                                  select_merge ? BMX_SELECT_MERGE : 0u, sel_s.data(), sel_e.data(), nullptr, hits, &taken);
+            if (rc != BMX_OK) {
+                fprintf(stderr, "bmx_spans_select failed: %d (%s)\n", rc, bmx_last_error());
+                return 1;
+            }
+            std::string result(have_replace ? n + taken * replace_str.size() + 1 : n + 1, '\0');
+            rc = have_replace ? bmx_replace(ctx, text.data(), n, sel_s.data(), sel_e.data(), 0, taken, replace_str.data(), replace_str.size(),
+                                            &result[0], result.size(), &n_new)
+                              : bmx_extract(ctx, text.data(), n, sel_s.data(), sel_e.data(), 0, taken, &result[0], result.size(),
+                                            blob_off.data(), &n_new);
+            if (rc != BMX_OK) {
+                fprintf(stderr, "%s failed: %d (%s)\n", have_replace ? "bmx_replace" : "bmx_extract", rc, bmx_last_error());
+                return 1;
+            }
+            FILE *dst = out_path.empty() ? stdout : fopen(out_path.c_str(), "wb");
+            if (!dst) {
+                fprintf(stderr, "cannot write %s\n", out_path.c_str());
+                return 1;
+            }
+            if (have_replace) {
+                fwrite(result.data(), 1, n_new, dst);
+                fprintf(stderr, "replaced %llu of %llu matches: %llu bytes -> %llu bytes\n", (unsigned long long)taken, (unsigned long long)hits,
+                        (unsigned long long)n, (unsigned long long)n_new);
+            } else {
+                for (uint64_t i = 0; i < taken && i < max_print; ++i) {
+                    fwrite(result.data() + blob_off[i], 1, blob_off[i + 1] - blob_off[i], dst);
+                    fputc('\n', dst);
+                }
+                fprintf(stderr, "matches: %llu of %llu taken (%llu bytes)\n", (unsigned long long)taken, (unsigned long long)hits,
+                        (unsigned long long)n_new);
+            }
+            if (dst != stdout) fclose(dst);
+            bmx_ctx_destroy(ctx);
+            return 0;
+        }
         rc = bmx_rows_of(ctx, off.data(), rows, starts.data(), len ? nullptr : ends.data(), len, hits, row.data());
         if (rc == BMX_OK)
             rc = bmx_rows_matching(ctx, row.data(), hits, rows, lines_invert ? BMX_ROWS_INVERT : 0u, out.data(),

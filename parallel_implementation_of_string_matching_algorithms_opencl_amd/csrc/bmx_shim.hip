@@ -116,6 +116,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_index_state_free(ctx->index);
     bmx_internal_align_free(ctx->align);
     bmx_internal_rows_free(ctx->rows);
+    bmx_internal_subst_free(ctx->subst);
     delete ctx;
 }
 
@@ -238,6 +239,64 @@ int bmx_rows_matching_device(bmx_ctx *ctx, const uint64_t *d_row, uint64_t count
 }
 
 float bmx_last_rows_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_rows_ms(ctx->rows) : -1.0f; }
+
+// ---- non-overlapping match selection, replace and extract (bmx_subst.hip) ------------------------
+int bmx_spans_select_device(bmx_ctx *ctx, const uint64_t *d_starts, const uint64_t *d_ends, uint64_t len, uint64_t count,
+                            const uint64_t *d_row, uint32_t flags, uint64_t *d_starts_out, uint64_t *d_ends_out, uint64_t *d_index_out,
+                            uint64_t capacity, uint64_t *n_out, void *stream_v)
+{
+    if (!bmx_select_args_ok(d_starts, d_ends, len, count, flags, d_starts_out, d_ends_out, capacity, n_out)) return BMX_ERR_ARG;
+    if (count == 0) {
+        *n_out = 0;
+        return BMX_OK;
+    }
+    if (!ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_select(&ctx->subst, ctx->select_tile_shift, d_starts, d_ends, len, count, d_row, flags, d_starts_out, d_ends_out,
+                               d_index_out, capacity, n_out, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_replace_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_starts,
+                       const uint64_t *d_ends, uint64_t len, uint64_t count, const void *repl, uint64_t repl_len, void *d_out,
+                       uint64_t capacity, uint64_t *n_out, void *stream_v)
+{
+    if (!bmx_subst_copy_args_ok(d_text, n, d_starts, d_ends, len, count, repl, repl_len, d_out, capacity, false, nullptr, n_out))
+        return BMX_ERR_ARG;
+    if (count == 0 && (n == 0 || capacity == 0)) {
+        *n_out = n;
+        return BMX_OK;
+    }
+    if (!ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (count == 0) { // no span: the text itself
+        *n_out = n;
+        HIPCHK(hipMemcpyAsync(d_out, d_text, std::min(n, capacity), hipMemcpyDeviceToDevice, (hipStream_t)stream_v));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream_v));
+        return n > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+    }
+    return bmx_internal_subst_copy(&ctx->subst, ctx->num_cu, d_text, n, base_offset, d_starts, d_ends, len, count, repl, repl_len, d_out,
+                                   capacity, nullptr, n_out, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_extract_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_starts,
+                       const uint64_t *d_ends, uint64_t len, uint64_t count, void *d_blob, uint64_t capacity, uint64_t *d_off,
+                       uint64_t *n_out, void *stream_v)
+{
+    if (!bmx_subst_copy_args_ok(d_text, n, d_starts, d_ends, len, count, nullptr, 0, d_blob, capacity, true, d_off, n_out))
+        return BMX_ERR_ARG;
+    if (!ctx) return BMX_ERR_ARG;
+    *n_out = 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (count == 0) { // no span: the single offset 0
+        HIPCHK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), (hipStream_t)stream_v));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream_v));
+        return BMX_OK;
+    }
+    return bmx_internal_subst_copy(&ctx->subst, ctx->num_cu, d_text, n, base_offset, d_starts, d_ends, len, count, nullptr, 0, d_blob,
+                                   capacity, d_off, n_out, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_subst_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_subst_ms(ctx->subst) : -1.0f; }
 
 // ---- approximate search (bmx_approx.hip) -------------------------------------------------------
 int bmx_search_approx_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
@@ -665,6 +724,7 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "sa_flags") ctx->sa_flags = value;
     else if (k == "index_no_dir") ctx->index_no_dir = value != 0;
     else if (k == "align_ws_kib") ctx->align_ws_kib = value;
+    else if (k == "select_tile_shift" && (value == 0 || (value >= 3 && value <= 8))) ctx->select_tile_shift = value;
     else if (k == "regex_star_force_slow") ctx->regex_star_knobs.force_slow = value != 0;
     else if (k == "regex_star_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_star_knobs.piece_shift = value;
     else if (k == "regex_star_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_knobs.warm = value;
@@ -697,6 +757,9 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "dict") state = ctx->dict;
     else if (k == "rows") { // (its own state: the tile is fixed, so out3[0] is log2 of its bytes)
         bmx_internal_rows_last(ctx->rows, out3);
+        return BMX_OK;
+    } else if (k == "select") { // (its own state too: log2 T, levels, tiles of the last selection)
+        bmx_internal_subst_last(ctx->subst, out3);
         return BMX_OK;
     } else return BMX_ERR_ARG;
     bmx::ordered_last_launch(state, out3);

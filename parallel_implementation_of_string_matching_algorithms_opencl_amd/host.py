@@ -72,6 +72,8 @@ CIGAR_X = 8
 _CIGAR_CHARS = "MIDNSHP=X"
 ROW_NONE = 0xFFFFFFFFFFFFFFFF  # the row of a match that lies in no row (BMX_ROW_NONE); -1 in the int64 tensors of Rows.of
 ROWS_INVERT = 1  # Rows.matching: the rows without an entry (BMX_ROWS_INVERT)
+SELECT_MERGE = 1  # select_spans_device: the connected regions of the union of the spans (BMX_SELECT_MERGE)
+MAX_REPLACEMENT = 65536  # bytes of a replacement (BMX_MAX_REPLACEMENT)
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -284,6 +286,19 @@ SYMBOLS = [
     ("bmx_rows_of", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("bmx_rows_matching", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                     _u64p]),
+    ("bmx_spans_select_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_replace_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_extract_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, _u64p, C.c_void_p]),
+    ("bmx_last_subst_ms", C.c_float, [C.c_void_p]),
+    ("bmx_spans_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_replace", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                              C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_extract", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                              C.c_uint64, C.c_void_p, _u64p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     ("bmx_plant_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, _u64p,
                                    C.c_uint64, C.c_void_p]),
@@ -545,13 +560,15 @@ class Context:
 
     def set_knob(self, name: str, value: int):
         """libbmx_exp.so only (bmx_exp_set_knob): max_grid, no_dense, no_text_sample, multi_no_qgram, ed_lag, ed_group, ed_step_x,
-        ed_stamp_block, sa_flags, index_no_dir, align_ws_kib, ordered_seq, tile_piece_shift, tile_max_grid (include/bmx_exp.h)."""
+        ed_stamp_block, sa_flags, index_no_dir, align_ws_kib, ordered_seq, tile_piece_shift, tile_max_grid, select_tile_shift
+        (include/bmx_exp.h)."""
         self._chk(self._L.bmx_exp_set_knob(self._h, name.encode(), int(value)), "bmx_exp_set_knob")
 
     def last_launch(self, session: str) -> Tuple[int, int, int]:
         """libbmx_exp.so only (bmx_exp_last_launch): (piece shift, workgroups, tiles) of the last launch of the session
         "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_star" or "dict"; "rows": (log2 of the bytes
-        of a tile, workgroups, tiles) of the last rows_split_device."""
+        of a tile, workgroups, tiles) of the last rows_split_device; "select": (log2 T, levels of pointer jumping, tiles of T
+        entries) of the last select_spans_device."""
         out = (C.c_uint64 * 3)()
         self._chk(self._L.bmx_exp_last_launch(self._h, session.encode(), out), "bmx_exp_last_launch")
         return int(out[0]), int(out[1]), int(out[2])
@@ -1747,10 +1764,17 @@ class Context:
         runs across a row boundary counts for no row; `.` matches the delimiter too, so write ``[^\\x0a]*`` for ``.*`` on
         lines.  regex_star: the starts come from a window of min(MAX_REGEX_STAR_WINDOW, rows.longest) bytes (or ``window``);
         an end whose shortest match is longer than the window is not attributed to any row."""
-        import torch
-
         if rows is None:
             rows = self.rows_split_device(d_text, delim)
+        starts, ends, length = self._match_spans_device(d_text, expr, kind, flags, k, window, False, rows)
+        ids = rows.of(starts=starts, ends=ends, length=length)
+        return rows.matching(ids, invert=invert)
+
+    def _match_spans_device(self, d_text, expr, kind, flags, k, window, longest, rows):
+        """(starts, ends, length) of every match of ``expr`` in the resident text, in one of the three forms of Rows.of:
+        the existing search of ``kind`` and, for the kinds that report ends, the existing starts post-pass (``longest``: the
+        smallest start of every end where the pass has that flag).  ``rows`` (may be None) bounds regex_star's window."""
+        import torch
 
         def complete(call):  # call(out) -> (list, ..., total): once more with room for all where the first guess was short
             res = call(None)
@@ -1760,38 +1784,146 @@ class Context:
 
         if kind == "exact":
             starts, _ = complete(lambda out: self.search_device(d_text, expr, out=out))
-            ids = rows.of(starts=starts, length=len(_pat_bytes(expr)))
-        elif kind == "classes":
+            return starts, None, len(_pat_bytes(expr))
+        if kind == "classes":
             cls = _classes(expr, flags)
             starts, _ = complete(lambda out: self.search_classes_device(d_text, cls, out=out))
-            ids = rows.of(starts=starts, length=cls.shape[0])
-        elif kind == "hamming":
+            return starts, None, cls.shape[0]
+        if kind == "hamming":
             pat, cls = self._hamming_pattern(expr, flags)
             starts, _, _ = complete(lambda out: self.search_hamming_device(d_text, expr, k, flags=flags, out=out))
-            ids = rows.of(starts=starts, length=len(pat) if pat is not None else cls.shape[0])
-        elif kind == "gaps":
+            return starts, None, len(pat) if pat is not None else cls.shape[0]
+        if kind == "gaps":
             pair = _gaps(expr, flags)
             ends, _ = complete(lambda out: self.search_gaps_device(d_text, pair, out=out))
-            ids = rows.of(starts=self.gaps_starts_device(d_text, pair, ends), ends=ends)
-        elif kind == "regex":
+            return self.gaps_starts_device(d_text, pair, ends, longest=longest), ends, 0
+        if kind == "regex":
             re_ = _regex(expr, flags)
             ends, _ = complete(lambda out: self.search_regex_device(d_text, re_, out=out))
-            ids = rows.of(starts=self.regex_starts_device(d_text, re_, ends), ends=ends)
-        elif kind == "regex_star":
+            return self.regex_starts_device(d_text, re_, ends, longest=longest), ends, 0
+        if kind == "regex_star":
             re_ = _regex(expr, flags, star=True)
             ends, _ = complete(lambda out: self.search_regex_star_device(d_text, re_, out=out))
-            w = window if window is not None else min(MAX_REGEX_STAR_WINDOW, max(rows.longest, 1))
-            ids = rows.of(starts=self.regex_star_starts_device(d_text, re_, ends, window=w), ends=ends)
-        elif kind == "approx":
+            w = window if window is not None else min(MAX_REGEX_STAR_WINDOW, max(rows.longest, 1) if rows is not None else 4096)
+            return self.regex_star_starts_device(d_text, re_, ends, window=w, longest=longest), ends, 0
+        if kind == "approx":
             ends, dist, _ = complete(lambda out: self.search_approx_device(d_text, expr, k, out=out))
-            starts = self.approx_spans_device(d_text, expr, k, ends, dist)[0]
-            ids = rows.of(starts=starts, ends=ends)
-        else:
-            raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_star | approx")
-        return rows.matching(ids, invert=invert)
+            return self.approx_spans_device(d_text, expr, k, ends, dist)[0], ends, 0
+        raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_star | approx")
 
     def last_rows_ms(self) -> float:
         return float(self._L.bmx_last_rows_ms(self._h))
+
+    # -- non-overlapping match selection, replace and extract ------------------------------
+    @staticmethod
+    def _span_lists(starts, ends, length):
+        lst = starts if starts is not None else ends
+        if lst is None:
+            raise ValueError("starts, ends or both")
+        for t in (starts, ends):
+            if t is not None and (t.element_size() != 8 or t.numel() != lst.numel()):
+                raise ValueError("starts, ends: 8-byte entries, as many of one as of the other")
+        return lst, (lambda t: C.c_void_p(t.data_ptr()) if t is not None else None)
+
+    def select_spans_device(self, starts=None, ends=None, length: int = 0, rows=None, merge: bool = False, index: bool = False,
+                            out=None, stream=None):
+        """The non-overlapping matches of a list, left to right (bmx_spans_select_device): (starts, ends), or with ``index``
+        (starts, ends, indices), int64 CUDA tensors.  ``starts`` and ``ends`` (the last byte of a match), or one of them and
+        the ``length`` of every match.  An entry is skipped whose start is -1 (UINT64_MAX), whose end lies below its start,
+        or whose entry of ``rows`` (what Rows.of returned for the list) is -1.  Default: an entry is taken iff it starts
+        behind the end of the last one taken (re.finditer for lists of one length; leftmost-shortest otherwise).  ``merge``:
+        the connected regions of the union of the spans.  ``out``: a pair (or triple) of tensors to fill; fewer entries than
+        there are raises BmxError(ERR_CAPACITY)."""
+        import torch
+
+        lst, ptr = self._span_lists(starts, ends, length)
+        count = lst.numel()
+        dev = lst.device
+        if out is None:
+            out = tuple(torch.empty(max(count, 1), dtype=torch.int64, device=dev) for _ in range(3 if index else 2))
+        cap = min(t.numel() for t in out)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_spans_select_device(self._h, ptr(starts), ptr(ends), int(length), count, ptr(rows),
+                                             SELECT_MERGE if merge else 0, ptr(out[0]), ptr(out[1]), ptr(out[2]) if index else None,
+                                             cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_spans_select_device")
+        return tuple(t[: int(total.value)] for t in out)
+
+    def replace_device(self, d_text, starts, ends, repl, length: int = 0, n: Optional[int] = None, base_offset: int = 0, out=None,
+                       stream=None):
+        """(tensor, n_out): the view ``d_text[0:n)`` with the bytes of every span replaced by the literal ``repl``
+        (bmx_replace_device).  The spans: ascending and pairwise disjoint inside [base_offset, base_offset + n), as
+        select_spans_device returns them, in one of the three forms.  ``out``: a uint8 CUDA tensor that does not overlap the
+        text (too small: BmxError(ERR_CAPACITY)); without it the call counts first and allocates n_out bytes."""
+        import torch
+
+        lst, ptr = self._span_lists(starts, ends, length)
+        count = lst.numel()
+        repl = _pat_bytes(repl) if len(repl) else b""
+        n = d_text.numel() if n is None else n
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(d_text.device)).cuda_stream)
+        total = C.c_uint64(0)
+
+        def call(buf, cap):
+            return self._L.bmx_replace_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, ptr(starts), ptr(ends),
+                                              int(length), count, repl, len(repl), ptr(buf), cap, C.byref(total), s)
+
+        if out is None:
+            self._chk(call(None, 0), "bmx_replace_device")
+            out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=d_text.device)
+        self._chk(call(out, out.numel()), "bmx_replace_device")
+        return out[: int(total.value)], int(total.value)
+
+    def extract_device(self, d_text, starts, ends, length: int = 0, n: Optional[int] = None, base_offset: int = 0, out=None,
+                       stream=None):
+        """(blob, offsets): the bytes of every span one after the other (uint8) and count + 1 int64 offsets into them
+        (bmx_extract_device), the column layout of edit_distance_batch_device and Index queries.  Spans as for
+        replace_device.  ``out``: a uint8 CUDA tensor for the blob."""
+        import torch
+
+        lst, ptr = self._span_lists(starts, ends, length)
+        count = lst.numel()
+        n = d_text.numel() if n is None else n
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(d_text.device)).cuda_stream)
+        off = torch.empty(count + 1, dtype=torch.int64, device=d_text.device)
+        total = C.c_uint64(0)
+
+        def call(buf, cap):
+            return self._L.bmx_extract_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, ptr(starts), ptr(ends),
+                                              int(length), count, ptr(buf), cap, ptr(off), C.byref(total), s)
+
+        if out is None:
+            self._chk(call(None, 0), "bmx_extract_device")
+            out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=d_text.device)
+        self._chk(call(out, out.numel()), "bmx_extract_device")
+        return out[: int(total.value)], off
+
+    def _selected_spans_device(self, d_text, expr, kind, rows, merge, longest, flags, k, window):
+        longest = merge if longest is None else longest
+        starts, ends, length = self._match_spans_device(d_text, expr, kind, flags, k, window, longest, rows)
+        ids = rows.of(starts=starts, ends=ends, length=length) if rows is not None else None
+        return self.select_spans_device(starts, ends, length, rows=ids, merge=merge)
+
+    def sub_device(self, d_text, expr, repl, kind: str = "regex", rows: Optional["Rows"] = None, merge: bool = False,
+                   longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None):
+        """(tensor, n_out): the resident text with every non-overlapping match of ``expr`` replaced by the literal ``repl``
+        (re.sub, sed s/x/y/g): the search of ``kind`` (as grep_device), its starts post-pass, select_spans_device and
+        replace_device.  ``merge``: whole regions of overlapping matches are replaced (``[0-9]+`` then replaces the maximal
+        digit runs); ``longest`` (default: ``merge``) asks the starts pass for the smallest start of every end.  ``rows``: a
+        Rows; a match that runs across a row boundary is then left alone."""
+        s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window)
+        return self.replace_device(d_text, s, e, repl)
+
+    def findall_device(self, d_text, expr, kind: str = "regex", rows: Optional["Rows"] = None, merge: bool = False,
+                       longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None):
+        """(blob, offsets): the non-overlapping matches of ``expr`` as a string column (re.findall, grep -o): the route of
+        sub_device into extract_device."""
+        s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window)
+        return self.extract_device(d_text, s, e)
+
+    def last_subst_ms(self) -> float:
+        return float(self._L.bmx_last_subst_ms(self._h))
 
     # -- synthetic corpus in HBM ------------------------------------------
     def gen_text(self, d_dst, start: int, seed: int, kind: int = 0, length: Optional[int] = None):
@@ -2393,6 +2525,57 @@ def grep(text, expr, **kw) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     d_text = torch.from_numpy(buf.copy()).cuda()
     rows, counts = ctx.grep_device(d_text, expr, **kw)
     return rows.cpu().numpy(), (counts.cpu().numpy() if counts is not None else None)
+
+
+def _resident(text):
+    import torch
+
+    _, _, keep = _host_text(text)
+    buf = np.frombuffer(keep, dtype=np.uint8) if isinstance(keep, bytes) else keep.reshape(-1)
+    return torch.from_numpy(buf.copy()).cuda()
+
+
+def sub(text, expr, repl, **kw) -> bytes:
+    """(text, expression, literal) -> the text with every non-overlapping match replaced (re.sub without back-references).
+    The keywords are Context.sub_device's; ``rows=True`` keeps matches that cross a line break out."""
+    ctx = default_context()
+    d_text = _resident(text)
+    if kw.get("rows") is True:
+        kw["rows"] = ctx.rows_split_device(d_text)
+    out, _ = ctx.sub_device(d_text, expr, repl, **kw)
+    return out.cpu().numpy().tobytes()
+
+
+def findall(text, expr, **kw) -> list:
+    """(text, expression) -> the non-overlapping matches as a list of bytes (re.findall).  The keywords are
+    Context.findall_device's."""
+    ctx = default_context()
+    d_text = _resident(text)
+    if kw.get("rows") is True:
+        kw["rows"] = ctx.rows_split_device(d_text)
+    blob, off = ctx.findall_device(d_text, expr, **kw)
+    blob, off = blob.cpu().numpy().tobytes(), off.cpu().numpy()
+    return [blob[off[i]:off[i + 1]] for i in range(off.size - 1)]
+
+
+def select_spans(starts=None, ends=None, length: int = 0, rows=None, merge: bool = False, index: bool = False):
+    """Host lists -> (starts, ends[, indices]) as uint64 arrays: the non-overlapping matches of the list, or with ``merge``
+    the regions of its union (bmx_spans_select)."""
+    L = lib()
+    arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+    starts, ends, rows = arr(starts), arr(ends), arr(rows)
+    lst = starts if starts is not None else ends
+    if lst is None:
+        raise ValueError("starts, ends or both")
+    count = lst.size
+    outs = [np.empty(max(count, 1), dtype=np.uint64) for _ in range(3 if index else 2)]
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    total = C.c_uint64(0)
+    rc = L.bmx_spans_select(default_context()._h if count else None, ptr(starts), ptr(ends), int(length), count, ptr(rows),
+                            SELECT_MERGE if merge else 0, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]) if index else None, count,
+                            C.byref(total))
+    _check(rc, "bmx_spans_select")
+    return tuple(o[: int(total.value)].copy() for o in outs)
 
 
 def search_approx(text, pattern, k: int) -> Tuple[np.ndarray, np.ndarray]:
