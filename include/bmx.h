@@ -1266,6 +1266,69 @@ int bmx_gen_text_device(bmx_ctx *ctx, void *d_dst, uint64_t start, uint64_t len,
 int bmx_plant_device(bmx_ctx *ctx, void *d_dst, uint64_t start, uint64_t len, const char *pat,
                      int32_t m, const uint64_t *offsets, uint64_t count, void *stream);
 
+/* ---- leftmost-longest regex matching: every match START, and the end of every start ------- */
+
+/* grep -o, sed s///g and awk take the leftmost start and, from it, the longest match.  The searches above report ENDS and
+ * bmx_regex_starts_device one start per end, which cannot answer that: on "ab" the expression ab|b ends at 1 with the
+ * starts {0, 1} and each flag keeps one of them.  The entries below are the mirror image of bmx_search_regex_device for
+ * the STAR-FREE automata (valid by its rule): one pass reports every start at which some match begins, a post-pass gives
+ * each start of a list its shortest or longest end, and bmx_spans_select_device's disjoint rule on the list
+ * (s, longest end from s), which is sorted by s, yields exactly the leftmost-longest matches.
+ *
+ * The reversed automaton, pure host code, no GPU: position i becomes m - 1 - i, first and last swap, follow[] is
+ * transposed (and so points upward again for a star-free automaton), the classes are mirrored; min_len and max_len are
+ * kept.  text[s..j] matches `re` iff its mirror image matches `out`; applied twice it gives the input back.  Accepts
+ * every automaton that bmx_search_regex_star_device accepts; BMX_ERR_ARG for NULL pointers or one that is not valid.  out
+ * may be re. */
+int bmx_regex_reverse(const bmx_regex *re, bmx_regex *out);
+/* Semantics: every START s in [0, n - tail) for which text[s..j] matches for some j < n, each start once, ascending,
+ * reported as base_offset + s.  A match must end inside the view.  A match spans at most max_len bytes, so a shard passes
+ * a view that runs max_len - 1 bytes (clipped at the text's end) past its last owned start, with tail = that amount: the
+ * shards' lists then concatenate to the whole text's list (the mirror of `lead`).  tail == n returns BMX_OK with no
+ * match and puts nothing on the stream.
+ * Two identities: the list holds every entry of bmx_regex_starts_device (either flag) over bmx_search_regex_device's
+ * ends; it equals n - 1 - e over the ends e of bmx_search_regex_device on the reversed text with bmx_regex_reverse(re).
+ * Any byte values in text and classes; n < 2^40, any alignment of d_text.  No byte outside the aligned 16-byte lines that
+ * hold text[0..n) is read, none above the line of text[n - 1].
+ * Capacity: the stored entries are the LOWEST `capacity` starts; *n_matches is the true total, and a larger total
+ * returns BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers where needed, an automaton that is
+ * not valid -- one with a cycle is not --, tail > n, n too large) return BMX_ERR_ARG before any HIP call, with
+ * ctx = NULL too.  The look-back time-out and BMX_ERR_HIP in place of a partly ordered list: as for
+ * bmx_search_regex_device.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising
+ * that stream.  The lane runs the reversed automaton DOWN the text in place (csrc/bmx_regex_begins_kernel.h): no copy of
+ * the text is made. */
+int bmx_search_regex_begins_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t tail, uint64_t base_offset,
+                                   const bmx_regex *re, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Device time (ms, HIP events around the kernel) of the last bmx_search_regex_begins_device on ctx; < 0 if none. */
+float bmx_last_regex_begins_ms(bmx_ctx *ctx);
+/* The END of a match for every start of a device-resident list, as bmx_search_regex_begins_device returns it for the same
+ * view, automaton and base_offset: d_ends[i] = base_offset + j with text[s_i..j] a match, d_starts[i] = base_offset + s_i.
+ * By default j is the SMALLEST such end (the shortest match), with BMX_REGEX_LONGEST the largest j < n of the view.  One
+ * list entry per lane; the lane runs the automaton anchored at s_i over at most max_len bytes upwards.
+ * d_limit (NULL: the view's last byte): d_limit[i], in the coordinates of d_starts, is the last byte a match of entry i
+ * may use -- the last byte of its row, say: a.{0,3}b then does not reach across a line break.  An entry from which no
+ * match begins within its limit gets UINT64_MAX (bmx_spans_select_device skips such entries) and is not an error.
+ * Errors: NULL pointers where needed, an automaton that is not valid, n out of range and unknown flag bits return
+ * BMX_ERR_ARG before any HIP call, with ctx = NULL too; count == 0 returns BMX_OK and launches nothing.  An entry outside
+ * [base_offset, base_offset + n) reads no byte and raises a status word, and so does, WITHOUT d_limit, an entry at which
+ * no match begins (a list of another expression or text): the call then returns BMX_ERR_ARG and the outputs are
+ * unspecified.  No byte outside the aligned 16-byte lines that hold text[0..n) is read, none above text[n - 1]'s line.
+ * One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising it. */
+int bmx_regex_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                          const uint64_t *d_starts, uint64_t count, const uint64_t *d_limit /* NULL: the view's last byte */,
+                          uint32_t flags, uint64_t *d_ends, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_regex_begins_device with tail = 0, download). */
+int bmx_search_regex_begins(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                            uint64_t *starts, uint64_t capacity, uint64_t *n_matches);
+/* Host buffers in, host buffers out: upload, bmx_search_regex_begins_device, bmx_regex_ends_device (flags:
+ * BMX_REGEX_LONGEST or 0; no limit), download.  ends[i] belongs to starts[i]; capacity and *n_matches as above. */
+int bmx_search_regex_begins_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                  uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+/* The counterpart of bmx_text_upload for a caller without the HIP runtime's headers (the driver chains the two device
+ * entries above with a per-line limit): `bytes` bytes from d_src on ctx's device to dst, a blocking copy.  BMX_ERR_ARG for
+ * a NULL context, or NULL pointers with bytes > 0; bytes == 0 does nothing. */
+int bmx_device_download(bmx_ctx *ctx, void *dst, const void *d_src, uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

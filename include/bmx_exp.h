@@ -31,16 +31,19 @@ extern "C" {
  * the first launch even when nothing is tainted), "regex_star_piece_shift" (0, or 4..12: log2 of the ends per lane of THAT
  * search, in front of "tile_piece_shift"; 4 and 5 make chains of pieces that cross tiles and workgroups on texts of a few
  * KiB) and "regex_star_warm" (0 = the rule, else the bytes of the pair warm-up, a multiple of 16 up to 65,536).
+ * The regex begins search (bmx_search_regex_begins_device) takes the two geometry knobs as well and has
+ * "regex_begins_piece_shift" (0, or 4..12: log2 of the starts per lane of THAT search, in front of "tile_piece_shift", kept
+ * in the context; 4 makes lanes of 16 starts, fewer than a longest match has bytes).
  * "select_tile_shift": 0 = the production tile of bmx_spans_select_device (T = 2^8 entries), else 3..8 = log2 T, from the
  * context's next selection on: lists of a few hundred entries then reach three levels of its pointer jumping.
  * BMX_ERR_ARG for an unknown name, a "select_tile_shift" outside that range, a negative "ordered_seq" or "tile_max_grid" and a "tile_piece_shift",
- * "regex_star_piece_shift" or "regex_star_warm" outside those ranges. */
+ * "regex_star_piece_shift", "regex_begins_piece_shift" or "regex_star_warm" outside those ranges. */
 int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value);
 
 /* What the last launch of one ordered-output session of the context ran with: out3 = {log2 of the ends per lane (the
  * dictionary search: 6 + log2 of the rounds per tile), workgroups started, tiles}; zeros before the session's first launch.
- * session: "approx" (also the approximate search over classes), "approx_long", "classes", "hamming", "gaps", "regex" or
- * "dict".  Tests assert with it that the geometry they forced ("tile_piece_shift", "tile_max_grid") is the one that ran.
+ * session: "approx" (also the approximate search over classes), "approx_long", "classes", "hamming", "gaps", "regex",
+ * "regex_begins" (the begins search: starts per lane) or "dict".  Tests assert with it that the geometry they forced ("tile_piece_shift", "tile_max_grid") is the one that ran.
  * "rows": the last bmx_rows_split_device, out3 = {log2 of the bytes of a tile, workgroups started, tiles}; a workgroup is
  * eight waves, each with an eighth of the tile, read in batches of eight rounds of 1 KiB (the first entry is there
  * before any split).

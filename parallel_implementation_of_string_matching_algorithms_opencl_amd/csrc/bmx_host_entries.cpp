@@ -702,6 +702,79 @@ int bmx_search_regex_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const 
     return c.rc;
 }
 
+// The reversed automaton (pure host code; the starts pass and the begins search of bmx_regex.hip run it): bit i stands for
+// position m - 1 - i, first and last swap, follow is transposed, the classes are mirrored.
+int bmx_regex_reverse(const bmx_regex *re, bmx_regex *out)
+{
+    if (!bmx_regex_star_ok(re) || !out) return BMX_ERR_ARG;
+    const int32_t m = re->m;
+    const auto flip = [m](uint64_t set) {
+        uint64_t r = 0;
+        for (; set != 0; set &= set - 1) r |= 1ull << (m - 1 - __builtin_ctzll(set));
+        return r;
+    };
+    bmx_regex r;
+    std::memset(&r, 0, sizeof r);
+    r.m = m;
+    r.min_len = re->min_len;
+    r.max_len = re->max_len;
+    r.first = flip(re->last);
+    r.last = flip(re->first);
+    for (int32_t i = 0; i < m; ++i) {
+        for (uint64_t f = re->follow[i]; f != 0; f &= f - 1) r.follow[m - 1 - __builtin_ctzll(f)] |= 1ull << (m - 1 - i);
+        std::memcpy(r.classes + (size_t)(m - 1 - i) * BMX_CLASS_BYTES, re->classes + (size_t)i * BMX_CLASS_BYTES, BMX_CLASS_BYTES);
+    }
+    *out = r; // (out may be re)
+    return BMX_OK;
+}
+
+int bmx_search_regex_begins(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint64_t *starts, uint64_t capacity,
+                            uint64_t *n_matches)
+{
+    if (!bmx_regex_begins_args_ok(n, 0, re, starts, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_begins", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_begins_device(c.ctx(), d_text, n, 0, 0, re, d_starts, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(starts, d_starts, std::min(total, dev_cap) * sizeof(uint64_t), "regex match starts");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+int bmx_search_regex_begins_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint32_t flags,
+                                  uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_regex_begins_args_ok(n, 0, re, starts, capacity) || (capacity > 0 && !ends) || (n > 0 && !text) ||
+        (flags & ~BMX_REGEX_LONGEST))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_begins_spans", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_begins_device(c.ctx(), d_text, n, 0, 0, re, d_starts, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    const int erc = bmx_regex_ends_device(c.ctx(), d_text, n, 0, re, d_starts, stored, nullptr, flags, d_ends, nullptr);
+    if (erc != BMX_OK) return erc;
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "regex match starts");
+    c.download(ends, d_ends, stored * sizeof(uint64_t), "regex match ends");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
 int bmx_search_regex_star(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint64_t *ends, uint64_t capacity,
                           uint64_t *n_matches)
 {

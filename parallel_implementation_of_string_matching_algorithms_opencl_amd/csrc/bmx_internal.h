@@ -115,6 +115,16 @@ int bmx_internal_regex_starts(void **state, const void *d_text, uint64_t n, uint
 void bmx_internal_regex_free(void *state);
 float bmx_internal_regex_ms(const void *state);
 constexpr uint64_t BMX_REGEX_STARTS_NO_MATCH = 2; // *bad_out: some end had no match (csrc/bmx_regex_kernel.h, REGEX_BAD_START)
+// ... its mirror image: every start (a state of its own; piece_shift: 0, or log2 of the starts per lane -- libbmx_exp.so's
+// knob) and the end of every start of a list (d_limit: NULL, or the last byte each entry may use)
+int bmx_internal_regex_begins(void **state, int num_cu, int piece_shift, const void *d_text, uint64_t n, uint64_t tail,
+                              uint64_t base_offset, const bmx_regex *re, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
+                              hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_regex_ends(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                            const uint64_t *d_starts, uint64_t count, const uint64_t *d_limit, uint32_t flags, uint64_t *d_ends,
+                            hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_regex_begins_free(void *state);
+float bmx_internal_regex_begins_ms(const void *state);
 // bmx_regex_star.hip.  What (libbmx_exp.so) bmx_exp_set_knob sets:
 struct bmx_regex_star_knobs {
     int piece_shift = 0;     // 0, or log2 of the ends per lane (4..12; the shared "tile_piece_shift" begins at 6)
@@ -244,6 +254,8 @@ struct bmx_ctx {
     void *hamming = nullptr; // k-mismatch search: the same again (bmx_hamming.hip)
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *regex = nullptr; // regular-expression search: the same as the gapped search's, its own (bmx_regex.hip)
+    void *regex_begins = nullptr; // ... its begins search and ends pass: the same again, their own (bmx_regex.hip)
+    int regex_begins_piece_shift = 0; // libbmx_exp.so: 0, or log2 of the starts per lane of the begins search (4..12)
     void *regex_star = nullptr; // ... with unbounded repetition: the same, the taint words and the slow path's workspace (bmx_regex_star.hip)
     bmx_regex_star_knobs regex_star_knobs;
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
@@ -338,6 +350,19 @@ inline bool bmx_regex_starts_args_ok(uint64_t n, const bmx_regex *re, const uint
 {
     if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
     return count == 0 || (ends && starts);
+}
+
+// ... every start: the view runs `tail` bytes past the last owned start
+inline bool bmx_regex_begins_args_ok(uint64_t n, uint64_t tail, const bmx_regex *re, const void *starts, uint64_t capacity)
+{
+    return bmx_regex_ok(re) && tail <= n && n < (1ull << 40) && (capacity == 0 || starts);
+}
+// ... and the ends of the matches that begin there
+inline bool bmx_regex_ends_args_ok(uint64_t n, const bmx_regex *re, const uint64_t *starts, uint64_t count, uint32_t flags,
+                                   const uint64_t *ends)
+{
+    if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
+    return count == 0 || (starts && ends);
 }
 
 // ... with unbounded repetition: follow[] may hold any bit below m

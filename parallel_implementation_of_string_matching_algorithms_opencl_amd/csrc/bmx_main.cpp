@@ -52,6 +52,11 @@
 //                             expression, the elements of --classes with groups ( ), alternation | and ? {a} {a,b} on
 //                             elements and groups (bmx_compile_regex); prints what --gaps prints, `regex matches: N` in
 //                             place of `gapped matches: N`.  It goes with none of --gaps, --classes, --approx, --hamming
+//   bmx_cli --regex EXPR --begins [--spans [--longest]] [--icase] [--iupac] [--text F] [--positions] [--max-print K]
+//                             the mirror image (bmx_search_regex_begins): every START at which a match begins, each once;
+//                             `regex match starts: N`, and with --positions one `Start at : P` line per start.  With
+//                             --spans the end of every start as well (bmx_search_regex_begins_spans: the smallest one,
+//                             with --longest the largest) and `Match at : S E` lines
 //   bmx_cli --regex-star EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K]
 //           [--starts --window N [--longest]]
 //                             the same with unbounded repetition: EXPR may use * + {a,} (bmx_compile_regex_star,
@@ -102,7 +107,10 @@
 //                             union of the longest match of every end), replaced by STR (bmx_replace: the new text on
 //                             stdout or in F, a total line on stderr: sed s/x/STR/g) or printed one per line
 //                             (bmx_extract, at most --max-print of them: grep -o); with --lines a match that crosses a
-//                             line break is left alone
+//                             line break is left alone.  --posix (with --regex, without --merge): the leftmost-longest
+//                             matches, as grep -o and sed take them -- every start with its longest end
+//                             (bmx_search_regex_begins_spans; with --lines the longest end inside the start's line,
+//                             bmx_regex_ends_device with a limit), then the same selection
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -201,6 +209,7 @@ int main(int argc, char **argv)
     std::string gaps_expr, regex_expr;
     bool have_regex = false, regex_star = false, regex_both = false;
     uint32_t star_window = 0;
+    bool regex_begins = false, begins_spans = false, begins_longest = false, posix = false; // --begins [--spans [--longest]], --posix
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
     std::string must_spec;
     bool positions = false, spans = false, spans_best = false, with_lcp = false, cigar = false, lines_mode = false, lines_invert = false;
@@ -248,6 +257,8 @@ int main(int argc, char **argv)
         else if (a == "--gaps") gaps_expr = need("--gaps"), have_gaps = true;
         else if (a == "--regex") regex_both = have_regex, regex_expr = need("--regex"), have_regex = true;
         else if (a == "--regex-star") regex_both = have_regex, regex_expr = need("--regex-star"), have_regex = regex_star = true;
+        else if (a == "--begins") regex_begins = true;
+        else if (a == "--posix") posix = true;
         else if (a == "--window") star_window = (uint32_t)strtoul(need("--window"), nullptr, 10);
         else if (a == "--prosite") class_flags |= BMX_GAPS_PROSITE;
         else if (a == "--starts") gaps_starts = true;
@@ -273,6 +284,18 @@ int main(int argc, char **argv)
         return 2;
     }
     if (!map_path.empty()) seeds_path = map_path; // the same query file, read below
+    if (regex_begins) { // --spans and --longest are the begins search's here
+        begins_spans = spans, begins_longest = gaps_longest;
+        spans = gaps_longest = false;
+        if (!have_regex || regex_star || gaps_starts || posix || lines_mode || have_replace || only_matching || (begins_longest && !begins_spans)) {
+            fprintf(stderr, "--begins needs --regex EXPR and goes with --spans [--longest], --positions and --max-print only\n");
+            return 2;
+        }
+    }
+    if (posix && (!have_regex || regex_star || select_merge || !(have_replace || only_matching))) {
+        fprintf(stderr, "--posix needs --regex EXPR with --replace STR or --only-matching, without --merge\n");
+        return 2;
+    }
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
         return 2;
@@ -670,6 +693,31 @@ int main(int argc, char **argv)
             // (the star search: a match longer than the longest row lies in no row)
             const uint32_t window = (uint32_t)std::min<uint64_t>(BMX_MAX_REGEX_STAR_WINDOW, std::max<uint64_t>(longest, 1));
             what = regex_star ? "bmx_search_regex_star_spans" : "bmx_search_regex_spans";
+            if (posix && !lines_mode) { // every start with its longest end: the selection below gives leftmost-longest
+                what = "bmx_search_regex_begins_spans";
+                rc = bmx_search_regex_begins_spans(ctx, text.data(), n, &re, BMX_REGEX_LONGEST, starts.data(), ends.data(), room, &hits);
+            } else if (posix) { // ... its longest end inside its line: the ends pass with the line's last byte as the limit
+                what = "bmx_search_regex_begins_device / bmx_regex_ends_device";
+                void *d_text = nullptr, *d_limit = nullptr;
+                uint64_t *d_starts = nullptr, *d_ends = nullptr;
+                rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+                if (rc == BMX_OK) rc = bmx_device_alloc(ctx, room * sizeof(uint64_t), (void **)&d_starts);
+                if (rc == BMX_OK) rc = bmx_device_alloc(ctx, room * sizeof(uint64_t), (void **)&d_ends);
+                if (rc == BMX_OK) rc = bmx_search_regex_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr);
+                if (rc == BMX_OK) rc = bmx_device_download(ctx, starts.data(), d_starts, hits * sizeof(uint64_t));
+                std::vector<uint64_t> limit(hits ? hits : 1);
+                for (uint64_t i = 0; i < hits && rc == BMX_OK; ++i) // off[0] = 0 and off[rows] = n: every start lies in a row
+                    limit[i] = *std::upper_bound(off.begin(), off.begin() + rows + 1, starts[i]) - 1;
+                if (rc == BMX_OK) rc = bmx_text_upload(ctx, reinterpret_cast<const char *>(limit.data()), hits * sizeof(uint64_t), &d_limit);
+                if (rc == BMX_OK)
+                    rc = bmx_regex_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit), BMX_REGEX_LONGEST,
+                                               d_ends, nullptr);
+                if (rc == BMX_OK) rc = bmx_device_download(ctx, ends.data(), d_ends, hits * sizeof(uint64_t));
+                bmx_device_free(ctx, d_limit);
+                bmx_device_free(ctx, d_ends);
+                bmx_device_free(ctx, d_starts);
+                bmx_device_free(ctx, d_text);
+            } else
             rc = regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, longest_flag, starts.data(), ends.data(), room, &hits)
                             : bmx_search_regex_spans(ctx, text.data(), n, &re, longest_flag, starts.data(), ends.data(), room, &hits);
         } else if (have_gaps) {
@@ -773,6 +821,39 @@ int main(int argc, char **argv)
         else
             printf("text %s: %llu bytes, regular expression %s: %d positions, matches of %d to %d bytes\n", text_path.c_str(),
                    (unsigned long long)n, regex_expr.c_str(), re.m, re.min_len, re.max_len);
+        if (regex_begins) { // the starts (and an end of each) through the host-buffer entry points
+            bmx_ctx *ctx = nullptr;
+            int rc = bmx_ctx_create(device, &ctx);
+            if (rc != BMX_OK) {
+                fprintf(stderr, "no device %d: %d (%s)\n", device, rc, bmx_last_error());
+                return 1;
+            }
+            const uint64_t room = n ? n : 1; // at most one hit per start
+            std::vector<uint64_t> starts(room), ends(begins_spans ? room : 1);
+            uint64_t got = 0;
+            rc = begins_spans ? bmx_search_regex_begins_spans(ctx, text.data(), n, &re, begins_longest ? BMX_REGEX_LONGEST : 0u, starts.data(),
+                                                              ends.data(), room, &got)
+                              : bmx_search_regex_begins(ctx, text.data(), n, &re, starts.data(), room, &got);
+            if (rc != BMX_OK) {
+                fprintf(stderr, "%s failed: %d (%s)\n", begins_spans ? "bmx_search_regex_begins_spans" : "bmx_search_regex_begins", rc,
+                        bmx_last_error());
+                return 1;
+            }
+            printf("regex match starts: %llu\n", (unsigned long long)got);
+            if (got) {
+                printf("first start: %llu\n", (unsigned long long)starts[0]);
+                printf("last start: %llu\n", (unsigned long long)starts[got - 1]);
+            }
+            if (positions) {
+                for (uint64_t i = 0; i < got && i < max_print; ++i) {
+                    if (begins_spans) printf("Match at : %llu %llu\n", (unsigned long long)starts[i], (unsigned long long)ends[i]);
+                    else printf("Start at : %llu\n", (unsigned long long)starts[i]);
+                }
+                if (got > max_print) printf("... %llu more\n", (unsigned long long)(got - max_print));
+            }
+            bmx_ctx_destroy(ctx);
+            return 0;
+        }
         bmx_ctx *ctx = nullptr;
         int rc = bmx_ctx_create(device, &ctx);
         void *d_text = nullptr;

@@ -109,6 +109,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_hamming_free(ctx->hamming);
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_regex_free(ctx->regex);
+    bmx_internal_regex_begins_free(ctx->regex_begins);
     bmx_internal_regex_star_free(ctx->regex_star);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
@@ -428,6 +429,30 @@ int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64
                                      (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
+// ... the mirror image: every start, and the end of every start of a list
+int bmx_search_regex_begins_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t tail, uint64_t base_offset,
+                                   const bmx_regex *re, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_regex_begins_args_ok(n, tail, re, d_starts, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_begins(&ctx->regex_begins, ctx->num_cu, ctx->regex_begins_piece_shift, d_text, n, tail, base_offset, re,
+                                     d_starts, capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_begins_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_begins_ms(ctx->regex_begins) : -1.0f; }
+
+int bmx_regex_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                          const uint64_t *d_starts, uint64_t count, const uint64_t *d_limit, uint32_t flags, uint64_t *d_ends,
+                          void *stream_v)
+{
+    if (!bmx_regex_ends_args_ok(n, re, d_starts, count, flags, d_ends)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (a start needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_ends(&ctx->regex_begins, d_text, n, base_offset, re, d_starts, count, d_limit, flags, d_ends,
+                                   (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
 // ---- regular-expression search with unbounded repetition (bmx_regex_star.hip; bmx_compile_regex_star is
 // bmx_regex_compile.cpp) ------
 int bmx_search_regex_star_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
@@ -700,6 +725,15 @@ int bmx_text_upload(bmx_ctx *ctx, const char *text, uint64_t n, void **d_text_ou
     return BMX_OK;
 }
 
+int bmx_device_download(bmx_ctx *ctx, void *dst, const void *d_src, uint64_t bytes)
+{
+    if (!ctx || (bytes > 0 && (!dst || !d_src))) return BMX_ERR_ARG;
+    if (bytes == 0) return BMX_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
+    return BMX_OK;
+}
+
 #ifdef BMX_EXPERIMENTS
 // libbmx_exp.so only: the measurement / test switches of a context (round 2 read them from the environment on every call,
 // in the product library too).  Returns BMX_ERR_ARG for an unknown name.
@@ -727,16 +761,17 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "select_tile_shift" && (value == 0 || (value >= 3 && value <= 8))) ctx->select_tile_shift = value;
     else if (k == "regex_star_force_slow") ctx->regex_star_knobs.force_slow = value != 0;
     else if (k == "regex_star_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_star_knobs.piece_shift = value;
+    else if (k == "regex_begins_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_begins_piece_shift = value;
     else if (k == "regex_star_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_knobs.warm = value;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_star, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else if (k == "tile_piece_shift" && (value == 0 || (value >= 6 && value <= 12))) {
         // the dictionary's tile is 2^(value - 6) rounds of 8 KiB and at most 256 KiB: a context with a dictionary session
         // takes no 12
         if ((uint32_t)value > bmx::ORDERED_DICT_MAX_PIECE_SHIFT && ctx->dict) return BMX_ERR_ARG;
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_star, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
     } else if (k == "tile_max_grid" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_star, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }
@@ -753,6 +788,7 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "hamming") state = ctx->hamming;
     else if (k == "gaps") state = ctx->gaps;
     else if (k == "regex") state = ctx->regex;
+    else if (k == "regex_begins") state = ctx->regex_begins;
     else if (k == "regex_star") state = ctx->regex_star;
     else if (k == "dict") state = ctx->dict;
     else if (k == "rows") { // (its own state: the tile is fixed, so out3[0] is log2 of its bytes)

@@ -25,6 +25,10 @@
 //                         TILE_WRITE: hit number i of the lane goes to slot base + i if that is below a.cap.
 //   ordinal(e)            the ordinal in lane of the parked entry e
 //   also(a, idx, e)       what the entry stores at slot idx besides its position (the approximate search: the distance)
+//   ORDINAL_DESCENDS      optional, true for a policy whose lanes meet their hits in DESCENDING position (the regex begins
+//                         search walks downwards): ordinal(e) then counts from the lane's highest hit, a parked hit goes to
+//                         prefix + lane_base[lane + 1] - 1 - ordinal (lane_base[] gets the tile's sum as one more entry),
+//                         and walk<TILE_WRITE> gets the slot one past the lane's last as `base` and writes downwards
 // and x... are further by-value kernel arguments handed through to walk (the gapped search: its four mask words; the
 // k-mismatch search: its `must` mask and counter bias).
 #pragma once
@@ -95,12 +99,19 @@ struct tile_fill_takes_x : std::false_type {};
 template <typename P>
 struct tile_fill_takes_x<P, typename std::enable_if<P::FILL_TAKES_X>::type> : std::true_type {};
 
+// P::ORDINAL_DESCENDS, false for a policy that does not say
+template <typename P, typename = void>
+struct tile_ordinal_descends : std::false_type {};
+template <typename P>
+struct tile_ordinal_descends<P, typename std::enable_if<P::ORDINAL_DESCENDS>::type> : std::true_type {};
+
 template <typename P, typename... X>
 __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, const X... x)
 {
     __shared__ typename P::Elem tab[P::TAB];
     __shared__ uint64_t stage[TILE_STAGE];
-    __shared__ uint32_t lane_base[TILE_BLOCK]; // hits per lane, then their exclusive scan
+    constexpr int DESC = tile_ordinal_descends<P>::value ? 1 : 0;
+    __shared__ uint32_t lane_base[TILE_BLOCK + DESC]; // hits per lane, then their exclusive scan (DESC: and their sum)
     __shared__ uint32_t stage_n;
     __shared__ uint64_t sh_tile, sh_prefix;
     const uint32_t tid = threadIdx.x;
@@ -128,6 +139,7 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, cons
                 const uint64_t prefix = ordered_lookback(a, t, agg);
                 ordered_publish_total(a, t, prefix + agg);
                 sh_prefix = prefix;
+                if constexpr (DESC != 0) lane_base[TILE_BLOCK] = (uint32_t)agg;
             }
         }
         __syncthreads();
@@ -138,14 +150,15 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_kernel(const TileArgs a, cons
                 for (uint32_t j = tid; j < parked; j += TILE_BLOCK) {
                     const uint64_t e = stage[j];
                     const uint32_t pos = (uint32_t)e;
-                    const uint64_t idx = prefix + lane_base[pos >> ps] + P::ordinal(e);
+                    const uint64_t idx = DESC ? prefix + lane_base[(pos >> ps) + 1] - 1 - P::ordinal(e)
+                                              : prefix + lane_base[pos >> ps] + P::ordinal(e);
                     if (idx < a.cap) {
                         a.out[idx] = tile0 + pos + a.out_bias;
                         P::also(a, idx, e);
                     }
                 }
             } else if (lo < hi) { // dense tile: walk it again, writing every hit to its slot
-                (void)P::template walk<TILE_WRITE>(a, tab, lo, hi, tile0, stage, &stage_n, prefix + lane_base[tid], x...);
+                (void)P::template walk<TILE_WRITE>(a, tab, lo, hi, tile0, stage, &stage_n, prefix + lane_base[tid + DESC], x...);
             }
         }
         __syncthreads(); // the pool, the lane bases and stage_n are the next tile's

@@ -193,6 +193,16 @@ SYMBOLS = [
     ("bmx_last_regex_ms", C.c_float, [C.c_void_p]),
     ("bmx_regex_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_regex_reverse", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_begins_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                 C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_last_regex_begins_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_ends_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_begins", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_begins_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_uint64, _u64p]),
+    ("bmx_device_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("bmx_compile_regex_star", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     ("bmx_search_regex_star_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                                C.c_uint64, _u64p, C.c_void_p]),
@@ -526,6 +536,22 @@ def compile_regex_star(expr, flags: int = 0) -> Regex:
     return out
 
 
+def reverse_regex(expr_or_regex, flags: int = 0) -> Regex:
+    """The reversed automaton (bmx_regex_reverse): position i becomes m - 1 - i, first and last swap, follow is transposed,
+    the classes are mirrored; it matches the mirror image of what the input matches.  An expression is compiled with
+    compile_regex(expr, flags) first."""
+    re_ = _regex(expr_or_regex, flags)
+    out = Regex()
+    _check(lib().bmx_regex_reverse(C.byref(re_), C.byref(out)), "bmx_regex_reverse")
+    return out
+
+
+def _posix_args(kind="regex", merge=False, longest=None, **_):
+    """What posix=True of sub / findall goes with (checked before any GPU work)."""
+    if kind != "regex" or merge or longest is not None:
+        raise ValueError("posix: kind 'regex' only, without merge and without an explicit longest")
+
+
 def _regex(expr_or_regex, flags: int = 0, star: bool = False) -> Regex:
     """A Regex from an expression (str / bytes) or such a structure, passed through."""
     if isinstance(expr_or_regex, (str, bytes, bytearray)):
@@ -560,13 +586,13 @@ class Context:
 
     def set_knob(self, name: str, value: int):
         """libbmx_exp.so only (bmx_exp_set_knob): max_grid, no_dense, no_text_sample, multi_no_qgram, ed_lag, ed_group, ed_step_x,
-        ed_stamp_block, sa_flags, index_no_dir, align_ws_kib, ordered_seq, tile_piece_shift, tile_max_grid, select_tile_shift
-        (include/bmx_exp.h)."""
+        ed_stamp_block, sa_flags, index_no_dir, align_ws_kib, ordered_seq, tile_piece_shift, tile_max_grid, select_tile_shift,
+        regex_begins_piece_shift (include/bmx_exp.h)."""
         self._chk(self._L.bmx_exp_set_knob(self._h, name.encode(), int(value)), "bmx_exp_set_knob")
 
     def last_launch(self, session: str) -> Tuple[int, int, int]:
         """libbmx_exp.so only (bmx_exp_last_launch): (piece shift, workgroups, tiles) of the last launch of the session
-        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_star" or "dict"; "rows": (log2 of the bytes
+        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_begins", "regex_star" or "dict"; "rows": (log2 of the bytes
         of a tile, workgroups, tiles) of the last rows_split_device; "select": (log2 T, levels of pointer jumping, tiles of T
         entries) of the last select_spans_device."""
         out = (C.c_uint64 * 3)()
@@ -1243,6 +1269,92 @@ class Context:
     def last_regex_ms(self) -> float:
         return float(self._L.bmx_last_regex_ms(self._h))
 
+    # -- ... its mirror image: every match start, and the end of every start (leftmost-longest) -------
+    def search_regex_begins_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, tail: int = 0,
+                                   base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
+        """Every start s in [0, n - tail) of the view ``d_text[0:n)`` at which a match of the expression begins (and ends
+        inside the view), ascending, reported as base_offset + s (bmx_search_regex_begins_device).  ``tail``: a shard's view
+        runs max_len - 1 bytes past its last owned start.  The other arguments and the return value (starts view, true
+        total) are those of search_regex_device."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_regex_begins_device(self._h, C.c_void_p(d_text.data_ptr()), n, tail, base_offset, C.byref(re_),
+                                                    C.c_void_p(out.data_ptr()), cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_regex_begins_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def regex_ends_device(self, d_text, expr_or_regex, starts, *, longest: bool = False, limit=None, flags: int = 0,
+                          n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """An end for every start of ``starts`` (int64 / uint64 CUDA tensor, as search_regex_begins_device returns it for the
+        same view, expression and base_offset): the smallest one, or with ``longest`` the largest one of the view
+        (bmx_regex_ends_device).  ``limit``: a tensor like ``starts``, the last byte a match of each entry may use; an entry
+        without a match within its limit gets all ones (-1 as int64).  Returns the ends, a tensor like ``starts``."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags)
+        count = starts.numel()
+        if n is None:
+            n = d_text.numel()
+        if starts.element_size() != 8 or (limit is not None and (limit.element_size() != 8 or limit.numel() != count)):
+            raise ValueError("starts, limit: 8-byte entries, as many of one as of the other")
+        ends = torch.empty(max(count, 1), dtype=starts.dtype, device=starts.device)
+        s = stream if stream is not None else torch.cuda.current_stream(starts.device)
+        rc = self._L.bmx_regex_ends_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                           C.c_void_p(starts.data_ptr()), count,
+                                           C.c_void_p(limit.data_ptr()) if limit is not None else None,
+                                           REGEX_LONGEST if longest else 0, C.c_void_p(ends.data_ptr()), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_ends_device")
+        return ends[:count]
+
+    def search_regex_begins(self, text, expr_or_regex, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex_begins): ascending starts, uint64.  With ``capacity`` given and too small, raises
+        BmxError(ERR_CAPACITY); without it the list is always complete."""
+        re_ = _regex(expr_or_regex, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_begins(self._h, tptr, n, C.byref(re_), C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_begins")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_regex_begins_spans(self, text, expr_or_regex, flags: int = 0, longest: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_regex_begins_spans): (starts uint64, ends uint64), starts ascending and each once; each
+        end the smallest one for its start, or with ``longest`` the largest."""
+        re_ = _regex(expr_or_regex, flags)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_begins_spans(self._h, tptr, n, C.byref(re_), REGEX_LONGEST if longest else 0,
+                                                       C.c_void_p(starts.ctypes.data), C.c_void_p(ends.ctypes.data), cap,
+                                                       C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_begins_spans")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy()
+
+    def last_regex_begins_ms(self) -> float:
+        return float(self._L.bmx_last_regex_begins_ms(self._h))
+
     # -- regular-expression search with unbounded repetition: * + {a,} -------------------
     def search_regex_star_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
                                  base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
@@ -1899,27 +2011,53 @@ class Context:
         self._chk(call(out, out.numel()), "bmx_extract_device")
         return out[: int(total.value)], off
 
-    def _selected_spans_device(self, d_text, expr, kind, rows, merge, longest, flags, k, window):
+    def _posix_spans_device(self, d_text, expr, rows, flags):
+        """(starts, ends, row ids or None) of the longest match from every start at which one begins, starts ascending: the
+        begins search, with ``rows`` the last byte of each start's row as its limit, and the ends pass with ``longest``."""
+        import torch
+
+        re_ = _regex(expr, flags)
+        starts, total = self.search_regex_begins_device(d_text, re_)
+        if total > starts.numel():
+            starts, _ = self.search_regex_begins_device(d_text, re_, out=torch.empty(total, dtype=torch.int64, device=d_text.device))
+        if rows is None:
+            return starts, self.regex_ends_device(d_text, re_, starts, longest=True), None
+        if starts.numel() == 0:
+            return starts, starts.clone(), None
+        row = rows.of(starts=starts, length=1)
+        inside = row >= 0
+        limit = torch.where(inside, rows.offsets.to(torch.int64)[row.clamp(min=0) + 1] - 1, starts)
+        ends = self.regex_ends_device(d_text, re_, starts, longest=True, limit=limit)
+        ends = torch.where(inside, ends, torch.full_like(ends, -1))  # a start in no row has no match in a row
+        return starts, ends, rows.of(starts=starts, ends=ends)
+
+    def _selected_spans_device(self, d_text, expr, kind, rows, merge, longest, flags, k, window, posix=False):
+        if posix:
+            _posix_args(kind, merge, longest)
+            starts, ends, ids = self._posix_spans_device(d_text, expr, rows, flags)
+            return self.select_spans_device(starts, ends, 0, rows=ids)
         longest = merge if longest is None else longest
         starts, ends, length = self._match_spans_device(d_text, expr, kind, flags, k, window, longest, rows)
         ids = rows.of(starts=starts, ends=ends, length=length) if rows is not None else None
         return self.select_spans_device(starts, ends, length, rows=ids, merge=merge)
 
     def sub_device(self, d_text, expr, repl, kind: str = "regex", rows: Optional["Rows"] = None, merge: bool = False,
-                   longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None):
+                   longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None, posix: bool = False):
         """(tensor, n_out): the resident text with every non-overlapping match of ``expr`` replaced by the literal ``repl``
         (re.sub, sed s/x/y/g): the search of ``kind`` (as grep_device), its starts post-pass, select_spans_device and
         replace_device.  ``merge``: whole regions of overlapping matches are replaced (``[0-9]+`` then replaces the maximal
         digit runs); ``longest`` (default: ``merge``) asks the starts pass for the smallest start of every end.  ``rows``: a
-        Rows; a match that runs across a row boundary is then left alone."""
-        s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window)
+        Rows; a match that runs across a row boundary is then left alone.  ``posix`` (kind "regex" only, neither ``merge``
+        nor an explicit ``longest``: ValueError): the leftmost-longest matches, what grep -o, sed and awk take -- the begins
+        search, the longest end of every start (with ``rows``: inside the start's row) and the same selection."""
+        s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window, posix)
         return self.replace_device(d_text, s, e, repl)
 
     def findall_device(self, d_text, expr, kind: str = "regex", rows: Optional["Rows"] = None, merge: bool = False,
-                       longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None):
+                       longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None, posix: bool = False):
         """(blob, offsets): the non-overlapping matches of ``expr`` as a string column (re.findall, grep -o): the route of
-        sub_device into extract_device."""
-        s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window)
+        sub_device into extract_device (``posix``: as there)."""
+        s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window, posix)
         return self.extract_device(d_text, s, e)
 
     def last_subst_ms(self) -> float:
@@ -2487,6 +2625,14 @@ def search_regex(text, expr, flags: int = 0, spans: bool = False, longest: bool 
     return ctx.search_regex_spans(text, expr, flags, longest) if spans else ctx.search_regex(text, expr, flags)
 
 
+def search_regex_begins(text, expr, flags: int = 0, spans: bool = False, longest: bool = False):
+    """(text, star-free regular expression) -> ascending starts of every match, each once (bmx_search_regex_begins); with
+    ``spans`` the pair (starts, ends), each end the smallest one for its start (the shortest match) or with ``longest``
+    the largest."""
+    ctx = default_context()
+    return ctx.search_regex_begins_spans(text, expr, flags, longest) if spans else ctx.search_regex_begins(text, expr, flags)
+
+
 def search_regex_star(text, expr, flags: int = 0, spans: bool = False, longest: bool = False, window: int = 4096):
     """(text, regular expression with * + {a,}) -> ascending ends of every match (bmx_search_regex_star); with ``spans`` the
     pair (starts, ends), each start that of the shortest match of at most ``window`` bytes for its end, or with
@@ -2538,6 +2684,8 @@ def _resident(text):
 def sub(text, expr, repl, **kw) -> bytes:
     """(text, expression, literal) -> the text with every non-overlapping match replaced (re.sub without back-references).
     The keywords are Context.sub_device's; ``rows=True`` keeps matches that cross a line break out."""
+    if kw.get("posix"):
+        _posix_args(**kw)
     ctx = default_context()
     d_text = _resident(text)
     if kw.get("rows") is True:
@@ -2549,6 +2697,8 @@ def sub(text, expr, repl, **kw) -> bytes:
 def findall(text, expr, **kw) -> list:
     """(text, expression) -> the non-overlapping matches as a list of bytes (re.findall).  The keywords are
     Context.findall_device's."""
+    if kw.get("posix"):
+        _posix_args(**kw)
     ctx = default_context()
     d_text = _resident(text)
     if kw.get("rows") is True:
