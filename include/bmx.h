@@ -1329,6 +1329,60 @@ int bmx_search_regex_begins_spans(bmx_ctx *ctx /* NULL: device 0 */, const char 
  * a NULL context, or NULL pointers with bytes > 0; bytes == 0 does nothing. */
 int bmx_device_download(bmx_ctx *ctx, void *dst, const void *d_src, uint64_t bytes);
 
+/* ---- leftmost-longest matching for automata with a cycle (* + {a,}) ----------------------- */
+
+/* The same two passes for every automaton that bmx_search_regex_star_device accepts.  The entries above
+ * are unchanged and still refuse a cycle.
+ * Semantics: every START s in [0, n - tail) for which text[s..j] matches for some j < n of the view, each start once,
+ * ascending, reported as base_offset + s; exact for every valid automaton and every text.  A star-free automaton gives
+ * bmx_search_regex_begins_device's list.  A match must end inside the view, and as on the forward side there is no halo: a
+ * shard's list is a subset of the whole text's list and misses exactly the starts whose every match ends past the shard's
+ * view; `tail` is the mirror of `lead`.  tail == n returns BMX_OK with no match and puts nothing on the stream.
+ * How: the reversed automaton, masked to the positions a match can use, runs DOWN the text in place.  A lane walks a
+ * warm-up above its starts with two states, one from the empty set and one from every position; where the two meet the lane
+ * is exact, and where some lane's do not, the call drops its first list and repeats the search exactly: bounds and
+ * columns per piece numbered from the top of the view, a sweep, and the search again from the swept states
+ * (csrc/bmx_regex_star_begins_kernel.h).  The slow path's workspace (40 bytes per piece of 256..4,096 bytes and 8 bytes per
+ * column) is made on the first such call, kept in the context and freed with it.
+ * Any byte values in text and classes; n < 2^40, any alignment of d_text.  No byte outside the aligned 16-byte lines that
+ * hold text[0..n) is read, none above the line of text[n - 1].
+ * Capacity: the stored entries are the LOWEST `capacity` starts; *n_matches is the true total, and a larger total returns
+ * BMX_ERR_CAPACITY (capacity 0 counts only).  Argument errors (NULL pointers where needed, an automaton that is not valid,
+ * tail > n, n too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  The look-back time-out and
+ * BMX_ERR_HIP in place of a partly ordered list: as for bmx_search_regex_device.  All work goes on `stream` (NULL = the
+ * null stream); the call returns after synchronising that stream. */
+int bmx_search_regex_star_begins_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t tail, uint64_t base_offset,
+                                        const bmx_regex *re, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
+                                        void *stream);
+/* Device time (ms) of the last bmx_search_regex_star_begins_device on ctx: the one launch, or, where the call repeated the
+ * search, everything from the first launch to the last; < 0 if none. */
+float bmx_last_regex_star_begins_ms(bmx_ctx *ctx);
+/* Host buffers in, host buffers out (upload, bmx_search_regex_star_begins_device with tail = 0, download). */
+int bmx_search_regex_star_begins(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                 uint64_t *starts, uint64_t capacity, uint64_t *n_matches);
+/* The END of a match for every start of a device-resident list: bmx_regex_ends_device for an automaton that may have a
+ * cycle, with `window` (1..BMX_MAX_REGEX_STAR_WINDOW) in place of max_len: d_ends[i] is the smallest, with
+ * BMX_REGEX_LONGEST the largest end of a match that begins at d_starts[i] and uses at most `window` bytes, none past
+ * d_limit[i] (optional) and none past the view.  A lane stops as soon as its state is empty: the run is anchored at the
+ * start, so [0-9]+ reads to the end of its number and not to the end of its window.
+ * An entry with no such match gets UINT64_MAX (bmx_spans_select_device skips it).  That is an error (BMX_ERR_ARG) only
+ * without d_limit and for an acyclic automaton with max_len <= window, where no longer match can exist.
+ * CLIPPED: an entry whose state after `window` bytes still holds a position with a successor, where neither its limit nor
+ * the view's end would have stopped it, may have a longer match than the one reported (the next byte is not looked at: a
+ * run of [0-9]+ that fills the window exactly counts).  *n_clipped (may be NULL) is the number of such
+ * entries; a caller that needs the POSIX answer treats a non-zero count as a failure or repeats with a larger window.
+ * Other errors, the rule for entries outside the view, the bytes read and the stream rule: bmx_regex_ends_device's, with
+ * the validity rule of bmx_search_regex_star_device and window out of range among the argument errors. */
+int bmx_regex_star_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                               const uint64_t *d_starts, uint64_t count, const uint64_t *d_limit /* NULL: the view's last byte */,
+                               uint32_t window, uint32_t flags, uint64_t *d_ends, uint64_t *n_clipped /* NULL: not wanted */,
+                               void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_regex_star_begins_device, bmx_regex_star_ends_device (flags:
+ * BMX_REGEX_LONGEST or 0; no limit), download.  ends[i] belongs to starts[i]; capacity and *n_matches as above. */
+int bmx_search_regex_star_begins_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                       uint32_t window, uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity,
+                                       uint64_t *n_matches, uint64_t *n_clipped /* NULL: not wanted */);
+
 #ifdef __cplusplus
 }
 #endif

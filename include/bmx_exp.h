@@ -59,6 +59,14 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3);
  * "bmx_exp_last_launch" knows the session as "regex_star". */
 int bmx_exp_regex_star_last(bmx_ctx *ctx, uint64_t *out10);
 
+/* The same for the last bmx_search_regex_star_begins_device (pieces are counted from the top of the view).  That search
+ * has the knobs "regex_star_begins_force_slow", "regex_star_begins_piece_shift" (0, 4..12) and "regex_star_begins_warm"
+ * (0, or a multiple of 16 up to 65,536) of bmx_exp_set_knob, with the meaning and the ranges of the three "regex_star_"
+ * knobs above, takes "tile_piece_shift" / "tile_max_grid" / "ordered_seq", and is "regex_star_begins" in
+ * bmx_exp_last_launch.  "regex_star_ends_no_early_exit" (non-zero) makes bmx_regex_star_ends_device walk the whole window
+ * of every entry, to time what the early exit saves; the answers are the same. */
+int bmx_exp_regex_star_begins_last(bmx_ctx *ctx, uint64_t *out10);
+
 /* Read-only sweep of n bytes at d_text (16-byte aligned) with plain global loads into registers, XOR-folded: no LDS,
  * no barrier, no tiles (csrc/bmx_probe_kernel.h).  unroll = loads in flight per lane (1, 2, 4, 8, 16), nt = cache
  * policy, block threads per workgroup, blocks_per_cu workgroups per CU.  ms_out[i] = duration of launch i. */

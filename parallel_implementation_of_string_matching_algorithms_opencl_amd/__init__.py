@@ -16,6 +16,6 @@ from .host import (BmxError, CLASS_ICASE, CLASS_IUPAC, Context, Dictionary, GAPS
                    align, build_tables, cigar_strings, compile_classes, compile_gaps, compile_regex, compile_regex_star, edit_distance_batch,
                    grep, index_count, index_map, index_seeds, lcp_array, longest_repeat, rows_split, search, search_approx, search_classes,
                    search_dict, search_gaps, search_hamming, search_ranges, search_regex, search_regex_star)
-from .host import reverse_regex, search_regex_begins  # noqa: F401
+from .host import reverse_regex, search_regex_begins, search_regex_star_begins  # noqa: F401
 
 __version__ = "0.1.0"

@@ -822,6 +822,55 @@ int bmx_search_regex_star_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, c
     return c.rc;
 }
 
+int bmx_search_regex_star_begins(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint64_t *starts,
+                                 uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_regex_star_begins_args_ok(n, 0, re, starts, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_star_begins", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_star_begins_device(c.ctx(), d_text, n, 0, 0, re, d_starts, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(starts, d_starts, std::min(total, dev_cap) * sizeof(uint64_t), "regex match starts");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+int bmx_search_regex_star_begins_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint32_t window,
+                                       uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches,
+                                       uint64_t *n_clipped)
+{
+    if (!bmx_regex_star_begins_args_ok(n, 0, re, starts, capacity) || (capacity > 0 && !ends) || (n > 0 && !text) ||
+        (flags & ~BMX_REGEX_LONGEST) || window < 1 || window > BMX_MAX_REGEX_STAR_WINDOW)
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n_clipped) *n_clipped = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_star_begins_spans", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_star_begins_device(c.ctx(), d_text, n, 0, 0, re, d_starts, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    const int erc = bmx_regex_star_ends_device(c.ctx(), d_text, n, 0, re, d_starts, stored, nullptr, window, flags, d_ends, n_clipped, nullptr);
+    if (erc != BMX_OK) return erc;
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "regex match starts");
+    c.download(ends, d_ends, stored * sizeof(uint64_t), "regex match ends");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
 int bmx_dict_search(bmx_ctx *ctx_in, const char *text, uint64_t n, const char *const *pats, const int32_t *ms, int32_t K,
                     uint64_t *pos, uint32_t *pid, uint64_t capacity, uint64_t *n_matches)
 {

@@ -141,6 +141,26 @@ float bmx_internal_regex_star_ms(const void *state);
 void bmx_internal_regex_star_last(const void *state, uint64_t out10[10]); // libbmx_exp.so only
 uint32_t bmx_internal_regex_star_piece_shift(uint64_t n, uint64_t resident_lanes); // log2 of the ends per lane
 uint32_t bmx_internal_regex_star_warm(uint32_t piece_shift);                       // bytes of the pair warm-up
+// ... what its slow path runs between its kernels, also for the begins search: the column offsets by a scan, and the sweep
+int bmx_internal_regex_star_offsets(const char *where, void **d_scan, size_t *scan_cap, const uint64_t *d_u, uint64_t n_pieces,
+                                    uint64_t *d_off, uint64_t *h_total, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_regex_star_sweep(const char *where, uint64_t n_pieces, const uint64_t *d_e, const uint64_t *d_u, const uint64_t *d_off,
+                                  const uint64_t *d_base, const uint64_t *d_cols, uint64_t *d_entry, hipStream_t stream, char *err,
+                                  size_t errlen);
+// bmx_regex_star_begins.hip: its mirror image, every start (a state and knobs of its own, the piece and warm-up rules
+// above), and the end of every start of a list within a window (*bad_out: the status bits, of which only a start outside
+// the view is an error there; *clipped_out: the entries whose state outlived the window)
+int bmx_internal_regex_star_begins(void **state, int num_cu, const bmx_regex_star_knobs *knobs, const void *d_text, uint64_t n,
+                                   uint64_t tail, uint64_t base_offset, const bmx_regex *re, uint64_t *d_starts, uint64_t capacity,
+                                   uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_regex_star_ends(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                 const uint64_t *d_starts, uint64_t count, const uint64_t *d_limit, uint32_t window, uint32_t flags,
+                                 bool early_exit, uint64_t *d_ends, uint64_t *bad_out, uint64_t *clipped_out, hipStream_t stream,
+                                 char *err, size_t errlen);
+void bmx_internal_regex_star_begins_free(void *state);
+float bmx_internal_regex_star_begins_ms(const void *state);
+void bmx_internal_regex_star_begins_last(const void *state, uint64_t out10[10]); // libbmx_exp.so only
+constexpr uint64_t BMX_REGEX_STAR_ENDS_NO_MATCH = 2; // *bad_out: some start had no match (csrc/bmx_regex_star_begins_kernel.h)
 // bmx_ed_batch.hip
 int bmx_internal_ed_batch(void **state, bmx_ctx *ctx, const void *d_a, uint64_t a_bytes, const uint64_t *d_a_off, uint64_t a_count,
                           const void *d_b, uint64_t b_bytes, const uint64_t *d_b_off, uint64_t count, uint32_t limit,
@@ -258,6 +278,9 @@ struct bmx_ctx {
     int regex_begins_piece_shift = 0; // libbmx_exp.so: 0, or log2 of the starts per lane of the begins search (4..12)
     void *regex_star = nullptr; // ... with unbounded repetition: the same, the taint words and the slow path's workspace (bmx_regex_star.hip)
     bmx_regex_star_knobs regex_star_knobs;
+    void *regex_star_begins = nullptr; // ... and its begins search and ends pass: the same again, their own (bmx_regex_star_begins.hip)
+    bmx_regex_star_knobs regex_star_begins_knobs;
+    bool regex_star_ends_no_early_exit = false; // libbmx_exp.so: the ends pass walks its whole window (to time the early exit)
     void *approx = nullptr; // approximate search: look-back words, ticket, pinned result words, events (bmx_approx.hip)
     void *approx_long = nullptr; // ... for patterns of more than 64 bytes: the same kind of state, its own (bmx_approx_long.hip)
     bool approx_last_long = false; // which of the two the last approximate search on this context used (bmx_last_approx_ms)
@@ -377,6 +400,19 @@ inline bool bmx_regex_star_starts_args_ok(uint64_t n, const bmx_regex *re, const
     if (!bmx_regex_star_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
     if (window < 1 || window > BMX_MAX_REGEX_STAR_WINDOW) return false;
     return count == 0 || (ends && starts);
+}
+
+// ... every start of such an automaton, and the ends of the matches that begin there, within a window
+inline bool bmx_regex_star_begins_args_ok(uint64_t n, uint64_t tail, const bmx_regex *re, const void *starts, uint64_t capacity)
+{
+    return bmx_regex_star_ok(re) && tail <= n && n < (1ull << 40) && (capacity == 0 || starts);
+}
+inline bool bmx_regex_star_ends_args_ok(uint64_t n, const bmx_regex *re, const uint64_t *starts, uint64_t count, uint32_t window,
+                                        uint32_t flags, const uint64_t *ends)
+{
+    if (!bmx_regex_star_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
+    if (window < 1 || window > BMX_MAX_REGEX_STAR_WINDOW) return false;
+    return count == 0 || (starts && ends);
 }
 
 // match spans (pat: the string or the classes)

@@ -64,6 +64,12 @@
 //                             bytes`.  --starts needs --window N (1..65536): the start of the shortest (--longest: the
 //                             longest) match of at most N bytes, 18446744073709551615 where there is none.  It goes with
 //                             none of --regex, --gaps, --classes, --approx, --hamming
+//   bmx_cli --regex-star EXPR --begins [--spans --window N [--longest]] [--icase] [--iupac] [--text F] [--positions] [--max-print K]
+//                             what --regex EXPR --begins prints, for an expression with * + {a,}
+//                             (bmx_search_regex_star_begins); with --spans the smallest (--longest: the largest) end among
+//                             the matches of at most N bytes from every start, 18446744073709551615 where there is none
+//                             (bmx_search_regex_star_begins_spans), and `clipped by the window of N bytes: C`, the starts
+//                             whose longest match may be longer than N
 //   bmx_cli --approx K --spans [--best] [--pattern F | --classes EXPR [--icase] [--iupac]] [--text F] [--max-print K]
 //                             after what --approx prints: the span of every match (bmx_search_approx_spans), the total
 //                             and one `start end dist` line per span (at most --max-print of them); --best keeps one
@@ -107,10 +113,12 @@
 //                             union of the longest match of every end), replaced by STR (bmx_replace: the new text on
 //                             stdout or in F, a total line on stderr: sed s/x/STR/g) or printed one per line
 //                             (bmx_extract, at most --max-print of them: grep -o); with --lines a match that crosses a
-//                             line break is left alone.  --posix (with --regex, without --merge): the leftmost-longest
+//                             line break is left alone.  --posix (with --regex or --regex-star, without --merge): the leftmost-longest
 //                             matches, as grep -o and sed take them -- every start with its longest end
 //                             (bmx_search_regex_begins_spans; with --lines the longest end inside the start's line,
-//                             bmx_regex_ends_device with a limit), then the same selection
+//                             bmx_regex_ends_device with a limit), then the same selection.  With --regex-star it needs
+//                             --window N (bmx_search_regex_star_begins_spans, bmx_regex_star_ends_device) and fails, exit
+//                             status 1, if some match may be longer than N bytes: it never prints a shorter one
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -287,13 +295,13 @@ int main(int argc, char **argv)
     if (regex_begins) { // --spans and --longest are the begins search's here
         begins_spans = spans, begins_longest = gaps_longest;
         spans = gaps_longest = false;
-        if (!have_regex || regex_star || gaps_starts || posix || lines_mode || have_replace || only_matching || (begins_longest && !begins_spans)) {
-            fprintf(stderr, "--begins needs --regex EXPR and goes with --spans [--longest], --positions and --max-print only\n");
+        if (!have_regex || gaps_starts || posix || lines_mode || have_replace || only_matching || (begins_longest && !begins_spans)) {
+            fprintf(stderr, "--begins needs --regex EXPR or --regex-star EXPR and goes with --spans [--longest], --positions and --max-print only\n");
             return 2;
         }
     }
-    if (posix && (!have_regex || regex_star || select_merge || !(have_replace || only_matching))) {
-        fprintf(stderr, "--posix needs --regex EXPR with --replace STR or --only-matching, without --merge\n");
+    if (posix && (!have_regex || select_merge || !(have_replace || only_matching))) {
+        fprintf(stderr, "--posix needs --regex EXPR or --regex-star EXPR with --replace STR or --only-matching, without --merge\n");
         return 2;
     }
     if ((spans && approx_k < 0) || (spans_best && !spans)) {
@@ -332,9 +340,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "--regex goes with none of --gaps, --prosite, --classes, --approx, --hamming\n");
         return 2;
     }
-    if (regex_both || (regex_star && gaps_starts && (star_window < 1 || star_window > BMX_MAX_REGEX_STAR_WINDOW)) ||
-        (star_window != 0 && !(regex_star && gaps_starts))) {
-        fprintf(stderr, "--regex-star goes without --regex; its --starts needs --window N with 1 <= N <= 65536, and --window goes with nothing else\n");
+    const bool star_windowed = regex_star && (gaps_starts || begins_spans || posix); // what looks for a match's other end
+    if (regex_both || (star_windowed && (star_window < 1 || star_window > BMX_MAX_REGEX_STAR_WINDOW)) || (star_window != 0 && !star_windowed)) {
+        fprintf(stderr, "--regex-star goes without --regex; its --starts, its --begins --spans and its --posix need --window N with 1 <= N <= 65536, "
+                        "and --window goes with nothing else\n");
         return 2;
     }
     if ((gaps_starts && !have_gaps && !have_regex) || ((class_flags & BMX_GAPS_PROSITE) && !have_gaps)) {
@@ -693,7 +702,12 @@ int main(int argc, char **argv)
             // (the star search: a match longer than the longest row lies in no row)
             const uint32_t window = (uint32_t)std::min<uint64_t>(BMX_MAX_REGEX_STAR_WINDOW, std::max<uint64_t>(longest, 1));
             what = regex_star ? "bmx_search_regex_star_spans" : "bmx_search_regex_spans";
-            if (posix && !lines_mode) { // every start with its longest end: the selection below gives leftmost-longest
+            uint64_t clipped = 0; // --regex-star --posix: the starts whose longest match may be longer than the window
+            if (posix && !lines_mode && regex_star) {
+                what = "bmx_search_regex_star_begins_spans";
+                rc = bmx_search_regex_star_begins_spans(ctx, text.data(), n, &re, star_window, BMX_REGEX_LONGEST, starts.data(), ends.data(), room,
+                                                        &hits, &clipped);
+            } else if (posix && !lines_mode) { // every start with its longest end: the selection below gives leftmost-longest
                 what = "bmx_search_regex_begins_spans";
                 rc = bmx_search_regex_begins_spans(ctx, text.data(), n, &re, BMX_REGEX_LONGEST, starts.data(), ends.data(), room, &hits);
             } else if (posix) { // ... its longest end inside its line: the ends pass with the line's last byte as the limit
@@ -703,15 +717,19 @@ int main(int argc, char **argv)
                 rc = bmx_text_upload(ctx, text.data(), n, &d_text);
                 if (rc == BMX_OK) rc = bmx_device_alloc(ctx, room * sizeof(uint64_t), (void **)&d_starts);
                 if (rc == BMX_OK) rc = bmx_device_alloc(ctx, room * sizeof(uint64_t), (void **)&d_ends);
-                if (rc == BMX_OK) rc = bmx_search_regex_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr);
+                if (rc == BMX_OK)
+                    rc = regex_star ? bmx_search_regex_star_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr)
+                                    : bmx_search_regex_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr);
                 if (rc == BMX_OK) rc = bmx_device_download(ctx, starts.data(), d_starts, hits * sizeof(uint64_t));
                 std::vector<uint64_t> limit(hits ? hits : 1);
                 for (uint64_t i = 0; i < hits && rc == BMX_OK; ++i) // off[0] = 0 and off[rows] = n: every start lies in a row
                     limit[i] = *std::upper_bound(off.begin(), off.begin() + rows + 1, starts[i]) - 1;
                 if (rc == BMX_OK) rc = bmx_text_upload(ctx, reinterpret_cast<const char *>(limit.data()), hits * sizeof(uint64_t), &d_limit);
                 if (rc == BMX_OK)
-                    rc = bmx_regex_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit), BMX_REGEX_LONGEST,
-                                               d_ends, nullptr);
+                    rc = regex_star ? bmx_regex_star_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit),
+                                                                 star_window, BMX_REGEX_LONGEST, d_ends, &clipped, nullptr)
+                                    : bmx_regex_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit),
+                                                            BMX_REGEX_LONGEST, d_ends, nullptr);
                 if (rc == BMX_OK) rc = bmx_device_download(ctx, ends.data(), d_ends, hits * sizeof(uint64_t));
                 bmx_device_free(ctx, d_limit);
                 bmx_device_free(ctx, d_ends);
@@ -720,6 +738,11 @@ int main(int argc, char **argv)
             } else
             rc = regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, longest_flag, starts.data(), ends.data(), room, &hits)
                             : bmx_search_regex_spans(ctx, text.data(), n, &re, longest_flag, starts.data(), ends.data(), room, &hits);
+            if (rc == BMX_OK && clipped != 0) { // never a shorter match than POSIX's
+                fprintf(stderr, "--posix: %llu match(es) may be longer than the window of %u bytes; pass a larger --window\n",
+                        (unsigned long long)clipped, star_window);
+                return 1;
+            }
         } else if (have_gaps) {
             what = "bmx_search_gaps_spans";
             rc = bmx_search_gaps_spans(ctx, text.data(), n, classes.data(), m, gaps_optional, longest_flag, starts.data(), ends.data(), room, &hits);
@@ -830,16 +853,22 @@ int main(int argc, char **argv)
             }
             const uint64_t room = n ? n : 1; // at most one hit per start
             std::vector<uint64_t> starts(room), ends(begins_spans ? room : 1);
-            uint64_t got = 0;
-            rc = begins_spans ? bmx_search_regex_begins_spans(ctx, text.data(), n, &re, begins_longest ? BMX_REGEX_LONGEST : 0u, starts.data(),
-                                                              ends.data(), room, &got)
-                              : bmx_search_regex_begins(ctx, text.data(), n, &re, starts.data(), room, &got);
+            uint64_t got = 0, clipped = 0;
+            const uint32_t span_flags = begins_longest ? BMX_REGEX_LONGEST : 0u;
+            if (regex_star)
+                rc = begins_spans ? bmx_search_regex_star_begins_spans(ctx, text.data(), n, &re, star_window, span_flags, starts.data(), ends.data(),
+                                                                       room, &got, &clipped)
+                                  : bmx_search_regex_star_begins(ctx, text.data(), n, &re, starts.data(), room, &got);
+            else
+                rc = begins_spans ? bmx_search_regex_begins_spans(ctx, text.data(), n, &re, span_flags, starts.data(), ends.data(), room, &got)
+                                  : bmx_search_regex_begins(ctx, text.data(), n, &re, starts.data(), room, &got);
             if (rc != BMX_OK) {
-                fprintf(stderr, "%s failed: %d (%s)\n", begins_spans ? "bmx_search_regex_begins_spans" : "bmx_search_regex_begins", rc,
+                fprintf(stderr, "bmx_search_regex%s_begins%s failed: %d (%s)\n", regex_star ? "_star" : "", begins_spans ? "_spans" : "", rc,
                         bmx_last_error());
                 return 1;
             }
             printf("regex match starts: %llu\n", (unsigned long long)got);
+            if (regex_star && begins_spans) printf("clipped by the window of %u bytes: %llu\n", star_window, (unsigned long long)clipped);
             if (got) {
                 printf("first start: %llu\n", (unsigned long long)starts[0]);
                 printf("last start: %llu\n", (unsigned long long)starts[got - 1]);

@@ -81,6 +81,44 @@ float elapsed_us(hipEvent_t a, hipEvent_t b)
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? 1000.0f * ms : 0.0f;
 }
 
+} // namespace
+
+// What the slow path has between its own kernels, for this file and for bmx_regex_star_begins.hip, whose pieces are numbered
+// from the top of the view and are otherwise the same.  The column offsets: the exclusive scan of popcount(u[l]) over
+// [0, n_pieces] into d_off (the scan's temporary storage grows in *d_scan / *scan_cap), the total into the pinned *h_total
+// once `stream` is synchronised.
+int bmx_internal_regex_star_offsets(const char *where, void **d_scan, size_t *scan_cap, const uint64_t *d_u, uint64_t n_pieces,
+                                    uint64_t *d_off, uint64_t *h_total, hipStream_t stream, char *err, size_t errlen)
+{
+    auto counts = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), bmx::RegexStarColumns{d_u, n_pieces});
+    size_t scan_bytes = 0;
+    BMX_HIP(where, rocprim::exclusive_scan(nullptr, scan_bytes, counts, d_off, uint64_t(0), (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), stream));
+    if (scan_bytes > *scan_cap) {
+        if (*d_scan) (void)hipFree(*d_scan);
+        *d_scan = nullptr, *scan_cap = 0;
+        BMX_HIP(where, hipMalloc(d_scan, scan_bytes));
+        *scan_cap = scan_bytes;
+    }
+    BMX_HIP(where, rocprim::exclusive_scan(*d_scan, scan_bytes, counts, d_off, uint64_t(0), (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), stream));
+    BMX_HIP(where, hipMemcpyAsync(h_total, d_off + n_pieces, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(where, hipStreamSynchronize(stream));
+    return BMX_OK;
+}
+
+// ... and star_sweep_kernel over the pieces [0, n_pieces)
+int bmx_internal_regex_star_sweep(const char *where, uint64_t n_pieces, const uint64_t *d_e, const uint64_t *d_u, const uint64_t *d_off,
+                                  const uint64_t *d_base, const uint64_t *d_cols, uint64_t *d_entry, hipStream_t stream, char *err,
+                                  size_t errlen)
+{
+    const uint32_t blocks = (uint32_t)((n_pieces + bmx::REGEX_STAR_BLOCK - 1) / bmx::REGEX_STAR_BLOCK);
+    hipLaunchKernelGGL(bmx::star_sweep_kernel, dim3(blocks), dim3(bmx::REGEX_STAR_BLOCK), 0, stream, n_pieces, d_e, d_u, d_off, d_base, d_cols,
+                       d_entry);
+    BMX_HIP(where, hipGetLastError());
+    return BMX_OK;
+}
+
+namespace {
+
 // The exact list by R1, the sweep and R2.  `a` is the argument block as the first launch left it (geometry and table).
 int slow_path(StarState *st, int slot, int num_cu, bmx::TileArgs a, bmx::RegexStarX x, const void *d_text, uint64_t n, uint64_t lead,
               uint64_t base_offset, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err,
@@ -106,18 +144,8 @@ int slow_path(StarState *st, int slot, int num_cu, bmx::TileArgs a, bmx::RegexSt
     hipLaunchKernelGGL(BMX_STAR_PICK(star_bounds_kernel), dim3(blocks), dim3(bmx::REGEX_STAR_BLOCK), 0, stream, a, x, n_pieces, d_e, d_u);
     BMX_HIP(WHERE, hipGetLastError());
 
-    auto counts = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), bmx::RegexStarColumns{d_u, n_pieces});
-    size_t scan_bytes = 0;
-    BMX_HIP(WHERE, rocprim::exclusive_scan(nullptr, scan_bytes, counts, d_off, uint64_t(0), (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), stream));
-    if (scan_bytes > st->scan_cap) {
-        if (st->d_scan) (void)hipFree(st->d_scan);
-        st->d_scan = nullptr, st->scan_cap = 0;
-        BMX_HIP(WHERE, hipMalloc(&st->d_scan, scan_bytes));
-        st->scan_cap = scan_bytes;
-    }
-    BMX_HIP(WHERE, rocprim::exclusive_scan(st->d_scan, scan_bytes, counts, d_off, uint64_t(0), (size_t)n_pieces + 1, rocprim::plus<uint64_t>(), stream));
-    BMX_HIP(WHERE, hipMemcpyAsync(&st->h_words[1], d_off + n_pieces, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    BMX_HIP(WHERE, hipStreamSynchronize(stream));
+    int orc = bmx_internal_regex_star_offsets(WHERE, &st->d_scan, &st->scan_cap, d_u, n_pieces, d_off, &st->h_words[1], stream, err, errlen);
+    if (orc != BMX_OK) return orc;
     const uint64_t n_cols = st->h_words[1];
     if (n_cols > st->cols_cap) {
         if (st->d_cols) (void)hipFree(st->d_cols);
@@ -135,9 +163,8 @@ int slow_path(StarState *st, int slot, int num_cu, bmx::TileArgs a, bmx::RegexSt
     }
 #undef BMX_STAR_PICK
     BMX_HIP(WHERE, hipEventRecord(st->ev[1], stream));
-    hipLaunchKernelGGL(bmx::star_sweep_kernel, dim3(blocks), dim3(bmx::REGEX_STAR_BLOCK), 0, stream, n_pieces, d_e, d_u, d_off, d_base,
-                       st->d_cols, d_entry);
-    BMX_HIP(WHERE, hipGetLastError());
+    orc = bmx_internal_regex_star_sweep(WHERE, n_pieces, d_e, d_u, d_off, d_base, st->d_cols, d_entry, stream, err, errlen);
+    if (orc != BMX_OK) return orc;
     BMX_HIP(WHERE, hipEventRecord(st->ev[2], stream));
 
     x.entry = d_entry;

@@ -111,6 +111,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_regex_free(ctx->regex);
     bmx_internal_regex_begins_free(ctx->regex_begins);
     bmx_internal_regex_star_free(ctx->regex_star);
+    bmx_internal_regex_star_begins_free(ctx->regex_star_begins);
     bmx_internal_ed_batch_free(ctx->ed_batch);
     bmx_internal_spans_free(ctx->spans);
     bmx_internal_dict_state_free(ctx->dict);
@@ -488,6 +489,44 @@ int bmx_regex_star_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, u
                                               sizeof g_err);
 }
 
+// ... the mirror image: every start, and the end of every start of a list within a window (bmx_regex_star_begins.hip)
+int bmx_search_regex_star_begins_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t tail, uint64_t base_offset,
+                                        const bmx_regex *re, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches,
+                                        void *stream_v)
+{
+    if (!bmx_regex_star_begins_args_ok(n, tail, re, d_starts, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_star_begins(&ctx->regex_star_begins, ctx->num_cu, &ctx->regex_star_begins_knobs, d_text, n, tail,
+                                          base_offset, re, d_starts, capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_star_begins_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_star_begins_ms(ctx->regex_star_begins) : -1.0f; }
+
+int bmx_regex_star_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                               const uint64_t *d_starts, uint64_t count, const uint64_t *d_limit, uint32_t window, uint32_t flags,
+                               uint64_t *d_ends, uint64_t *n_clipped, void *stream_v)
+{
+    if (!bmx_regex_star_ends_args_ok(n, re, d_starts, count, window, flags, d_ends)) return BMX_ERR_ARG;
+    if (n_clipped) *n_clipped = 0;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (a start needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    uint64_t bad = 0, clipped = 0;
+    const int rc = bmx_internal_regex_star_ends(&ctx->regex_star_begins, d_text, n, base_offset, re, d_starts, count, d_limit, window,
+                                                flags, !ctx->regex_star_ends_no_early_exit, d_ends, &bad, &clipped,
+                                                (hipStream_t)stream_v, g_err, sizeof g_err);
+    if (rc != BMX_OK) return rc;
+    if (n_clipped) *n_clipped = clipped;
+    if (!(bad & BMX_REGEX_STAR_ENDS_NO_MATCH)) return BMX_OK;
+    int32_t min_len = 0, max_len = 0;
+    bmx_regex_star_lengths(re->m, re->first, re->last, re->follow, &min_len, &max_len, nullptr);
+    if (max_len != BMX_REGEX_UNBOUNDED && (max_len <= 0 || (uint32_t)max_len <= window)) { // no longer match can exist
+        set_err("bmx_regex_star_ends_device: a start at which no match of this expression begins");
+        return BMX_ERR_ARG;
+    }
+    return BMX_OK;
+}
+
 // ---- match spans of the approximate search (bmx_spans.hip) --------------------------------------
 namespace {
 int spans_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const char *pat, const uint8_t *classes,
@@ -763,15 +802,19 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "regex_star_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_star_knobs.piece_shift = value;
     else if (k == "regex_begins_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_begins_piece_shift = value;
     else if (k == "regex_star_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_knobs.warm = value;
+    else if (k == "regex_star_begins_force_slow") ctx->regex_star_begins_knobs.force_slow = value != 0;
+    else if (k == "regex_star_begins_piece_shift" && (value == 0 || (value >= 4 && value <= 12))) ctx->regex_star_begins_knobs.piece_shift = value;
+    else if (k == "regex_star_begins_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_begins_knobs.warm = value;
+    else if (k == "regex_star_ends_no_early_exit") ctx->regex_star_ends_no_early_exit = value != 0;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else if (k == "tile_piece_shift" && (value == 0 || (value >= 6 && value <= 12))) {
         // the dictionary's tile is 2^(value - 6) rounds of 8 KiB and at most 256 KiB: a context with a dictionary session
         // takes no 12
         if ((uint32_t)value > bmx::ORDERED_DICT_MAX_PIECE_SHIFT && ctx->dict) return BMX_ERR_ARG;
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
     } else if (k == "tile_max_grid" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }
@@ -790,6 +833,7 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "regex") state = ctx->regex;
     else if (k == "regex_begins") state = ctx->regex_begins;
     else if (k == "regex_star") state = ctx->regex_star;
+    else if (k == "regex_star_begins") state = ctx->regex_star_begins;
     else if (k == "dict") state = ctx->dict;
     else if (k == "rows") { // (its own state: the tile is fixed, so out3[0] is log2 of its bytes)
         bmx_internal_rows_last(ctx->rows, out3);
@@ -807,6 +851,14 @@ int bmx_exp_regex_star_last(bmx_ctx *ctx, uint64_t *out10)
 {
     if (!ctx || !out10) return BMX_ERR_ARG;
     bmx_internal_regex_star_last(ctx->regex_star, out10);
+    return BMX_OK;
+}
+
+// ... and the last bmx_search_regex_star_begins_device
+int bmx_exp_regex_star_begins_last(bmx_ctx *ctx, uint64_t *out10)
+{
+    if (!ctx || !out10) return BMX_ERR_ARG;
+    bmx_internal_regex_star_begins_last(ctx->regex_star_begins, out10);
     return BMX_OK;
 }
 

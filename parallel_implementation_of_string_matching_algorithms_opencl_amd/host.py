@@ -212,6 +212,14 @@ SYMBOLS = [
     ("bmx_last_regex_star_ms", C.c_float, [C.c_void_p]),
     ("bmx_regex_star_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_star_begins_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                      C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_last_regex_star_begins_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_star_ends_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _u64p, C.c_void_p]),
+    ("bmx_search_regex_star_begins", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_star_begins_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_uint64, _u64p, _u64p]),
     ("bmx_approx_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           _u64p, C.c_void_p]),
@@ -326,6 +334,7 @@ EXP_SYMBOLS = [
     ("bmx_exp_set_knob", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("bmx_exp_last_launch", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]),
     ("bmx_exp_regex_star_last", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("bmx_exp_regex_star_begins_last", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("bmx_probe_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.POINTER(C.c_float), C.c_void_p]),
     ("bmx_exp_ed_stamps", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -548,8 +557,8 @@ def reverse_regex(expr_or_regex, flags: int = 0) -> Regex:
 
 def _posix_args(kind="regex", merge=False, longest=None, **_):
     """What posix=True of sub / findall goes with (checked before any GPU work)."""
-    if kind != "regex" or merge or longest is not None:
-        raise ValueError("posix: kind 'regex' only, without merge and without an explicit longest")
+    if kind not in ("regex", "regex_star") or merge or longest is not None:
+        raise ValueError("posix: kind 'regex' or 'regex_star' only, without merge and without an explicit longest")
 
 
 def _regex(expr_or_regex, flags: int = 0, star: bool = False) -> Regex:
@@ -587,12 +596,13 @@ class Context:
     def set_knob(self, name: str, value: int):
         """libbmx_exp.so only (bmx_exp_set_knob): max_grid, no_dense, no_text_sample, multi_no_qgram, ed_lag, ed_group, ed_step_x,
         ed_stamp_block, sa_flags, index_no_dir, align_ws_kib, ordered_seq, tile_piece_shift, tile_max_grid, select_tile_shift,
-        regex_begins_piece_shift (include/bmx_exp.h)."""
+        regex_begins_piece_shift, regex_star_begins_force_slow, regex_star_begins_piece_shift, regex_star_begins_warm,
+        regex_star_ends_no_early_exit (include/bmx_exp.h)."""
         self._chk(self._L.bmx_exp_set_knob(self._h, name.encode(), int(value)), "bmx_exp_set_knob")
 
     def last_launch(self, session: str) -> Tuple[int, int, int]:
         """libbmx_exp.so only (bmx_exp_last_launch): (piece shift, workgroups, tiles) of the last launch of the session
-        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_begins", "regex_star" or "dict"; "rows": (log2 of the bytes
+        "approx", "approx_long", "classes", "hamming", "gaps", "regex", "regex_begins", "regex_star", "regex_star_begins" or "dict"; "rows": (log2 of the bytes
         of a tile, workgroups, tiles) of the last rows_split_device; "select": (log2 T, levels of pointer jumping, tiles of T
         entries) of the last select_spans_device."""
         out = (C.c_uint64 * 3)()
@@ -603,6 +613,13 @@ class Context:
         """libbmx_exp.so only (bmx_exp_regex_star_last): what the last search_regex_star_device did."""
         out = (C.c_uint64 * 10)()
         self._chk(self._L.bmx_exp_regex_star_last(self._h, out), "bmx_exp_regex_star_last")
+        keys = ["tainted", "slow", "piece_shift", "warm", "pieces", "columns", "first_us", "r1_us", "sweep_us", "r2_us"]
+        return dict(zip(keys, [int(v) for v in out]))
+
+    def regex_star_begins_last(self) -> dict:
+        """libbmx_exp.so only (bmx_exp_regex_star_begins_last): what the last search_regex_star_begins_device did."""
+        out = (C.c_uint64 * 10)()
+        self._chk(self._L.bmx_exp_regex_star_begins_last(self._h, out), "bmx_exp_regex_star_begins_last")
         keys = ["tainted", "slow", "piece_shift", "warm", "pieces", "columns", "first_us", "r1_us", "sweep_us", "r2_us"]
         return dict(zip(keys, [int(v) for v in out]))
 
@@ -1441,6 +1458,99 @@ class Context:
     def last_regex_star_ms(self) -> float:
         return float(self._L.bmx_last_regex_star_ms(self._h))
 
+    # -- ... its mirror image: every match start of an expression with * + {a,}, and the end of every start ----
+    def search_regex_star_begins_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, tail: int = 0,
+                                        base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
+        """Every start s in [0, n - tail) of the view ``d_text[0:n)`` at which a match of the expression begins (and ends
+        inside the view), ascending and exact, reported as base_offset + s (bmx_search_regex_star_begins_device).
+        ``expr_or_regex``: an expression for compile_regex_star(expr, flags) or a Regex, which may have a cycle.  The other
+        arguments and the return value (starts view, true total) are those of search_regex_begins_device."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags, star=True)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_regex_star_begins_device(self._h, C.c_void_p(d_text.data_ptr()), n, tail, base_offset,
+                                                         C.byref(re_), C.c_void_p(out.data_ptr()), cap, C.byref(total),
+                                                         C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_regex_star_begins_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def regex_star_ends_device(self, d_text, expr_or_regex, starts, *, window: int = 4096, longest: bool = False, limit=None,
+                               flags: int = 0, n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """(ends, clipped): an end for every start of ``starts`` (int64 / uint64 CUDA tensor, as
+        search_regex_star_begins_device returns it for the same view, expression and base_offset) among the matches of at
+        most ``window`` bytes: the smallest one, or with ``longest`` the largest; all ones (-1 as int64) where there is none
+        (bmx_regex_star_ends_device).  ``limit``: a tensor like ``starts``, the last byte a match of each entry may use.
+        ``clipped``: the entries whose run could still be extended after ``window`` bytes inside their limit and the view,
+        i.e. whose longest match may be longer than the one reported."""
+        import torch
+
+        re_ = _regex(expr_or_regex, flags, star=True)
+        count = starts.numel()
+        if n is None:
+            n = d_text.numel()
+        if starts.element_size() != 8 or (limit is not None and (limit.element_size() != 8 or limit.numel() != count)):
+            raise ValueError("starts, limit: 8-byte entries, as many of one as of the other")
+        ends = torch.empty(max(count, 1), dtype=starts.dtype, device=starts.device)
+        s = stream if stream is not None else torch.cuda.current_stream(starts.device)
+        clipped = C.c_uint64(0)
+        rc = self._L.bmx_regex_star_ends_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                                C.c_void_p(starts.data_ptr()), count,
+                                                C.c_void_p(limit.data_ptr()) if limit is not None else None, int(window),
+                                                REGEX_LONGEST if longest else 0, C.c_void_p(ends.data_ptr()), C.byref(clipped),
+                                                C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_star_ends_device")
+        return ends[:count], int(clipped.value)
+
+    def search_regex_star_begins(self, text, expr_or_regex, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex_star_begins): ascending starts, uint64.  With ``capacity`` given and too small,
+        raises BmxError(ERR_CAPACITY); without it the list is always complete."""
+        re_ = _regex(expr_or_regex, flags, star=True)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_star_begins(self._h, tptr, n, C.byref(re_), C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_star_begins")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_regex_star_begins_spans(self, text, expr_or_regex, flags: int = 0, longest: bool = False,
+                                       window: int = 4096) -> Tuple[np.ndarray, np.ndarray, int]:
+        """Host buffers (bmx_search_regex_star_begins_spans): (starts uint64, ends uint64, clipped), starts ascending and
+        each once; each end that of the shortest match of at most ``window`` bytes from its start, with ``longest`` of the
+        longest such, UINT64_MAX where there is none; ``clipped`` as in regex_star_ends_device."""
+        re_ = _regex(expr_or_regex, flags, star=True)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            total, clipped = C.c_uint64(0), C.c_uint64(0)
+            rc = self._L.bmx_search_regex_star_begins_spans(self._h, tptr, n, C.byref(re_), int(window),
+                                                            REGEX_LONGEST if longest else 0, C.c_void_p(starts.ctypes.data),
+                                                            C.c_void_p(ends.ctypes.data), cap, C.byref(total), C.byref(clipped))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_star_begins_spans")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy(), int(clipped.value)
+
+    def last_regex_star_begins_ms(self) -> float:
+        return float(self._L.bmx_last_regex_star_begins_ms(self._h))
+
     # -- match spans of the approximate search: (start, end, distance) -------------------
     def approx_spans_device(self, d_text, pattern_or_classes, k: int, ends, dist=None, *, best: bool = False, flags: int = 0,
                             n: Optional[int] = None, base_offset: int = 0, stream=None):
@@ -2011,30 +2121,44 @@ class Context:
         self._chk(call(out, out.numel()), "bmx_extract_device")
         return out[: int(total.value)], off
 
-    def _posix_spans_device(self, d_text, expr, rows, flags):
+    def _posix_spans_device(self, d_text, expr, rows, flags, kind="regex", window=None):
         """(starts, ends, row ids or None) of the longest match from every start at which one begins, starts ascending: the
-        begins search, with ``rows`` the last byte of each start's row as its limit, and the ends pass with ``longest``."""
+        begins search, with ``rows`` the last byte of each start's row as its limit, and the ends pass with ``longest``.
+        kind "regex_star": the entries that take a cycle, the ends within ``window`` bytes (by _match_spans_device's rule:
+        the longest row, else 4,096, at most MAX_REGEX_STAR_WINDOW); an entry the window cut short is a ValueError."""
         import torch
 
-        re_ = _regex(expr, flags)
-        starts, total = self.search_regex_begins_device(d_text, re_)
+        star = kind == "regex_star"
+        re_ = _regex(expr, flags, star=star)
+        begins = self.search_regex_star_begins_device if star else self.search_regex_begins_device
+        starts, total = begins(d_text, re_)
         if total > starts.numel():
-            starts, _ = self.search_regex_begins_device(d_text, re_, out=torch.empty(total, dtype=torch.int64, device=d_text.device))
+            starts, _ = begins(d_text, re_, out=torch.empty(total, dtype=torch.int64, device=d_text.device))
+
+        def longest_ends(limit):
+            if not star:
+                return self.regex_ends_device(d_text, re_, starts, longest=True, limit=limit)
+            w = window if window is not None else min(MAX_REGEX_STAR_WINDOW, max(rows.longest, 1) if rows is not None else 4096)
+            ends, clipped = self.regex_star_ends_device(d_text, re_, starts, window=w, longest=True, limit=limit)
+            if clipped > 0:
+                raise ValueError(f"posix: {clipped} match(es) may be longer than the window of {w} bytes; pass a larger window")
+            return ends
+
         if rows is None:
-            return starts, self.regex_ends_device(d_text, re_, starts, longest=True), None
+            return starts, longest_ends(None), None
         if starts.numel() == 0:
             return starts, starts.clone(), None
         row = rows.of(starts=starts, length=1)
         inside = row >= 0
         limit = torch.where(inside, rows.offsets.to(torch.int64)[row.clamp(min=0) + 1] - 1, starts)
-        ends = self.regex_ends_device(d_text, re_, starts, longest=True, limit=limit)
+        ends = longest_ends(limit)
         ends = torch.where(inside, ends, torch.full_like(ends, -1))  # a start in no row has no match in a row
         return starts, ends, rows.of(starts=starts, ends=ends)
 
     def _selected_spans_device(self, d_text, expr, kind, rows, merge, longest, flags, k, window, posix=False):
         if posix:
             _posix_args(kind, merge, longest)
-            starts, ends, ids = self._posix_spans_device(d_text, expr, rows, flags)
+            starts, ends, ids = self._posix_spans_device(d_text, expr, rows, flags, kind, window)
             return self.select_spans_device(starts, ends, 0, rows=ids)
         longest = merge if longest is None else longest
         starts, ends, length = self._match_spans_device(d_text, expr, kind, flags, k, window, longest, rows)
@@ -2047,9 +2171,11 @@ class Context:
         (re.sub, sed s/x/y/g): the search of ``kind`` (as grep_device), its starts post-pass, select_spans_device and
         replace_device.  ``merge``: whole regions of overlapping matches are replaced (``[0-9]+`` then replaces the maximal
         digit runs); ``longest`` (default: ``merge``) asks the starts pass for the smallest start of every end.  ``rows``: a
-        Rows; a match that runs across a row boundary is then left alone.  ``posix`` (kind "regex" only, neither ``merge``
-        nor an explicit ``longest``: ValueError): the leftmost-longest matches, what grep -o, sed and awk take -- the begins
-        search, the longest end of every start (with ``rows``: inside the start's row) and the same selection."""
+        Rows; a match that runs across a row boundary is then left alone.  ``posix`` (kind "regex" or "regex_star" only,
+        neither ``merge`` nor an explicit ``longest``: ValueError): the leftmost-longest matches, what grep -o, sed and awk
+        take -- the begins search, the longest end of every start (with ``rows``: inside the start's row) and the same
+        selection.  For "regex_star" the ends are looked for within ``window`` bytes (default: the longest row, else 4,096);
+        a match that may be longer than that raises ValueError, it is never returned shorter."""
         s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window, posix)
         return self.replace_device(d_text, s, e, repl)
 
@@ -2623,6 +2749,16 @@ def search_regex(text, expr, flags: int = 0, spans: bool = False, longest: bool 
     (starts, ends), each start the largest one for its end (the shortest match) or with ``longest`` the smallest."""
     ctx = default_context()
     return ctx.search_regex_spans(text, expr, flags, longest) if spans else ctx.search_regex(text, expr, flags)
+
+
+def search_regex_star_begins(text, expr, flags: int = 0, spans: bool = False, longest: bool = False, window: int = 4096):
+    """(text, regular expression with * + {a,}) -> ascending starts of every match, each once
+    (bmx_search_regex_star_begins); with ``spans`` (starts, ends, clipped), each end the smallest one within ``window`` bytes
+    of its start, or with ``longest`` the largest."""
+    ctx = default_context()
+    if spans:
+        return ctx.search_regex_star_begins_spans(text, expr, flags, longest, window)
+    return ctx.search_regex_star_begins(text, expr, flags)
 
 
 def search_regex_begins(text, expr, flags: int = 0, spans: bool = False, longest: bool = False):
