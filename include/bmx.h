@@ -634,7 +634,8 @@ int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_r
  * lead > n, n too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer
  * than its bound (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly
  * ordered.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream.
- * Out of scope: unbounded repetition (* + {a,}), anchors, back-references, capture groups, more than 64 positions. */
+ * Out of scope: unbounded repetition (* + {a,}; bmx_search_regex_star_device below), back-references, capture groups, more
+ * than 64 positions.  Anchors and word boundaries: bmx_compile_regex_anchored and bmx_search_regex_anchored_device below. */
 int bmx_search_regex_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                             const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
 /* Host buffers in, host buffers out (upload, bmx_search_regex_device with lead = 0, download). */
@@ -1382,6 +1383,85 @@ int bmx_regex_star_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uin
 int bmx_search_regex_star_begins_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
                                        uint32_t window, uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity,
                                        uint64_t *n_matches, uint64_t *n_clipped /* NULL: not wanted */);
+
+/* ---- anchored regular-expression search: ^ $ \b \B \< \>, whole word, whole line ------------- */
+
+/* ^ERROR, timeout$, \bcat\b, grep -w, grep -x for the STAR-FREE expressions (csrc/bmx_regex_anchored_kernel.h, DESIGN.md
+ * s32).  A caller cannot build these from the entries above: the searches report an end once while several starts share
+ * it, so a filter over the finished list by "the byte before the start" has no start to look at, and the starts pass
+ * keeps one start per end.  The condition sits in the automaton's step instead.
+ *
+ * The model is plain data beside an unchanged bmx_regex: a class of admissible bytes BEFORE the match for every position
+ * of `first`, a class of admissible bytes AFTER it for every position of `last` (encoded as for bmx_search_classes).
+ * text[s..j] is an ANCHORED match iff it is a match by bmx_regex's definition along a path i_0 .. i_{L-1} and prev(s) is in
+ * before[i_0] and next(j) is in after[i_{L-1}], where prev(s) = text[s - 1], or the call's `left` byte when s == 0, and
+ * next(j) = text[j + 1], or the call's `right` byte when j == n - 1.  left and right are byte values 0..255: a caller with
+ * the whole text passes 0x0A for both (outside the text counts as a line break), a shard passes the real neighbour; no
+ * entry reads a byte outside the view for them.  A full class is "no condition", an empty one is legal ("no match begins /
+ * ends at this position"), so every struct goes with a valid bmx_regex.  The gate applies where a path enters through
+ * `first` or leaves through `last`, not where the same position is reached through follow[]: ^a?b and ^a|b$ come out right.
+ * With every class full each entry below returns exactly the list of its unanchored counterpart. */
+typedef struct bmx_regex_anchors {
+    uint8_t before[BMX_MAX_REGEX_POSITIONS * BMX_CLASS_BYTES]; /* read for positions in `first` only */
+    uint8_t after [BMX_MAX_REGEX_POSITIONS * BMX_CLASS_BYTES]; /* read for positions in `last` only  */
+} bmx_regex_anchors;
+#define BMX_REGEX_WORD 4u /* grep -w: no word byte before the match and none after it */
+#define BMX_REGEX_LINE 8u /* grep -x: a line break before the match and one after it   */
+/* bmx_compile_regex's grammar (star-free) plus the zero-width atoms ^ $ \b \B \< \> outside sets; \^ and \$ are literals.
+ * With W = [A-Za-z0-9_] they mean what Python's re means on bytes with re.MULTILINE:
+ *   ^  the previous byte is \n            $  the next byte is \n
+ *   \b exactly one of the previous and the next byte is in W      \B both or neither
+ *   \< the previous byte is not in W, the next is                 \> the previous byte is in W, the next is not
+ * BMX_REGEX_WORD intersects ~W into every `before` of `first` and every `after` of `last`, BMX_REGEX_LINE does the same with
+ * {\n}; BMX_CLASS_ICASE and BMX_CLASS_IUPAC as in bmx_compile_regex.
+ * Several conditions at one boundary intersect, several ways into one first position unite.  A condition that depends on
+ * the match's own edge byte (\b in front of [a-z.]) splits that position into copies by the kind of byte (line break,
+ * word byte, other), each with its own `before` or `after` class and the same follow sets, numbered upward.  An assertion
+ * between two consumed positions is decided from their two classes: the edge stays if it holds for every byte pair and
+ * goes if it holds for none.  The result is exact or the call fails; it never approximates.
+ * BMX_ERR_ARG with a text in bmx_last_error and *re, *an untouched: every error of bmx_compile_regex; a quantifier on an
+ * assertion (^*, \b?, ${2}); an expression that matches the empty string once assertions are ignored (^, ^$, \b); an
+ * assertion between two positions that their classes do not decide ([a-z.]\b[a-z.]); more than 64 positions after
+ * splitting; an expression left with no possible match (a\bb).
+ * For an expression without assertions and without the two flags *re equals bmx_compile_regex's output byte for byte and
+ * every class of *an is full.  Pure host code, no GPU. */
+int bmx_compile_regex_anchored(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *re, bmx_regex_anchors *an);
+/* Every END of an anchored match in [lead, n): semantics, capacity rule, argument errors before any HIP call (left or right
+ * above 255 among them), stream rule and wait bound as bmx_search_regex_device.  The shard contract is unchanged: a view
+ * begins max_len - 1 bytes before the first owned end, left and right are the bytes next to the VIEW, and the shards'
+ * lists concatenate to the whole text's list.  One small copy (the two gate tables) and one kernel launch on `stream`. */
+int bmx_search_regex_anchored_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                     const bmx_regex *re, const bmx_regex_anchors *an, uint32_t left, uint32_t right,
+                                     uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Device time (ms) of the last bmx_search_regex_anchored_device on ctx; < 0 if none. */
+float bmx_last_regex_anchored_ms(bmx_ctx *ctx);
+/* The START of an anchored match for every end of a list: bmx_regex_starts_device with the two conditions (the largest
+ * start by default, the smallest with BMX_REGEX_LONGEST).  Errors, status word, bytes read and stream rule as there. */
+int bmx_regex_anchored_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                     const bmx_regex_anchors *an, uint32_t left, uint32_t right, const uint64_t *d_ends,
+                                     uint64_t count, uint32_t flags, uint64_t *d_starts, void *stream);
+/* Every START of an anchored match in [0, n - tail), ascending: bmx_search_regex_begins_device with the two conditions. */
+int bmx_search_regex_anchored_begins_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t tail, uint64_t base_offset,
+                                            const bmx_regex *re, const bmx_regex_anchors *an, uint32_t left, uint32_t right,
+                                            uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches, void *stream);
+float bmx_last_regex_anchored_begins_ms(bmx_ctx *ctx);
+/* The END of an anchored match for every start of a list: bmx_regex_ends_device with the two conditions.  d_limit bounds
+ * the bytes a match may USE; the byte after a match that ends on its limit is still the text's. */
+int bmx_regex_anchored_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                   const bmx_regex_anchors *an, uint32_t left, uint32_t right, const uint64_t *d_starts,
+                                   uint64_t count, const uint64_t *d_limit /* NULL: the view's last byte */, uint32_t flags,
+                                   uint64_t *d_ends, void *stream);
+/* Host buffers in, host buffers out, with left = right = 0x0A; otherwise as their unanchored counterparts.  ctx may be NULL. */
+int bmx_search_regex_anchored(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                              const bmx_regex_anchors *an, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+int bmx_search_regex_anchored_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                    const bmx_regex_anchors *an, uint32_t flags, uint64_t *starts, uint64_t *ends,
+                                    uint64_t capacity, uint64_t *n_matches);
+int bmx_search_regex_anchored_begins(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                     const bmx_regex_anchors *an, uint64_t *starts, uint64_t capacity, uint64_t *n_matches);
+int bmx_search_regex_anchored_begins_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                                           const bmx_regex_anchors *an, uint32_t flags, uint64_t *starts, uint64_t *ends,
+                                           uint64_t capacity, uint64_t *n_matches);
 
 #ifdef __cplusplus
 }

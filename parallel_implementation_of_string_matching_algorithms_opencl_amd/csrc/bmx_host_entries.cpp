@@ -775,6 +775,74 @@ int bmx_search_regex_begins_spans(bmx_ctx *ctx_in, const char *text, uint64_t n,
     return c.rc;
 }
 
+// The anchored forms: the whole text is there, so outside it counts as a line break on both sides.
+namespace {
+constexpr uint32_t OUTSIDE = 0x0A;
+
+// ends (begins == false) or starts of the anchored matches, and where `other` is wanted the other side of each
+int regex_anchored_host(const char *where, bool begins, bool spans, bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re,
+                        const bmx_regex_anchors *an, uint32_t flags, uint64_t *list, uint64_t *other, uint64_t capacity,
+                        uint64_t *n_matches)
+{
+    if (!bmx_regex_args_ok(n, 0, re, list, capacity) || !an || (spans && capacity > 0 && !other) || (n > 0 && !text) ||
+        (flags & ~BMX_REGEX_LONGEST))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c(where, ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_list = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_other = dev_cap && spans ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = begins ? bmx_search_regex_anchored_begins_device(c.ctx(), d_text, n, 0, 0, re, an, OUTSIDE, OUTSIDE, d_list, dev_cap, &total, nullptr)
+                  : bmx_search_regex_anchored_device(c.ctx(), d_text, n, 0, 0, re, an, OUTSIDE, OUTSIDE, d_list, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    if (spans) {
+        const int prc = begins ? bmx_regex_anchored_ends_device(c.ctx(), d_text, n, 0, re, an, OUTSIDE, OUTSIDE, d_list, stored, nullptr,
+                                                                flags, d_other, nullptr)
+                               : bmx_regex_anchored_starts_device(c.ctx(), d_text, n, 0, re, an, OUTSIDE, OUTSIDE, d_list, stored, flags,
+                                                                  d_other, nullptr);
+        if (prc != BMX_OK) return prc;
+    }
+    c.download(list, d_list, stored * sizeof(uint64_t), "anchored regex matches");
+    if (spans) c.download(other, d_other, stored * sizeof(uint64_t), "anchored regex matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+} // namespace
+
+int bmx_search_regex_anchored(bmx_ctx *ctx, const char *text, uint64_t n, const bmx_regex *re, const bmx_regex_anchors *an,
+                              uint64_t *ends, uint64_t capacity, uint64_t *n_matches)
+{
+    return regex_anchored_host("bmx_search_regex_anchored", false, false, ctx, text, n, re, an, 0, ends, nullptr, capacity, n_matches);
+}
+
+int bmx_search_regex_anchored_spans(bmx_ctx *ctx, const char *text, uint64_t n, const bmx_regex *re, const bmx_regex_anchors *an,
+                                    uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches)
+{
+    return regex_anchored_host("bmx_search_regex_anchored_spans", false, true, ctx, text, n, re, an, flags, ends, starts, capacity,
+                               n_matches);
+}
+
+int bmx_search_regex_anchored_begins(bmx_ctx *ctx, const char *text, uint64_t n, const bmx_regex *re, const bmx_regex_anchors *an,
+                                     uint64_t *starts, uint64_t capacity, uint64_t *n_matches)
+{
+    return regex_anchored_host("bmx_search_regex_anchored_begins", true, false, ctx, text, n, re, an, 0, starts, nullptr, capacity,
+                               n_matches);
+}
+
+int bmx_search_regex_anchored_begins_spans(bmx_ctx *ctx, const char *text, uint64_t n, const bmx_regex *re,
+                                           const bmx_regex_anchors *an, uint32_t flags, uint64_t *starts, uint64_t *ends,
+                                           uint64_t capacity, uint64_t *n_matches)
+{
+    return regex_anchored_host("bmx_search_regex_anchored_begins_spans", true, true, ctx, text, n, re, an, flags, starts, ends, capacity,
+                               n_matches);
+}
+
 int bmx_search_regex_star(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, uint64_t *ends, uint64_t capacity,
                           uint64_t *n_matches)
 {

@@ -125,6 +125,26 @@ int bmx_internal_regex_ends(void **state, const void *d_text, uint64_t n, uint64
                             hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_regex_begins_free(void *state);
 float bmx_internal_regex_begins_ms(const void *state);
+// bmx_regex_anchored.hip: the four of them with a condition on the byte before and after a match (left, right: the bytes
+// next to the view); a state for the forward pair and one for the begins pair
+int bmx_internal_regex_anchored(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                const bmx_regex *re, const bmx_regex_anchors *an, uint32_t left, uint32_t right, uint64_t *d_ends,
+                                uint64_t capacity, uint64_t *n_matches, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_regex_anchored_starts(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                       const bmx_regex_anchors *an, uint32_t left, uint32_t right, const uint64_t *d_ends,
+                                       uint64_t count, uint32_t flags, uint64_t *d_starts, hipStream_t stream, char *err, size_t errlen);
+int bmx_internal_regex_anchored_begins(void **state, int num_cu, int piece_shift, const void *d_text, uint64_t n, uint64_t tail,
+                                       uint64_t base_offset, const bmx_regex *re, const bmx_regex_anchors *an, uint32_t left,
+                                       uint32_t right, uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches, hipStream_t stream,
+                                       char *err, size_t errlen);
+int bmx_internal_regex_anchored_ends(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                     const bmx_regex_anchors *an, uint32_t left, uint32_t right, const uint64_t *d_starts,
+                                     uint64_t count, const uint64_t *d_limit, uint32_t flags, uint64_t *d_ends, hipStream_t stream,
+                                     char *err, size_t errlen);
+void bmx_internal_regex_anchored_free(void *state);
+void bmx_internal_regex_anchored_begins_free(void *state);
+float bmx_internal_regex_anchored_ms(const void *state);
+float bmx_internal_regex_anchored_begins_ms(const void *state);
 // bmx_regex_star.hip.  What (libbmx_exp.so) bmx_exp_set_knob sets:
 struct bmx_regex_star_knobs {
     int piece_shift = 0;     // 0, or log2 of the ends per lane (4..12; the shared "tile_piece_shift" begins at 6)
@@ -276,6 +296,8 @@ struct bmx_ctx {
     void *regex = nullptr; // regular-expression search: the same as the gapped search's, its own (bmx_regex.hip)
     void *regex_begins = nullptr; // ... its begins search and ends pass: the same again, their own (bmx_regex.hip)
     int regex_begins_piece_shift = 0; // libbmx_exp.so: 0, or log2 of the starts per lane of the begins search (4..12)
+    void *regex_anchored = nullptr; // ... anchored: the same and the gate tables (bmx_regex_anchored.hip)
+    void *regex_anchored_begins = nullptr; // ... and its begins search and ends pass (regex_begins_piece_shift applies)
     void *regex_star = nullptr; // ... with unbounded repetition: the same, the taint words and the slow path's workspace (bmx_regex_star.hip)
     bmx_regex_star_knobs regex_star_knobs;
     void *regex_star_begins = nullptr; // ... and its begins search and ends pass: the same again, their own (bmx_regex_star_begins.hip)
@@ -387,6 +409,9 @@ inline bool bmx_regex_ends_args_ok(uint64_t n, const bmx_regex *re, const uint64
     if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
     return count == 0 || (starts && ends);
 }
+
+// ... anchored: every struct of classes goes with a valid automaton; the two neighbour bytes are byte values
+inline bool bmx_regex_anchors_ok(const bmx_regex_anchors *an, uint32_t left, uint32_t right) { return an && left <= 255 && right <= 255; }
 
 // ... with unbounded repetition: follow[] may hold any bit below m
 inline bool bmx_regex_star_ok(const bmx_regex *re) { return re && bmx_regex_star_sets_ok(re->m, re->first, re->last, re->follow); }

@@ -57,6 +57,11 @@
 //                             `regex match starts: N`, and with --positions one `Start at : P` line per start.  With
 //                             --spans the end of every start as well (bmx_search_regex_begins_spans: the smallest one,
 //                             with --longest the largest) and `Match at : S E` lines
+//   bmx_cli --regex-anchored EXPR [--word] [--line] ...
+//                             --regex with the zero-width atoms ^ $ \b \B \< \> in EXPR (bmx_compile_regex_anchored,
+//                             bmx_search_regex_anchored*; outside the text counts as a line break); --word is grep -w, --line
+//                             is grep -x.  It takes every companion of --regex: --starts, --longest, --begins, --spans,
+//                             --lines, --invert, --posix, --replace, --only-matching
 //   bmx_cli --regex-star EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K]
 //           [--starts --window N [--longest]]
 //                             the same with unbounded repetition: EXPR may use * + {a,} (bmx_compile_regex_star,
@@ -216,6 +221,8 @@ int main(int argc, char **argv)
     bool have_classes = false, have_gaps = false, gaps_starts = false, gaps_longest = false;
     std::string gaps_expr, regex_expr;
     bool have_regex = false, regex_star = false, regex_both = false;
+    bool regex_anchored = false; // --regex-anchored EXPR [--word] [--line]
+    uint32_t anchor_flags = 0;
     uint32_t star_window = 0;
     bool regex_begins = false, begins_spans = false, begins_longest = false, posix = false; // --begins [--spans [--longest]], --posix
     int iters = 10, device = 0, ranges = 0, gpus = 0, approx_k = -1, hamming_k = -1;
@@ -265,6 +272,9 @@ int main(int argc, char **argv)
         else if (a == "--gaps") gaps_expr = need("--gaps"), have_gaps = true;
         else if (a == "--regex") regex_both = have_regex, regex_expr = need("--regex"), have_regex = true;
         else if (a == "--regex-star") regex_both = have_regex, regex_expr = need("--regex-star"), have_regex = regex_star = true;
+        else if (a == "--regex-anchored") regex_both = have_regex, regex_expr = need("--regex-anchored"), have_regex = regex_anchored = true;
+        else if (a == "--word") anchor_flags |= BMX_REGEX_WORD;
+        else if (a == "--line") anchor_flags |= BMX_REGEX_LINE;
         else if (a == "--begins") regex_begins = true;
         else if (a == "--posix") posix = true;
         else if (a == "--window") star_window = (uint32_t)strtoul(need("--window"), nullptr, 10);
@@ -336,6 +346,10 @@ int main(int argc, char **argv)
         p = *end ? end + 1 : end;
     }
 
+    if (anchor_flags != 0 && !regex_anchored) {
+        fprintf(stderr, "--word and --line go with --regex-anchored EXPR\n");
+        return 2;
+    }
     if (have_regex && (have_gaps || have_classes || approx_k >= 0 || hamming_k >= 0 || (class_flags & BMX_GAPS_PROSITE))) {
         fprintf(stderr, "--regex goes with none of --gaps, --prosite, --classes, --approx, --hamming\n");
         return 2;
@@ -694,8 +708,10 @@ int main(int argc, char **argv)
         const char *what = "bmx_search";
         if (have_regex) {
             bmx_regex re;
-            if ((regex_star ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
-                            : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
+            bmx_regex_anchors an; // (full where the expression has no assertions: read by the anchored entries only)
+            if ((regex_anchored ? bmx_compile_regex_anchored(regex_expr.data(), regex_expr.size(), class_flags | anchor_flags, &re, &an)
+                 : regex_star   ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
+                                : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
                 fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
                 return 1;
             }
@@ -709,7 +725,9 @@ int main(int argc, char **argv)
                                                         &hits, &clipped);
             } else if (posix && !lines_mode) { // every start with its longest end: the selection below gives leftmost-longest
                 what = "bmx_search_regex_begins_spans";
-                rc = bmx_search_regex_begins_spans(ctx, text.data(), n, &re, BMX_REGEX_LONGEST, starts.data(), ends.data(), room, &hits);
+                rc = regex_anchored ? bmx_search_regex_anchored_begins_spans(ctx, text.data(), n, &re, &an, BMX_REGEX_LONGEST, starts.data(),
+                                                                             ends.data(), room, &hits)
+                                    : bmx_search_regex_begins_spans(ctx, text.data(), n, &re, BMX_REGEX_LONGEST, starts.data(), ends.data(), room, &hits);
             } else if (posix) { // ... its longest end inside its line: the ends pass with the line's last byte as the limit
                 what = "bmx_search_regex_begins_device / bmx_regex_ends_device";
                 void *d_text = nullptr, *d_limit = nullptr;
@@ -718,15 +736,18 @@ int main(int argc, char **argv)
                 if (rc == BMX_OK) rc = bmx_device_alloc(ctx, room * sizeof(uint64_t), (void **)&d_starts);
                 if (rc == BMX_OK) rc = bmx_device_alloc(ctx, room * sizeof(uint64_t), (void **)&d_ends);
                 if (rc == BMX_OK)
-                    rc = regex_star ? bmx_search_regex_star_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr)
-                                    : bmx_search_regex_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr);
+                    rc = regex_anchored ? bmx_search_regex_anchored_begins_device(ctx, d_text, n, 0, 0, &re, &an, '\n', '\n', d_starts, room, &hits, nullptr)
+                         : regex_star   ? bmx_search_regex_star_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr)
+                                        : bmx_search_regex_begins_device(ctx, d_text, n, 0, 0, &re, d_starts, room, &hits, nullptr);
                 if (rc == BMX_OK) rc = bmx_device_download(ctx, starts.data(), d_starts, hits * sizeof(uint64_t));
                 std::vector<uint64_t> limit(hits ? hits : 1);
                 for (uint64_t i = 0; i < hits && rc == BMX_OK; ++i) // off[0] = 0 and off[rows] = n: every start lies in a row
                     limit[i] = *std::upper_bound(off.begin(), off.begin() + rows + 1, starts[i]) - 1;
                 if (rc == BMX_OK) rc = bmx_text_upload(ctx, reinterpret_cast<const char *>(limit.data()), hits * sizeof(uint64_t), &d_limit);
                 if (rc == BMX_OK)
-                    rc = regex_star ? bmx_regex_star_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit),
+                    rc = regex_anchored ? bmx_regex_anchored_ends_device(ctx, d_text, n, 0, &re, &an, '\n', '\n', d_starts, hits,
+                                                                         static_cast<const uint64_t *>(d_limit), BMX_REGEX_LONGEST, d_ends, nullptr)
+                         : regex_star ? bmx_regex_star_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit),
                                                                  star_window, BMX_REGEX_LONGEST, d_ends, &clipped, nullptr)
                                     : bmx_regex_ends_device(ctx, d_text, n, 0, &re, d_starts, hits, static_cast<const uint64_t *>(d_limit),
                                                             BMX_REGEX_LONGEST, d_ends, nullptr);
@@ -736,7 +757,8 @@ int main(int argc, char **argv)
                 bmx_device_free(ctx, d_starts);
                 bmx_device_free(ctx, d_text);
             } else
-            rc = regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, longest_flag, starts.data(), ends.data(), room, &hits)
+            rc = regex_anchored ? bmx_search_regex_anchored_spans(ctx, text.data(), n, &re, &an, longest_flag, starts.data(), ends.data(), room, &hits)
+                 : regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, longest_flag, starts.data(), ends.data(), room, &hits)
                             : bmx_search_regex_spans(ctx, text.data(), n, &re, longest_flag, starts.data(), ends.data(), room, &hits);
             if (rc == BMX_OK && clipped != 0) { // never a shorter match than POSIX's
                 fprintf(stderr, "--posix: %llu match(es) may be longer than the window of %u bytes; pass a larger --window\n",
@@ -833,8 +855,10 @@ int main(int argc, char **argv)
     }
     if (have_regex) {
         bmx_regex re;
-        if ((regex_star ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
-                        : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
+        bmx_regex_anchors an; // (read by the anchored entries only)
+        if ((regex_anchored ? bmx_compile_regex_anchored(regex_expr.data(), regex_expr.size(), class_flags | anchor_flags, &re, &an)
+             : regex_star   ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
+                            : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
             fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
             return 1;
         }
@@ -855,7 +879,10 @@ int main(int argc, char **argv)
             std::vector<uint64_t> starts(room), ends(begins_spans ? room : 1);
             uint64_t got = 0, clipped = 0;
             const uint32_t span_flags = begins_longest ? BMX_REGEX_LONGEST : 0u;
-            if (regex_star)
+            if (regex_anchored)
+                rc = begins_spans ? bmx_search_regex_anchored_begins_spans(ctx, text.data(), n, &re, &an, span_flags, starts.data(), ends.data(), room, &got)
+                                  : bmx_search_regex_anchored_begins(ctx, text.data(), n, &re, &an, starts.data(), room, &got);
+            else if (regex_star)
                 rc = begins_spans ? bmx_search_regex_star_begins_spans(ctx, text.data(), n, &re, star_window, span_flags, starts.data(), ends.data(),
                                                                        room, &got, &clipped)
                                   : bmx_search_regex_star_begins(ctx, text.data(), n, &re, starts.data(), room, &got);
@@ -898,7 +925,8 @@ int main(int argc, char **argv)
         uint64_t hits = 0;
         for (int it = 0; it < iters; ++it) {
             auto t0 = std::chrono::steady_clock::now();
-            rc = regex_star ? bmx_search_regex_star_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr)
+            rc = regex_anchored ? bmx_search_regex_anchored_device(ctx, d_text, n, 0, 0, &re, &an, '\n', '\n', d_ends, cap, &hits, nullptr)
+                 : regex_star ? bmx_search_regex_star_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr)
                             : bmx_search_regex_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr);
             auto t1 = std::chrono::steady_clock::now();
             if (rc != BMX_OK) {
@@ -906,10 +934,11 @@ int main(int argc, char **argv)
                 return 1;
             }
             total += std::chrono::duration<double>(t1 - t0).count();
-            kernel_ms += regex_star ? bmx_last_regex_star_ms(ctx) : bmx_last_regex_ms(ctx);
+            kernel_ms += regex_anchored ? bmx_last_regex_anchored_ms(ctx) : regex_star ? bmx_last_regex_star_ms(ctx) : bmx_last_regex_ms(ctx);
         }
         if (iters <= 0) { // no timed call has counted: a counting call
-            rc = regex_star ? bmx_search_regex_star(ctx, text.data(), n, &re, nullptr, 0, &hits)
+            rc = regex_anchored ? bmx_search_regex_anchored(ctx, text.data(), n, &re, &an, nullptr, 0, &hits)
+                 : regex_star ? bmx_search_regex_star(ctx, text.data(), n, &re, nullptr, 0, &hits)
                             : bmx_search_regex(ctx, text.data(), n, &re, nullptr, 0, &hits);
             if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) hits = 0;
         }
@@ -917,7 +946,10 @@ int main(int argc, char **argv)
         std::vector<uint64_t> ends(hits ? hits : 1), starts(gaps_starts && hits ? hits : 1);
         uint64_t got = 0;
         const uint32_t span_flags = gaps_longest ? BMX_REGEX_LONGEST : 0u;
-        if (regex_star)
+        if (regex_anchored)
+            rc = gaps_starts ? bmx_search_regex_anchored_spans(ctx, text.data(), n, &re, &an, span_flags, starts.data(), ends.data(), hits, &got)
+                             : bmx_search_regex_anchored(ctx, text.data(), n, &re, &an, ends.data(), hits, &got);
+        else if (regex_star)
             rc = gaps_starts ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, star_window, span_flags, starts.data(), ends.data(),
                                                            hits, &got)
                              : bmx_search_regex_star(ctx, text.data(), n, &re, ends.data(), hits, &got);

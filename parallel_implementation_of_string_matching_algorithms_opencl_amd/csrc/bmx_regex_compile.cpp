@@ -17,6 +17,11 @@
 // every other expansion step makes a position: the work is bounded by the 64 positions, not by the counts.
 // With the switch: X+ links every last position of X to the first positions of X (the one rule that makes follow[] point
 // downward or at itself), X* is (X+)? and X{a,} is a - 1 copies of X followed by X+ (a == 0: X*).
+// bmx_compile_regex_anchored is the star-free grammar behind a second switch (Compiler::anchored): ^ $ \b \B \< \> parse
+// as zero-width atoms, the expansion carries a relation between the byte before and the byte after a boundary where the
+// plain one carries a bit (aexpand), and resolve() turns the relations into struct bmx_regex_anchors, splitting a position
+// whose condition depends on its own byte and deciding every assertion between two positions from their classes
+// (DESIGN.md s32).  The two plain entries never see an assertion: without the switch ^ and $ are literals.
 #include "bmx.h"
 
 #include <cstdio>
@@ -73,10 +78,55 @@ bool number(const uint8_t *e, uint64_t len, uint64_t &at, int &value)
     return true;
 }
 
-enum Kind { ELEM, CAT, ALT, REP };
+// ---- assertions (bmx_compile_regex_anchored) ----
+// Every assertion is a relation between the byte before and the byte after a boundary, and every one of them sees a byte
+// only as one of three categories: the line break, a word byte (W = [A-Za-z0-9_]), any other.  A relation is therefore a set
+// of (category before, category after) pairs: bit 3 * before + after of nine.  Relations at one boundary intersect,
+// alternatives unite, and whether a relation holds between two classes is a question about the categories they touch.
+enum Cat { CAT_NL = 0, CAT_WORD = 1, CAT_OTHER = 2 };
+constexpr int REL_FULL = 0x1FF;
+constexpr int REL_BOL = 0x007;      // before is the line break
+constexpr int REL_EOL = 0x049;      // after is the line break
+constexpr int REL_WB = 0x0AA;       // exactly one side is a word byte
+constexpr int REL_NWB = REL_FULL & ~REL_WB;
+constexpr int REL_WSTART = 0x082;   // before is no word byte, after is one
+constexpr int REL_WEND = 0x028;     // before is a word byte, after is none
+constexpr int REL_BEFORE_NOT_WORD = 0x1C7, REL_AFTER_NOT_WORD = 0x16D;
+
+int cat_of(unsigned c)
+{
+    if (c == '\n') return CAT_NL;
+    return (c >= '0' && c <= '9') || (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || c == '_' ? CAT_WORD : CAT_OTHER;
+}
+
+// The relation of the assertion at e[at], 0 where none stands there.  ^ and $ take one byte, the others two.
+int assertion_at(const uint8_t *e, uint64_t len, uint64_t at)
+{
+    if (e[at] == '^') return REL_BOL;
+    if (e[at] == '$') return REL_EOL;
+    if (e[at] != '\\' || at + 1 >= len) return 0;
+    switch (e[at + 1]) {
+    case 'b': return REL_WB;
+    case 'B': return REL_NWB;
+    case '<': return REL_WSTART;
+    case '>': return REL_WEND;
+    }
+    return 0;
+}
+
+// What an expression with assertions expands to: as Frag, with a relation where Frag has a bit.  eps: the relation under
+// which it matches the empty string (0 where it cannot); nullable: whether it does once assertions are ignored.
+// first[p] relates the byte before the match to position p's byte, last[p] position p's byte to the byte after.
+struct AFrag {
+    bool nullable;
+    uint16_t eps;
+    uint16_t first[BMX_MAX_REGEX_POSITIONS], last[BMX_MAX_REGEX_POSITIONS];
+};
+
+enum Kind { ELEM, CAT, ALT, REP, ASSERT };
 struct Node {
     Kind kind;
-    int a = 1, b = 1;          // REP (b == UNBOUNDED: no upper count)
+    int a = 1, b = 1;          // REP (b == UNBOUNDED: no upper count); ASSERT: a is its relation (below)
     bool has_element = false;  // some element stands below it
     std::vector<int> kids;     // CAT, ALT: any number; REP: one
     uint8_t cls[BMX_CLASS_BYTES]; // ELEM
@@ -92,8 +142,10 @@ struct Compiler {
     uint64_t len;
     uint32_t flags;
     bool star = false; // the grammar of bmx_compile_regex_star
+    bool anchored = false; // the grammar of bmx_compile_regex_anchored: ^ $ \b \B \< \> are zero-width atoms
     uint64_t at = 0;
     const char *why = nullptr;
+    bool has_assertion = false;
     std::vector<Node> nodes;
     bmx_regex re;
 
@@ -135,6 +187,17 @@ struct Compiler {
         const unsigned c = e[at];
         if (!star && (c == '*' || c == '+')) return fail("* and +: unbounded repetition is out of scope");
         if (c == '?' || c == '{' || c == '*' || c == '+') return fail("a quantifier with nothing in front of it");
+        if (anchored) {
+            const int rel = assertion_at(e, len, at);
+            if (rel != 0) {
+                at += c == '\\' ? 2 : 1;
+                if (at < len && (e[at] == '?' || e[at] == '{' || e[at] == '*' || e[at] == '+')) return fail("a quantifier on an assertion");
+                out = make(ASSERT);
+                nodes[out].a = rel;
+                has_assertion = true;
+                return true;
+            }
+        }
         int atom;
         if (c == '(') {
             if (depth + 1 > MAX_DEPTH) return fail("groups nested deeper than 32");
@@ -216,6 +279,7 @@ struct Compiler {
         out = empty;
         if (!nodes[id].has_element) return true; // the empty string, whatever its counts
         switch (nodes[id].kind) {
+        case ASSERT: return true; // (has no element: not reached; the anchored grammar expands with aexpand)
         case ELEM: {
             if (re.m >= BMX_MAX_REGEX_POSITIONS) return fail("more than 64 positions after expansion");
             std::memcpy(re.classes + (size_t)re.m * BMX_CLASS_BYTES, nodes[id].cls, BMX_CLASS_BYTES);
@@ -265,7 +329,176 @@ struct Compiler {
         }
         return false;
     }
+
+    // ---- the same expansion with relations (anchored) ----
+    uint16_t edge[BMX_MAX_REGEX_POSITIONS][BMX_MAX_REGEX_POSITIONS]; // [l][r]: the relation under which r may follow l (0: never)
+
+    AFrag acat(const AFrag &f, const AFrag &g)
+    {
+        AFrag r;
+        for (int l = 0; l < re.m; ++l) {
+            if (!f.last[l]) continue;
+            for (int p = 0; p < re.m; ++p) edge[l][p] |= f.last[l] & g.first[p]; // both speak of the same boundary
+        }
+        for (int p = 0; p < BMX_MAX_REGEX_POSITIONS; ++p) {
+            r.first[p] = f.first[p] | (g.first[p] & f.eps);
+            r.last[p] = g.last[p] | (f.last[p] & g.eps);
+        }
+        r.eps = f.eps & g.eps;
+        r.nullable = f.nullable && g.nullable;
+        return r;
+    }
+
+    bool aexpand(int id, AFrag &out)
+    {
+        std::memset(&out, 0, sizeof out);
+        out.nullable = true, out.eps = REL_FULL;
+        switch (nodes[id].kind) {
+        case ASSERT:
+            out.eps = (uint16_t)nodes[id].a;
+            return true;
+        case ELEM:
+            if (re.m >= BMX_MAX_REGEX_POSITIONS) return fail("more than 64 positions after expansion");
+            std::memcpy(re.classes + (size_t)re.m * BMX_CLASS_BYTES, nodes[id].cls, BMX_CLASS_BYTES);
+            out.nullable = false, out.eps = 0;
+            out.first[re.m] = out.last[re.m] = REL_FULL;
+            ++re.m;
+            return true;
+        case CAT:
+            for (size_t i = 0; i < nodes[id].kids.size(); ++i) {
+                AFrag g;
+                if (!aexpand(nodes[id].kids[i], g)) return false;
+                out = acat(out, g);
+            }
+            return true;
+        case ALT: {
+            AFrag r;
+            std::memset(&r, 0, sizeof r);
+            for (size_t i = 0; i < nodes[id].kids.size(); ++i) {
+                AFrag g;
+                if (!aexpand(nodes[id].kids[i], g)) return false;
+                r.nullable |= g.nullable, r.eps |= g.eps;
+                for (int p = 0; p < BMX_MAX_REGEX_POSITIONS; ++p) r.first[p] |= g.first[p], r.last[p] |= g.last[p];
+            }
+            out = r;
+            return true;
+        }
+        case REP: {
+            // a subtree without an element makes no position: one copy says all (X{a,b} of assertions alone is X, or empty)
+            const int copies = nodes[id].has_element ? nodes[id].b : 1;
+            for (int i = 0; i < copies; ++i) {
+                AFrag g;
+                if (!aexpand(nodes[id].kids[0], g)) return false;
+                if (i >= nodes[id].a) g.nullable = true, g.eps = REL_FULL;
+                out = acat(out, g);
+            }
+            return true;
+        }
+        }
+        return false;
+    }
 };
+
+// bit k: the class holds a byte of category k
+int class_cats(const uint8_t *cls)
+{
+    int cats = 0;
+    for (unsigned c = 0; c < 256; ++c)
+        if ((cls[c >> 3] >> (c & 7)) & 1u) cats |= 1 << cat_of(c);
+    return cats;
+}
+
+// the class of all bytes whose category is in `cats`
+void cats_class(int cats, uint8_t *cls)
+{
+    std::memset(cls, 0, BMX_CLASS_BYTES);
+    for (unsigned c = 0; c < 256; ++c)
+        if ((cats >> cat_of(c)) & 1) cls[c >> 3] |= (uint8_t)(1u << (c & 7));
+}
+
+// From the expansion with relations to plain data: the automaton and the two classes per position.  A first position
+// whose admissible bytes before it depend on the category of its own byte (\b in front of [a-z.]) is split by category
+// into copies that stand side by side, and so is a last position; then every relation on an edge is decided from the
+// two classes, or the expression is refused.  Returns NULL, or why not.
+const char *resolve(const Compiler &c, const AFrag &f, uint32_t flags, bmx_regex *re_out, bmx_regex_anchors *an_out)
+{
+    const int m = c.re.m;
+    uint16_t F[BMX_MAX_REGEX_POSITIONS], L[BMX_MAX_REGEX_POSITIONS];
+    for (int p = 0; p < m; ++p) {
+        F[p] = f.first[p], L[p] = f.last[p];
+        if (flags & BMX_REGEX_WORD) F[p] &= REL_BEFORE_NOT_WORD, L[p] &= REL_AFTER_NOT_WORD;
+        if (flags & BMX_REGEX_LINE) F[p] &= REL_BOL, L[p] &= REL_EOL;
+    }
+    struct Copy {
+        int of, cats, before, after; // the position it copies; the categories it keeps; categories admitted before / after it
+    };
+    std::vector<Copy> copies;
+    int begin[BMX_MAX_REGEX_POSITIONS + 1];
+    for (int p = 0; p < m; ++p) {
+        begin[p] = (int)copies.size();
+        const int cats = class_cats(c.re.classes + (size_t)p * BMX_CLASS_BYTES);
+        int before[3], after[3];
+        for (int b = 0; b < 3; ++b) {
+            before[b] = after[b] = 0;
+            for (int a = 0; a < 3; ++a) {
+                if ((F[p] >> (3 * a + b)) & 1) before[b] |= 1 << a;
+                if ((L[p] >> (3 * b + a)) & 1) after[b] |= 1 << a;
+            }
+        }
+        if (cats == 0) { // an empty class consumes nothing: kept as one position, for the numbering
+            copies.push_back({p, 0, before[0] & before[1] & before[2], after[0] & after[1] & after[2]});
+            continue;
+        }
+        for (int b = 0; b < 3; ++b) { // categories with the same answers on both sides stay together
+            if (!((cats >> b) & 1)) continue;
+            size_t q = begin[p];
+            while (q < copies.size() && (copies[q].before != before[b] || copies[q].after != after[b])) ++q;
+            if (q == copies.size()) copies.push_back({p, 0, before[b], after[b]});
+            copies[q].cats |= 1 << b;
+        }
+    }
+    begin[m] = (int)copies.size();
+    const int m2 = (int)copies.size();
+    if (m2 > BMX_MAX_REGEX_POSITIONS) return "more than 64 positions after splitting";
+
+    bmx_regex re;
+    bmx_regex_anchors an;
+    std::memset(&re, 0, sizeof re);
+    std::memset(&an, 0xFF, sizeof an); // a full class: no condition
+    re.m = m2;
+    for (int q = 0; q < m2; ++q) {
+        const Copy &k = copies[q];
+        uint8_t keep[BMX_CLASS_BYTES];
+        cats_class(k.cats, keep);
+        for (int t = 0; t < BMX_CLASS_BYTES; ++t)
+            re.classes[(size_t)q * BMX_CLASS_BYTES + t] = c.re.classes[(size_t)k.of * BMX_CLASS_BYTES + t] & keep[t];
+        // (a copy that admits no byte on a side stays in the set with an empty class: it begins or ends no match)
+        if (f.first[k.of]) re.first |= 1ull << q, cats_class(k.before, an.before + (size_t)q * BMX_CLASS_BYTES);
+        if (f.last[k.of]) re.last |= 1ull << q, cats_class(k.after, an.after + (size_t)q * BMX_CLASS_BYTES);
+    }
+    for (int l = 0; l < m; ++l) {
+        for (int r = l + 1; r < m; ++r) {
+            const int rel = c.edge[l][r];
+            if (rel == 0) continue;
+            for (int ql = begin[l]; ql < begin[l + 1]; ++ql) {
+                for (int qr = begin[r]; qr < begin[r + 1]; ++qr) {
+                    int holds = 0, pairs = 0;
+                    for (int a = 0; a < 3; ++a)
+                        for (int b = 0; b < 3; ++b)
+                            if (((copies[ql].cats >> a) & 1) && ((copies[qr].cats >> b) & 1)) ++pairs, holds += (rel >> (3 * a + b)) & 1;
+                    if (rel != REL_FULL && holds != 0 && holds != pairs)
+                        return "an assertion between two positions whose classes do not decide it";
+                    if (rel == REL_FULL || holds != 0) re.follow[ql] |= 1ull << qr;
+                }
+            }
+        }
+    }
+    if (re.first != 0 && re.last != 0) bmx_regex_lengths(re.m, re.first, re.last, re.follow, &re.min_len, &re.max_len);
+    if (re.max_len == 0) return "the assertions leave no possible match";
+    *re_out = re;
+    *an_out = an;
+    return nullptr;
+}
 
 } // namespace
 
@@ -315,6 +548,40 @@ int compile(const char *where, bool star, const char *expr, uint64_t expr_len, u
 extern "C" int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
 {
     return compile("bmx_compile_regex", false, expr, expr_len, flags, out);
+}
+
+// The star-free grammar with the zero-width atoms: the same parser, the expansion with relations, then resolve().
+extern "C" int bmx_compile_regex_anchored(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *re, bmx_regex_anchors *an)
+{
+    const char *where = "bmx_compile_regex_anchored";
+    char text[192];
+    const char *why = nullptr;
+    Compiler c;
+    AFrag f;
+    if (!expr || !re || !an) why = "a NULL argument";
+    else if (flags & ~(BMX_CLASS_ICASE | BMX_CLASS_IUPAC | BMX_REGEX_WORD | BMX_REGEX_LINE)) why = "an unknown flag bit";
+    if (!why) {
+        c.e = reinterpret_cast<const uint8_t *>(expr);
+        c.len = expr_len;
+        c.flags = flags & (BMX_CLASS_ICASE | BMX_CLASS_IUPAC);
+        c.anchored = true;
+        std::memset(&c.re, 0, sizeof c.re);
+        std::memset(c.edge, 0, sizeof c.edge);
+        int root = 0;
+        bool ok = c.parse_alt(0, root);
+        if (ok && c.at < c.len) ok = c.fail("an unbalanced )");
+        if (ok) ok = c.aexpand(root, f);
+        if (ok && c.re.m == 0) ok = c.fail("zero positions");
+        if (ok && f.nullable) ok = c.fail("the expression matches the empty string once its assertions are ignored");
+        if (!ok) why = c.why ? c.why : "a bad expression";
+    }
+    if (!why) why = resolve(c, f, flags, re, an);
+    if (why) {
+        snprintf(text, sizeof text, "%s: %s", where, why);
+        bmx_internal_set_error(text);
+        return BMX_ERR_ARG;
+    }
+    return BMX_OK;
 }
 
 extern "C" int bmx_compile_regex_star(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)

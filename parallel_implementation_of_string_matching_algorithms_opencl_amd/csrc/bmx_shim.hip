@@ -110,6 +110,8 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_regex_free(ctx->regex);
     bmx_internal_regex_begins_free(ctx->regex_begins);
+    bmx_internal_regex_anchored_free(ctx->regex_anchored);
+    bmx_internal_regex_anchored_begins_free(ctx->regex_anchored_begins);
     bmx_internal_regex_star_free(ctx->regex_star);
     bmx_internal_regex_star_begins_free(ctx->regex_star_begins);
     bmx_internal_ed_batch_free(ctx->ed_batch);
@@ -452,6 +454,62 @@ int bmx_regex_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_regex_ends(&ctx->regex_begins, d_text, n, base_offset, re, d_starts, count, d_limit, flags, d_ends,
                                    (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+// ---- anchored regular-expression search (bmx_regex_anchored.hip; bmx_compile_regex_anchored is bmx_regex_compile.cpp) ------
+int bmx_search_regex_anchored_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                     const bmx_regex *re, const bmx_regex_anchors *an, uint32_t left, uint32_t right, uint64_t *d_ends,
+                                     uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_regex_args_ok(n, lead, re, d_ends, capacity) || !bmx_regex_anchors_ok(an, left, right) || !ctx || (n > 0 && !d_text))
+        return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_anchored(&ctx->regex_anchored, ctx->num_cu, d_text, n, lead, base_offset, re, an, left, right, d_ends,
+                                       capacity, n_matches, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_anchored_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_anchored_ms(ctx->regex_anchored) : -1.0f; }
+
+int bmx_regex_anchored_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                     const bmx_regex_anchors *an, uint32_t left, uint32_t right, const uint64_t *d_ends,
+                                     uint64_t count, uint32_t flags, uint64_t *d_starts, void *stream_v)
+{
+    if (!bmx_regex_starts_args_ok(n, re, d_ends, count, flags, d_starts) || !bmx_regex_anchors_ok(an, left, right)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_anchored_starts(&ctx->regex_anchored, d_text, n, base_offset, re, an, left, right, d_ends, count, flags,
+                                              d_starts, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+int bmx_search_regex_anchored_begins_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t tail, uint64_t base_offset,
+                                            const bmx_regex *re, const bmx_regex_anchors *an, uint32_t left, uint32_t right,
+                                            uint64_t *d_starts, uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_regex_begins_args_ok(n, tail, re, d_starts, capacity) || !bmx_regex_anchors_ok(an, left, right) || !ctx ||
+        (n > 0 && !d_text))
+        return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_anchored_begins(&ctx->regex_anchored_begins, ctx->num_cu, ctx->regex_begins_piece_shift, d_text, n, tail,
+                                              base_offset, re, an, left, right, d_starts, capacity, n_matches, (hipStream_t)stream_v,
+                                              g_err, sizeof g_err);
+}
+
+float bmx_last_regex_anchored_begins_ms(bmx_ctx *ctx)
+{
+    return ctx ? bmx_internal_regex_anchored_begins_ms(ctx->regex_anchored_begins) : -1.0f;
+}
+
+int bmx_regex_anchored_ends_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                                   const bmx_regex_anchors *an, uint32_t left, uint32_t right, const uint64_t *d_starts,
+                                   uint64_t count, const uint64_t *d_limit, uint32_t flags, uint64_t *d_ends, void *stream_v)
+{
+    if (!bmx_regex_ends_args_ok(n, re, d_starts, count, flags, d_ends) || !bmx_regex_anchors_ok(an, left, right)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (a start needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_anchored_ends(&ctx->regex_anchored_begins, d_text, n, base_offset, re, an, left, right, d_starts, count,
+                                            d_limit, flags, d_ends, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
 // ---- regular-expression search with unbounded repetition (bmx_regex_star.hip; bmx_compile_regex_star is
@@ -807,14 +865,14 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "regex_star_begins_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_begins_knobs.warm = value;
     else if (k == "regex_star_ends_no_early_exit") ctx->regex_star_ends_no_early_exit = value != 0;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else if (k == "tile_piece_shift" && (value == 0 || (value >= 6 && value <= 12))) {
         // the dictionary's tile is 2^(value - 6) rounds of 8 KiB and at most 256 KiB: a context with a dictionary session
         // takes no 12
         if ((uint32_t)value > bmx::ORDERED_DICT_MAX_PIECE_SHIFT && ctx->dict) return BMX_ERR_ARG;
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
     } else if (k == "tile_max_grid" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }
@@ -832,6 +890,8 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "gaps") state = ctx->gaps;
     else if (k == "regex") state = ctx->regex;
     else if (k == "regex_begins") state = ctx->regex_begins;
+    else if (k == "regex_anchored") state = ctx->regex_anchored;
+    else if (k == "regex_anchored_begins") state = ctx->regex_anchored_begins;
     else if (k == "regex_star") state = ctx->regex_star;
     else if (k == "regex_star_begins") state = ctx->regex_star_begins;
     else if (k == "dict") state = ctx->dict;

@@ -47,6 +47,8 @@ GAPS_PROSITE = 4  # a flag of compile_gaps, beside CLASS_ICASE and CLASS_IUPAC
 GAPS_LONGEST = 1  # a flag of gaps_starts_device
 MAX_REGEX_POSITIONS = 64
 REGEX_LONGEST = 1  # a flag of regex_starts_device
+REGEX_WORD = 4  # flags of compile_regex_anchored: grep -w ...
+REGEX_LINE = 8  # ... and grep -x
 REGEX_UNBOUNDED = -1  # Regex.max_len of an automaton with a cycle (compile_regex_star)
 MAX_REGEX_STAR_WINDOW = 65536  # regex_star_starts_device
 SPANS_BEST = 1
@@ -202,8 +204,26 @@ SYMBOLS = [
     ("bmx_search_regex_begins", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_search_regex_begins_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                 C.c_uint64, _u64p]),
+    ("bmx_compile_regex_anchored", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_anchored_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_last_regex_anchored_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_anchored_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                   C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_anchored_begins_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                          C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_last_regex_anchored_begins_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_anchored_ends_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                 C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_anchored", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_anchored_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_anchored_begins", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   _u64p]),
+    ("bmx_search_regex_anchored_begins_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                         C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_device_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
-    ("bmx_compile_regex_star", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("bmx_compile_regex_star",C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     ("bmx_search_regex_star_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                                C.c_uint64, _u64p, C.c_void_p]),
     ("bmx_search_regex_star", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
@@ -555,10 +575,50 @@ def reverse_regex(expr_or_regex, flags: int = 0) -> Regex:
     return out
 
 
+class RegexAnchors(C.Structure):
+    """struct bmx_regex_anchors (include/bmx.h), beside a Regex: the bytes admitted BEFORE a match for every position of
+    ``first`` and AFTER it for every position of ``last``, 32 bytes per position as compile_classes; a full class is no
+    condition."""
+    _fields_ = [("before", C.c_uint8 * (MAX_REGEX_POSITIONS * CLASS_BYTES)), ("after", C.c_uint8 * (MAX_REGEX_POSITIONS * CLASS_BYTES))]
+
+    @classmethod
+    def full(cls) -> "RegexAnchors":
+        """No condition anywhere: every anchored entry then returns its unanchored counterpart's list."""
+        out = cls()
+        C.memset(C.byref(out), 0xFF, C.sizeof(out))
+        return out
+
+    def before_array(self) -> np.ndarray:
+        return np.frombuffer(bytes(self.before), dtype=np.uint8).reshape(MAX_REGEX_POSITIONS, CLASS_BYTES).copy()
+
+    def after_array(self) -> np.ndarray:
+        return np.frombuffer(bytes(self.after), dtype=np.uint8).reshape(MAX_REGEX_POSITIONS, CLASS_BYTES).copy()
+
+
+def compile_regex_anchored(expr, flags: int = 0) -> Tuple[Regex, RegexAnchors]:
+    """A star-free regular expression with the zero-width atoms ``^ $ \\b \\B \\< \\>`` (bmx_compile_regex_anchored; what
+    Python's re means by them on bytes with re.MULTILINE; flags: compile_regex's, REGEX_WORD for grep -w, REGEX_LINE for
+    grep -x) -> (automaton, anchors).  Exact, or BmxError(ERR_ARG): it never approximates."""
+    e = _pat_bytes(expr)
+    re_, an = Regex(), RegexAnchors()
+    _check(lib().bmx_compile_regex_anchored(e, len(e), int(flags), C.byref(re_), C.byref(an)), "bmx_compile_regex_anchored")
+    return re_, an
+
+
+def _regex_anchored(expr_or_pair, flags: int = 0) -> Tuple[Regex, RegexAnchors]:
+    """(Regex, RegexAnchors) from an expression or such a pair, passed through."""
+    if isinstance(expr_or_pair, (str, bytes, bytearray)):
+        return compile_regex_anchored(expr_or_pair, flags)
+    if not (isinstance(expr_or_pair, tuple) and len(expr_or_pair) == 2 and isinstance(expr_or_pair[0], Regex)
+            and isinstance(expr_or_pair[1], RegexAnchors)):
+        raise ValueError("expr_or_pair: an expression or (Regex, RegexAnchors)")
+    return expr_or_pair
+
+
 def _posix_args(kind="regex", merge=False, longest=None, **_):
     """What posix=True of sub / findall goes with (checked before any GPU work)."""
-    if kind not in ("regex", "regex_star") or merge or longest is not None:
-        raise ValueError("posix: kind 'regex' or 'regex_star' only, without merge and without an explicit longest")
+    if kind not in ("regex", "regex_star", "regex_anchored") or merge or longest is not None:
+        raise ValueError("posix: kind 'regex', 'regex_star' or 'regex_anchored' only, without merge and without an explicit longest")
 
 
 def _regex(expr_or_regex, flags: int = 0, star: bool = False) -> Regex:
@@ -1372,6 +1432,130 @@ class Context:
     def last_regex_begins_ms(self) -> float:
         return float(self._L.bmx_last_regex_begins_ms(self._h))
 
+    # -- anchored regular-expression search: ^ $ \b \B \< \>, whole word, whole line -------
+    def _anchored_list_device(self, fn, what, d_text, expr_or_pair, flags, n, edge, base_offset, left, right, out, capacity, stream):
+        import torch
+
+        re_, an = _regex_anchored(expr_or_pair, flags)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = fn(self._h, C.c_void_p(d_text.data_ptr()), n, edge, base_offset, C.byref(re_), C.byref(an), int(left), int(right),
+                C.c_void_p(out.data_ptr()), cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, what, allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def search_regex_anchored_device(self, d_text, expr_or_pair, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
+                                     base_offset: int = 0, left: int = 10, right: int = 10, out=None,
+                                     capacity: Optional[int] = None, stream=None):
+        """Every end j in [lead, n) of the view at which an ANCHORED match ends (bmx_search_regex_anchored_device).
+        ``expr_or_pair``: an expression for compile_regex_anchored(expr, flags) or its result.  ``left`` / ``right``: the
+        bytes next to the view, 0x0A for a whole text, the real neighbours for a shard.  Otherwise search_regex_device."""
+        return self._anchored_list_device(self._L.bmx_search_regex_anchored_device, "bmx_search_regex_anchored_device", d_text,
+                                          expr_or_pair, flags, n, lead, base_offset, left, right, out, capacity, stream)
+
+    def search_regex_anchored_begins_device(self, d_text, expr_or_pair, *, flags: int = 0, n: Optional[int] = None, tail: int = 0,
+                                            base_offset: int = 0, left: int = 10, right: int = 10, out=None,
+                                            capacity: Optional[int] = None, stream=None):
+        """Every start s in [0, n - tail) of the view at which an anchored match begins
+        (bmx_search_regex_anchored_begins_device); otherwise search_regex_begins_device."""
+        return self._anchored_list_device(self._L.bmx_search_regex_anchored_begins_device, "bmx_search_regex_anchored_begins_device",
+                                          d_text, expr_or_pair, flags, n, tail, base_offset, left, right, out, capacity, stream)
+
+    def regex_anchored_starts_device(self, d_text, expr_or_pair, ends, *, longest: bool = False, flags: int = 0,
+                                     n: Optional[int] = None, base_offset: int = 0, left: int = 10, right: int = 10, stream=None):
+        """A start for every end of ``ends`` as search_regex_anchored_device returns it (bmx_regex_anchored_starts_device);
+        otherwise regex_starts_device."""
+        import torch
+
+        re_, an = _regex_anchored(expr_or_pair, flags)
+        count = ends.numel()
+        if n is None:
+            n = d_text.numel()
+        if ends.element_size() != 8:
+            raise ValueError("ends: 8-byte entries")
+        starts = torch.empty(max(count, 1), dtype=ends.dtype, device=ends.device)
+        s = stream if stream is not None else torch.cuda.current_stream(ends.device)
+        rc = self._L.bmx_regex_anchored_starts_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                                      C.byref(an), int(left), int(right), C.c_void_p(ends.data_ptr()), count,
+                                                      REGEX_LONGEST if longest else 0, C.c_void_p(starts.data_ptr()),
+                                                      C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_anchored_starts_device")
+        return starts[:count]
+
+    def regex_anchored_ends_device(self, d_text, expr_or_pair, starts, *, longest: bool = False, limit=None, flags: int = 0,
+                                   n: Optional[int] = None, base_offset: int = 0, left: int = 10, right: int = 10, stream=None):
+        """An end for every start of ``starts`` as search_regex_anchored_begins_device returns it
+        (bmx_regex_anchored_ends_device); otherwise regex_ends_device."""
+        import torch
+
+        re_, an = _regex_anchored(expr_or_pair, flags)
+        count = starts.numel()
+        if n is None:
+            n = d_text.numel()
+        if starts.element_size() != 8 or (limit is not None and (limit.element_size() != 8 or limit.numel() != count)):
+            raise ValueError("starts, limit: 8-byte entries, as many of one as of the other")
+        ends = torch.empty(max(count, 1), dtype=starts.dtype, device=starts.device)
+        s = stream if stream is not None else torch.cuda.current_stream(starts.device)
+        rc = self._L.bmx_regex_anchored_ends_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                                    C.byref(an), int(left), int(right), C.c_void_p(starts.data_ptr()), count,
+                                                    C.c_void_p(limit.data_ptr()) if limit is not None else None,
+                                                    REGEX_LONGEST if longest else 0, C.c_void_p(ends.data_ptr()),
+                                                    C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_anchored_ends_device")
+        return ends[:count]
+
+    def _anchored_host(self, fn, what, text, expr_or_pair, flags, spans, longest, capacity):
+        re_, an = _regex_anchored(expr_or_pair, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            a = np.empty(max(cap, 1), dtype=np.uint64)
+            b = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            if spans:
+                rc = fn(self._h, tptr, n, C.byref(re_), C.byref(an), REGEX_LONGEST if longest else 0, C.c_void_p(a.ctypes.data),
+                        C.c_void_p(b.ctypes.data), cap, C.byref(total))
+            else:
+                rc = fn(self._h, tptr, n, C.byref(re_), C.byref(an), C.c_void_p(a.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, what)
+            del keep
+            t = int(total.value)
+            return (a[:t].copy(), b[:t].copy()) if spans else a[:t].copy()
+
+    def search_regex_anchored(self, text, expr_or_pair, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex_anchored): ascending ends, uint64; outside the text counts as a line break."""
+        return self._anchored_host(self._L.bmx_search_regex_anchored, "bmx_search_regex_anchored", text, expr_or_pair, flags, False,
+                                   False, capacity)
+
+    def search_regex_anchored_spans(self, text, expr_or_pair, flags: int = 0, longest: bool = False):
+        """Host buffers (bmx_search_regex_anchored_spans): (starts, ends), ends ascending, as search_regex_spans."""
+        return self._anchored_host(self._L.bmx_search_regex_anchored_spans, "bmx_search_regex_anchored_spans", text, expr_or_pair,
+                                   flags, True, longest, None)
+
+    def search_regex_anchored_begins(self, text, expr_or_pair, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex_anchored_begins): ascending starts, uint64."""
+        return self._anchored_host(self._L.bmx_search_regex_anchored_begins, "bmx_search_regex_anchored_begins", text, expr_or_pair,
+                                   flags, False, False, capacity)
+
+    def search_regex_anchored_begins_spans(self, text, expr_or_pair, flags: int = 0, longest: bool = False):
+        """Host buffers (bmx_search_regex_anchored_begins_spans): (starts, ends), starts ascending, as search_regex_begins_spans."""
+        return self._anchored_host(self._L.bmx_search_regex_anchored_begins_spans, "bmx_search_regex_anchored_begins_spans", text,
+                                   expr_or_pair, flags, True, longest, None)
+
+    def last_regex_anchored_ms(self) -> float:
+        return float(self._L.bmx_last_regex_anchored_ms(self._h))
+
+    def last_regex_anchored_begins_ms(self) -> float:
+        return float(self._L.bmx_last_regex_anchored_begins_ms(self._h))
+
     # -- regular-expression search with unbounded repetition: * + {a,} -------------------
     def search_regex_star_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
                                  base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
@@ -2023,6 +2207,10 @@ class Context:
             re_ = _regex(expr, flags)
             ends, _ = complete(lambda out: self.search_regex_device(d_text, re_, out=out))
             return self.regex_starts_device(d_text, re_, ends, longest=longest), ends, 0
+        if kind == "regex_anchored":  # (the text is whole: outside it counts as a line break)
+            pair = _regex_anchored(expr, flags)
+            ends, _ = complete(lambda out: self.search_regex_anchored_device(d_text, pair, out=out))
+            return self.regex_anchored_starts_device(d_text, pair, ends, longest=longest), ends, 0
         if kind == "regex_star":
             re_ = _regex(expr, flags, star=True)
             ends, _ = complete(lambda out: self.search_regex_star_device(d_text, re_, out=out))
@@ -2031,7 +2219,7 @@ class Context:
         if kind == "approx":
             ends, dist, _ = complete(lambda out: self.search_approx_device(d_text, expr, k, out=out))
             return self.approx_spans_device(d_text, expr, k, ends, dist)[0], ends, 0
-        raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_star | approx")
+        raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_anchored | regex_star | approx")
 
     def last_rows_ms(self) -> float:
         return float(self._L.bmx_last_rows_ms(self._h))
@@ -2128,14 +2316,17 @@ class Context:
         the longest row, else 4,096, at most MAX_REGEX_STAR_WINDOW); an entry the window cut short is a ValueError."""
         import torch
 
-        star = kind == "regex_star"
-        re_ = _regex(expr, flags, star=star)
-        begins = self.search_regex_star_begins_device if star else self.search_regex_begins_device
+        star, anchored = kind == "regex_star", kind == "regex_anchored"
+        re_ = _regex_anchored(expr, flags) if anchored else _regex(expr, flags, star=star)
+        begins = (self.search_regex_anchored_begins_device if anchored else
+                  self.search_regex_star_begins_device if star else self.search_regex_begins_device)
         starts, total = begins(d_text, re_)
         if total > starts.numel():
             starts, _ = begins(d_text, re_, out=torch.empty(total, dtype=torch.int64, device=d_text.device))
 
         def longest_ends(limit):
+            if anchored:
+                return self.regex_anchored_ends_device(d_text, re_, starts, longest=True, limit=limit)
             if not star:
                 return self.regex_ends_device(d_text, re_, starts, longest=True, limit=limit)
             w = window if window is not None else min(MAX_REGEX_STAR_WINDOW, max(rows.longest, 1) if rows is not None else 4096)
@@ -2749,6 +2940,16 @@ def search_regex(text, expr, flags: int = 0, spans: bool = False, longest: bool 
     (starts, ends), each start the largest one for its end (the shortest match) or with ``longest`` the smallest."""
     ctx = default_context()
     return ctx.search_regex_spans(text, expr, flags, longest) if spans else ctx.search_regex(text, expr, flags)
+
+
+def search_regex_anchored(text, expr, flags: int = 0, spans: bool = False, longest: bool = False, begins: bool = False):
+    """(text, star-free regular expression with ^ $ \\b \\B \\< \\>; flags REGEX_WORD / REGEX_LINE for grep -w / -x) ->
+    ascending ends of every anchored match (bmx_search_regex_anchored), or with ``begins`` the ascending starts; with
+    ``spans`` the pair (starts, ends) as search_regex / search_regex_begins give it.  Outside the text counts as a line break."""
+    ctx = default_context()
+    if begins:
+        return ctx.search_regex_anchored_begins_spans(text, expr, flags, longest) if spans else ctx.search_regex_anchored_begins(text, expr, flags)
+    return ctx.search_regex_anchored_spans(text, expr, flags, longest) if spans else ctx.search_regex_anchored(text, expr, flags)
 
 
 def search_regex_star_begins(text, expr, flags: int = 0, spans: bool = False, longest: bool = False, window: int = 4096):
