@@ -635,7 +635,8 @@ int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_r
  * than its bound (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly
  * ordered.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream.
  * Out of scope: unbounded repetition (* + {a,}; bmx_search_regex_star_device below), back-references, capture groups, more
- * than 64 positions.  Anchors and word boundaries: bmx_compile_regex_anchored and bmx_search_regex_anchored_device below. */
+ * than 64 positions (up to 128: bmx_compile_regex_long and bmx_search_regex_long_device at the end of this file).  Anchors
+ * and word boundaries: bmx_compile_regex_anchored and bmx_search_regex_anchored_device below. */
 int bmx_search_regex_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                             const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
 /* Host buffers in, host buffers out (upload, bmx_search_regex_device with lead = 0, download). */
@@ -1462,6 +1463,61 @@ int bmx_search_regex_anchored_begins(bmx_ctx *ctx /* NULL: device 0 */, const ch
 int bmx_search_regex_anchored_begins_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
                                            const bmx_regex_anchors *an, uint32_t flags, uint64_t *starts, uint64_t *ends,
                                            uint64_t capacity, uint64_t *n_matches);
+
+/* ---- regular-expression search for expressions of up to 128 positions ---------------------- */
+
+/* a.{0,100}b, ATG([ACGT]{3}){2,40}(TAA|TAG|TGA), a PROSITE motif with x(20,40), a list of ten keywords in front of a
+ * counted class: counted repeats and keyword lists pass 64 positions quickly, and a.{0,100}b cannot be split into two
+ * searches at all.  The entries below are bmx_search_regex_device and bmx_regex_starts_device for the STAR-FREE
+ * expressions of up to 128 positions: the same recurrence on a state of four dwords per lane, the automaton's tables in a
+ * device buffer of the context instead of the kernel arguments (csrc/bmx_regex_long_kernel.h).  The
+ * 64-position entries above and struct bmx_regex are unchanged.
+ *
+ * The automaton is struct bmx_regex with sets of two words: position i is bit (i & 63) of word (i >> 6).  text[s..j] of
+ * length L >= 1 MATCHES iff there are positions i_0, .., i_{L-1} with i_0 in `first`, i_{t+1} in follow[i_t], i_{L-1} in
+ * `last` and text[s + t] in class i_t for every t.
+ * Valid: 1 <= m <= BMX_MAX_REGEX_LONG_POSITIONS; first and last non-empty; no bit at or above m in first, last or any
+ * follow[i]; follow[i] holds only bits j > i (acyclic, max_len <= m).  Empty classes and positions that no match can use
+ * are legal.  The entries recompute min_len and max_len and do not read the two fields or `pad`. */
+#define BMX_MAX_REGEX_LONG_POSITIONS 128
+typedef struct bmx_regex_long {
+    int32_t  m;                 /* positions, 1..128, numbered left to right after expansion */
+    int32_t  min_len, max_len;  /* shortest / longest match in bytes; filled by bmx_compile_regex_long */
+    int32_t  pad;               /* 0 */
+    uint64_t first[2], last[2]; /* bit (i & 63) of word (i >> 6): position i */
+    uint64_t follow[BMX_MAX_REGEX_LONG_POSITIONS][2];  /* follow[i]: the positions that may come right after i */
+    uint8_t  classes[BMX_MAX_REGEX_LONG_POSITIONS * BMX_CLASS_BYTES];  /* as for bmx_search_classes */
+} bmx_regex_long;
+/* bmx_compile_regex's grammar, flags and errors with the limit at 128 positions (unbounded repetition is still refused);
+ * error texts begin with "bmx_compile_regex_long: " and *out is untouched on error.  For an expression of at most 64
+ * positions first[0], last[0], follow[i][0], classes, m, min_len and max_len equal bmx_compile_regex's output and the
+ * high words are 0.  Pure host code, no GPU. */
+int bmx_compile_regex_long(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex_long *out);
+/* The same automaton in the wide struct (pure host code).  BMX_ERR_ARG for NULL or an `in` that is not valid for
+ * bmx_search_regex_device. */
+int bmx_regex_long_widen(const bmx_regex *in, bmx_regex_long *out);
+/* bmx_search_regex_device for a bmx_regex_long: every END j in [lead, n) at which some match ends, each once, ascending,
+ * reported as base_offset + j; the halo of a shard is max_len - 1 bytes; the capacity rule, n < 2^40, any alignment of
+ * d_text, BMX_ERR_HIP in place of a partly ordered list and the argument errors before any HIP call (with ctx = NULL too)
+ * are that entry's.  Any m in 1..128 is accepted, and for m <= 64 the list equals bmx_search_regex_device's.  An
+ * automaton in which no position of `last` can be reached returns an empty list without a launch.  One copy of the
+ * automaton's tables (6 KiB) and one kernel launch on `stream` (NULL = the null stream); the call returns after
+ * synchronising that stream. */
+int bmx_search_regex_long_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                 const bmx_regex_long *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
+/* Host buffers in, host buffers out (upload, bmx_search_regex_long_device with lead = 0, download). */
+int bmx_search_regex_long(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex_long *re,
+                          uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the kernel) of the last bmx_search_regex_long_device on ctx; < 0 if none. */
+float bmx_last_regex_long_ms(bmx_ctx *ctx);
+/* bmx_regex_starts_device for a bmx_regex_long: the START of a match for every end of a device-resident list, the largest
+ * one by default (the shortest match), with BMX_REGEX_LONGEST the smallest one of the view.  Status word, errors,
+ * count == 0, the bytes read and the stream rule are exactly that entry's. */
+int bmx_regex_long_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex_long *re,
+                                 const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_regex_long_device, bmx_regex_long_starts_device, download. */
+int bmx_search_regex_long_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex_long *re,
+                                uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ from .host import (BmxError, CLASS_ICASE, CLASS_IUPAC, Context, Dictionary, GAPS
                    grep, index_count, index_map, index_seeds, lcp_array, longest_repeat, rows_split, search, search_approx, search_classes,
                    search_dict, search_gaps, search_hamming, search_ranges, search_regex, search_regex_star)
 from .host import reverse_regex, search_regex_begins, search_regex_star_begins  # noqa: F401
+from .host import MAX_REGEX_LONG_POSITIONS, RegexLong, compile_regex_long, search_regex_long, widen_regex  # noqa: F401
 from .host import REGEX_LINE, REGEX_WORD, RegexAnchors, compile_regex_anchored, search_regex_anchored  # noqa: F401
 
 __version__ = "0.1.0"

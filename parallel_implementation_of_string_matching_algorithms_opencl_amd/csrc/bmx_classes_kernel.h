@@ -79,9 +79,11 @@ struct ClassesStep {
 // that holds the first warm-up byte and the one that holds end hi - 1.  step.chunk(tab, s, v, skip) runs one chunk and
 // returns its 16 hit bits; skip is the number of its bytes that lie in front of the view (non-zero for the chunk at
 // aligned byte 0 of an unaligned view only).
-template <bool WIDE, int PASS, typename Step>
-__device__ __forceinline__ uint32_t shift_and_walk(const TileArgs &a, const Step &step, const uint32_t *tab, uint64_t lo, uint64_t hi,
-                                                   uint64_t tile0, uint64_t *stage, uint32_t *stage_n, uint64_t base)
+// State: what a lane carries from byte to byte, all zero in front of the first byte walked (ShiftAndState, or the four
+// dwords of the long regular-expression search); Tab: the element type of the policy's LDS table.
+template <typename State, int PASS, typename Step, typename Tab>
+__device__ __forceinline__ uint32_t shift_and_walk_state(const TileArgs &a, const Step &step, const Tab *tab, uint64_t lo, uint64_t hi,
+                                                         uint64_t tile0, uint64_t *stage, uint32_t *stage_n, uint64_t base)
 {
     const uint64_t want = lo >= a.first + a.warm ? lo - a.warm : a.first;
     const uint64_t origin = want & ~127ull;                  // the line of the first byte walked
@@ -89,8 +91,7 @@ __device__ __forceinline__ uint32_t shift_and_walk(const TileArgs &a, const Step
     const int32_t r_lo = (int32_t)(lo - origin);
     const int32_t r_hi = (int32_t)(hi - origin);
     const tile_u32x4 *src = reinterpret_cast<const tile_u32x4 *>(a.text16) + (origin >> 4);
-    ShiftAndState<WIDE> s;
-    s.lo = s.hi = 0;
+    State s = State();
     uint32_t cnt = 0;
     for (int32_t line = 0; line < r_hi; line += 128, src += 8) {
         tile_u32x4 v[8];
@@ -128,6 +129,14 @@ __device__ __forceinline__ uint32_t shift_and_walk(const TileArgs &a, const Step
         }
     }
     return cnt;
+}
+
+// The walk on a Shift-And word of 32 or 64 bits.
+template <bool WIDE, int PASS, typename Step>
+__device__ __forceinline__ uint32_t shift_and_walk(const TileArgs &a, const Step &step, const uint32_t *tab, uint64_t lo, uint64_t hi,
+                                                   uint64_t tile0, uint64_t *stage, uint32_t *stage_n, uint64_t base)
+{
+    return shift_and_walk_state<ShiftAndState<WIDE>, PASS>(a, step, tab, lo, hi, tile0, stage, stage_n, base);
 }
 
 // The frame's policy of a Shift-And search: B in LDS with bit m - 1 in the top bit (WIDE: {low, high} pairs), the walk

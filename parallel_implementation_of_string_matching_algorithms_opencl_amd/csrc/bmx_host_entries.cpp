@@ -702,6 +702,53 @@ int bmx_search_regex_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const 
     return c.rc;
 }
 
+int bmx_search_regex_long(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex_long *re, uint64_t *ends, uint64_t capacity,
+                          uint64_t *n_matches)
+{
+    if (!bmx_regex_long_args_ok(n, 0, re, ends, capacity) || (n > 0 && !text)) return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_long", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_long_device(c.ctx(), d_text, n, 0, 0, re, d_ends, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    c.download(ends, d_ends, std::min(total, dev_cap) * sizeof(uint64_t), "regex matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+int bmx_search_regex_long_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex_long *re, uint32_t flags,
+                                uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_regex_long_args_ok(n, 0, re, ends, capacity) || (capacity > 0 && !starts) || (n > 0 && !text) ||
+        (flags & ~BMX_REGEX_LONGEST))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_long_spans", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_long_device(c.ctx(), d_text, n, 0, 0, re, d_ends, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    const int src = bmx_regex_long_starts_device(c.ctx(), d_text, n, 0, re, d_ends, stored, flags, d_starts, nullptr);
+    if (src != BMX_OK) return src;
+    c.download(ends, d_ends, stored * sizeof(uint64_t), "regex matches");
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "regex matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
 // The reversed automaton (pure host code; the starts pass and the begins search of bmx_regex.hip run it): bit i stands for
 // position m - 1 - i, first and last swap, follow is transposed, the classes are mirrored.
 int bmx_regex_reverse(const bmx_regex *re, bmx_regex *out)

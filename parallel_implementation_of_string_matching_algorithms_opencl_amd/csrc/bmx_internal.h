@@ -114,6 +114,15 @@ int bmx_internal_regex_starts(void **state, const void *d_text, uint64_t n, uint
                               uint64_t *bad_out, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_regex_free(void *state);
 float bmx_internal_regex_ms(const void *state);
+// bmx_regex_long.hip: the same two passes for automata of up to 128 positions (struct bmx_regex_long)
+int bmx_internal_regex_long(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                            const bmx_regex_long *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, hipStream_t stream,
+                            char *err, size_t errlen);
+int bmx_internal_regex_long_starts(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex_long *re,
+                                   const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, hipStream_t stream,
+                                   char *err, size_t errlen);
+void bmx_internal_regex_long_free(void *state);
+float bmx_internal_regex_long_ms(const void *state);
 constexpr uint64_t BMX_REGEX_STARTS_NO_MATCH = 2; // *bad_out: some end had no match (csrc/bmx_regex_kernel.h, REGEX_BAD_START)
 // ... its mirror image: every start (a state of its own; piece_shift: 0, or log2 of the starts per lane -- libbmx_exp.so's
 // knob) and the end of every start of a list (d_limit: NULL, or the last byte each entry may use)
@@ -294,6 +303,7 @@ struct bmx_ctx {
     void *hamming = nullptr; // k-mismatch search: the same again (bmx_hamming.hip)
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *regex = nullptr; // regular-expression search: the same as the gapped search's, its own (bmx_regex.hip)
+    void *regex_long = nullptr; // ... for up to 128 positions: the same and the block of its tables (bmx_regex_long.hip)
     void *regex_begins = nullptr; // ... its begins search and ends pass: the same again, their own (bmx_regex.hip)
     int regex_begins_piece_shift = 0; // libbmx_exp.so: 0, or log2 of the starts per lane of the begins search (4..12)
     void *regex_anchored = nullptr; // ... anchored: the same and the gate tables (bmx_regex_anchored.hip)
@@ -394,6 +404,19 @@ inline bool bmx_regex_starts_args_ok(uint64_t n, const bmx_regex *re, const uint
                                      const uint64_t *starts)
 {
     if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
+    return count == 0 || (ends && starts);
+}
+
+// ... for up to 128 positions: the same rules on struct bmx_regex_long
+inline bool bmx_regex_long_args_ok(uint64_t n, uint64_t lead, const bmx_regex_long *re, const void *ends, uint64_t capacity)
+{
+    return bmx_regex_long_sets_ok(re) && lead <= n && n < (1ull << 40) && (capacity == 0 || ends);
+}
+
+inline bool bmx_regex_long_starts_args_ok(uint64_t n, const bmx_regex_long *re, const uint64_t *ends, uint64_t count, uint32_t flags,
+                                          const uint64_t *starts)
+{
+    if (!bmx_regex_long_sets_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
     return count == 0 || (ends && starts);
 }
 

@@ -62,6 +62,11 @@
 //                             bmx_search_regex_anchored*; outside the text counts as a line break); --word is grep -w, --line
 //                             is grep -x.  It takes every companion of --regex: --starts, --longest, --begins, --spans,
 //                             --lines, --invert, --posix, --replace, --only-matching
+//   bmx_cli --regex-long EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K] [--starts [--longest]]
+//                             --regex for an expression of up to 128 positions after expansion (bmx_compile_regex_long,
+//                             bmx_search_regex_long*); it prints what --regex prints and takes --lines, --replace,
+//                             --only-matching and --merge as --regex does, but neither --begins nor --posix, and goes with
+//                             none of the other search flags
 //   bmx_cli --regex-star EXPR [--icase] [--iupac] [--text F] [--iters N] [--positions] [--max-print K]
 //           [--starts --window N [--longest]]
 //                             the same with unbounded repetition: EXPR may use * + {a,} (bmx_compile_regex_star,
@@ -222,6 +227,7 @@ int main(int argc, char **argv)
     std::string gaps_expr, regex_expr;
     bool have_regex = false, regex_star = false, regex_both = false;
     bool regex_anchored = false; // --regex-anchored EXPR [--word] [--line]
+    bool regex_long = false;     // --regex-long EXPR: up to 128 positions
     uint32_t anchor_flags = 0;
     uint32_t star_window = 0;
     bool regex_begins = false, begins_spans = false, begins_longest = false, posix = false; // --begins [--spans [--longest]], --posix
@@ -271,6 +277,7 @@ int main(int argc, char **argv)
         else if (a == "--classes") class_expr = need("--classes"), have_classes = true;
         else if (a == "--gaps") gaps_expr = need("--gaps"), have_gaps = true;
         else if (a == "--regex") regex_both = have_regex, regex_expr = need("--regex"), have_regex = true;
+        else if (a == "--regex-long") regex_both = have_regex, regex_expr = need("--regex-long"), have_regex = regex_long = true;
         else if (a == "--regex-star") regex_both = have_regex, regex_expr = need("--regex-star"), have_regex = regex_star = true;
         else if (a == "--regex-anchored") regex_both = have_regex, regex_expr = need("--regex-anchored"), have_regex = regex_anchored = true;
         else if (a == "--word") anchor_flags |= BMX_REGEX_WORD;
@@ -346,6 +353,10 @@ int main(int argc, char **argv)
         p = *end ? end + 1 : end;
     }
 
+    if (regex_long && (regex_begins || posix)) {
+        fprintf(stderr, "--regex-long goes with neither --begins nor --posix\n");
+        return 2;
+    }
     if (anchor_flags != 0 && !regex_anchored) {
         fprintf(stderr, "--word and --line go with --regex-anchored EXPR\n");
         return 2;
@@ -708,8 +719,10 @@ int main(int argc, char **argv)
         const char *what = "bmx_search";
         if (have_regex) {
             bmx_regex re;
+            bmx_regex_long rl; // (--regex-long: in place of re)
             bmx_regex_anchors an; // (full where the expression has no assertions: read by the anchored entries only)
             if ((regex_anchored ? bmx_compile_regex_anchored(regex_expr.data(), regex_expr.size(), class_flags | anchor_flags, &re, &an)
+                 : regex_long   ? bmx_compile_regex_long(regex_expr.data(), regex_expr.size(), class_flags, &rl)
                  : regex_star   ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
                                 : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
                 fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
@@ -717,7 +730,7 @@ int main(int argc, char **argv)
             }
             // (the star search: a match longer than the longest row lies in no row)
             const uint32_t window = (uint32_t)std::min<uint64_t>(BMX_MAX_REGEX_STAR_WINDOW, std::max<uint64_t>(longest, 1));
-            what = regex_star ? "bmx_search_regex_star_spans" : "bmx_search_regex_spans";
+            what = regex_star ? "bmx_search_regex_star_spans" : regex_long ? "bmx_search_regex_long_spans" : "bmx_search_regex_spans";
             uint64_t clipped = 0; // --regex-star --posix: the starts whose longest match may be longer than the window
             if (posix && !lines_mode && regex_star) {
                 what = "bmx_search_regex_star_begins_spans";
@@ -758,6 +771,7 @@ int main(int argc, char **argv)
                 bmx_device_free(ctx, d_text);
             } else
             rc = regex_anchored ? bmx_search_regex_anchored_spans(ctx, text.data(), n, &re, &an, longest_flag, starts.data(), ends.data(), room, &hits)
+                 : regex_long ? bmx_search_regex_long_spans(ctx, text.data(), n, &rl, longest_flag, starts.data(), ends.data(), room, &hits)
                  : regex_star ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, window, longest_flag, starts.data(), ends.data(), room, &hits)
                             : bmx_search_regex_spans(ctx, text.data(), n, &re, longest_flag, starts.data(), ends.data(), room, &hits);
             if (rc == BMX_OK && clipped != 0) { // never a shorter match than POSIX's
@@ -855,13 +869,16 @@ int main(int argc, char **argv)
     }
     if (have_regex) {
         bmx_regex re;
+        bmx_regex_long rl; // (--regex-long: in place of re)
         bmx_regex_anchors an; // (read by the anchored entries only)
         if ((regex_anchored ? bmx_compile_regex_anchored(regex_expr.data(), regex_expr.size(), class_flags | anchor_flags, &re, &an)
+             : regex_long   ? bmx_compile_regex_long(regex_expr.data(), regex_expr.size(), class_flags, &rl)
              : regex_star   ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
                             : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
             fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
             return 1;
         }
+        if (regex_long) re.m = rl.m, re.min_len = rl.min_len, re.max_len = rl.max_len; // (for the line below)
         if (re.max_len == BMX_REGEX_UNBOUNDED)
             printf("text %s: %llu bytes, regular expression %s: %d positions, matches of %d or more bytes\n", text_path.c_str(),
                    (unsigned long long)n, regex_expr.c_str(), re.m, re.min_len);
@@ -926,6 +943,7 @@ int main(int argc, char **argv)
         for (int it = 0; it < iters; ++it) {
             auto t0 = std::chrono::steady_clock::now();
             rc = regex_anchored ? bmx_search_regex_anchored_device(ctx, d_text, n, 0, 0, &re, &an, '\n', '\n', d_ends, cap, &hits, nullptr)
+                 : regex_long ? bmx_search_regex_long_device(ctx, d_text, n, 0, 0, &rl, d_ends, cap, &hits, nullptr)
                  : regex_star ? bmx_search_regex_star_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr)
                             : bmx_search_regex_device(ctx, d_text, n, 0, 0, &re, d_ends, cap, &hits, nullptr);
             auto t1 = std::chrono::steady_clock::now();
@@ -934,10 +952,11 @@ int main(int argc, char **argv)
                 return 1;
             }
             total += std::chrono::duration<double>(t1 - t0).count();
-            kernel_ms += regex_anchored ? bmx_last_regex_anchored_ms(ctx) : regex_star ? bmx_last_regex_star_ms(ctx) : bmx_last_regex_ms(ctx);
+            kernel_ms += regex_anchored ? bmx_last_regex_anchored_ms(ctx) : regex_long ? bmx_last_regex_long_ms(ctx) : regex_star ? bmx_last_regex_star_ms(ctx) : bmx_last_regex_ms(ctx);
         }
         if (iters <= 0) { // no timed call has counted: a counting call
             rc = regex_anchored ? bmx_search_regex_anchored(ctx, text.data(), n, &re, &an, nullptr, 0, &hits)
+                 : regex_long ? bmx_search_regex_long(ctx, text.data(), n, &rl, nullptr, 0, &hits)
                  : regex_star ? bmx_search_regex_star(ctx, text.data(), n, &re, nullptr, 0, &hits)
                             : bmx_search_regex(ctx, text.data(), n, &re, nullptr, 0, &hits);
             if (rc != BMX_OK && rc != BMX_ERR_CAPACITY) hits = 0;
@@ -949,6 +968,9 @@ int main(int argc, char **argv)
         if (regex_anchored)
             rc = gaps_starts ? bmx_search_regex_anchored_spans(ctx, text.data(), n, &re, &an, span_flags, starts.data(), ends.data(), hits, &got)
                              : bmx_search_regex_anchored(ctx, text.data(), n, &re, &an, ends.data(), hits, &got);
+        else if (regex_long)
+            rc = gaps_starts ? bmx_search_regex_long_spans(ctx, text.data(), n, &rl, span_flags, starts.data(), ends.data(), hits, &got)
+                             : bmx_search_regex_long(ctx, text.data(), n, &rl, ends.data(), hits, &got);
         else if (regex_star)
             rc = gaps_starts ? bmx_search_regex_star_spans(ctx, text.data(), n, &re, star_window, span_flags, starts.data(), ends.data(),
                                                            hits, &got)

@@ -14,7 +14,7 @@
 // standard recursion (Glushkov 1961; Berry and Sethi 1986).  follow[] only ever points upward: a concatenation links the
 // last positions of what stands left to the first positions of what stands right of it, and nothing else makes a link.
 // A subtree without an element is the empty string whatever its counts say, so it is never expanded more than once and
-// every other expansion step makes a position: the work is bounded by the 64 positions, not by the counts.
+// every other expansion step makes a position: the work is bounded by the entry's 64 or 128 positions, not by the counts.
 // With the switch: X+ links every last position of X to the first positions of X (the one rule that makes follow[] point
 // downward or at itself), X* is (X+)? and X{a,} is a - 1 copies of X followed by X+ (a == 0: X*).
 // bmx_compile_regex_anchored is the star-free grammar behind a second switch (Compiler::anchored): ^ $ \b \B \< \> parse
@@ -22,6 +22,9 @@
 // plain one carries a bit (aexpand), and resolve() turns the relations into struct bmx_regex_anchors, splitting a position
 // whose condition depends on its own byte and deciding every assertion between two positions from their classes
 // (DESIGN.md s32).  The two plain entries never see an assertion: without the switch ^ and $ are literals.
+// bmx_compile_regex_long is the star-free grammar with the limit at 128 positions (Compiler::limit): the expansion always
+// works on sets of 128 bits (Set, bmx_regex_sets.h) and each entry stores them into its own struct at the end, so for an
+// expression of at most 64 positions the long entry's low words are the short entry's sets.
 #include "bmx.h"
 
 #include <cstdio>
@@ -132,9 +135,17 @@ struct Node {
     uint8_t cls[BMX_CLASS_BYTES]; // ELEM
 };
 
+// The compiler's own automaton: sets of 128 bits whatever the entry's limit, turned into the entry's struct at the end.
+typedef bmx_set128 Set;
+struct Automaton {
+    int32_t m;
+    Set follow[BMX_MAX_REGEX_LONG_POSITIONS];
+    uint8_t classes[BMX_MAX_REGEX_LONG_POSITIONS * BMX_CLASS_BYTES];
+};
+
 struct Frag {
     bool nullable;
-    uint64_t first, last;
+    Set first, last;
 };
 
 struct Compiler {
@@ -147,7 +158,8 @@ struct Compiler {
     const char *why = nullptr;
     bool has_assertion = false;
     std::vector<Node> nodes;
-    bmx_regex re;
+    int limit = BMX_MAX_REGEX_POSITIONS; // positions after expansion (bmx_compile_regex_long: 128)
+    Automaton re;
 
     bool fail(const char *text)
     {
@@ -263,9 +275,9 @@ struct Compiler {
         return true;
     }
 
-    static Frag cat(Frag f, const Frag &g, uint64_t *follow)
+    static Frag cat(Frag f, const Frag &g, Set *follow)
     {
-        for (uint64_t l = f.last; l != 0; l &= l - 1) follow[__builtin_ctzll(l)] |= g.first;
+        for (Set l = f.last; l != 0; l &= l - 1) follow[bmx_set_low_bit(l)] |= g.first;
         Frag r;
         r.first = f.first | (f.nullable ? g.first : 0);
         r.last = g.last | (g.nullable ? f.last : 0);
@@ -281,10 +293,11 @@ struct Compiler {
         switch (nodes[id].kind) {
         case ASSERT: return true; // (has no element: not reached; the anchored grammar expands with aexpand)
         case ELEM: {
-            if (re.m >= BMX_MAX_REGEX_POSITIONS) return fail("more than 64 positions after expansion");
+            if (re.m >= limit)
+                return fail(limit == BMX_MAX_REGEX_POSITIONS ? "more than 64 positions after expansion" : "more than 128 positions after expansion");
             std::memcpy(re.classes + (size_t)re.m * BMX_CLASS_BYTES, nodes[id].cls, BMX_CLASS_BYTES);
             out.nullable = false;
-            out.first = out.last = 1ull << re.m;
+            out.first = out.last = (Set)1 << re.m;
             ++re.m;
             return true;
         }
@@ -312,14 +325,14 @@ struct Compiler {
                     Frag g;
                     if (!expand(nodes[id].kids[0], g)) return false;
                     if (i == copies - 1) {
-                        for (uint64_t l = g.last; l != 0; l &= l - 1) re.follow[__builtin_ctzll(l)] |= g.first;
+                        for (Set l = g.last; l != 0; l &= l - 1) re.follow[bmx_set_low_bit(l)] |= g.first;
                         if (nodes[id].a == 0) g.nullable = true;
                     }
                     out = cat(out, g, re.follow);
                 }
                 return true;
             }
-            for (int i = 0; i < nodes[id].b; ++i) { // (every copy makes a position, so 65 copies at the most)
+            for (int i = 0; i < nodes[id].b; ++i) { // (every copy makes a position, so limit + 1 copies at the most)
                 Frag g;
                 if (!expand(nodes[id].kids[0], g)) return false;
                 if (i >= nodes[id].a) g.nullable = true;
@@ -504,10 +517,12 @@ const char *resolve(const Compiler &c, const AFrag &f, uint32_t flags, bmx_regex
 
 namespace {
 
-int compile(const char *where, bool star, const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+// The plain grammar (star: with * + {a,}) up to `limit` positions: c.re and f on BMX_OK, else the error text is set.
+int compile(const char *where, bool star, int limit, const char *expr, uint64_t expr_len, uint32_t flags, bool have_out, Compiler &c,
+            Frag &f)
 {
     char text[160];
-    if (!expr || !out) {
+    if (!expr || !have_out) {
         snprintf(text, sizeof text, "%s: a NULL argument", where);
         bmx_internal_set_error(text);
         return BMX_ERR_ARG;
@@ -517,14 +532,14 @@ int compile(const char *where, bool star, const char *expr, uint64_t expr_len, u
         bmx_internal_set_error(text);
         return BMX_ERR_ARG;
     }
-    Compiler c;
     c.e = reinterpret_cast<const uint8_t *>(expr);
     c.len = expr_len;
     c.flags = flags;
     c.star = star;
+    c.limit = limit;
     std::memset(&c.re, 0, sizeof c.re);
     int root = 0;
-    Frag f = {true, 0, 0};
+    f = {true, 0, 0};
     bool ok = c.parse_alt(0, root);
     if (ok && c.at < c.len) ok = c.fail("an unbalanced )");
     if (ok) ok = c.expand(root, f);
@@ -535,11 +550,26 @@ int compile(const char *where, bool star, const char *expr, uint64_t expr_len, u
         bmx_internal_set_error(text);
         return BMX_ERR_ARG;
     }
-    c.re.first = f.first;
-    c.re.last = f.last;
-    if (star) bmx_regex_star_lengths(c.re.m, c.re.first, c.re.last, c.re.follow, &c.re.min_len, &c.re.max_len, nullptr);
-    else bmx_regex_lengths(c.re.m, c.re.first, c.re.last, c.re.follow, &c.re.min_len, &c.re.max_len);
-    *out = c.re;
+    return BMX_OK;
+}
+
+// ... into struct bmx_regex (at most 64 positions: the low word of every set is the whole set)
+int compile(const char *where, bool star, const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+{
+    Compiler c;
+    Frag f;
+    const int rc = compile(where, star, BMX_MAX_REGEX_POSITIONS, expr, expr_len, flags, out != nullptr, c, f);
+    if (rc != BMX_OK) return rc;
+    bmx_regex re;
+    std::memset(&re, 0, sizeof re);
+    re.m = c.re.m;
+    re.first = (uint64_t)f.first;
+    re.last = (uint64_t)f.last;
+    for (int32_t i = 0; i < re.m; ++i) re.follow[i] = (uint64_t)c.re.follow[i];
+    std::memcpy(re.classes, c.re.classes, sizeof re.classes);
+    if (star) bmx_regex_star_lengths(re.m, re.first, re.last, re.follow, &re.min_len, &re.max_len, nullptr);
+    else bmx_regex_lengths(re.m, re.first, re.last, re.follow, &re.min_len, &re.max_len);
+    *out = re;
     return BMX_OK;
 }
 
@@ -587,4 +617,42 @@ extern "C" int bmx_compile_regex_anchored(const char *expr, uint64_t expr_len, u
 extern "C" int bmx_compile_regex_star(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
 {
     return compile("bmx_compile_regex_star", true, expr, expr_len, flags, out);
+}
+
+// The star-free grammar up to 128 positions, into the struct with two-word sets.
+extern "C" int bmx_compile_regex_long(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex_long *out)
+{
+    Compiler c;
+    Frag f;
+    const int rc = compile("bmx_compile_regex_long", false, BMX_MAX_REGEX_LONG_POSITIONS, expr, expr_len, flags, out != nullptr, c, f);
+    if (rc != BMX_OK) return rc;
+    bmx_regex_long re;
+    std::memset(&re, 0, sizeof re);
+    re.m = c.re.m;
+    bmx_set128_store(f.first, re.first);
+    bmx_set128_store(f.last, re.last);
+    for (int32_t i = 0; i < re.m; ++i) bmx_set128_store(c.re.follow[i], re.follow[i]);
+    std::memcpy(re.classes, c.re.classes, sizeof re.classes);
+    bmx_regex_lengths_t<Set>(re.m, f.first, f.last, c.re.follow, &re.min_len, &re.max_len);
+    *out = re;
+    return BMX_OK;
+}
+
+// The automaton of a struct bmx_regex in the wide struct: the low words are its sets, the high words are empty.
+extern "C" int bmx_regex_long_widen(const bmx_regex *in, bmx_regex_long *out)
+{
+    if (!in || !out || !bmx_regex_sets_ok(in->m, in->first, in->last, in->follow)) {
+        bmx_internal_set_error("bmx_regex_long_widen: a NULL argument or an automaton that is not valid");
+        return BMX_ERR_ARG;
+    }
+    bmx_regex_long re;
+    std::memset(&re, 0, sizeof re);
+    re.m = in->m;
+    re.first[0] = in->first;
+    re.last[0] = in->last;
+    for (int32_t i = 0; i < in->m; ++i) re.follow[i][0] = in->follow[i];
+    std::memcpy(re.classes, in->classes, sizeof in->classes);
+    bmx_regex_lengths(in->m, in->first, in->last, in->follow, &re.min_len, &re.max_len);
+    *out = re;
+    return BMX_OK;
 }

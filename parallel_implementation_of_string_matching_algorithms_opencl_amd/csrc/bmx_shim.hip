@@ -109,6 +109,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_hamming_free(ctx->hamming);
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_regex_free(ctx->regex);
+    bmx_internal_regex_long_free(ctx->regex_long);
     bmx_internal_regex_begins_free(ctx->regex_begins);
     bmx_internal_regex_anchored_free(ctx->regex_anchored);
     bmx_internal_regex_anchored_begins_free(ctx->regex_anchored_begins);
@@ -430,6 +431,29 @@ int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64
     HIPCHK(hipSetDevice(ctx->device));
     return bmx_internal_regex_starts(&ctx->regex, d_text, n, base_offset, re, d_ends, count, 0, flags, d_starts, nullptr,
                                      (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+// ... for automata of up to 128 positions (bmx_regex_long.hip; bmx_compile_regex_long is bmx_regex_compile.cpp)
+int bmx_search_regex_long_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
+                                 const bmx_regex_long *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream_v)
+{
+    if (!bmx_regex_long_args_ok(n, lead, re, d_ends, capacity) || !ctx || (n > 0 && !d_text)) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_long(&ctx->regex_long, ctx->num_cu, d_text, n, lead, base_offset, re, d_ends, capacity, n_matches,
+                                   (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_long_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_long_ms(ctx->regex_long) : -1.0f; }
+
+int bmx_regex_long_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex_long *re,
+                                 const uint64_t *d_ends, uint64_t count, uint32_t flags, uint64_t *d_starts, void *stream_v)
+{
+    if (!bmx_regex_long_starts_args_ok(n, re, d_ends, count, flags, d_starts)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (an end needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_long_starts(&ctx->regex_long, d_text, n, base_offset, re, d_ends, count, flags, d_starts,
+                                          (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
 // ... the mirror image: every start, and the end of every start of a list
@@ -865,14 +889,14 @@ int bmx_exp_set_knob(bmx_ctx *ctx, const char *name, int value)
     else if (k == "regex_star_begins_warm" && value >= 0 && value <= 65536 && value % 16 == 0) ctx->regex_star_begins_knobs.warm = value;
     else if (k == "regex_star_ends_no_early_exit") ctx->regex_star_ends_no_early_exit = value != 0;
     else if (k == "ordered_seq" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_long, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_seq(session, (uint64_t)value);
     } else if (k == "tile_piece_shift" && (value == 0 || (value >= 6 && value <= 12))) {
         // the dictionary's tile is 2^(value - 6) rounds of 8 KiB and at most 256 KiB: a context with a dictionary session
         // takes no 12
         if ((uint32_t)value > bmx::ORDERED_DICT_MAX_PIECE_SHIFT && ctx->dict) return BMX_ERR_ARG;
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_long, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_piece_shift(session, (uint32_t)value);
     } else if (k == "tile_max_grid" && value >= 0) {
-        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
+        for (void *session : {ctx->approx, ctx->approx_long, ctx->classes, ctx->hamming, ctx->gaps, ctx->regex, ctx->regex_long, ctx->regex_begins, ctx->regex_anchored, ctx->regex_anchored_begins, ctx->regex_star, ctx->regex_star_begins, ctx->dict}) bmx::ordered_set_max_grid(session, (uint32_t)value);
     } else return BMX_ERR_ARG;
     return BMX_OK;
 }
@@ -889,6 +913,7 @@ int bmx_exp_last_launch(bmx_ctx *ctx, const char *session, uint64_t *out3)
     else if (k == "hamming") state = ctx->hamming;
     else if (k == "gaps") state = ctx->gaps;
     else if (k == "regex") state = ctx->regex;
+    else if (k == "regex_long") state = ctx->regex_long;
     else if (k == "regex_begins") state = ctx->regex_begins;
     else if (k == "regex_anchored") state = ctx->regex_anchored;
     else if (k == "regex_anchored_begins") state = ctx->regex_anchored_begins;

@@ -46,6 +46,7 @@ MAX_GAPS_PATTERN = 64
 GAPS_PROSITE = 4  # a flag of compile_gaps, beside CLASS_ICASE and CLASS_IUPAC
 GAPS_LONGEST = 1  # a flag of gaps_starts_device
 MAX_REGEX_POSITIONS = 64
+MAX_REGEX_LONG_POSITIONS = 128  # compile_regex_long, search_regex_long*
 REGEX_LONGEST = 1  # a flag of regex_starts_device
 REGEX_WORD = 4  # flags of compile_regex_anchored: grep -w ...
 REGEX_LINE = 8  # ... and grep -x
@@ -196,6 +197,16 @@ SYMBOLS = [
     ("bmx_regex_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.c_uint32, C.c_void_p, C.c_void_p]),
     ("bmx_regex_reverse", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("bmx_compile_regex_long", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("bmx_regex_long_widen", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_long_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_uint64, _u64p, C.c_void_p]),
+    ("bmx_search_regex_long", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_search_regex_long_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_uint64, _u64p]),
+    ("bmx_last_regex_long_ms", C.c_float, [C.c_void_p]),
+    ("bmx_regex_long_starts_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_uint32, C.c_void_p, C.c_void_p]),
     ("bmx_search_regex_begins_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                                  C.c_uint64, _u64p, C.c_void_p]),
     ("bmx_last_regex_begins_ms", C.c_float, [C.c_void_p]),
@@ -573,6 +584,56 @@ def reverse_regex(expr_or_regex, flags: int = 0) -> Regex:
     out = Regex()
     _check(lib().bmx_regex_reverse(C.byref(re_), C.byref(out)), "bmx_regex_reverse")
     return out
+
+
+class RegexLong(C.Structure):
+    """struct bmx_regex_long (include/bmx.h): the position automaton of a star-free regular expression of up to 128
+    positions, plain data.  A set is two words, position i bit (i & 63) of word (i >> 6); ``first_set`` / ``last_set`` /
+    ``follow_set(i)`` give one as a Python int."""
+    _fields_ = [("m", C.c_int32), ("min_len", C.c_int32), ("max_len", C.c_int32), ("pad", C.c_int32), ("first", C.c_uint64 * 2),
+                ("last", C.c_uint64 * 2), ("follow", (C.c_uint64 * 2) * MAX_REGEX_LONG_POSITIONS),
+                ("classes", C.c_uint8 * (MAX_REGEX_LONG_POSITIONS * CLASS_BYTES))]
+
+    @property
+    def first_set(self) -> int:
+        return int(self.first[0]) | int(self.first[1]) << 64
+
+    @property
+    def last_set(self) -> int:
+        return int(self.last[0]) | int(self.last[1]) << 64
+
+    def follow_set(self, i: int) -> int:
+        return int(self.follow[i][0]) | int(self.follow[i][1]) << 64
+
+    def class_array(self) -> np.ndarray:
+        """The classes of the m positions, uint8 [m, 32]."""
+        return np.frombuffer(bytes(self.classes), dtype=np.uint8).reshape(MAX_REGEX_LONG_POSITIONS, CLASS_BYTES)[: self.m].copy()
+
+
+def compile_regex_long(expr, flags: int = 0) -> RegexLong:
+    """A star-free regular expression of up to 128 positions (bmx_compile_regex_long: compile_regex's grammar, flags and
+    errors) -> its position automaton."""
+    e = _pat_bytes(expr)
+    out = RegexLong()
+    _check(lib().bmx_compile_regex_long(e, len(e), int(flags), C.byref(out)), "bmx_compile_regex_long")
+    return out
+
+
+def widen_regex(expr_or_regex, flags: int = 0) -> RegexLong:
+    """The automaton of a Regex (or of compile_regex(expr, flags)) in the wide structure (bmx_regex_long_widen)."""
+    re_ = _regex(expr_or_regex, flags)
+    out = RegexLong()
+    _check(lib().bmx_regex_long_widen(C.byref(re_), C.byref(out)), "bmx_regex_long_widen")
+    return out
+
+
+def _regex_long(expr_or_regex, flags: int = 0) -> RegexLong:
+    """A RegexLong from an expression (str / bytes) or such a structure, passed through."""
+    if isinstance(expr_or_regex, (str, bytes, bytearray)):
+        return compile_regex_long(expr_or_regex, flags)
+    if not isinstance(expr_or_regex, RegexLong):
+        raise ValueError("expr_or_regex: an expression or a RegexLong")
+    return expr_or_regex
 
 
 class RegexAnchors(C.Structure):
@@ -1345,6 +1406,86 @@ class Context:
 
     def last_regex_ms(self) -> float:
         return float(self._L.bmx_last_regex_ms(self._h))
+
+    # -- ... for expressions of up to 128 positions -------
+    def search_regex_long_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
+                                 base_offset: int = 0, out=None, capacity: Optional[int] = None, stream=None):
+        """search_regex_device for an expression of up to 128 positions (bmx_search_regex_long_device).
+        ``expr_or_regex``: an expression for compile_regex_long(expr, flags) or a RegexLong.  The other arguments and the
+        return value (ends view, true total) are those of search_regex_device."""
+        import torch
+
+        re_ = _regex_long(expr_or_regex, flags)
+        if n is None:
+            n = d_text.numel()
+        if out is None:
+            out = torch.empty(max(capacity if capacity is not None else 1 << 16, 1), dtype=torch.int64, device=d_text.device)
+        cap = out.numel() if capacity is None else min(capacity, out.numel())
+        s = stream if stream is not None else torch.cuda.current_stream(d_text.device)
+        total = C.c_uint64(0)
+        rc = self._L.bmx_search_regex_long_device(self._h, C.c_void_p(d_text.data_ptr()), n, lead, base_offset, C.byref(re_),
+                                                  C.c_void_p(out.data_ptr()), cap, C.byref(total), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_search_regex_long_device", allow=(ERR_CAPACITY,))
+        return out[: min(int(total.value), cap)], int(total.value)
+
+    def search_regex_long(self, text, expr_or_regex, flags: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """Host buffers (bmx_search_regex_long): ascending ends, uint64; ``capacity`` as in search_regex."""
+        re_ = _regex_long(expr_or_regex, flags)
+        tptr, n, keep = _host_text(text)
+        cap = capacity if capacity is not None else max(1, min(n, 1 << 20))
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_long(self._h, tptr, n, C.byref(re_), C.c_void_p(out.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_long")
+            del keep
+            return out[: int(total.value)].copy()
+
+    def search_regex_long_spans(self, text, expr_or_regex, flags: int = 0, longest: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers (bmx_search_regex_long_spans): (starts uint64, ends uint64) of every match, as search_regex_spans."""
+        re_ = _regex_long(expr_or_regex, flags)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_long_spans(self._h, tptr, n, C.byref(re_), REGEX_LONGEST if longest else 0,
+                                                     C.c_void_p(starts.ctypes.data), C.c_void_p(ends.ctypes.data), cap,
+                                                     C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_long_spans")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy()
+
+    def regex_long_starts_device(self, d_text, expr_or_regex, ends, *, longest: bool = False, flags: int = 0,
+                                 n: Optional[int] = None, base_offset: int = 0, stream=None):
+        """regex_starts_device for an expression of up to 128 positions (bmx_regex_long_starts_device): a start for every
+        end of ``ends`` as search_regex_long_device returns it.  Returns the starts, a tensor like ``ends``."""
+        import torch
+
+        re_ = _regex_long(expr_or_regex, flags)
+        count = ends.numel()
+        if n is None:
+            n = d_text.numel()
+        if ends.element_size() != 8:
+            raise ValueError("ends: 8-byte entries")
+        starts = torch.empty(max(count, 1), dtype=ends.dtype, device=ends.device)
+        s = stream if stream is not None else torch.cuda.current_stream(ends.device)
+        rc = self._L.bmx_regex_long_starts_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_),
+                                                  C.c_void_p(ends.data_ptr()), count, REGEX_LONGEST if longest else 0,
+                                                  C.c_void_p(starts.data_ptr()), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_long_starts_device")
+        return starts[:count]
+
+    def last_regex_long_ms(self) -> float:
+        return float(self._L.bmx_last_regex_long_ms(self._h))
 
     # -- ... its mirror image: every match start, and the end of every start (leftmost-longest) -------
     def search_regex_begins_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, tail: int = 0,
@@ -2162,7 +2303,7 @@ class Context:
                     flags: int = 0, k: int = 0, window: Optional[int] = None):
         """The rows of the resident text ``d_text`` that hold a match of ``expr``, ascending, and each one's number of
         matches: (rows, counts) as int64 CUDA tensors (grep -n / -c); with ``invert`` the rows that hold none and None
-        (grep -v).  ``kind``: exact | classes | hamming | gaps | regex | regex_star | approx, the search that reads ``expr``
+        (grep -v).  ``kind``: exact | classes | hamming | gaps | regex | regex_long | regex_star | approx, the search that reads ``expr``
         (``flags`` are its compile flags, ``k`` the mismatches or edits of hamming and approx).  ``rows``: a Rows in the
         view's coordinates (base_offset 0), or None for the lines of the text split at ``delim``.  Runs the existing search,
         for the kinds that report ends the existing starts post-pass with its default flags (the largest start of an
@@ -2207,6 +2348,10 @@ class Context:
             re_ = _regex(expr, flags)
             ends, _ = complete(lambda out: self.search_regex_device(d_text, re_, out=out))
             return self.regex_starts_device(d_text, re_, ends, longest=longest), ends, 0
+        if kind == "regex_long":
+            re_ = _regex_long(expr, flags)
+            ends, _ = complete(lambda out: self.search_regex_long_device(d_text, re_, out=out))
+            return self.regex_long_starts_device(d_text, re_, ends, longest=longest), ends, 0
         if kind == "regex_anchored":  # (the text is whole: outside it counts as a line break)
             pair = _regex_anchored(expr, flags)
             ends, _ = complete(lambda out: self.search_regex_anchored_device(d_text, pair, out=out))
@@ -2219,7 +2364,7 @@ class Context:
         if kind == "approx":
             ends, dist, _ = complete(lambda out: self.search_approx_device(d_text, expr, k, out=out))
             return self.approx_spans_device(d_text, expr, k, ends, dist)[0], ends, 0
-        raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_anchored | regex_star | approx")
+        raise ValueError("kind: exact | classes | hamming | gaps | regex | regex_long | regex_anchored | regex_star | approx")
 
     def last_rows_ms(self) -> float:
         return float(self._L.bmx_last_rows_ms(self._h))
@@ -2940,6 +3085,12 @@ def search_regex(text, expr, flags: int = 0, spans: bool = False, longest: bool 
     (starts, ends), each start the largest one for its end (the shortest match) or with ``longest`` the smallest."""
     ctx = default_context()
     return ctx.search_regex_spans(text, expr, flags, longest) if spans else ctx.search_regex(text, expr, flags)
+
+
+def search_regex_long(text, expr, flags: int = 0, spans: bool = False, longest: bool = False):
+    """search_regex for a star-free expression of up to 128 positions (bmx_search_regex_long, bmx_search_regex_long_spans)."""
+    ctx = default_context()
+    return ctx.search_regex_long_spans(text, expr, flags, longest) if spans else ctx.search_regex_long(text, expr, flags)
 
 
 def search_regex_anchored(text, expr, flags: int = 0, spans: bool = False, longest: bool = False, begins: bool = False):
