@@ -615,7 +615,8 @@ typedef struct bmx_regex {
  * An element is exactly one element of bmx_compile_classes (. [...] [^...] \xHH \c, any other byte; BMX_CLASS_ICASE and
  * BMX_CLASS_IUPAC as there, and no other flag), so \( \) \| \? \{ \* \+ are literals and inside a set these bytes are
  * literals anyway.  X{a,b} expands to a copies of X followed by b - a optional copies, for a group as for an element;
- * first, last, follow and nullability come from the standard Glushkov recursion.  Groups do not capture.
+ * first, last, follow and nullability come from the standard Glushkov recursion.  Groups do not capture here; bmx_compile_regex_groups at the end of this file makes
+ * the same automaton and the capture model beside it.
  * BMX_ERR_ARG, with *out untouched and a text in bmx_last_error: NULL arguments; an unknown flag bit; an unescaped * or +,
  * or {a,} (unbounded repetition is out of scope); unbalanced ( or ); a quantifier with nothing in front of it or right
  * after another quantifier (so (?: is an error); b == 0, a > b, a malformed or unterminated {...}; nesting deeper than 32;
@@ -634,8 +635,8 @@ int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_r
  * lead > n, n too large) return BMX_ERR_ARG before any HIP call, with ctx = NULL too.  A workgroup that waits longer
  * than its bound (~1 s) for its predecessors' counts makes the call return BMX_ERR_HIP: a list is never returned partly
  * ordered.  One kernel launch on `stream` (NULL = the null stream); the call returns after synchronising that stream.
- * Out of scope: unbounded repetition (* + {a,}; bmx_search_regex_star_device below), back-references, capture groups, more
- * than 64 positions (up to 128: bmx_compile_regex_long and bmx_search_regex_long_device at the end of this file).  Anchors
+ * Out of scope: unbounded repetition (* + {a,}; bmx_search_regex_star_device below), back-references inside the
+ * expression (capture groups: bmx_regex_groups_device at the end of this file), more than 64 positions (up to 128: bmx_compile_regex_long and bmx_search_regex_long_device at the end of this file).  Anchors
  * and word boundaries: bmx_compile_regex_anchored and bmx_search_regex_anchored_device below. */
 int bmx_search_regex_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,
                             const bmx_regex *re, uint64_t *d_ends, uint64_t capacity, uint64_t *n_matches, void *stream);
@@ -1213,7 +1214,7 @@ int bmx_rows_matching(bmx_ctx *ctx /* NULL: device 0 */, const uint64_t *row, ui
  *
  * bmx_replace_device.  d_starts / d_ends / len: `count` ascending, pairwise disjoint spans inside
  * [base_offset, base_offset + n) (a selection's output is one).  d_out receives the n bytes at d_text with every span's
- * bytes replaced by the repl_len bytes at `repl` (host memory, 0 <= repl_len <= BMX_MAX_REPLACEMENT, no back-references):
+ * bytes replaced by the repl_len bytes at `repl` (host memory, 0 <= repl_len <= BMX_MAX_REPLACEMENT, a literal; with group references: bmx_expand_device):
  * n' = n - sum(span lengths) + count * repl_len bytes.  Spans that are not ascending and disjoint, or that reach outside
  * the view, raise a status word: BMX_ERR_ARG.  d_out must not overlap d_text (BMX_ERR_ARG).
  * bmx_extract_device.  The same spans; d_blob receives their bytes one after the other and d_off the count + 1 offsets into
@@ -1518,6 +1519,120 @@ int bmx_regex_long_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, u
 /* Host buffers in, host buffers out: upload, bmx_search_regex_long_device, bmx_regex_long_starts_device, download. */
 int bmx_search_regex_long_spans(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex_long *re,
                                 uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t capacity, uint64_t *n_matches);
+
+/* ---- regex capture groups: the group spans of every match, templates in the replacement ---- */
+
+/* \3.\2.\1 on ([0-9]{4})-([0-9]{2})-([0-9]{2}), the code of (ERROR|FATAL): ([0-9]{2,4}) as a column, sed 's/\(..\)\(..\)/\2\1/g':
+ * a post-pass over a device-resident span list, one entry per lane (csrc/bmx_regex_groups_kernel.h), and a
+ * template where bmx_replace_device takes a literal.  For the STAR-FREE 64-position expressions; struct bmx_regex and every
+ * entry above are unchanged.  The reference has no such program.
+ *
+ * The model is plain data beside an unchanged bmx_regex.  It is what Python's `re` (bytes, DOTALL) returns as
+ * fullmatch(text, s, e + 1).regs.  For a span text[s..e], L = e - s + 1, that matches by bmx_regex's definition:
+ *   - the PREFERRED PATH i_0 .. i_{L-1} takes at every step t the first q in pref[previous] (the row of i_0 is
+ *     BMX_REGEX_START) such that text[s + t] is in the class of q and from q the rest of the span can still be consumed,
+ *     ending in `last` exactly at e;
+ *   - all groups begin unset; at every boundary t = 0..L the transition from the previous position (or START) to i_t (or
+ *     BMX_REGEX_END) fires its tags: the bits of open[from][to] set begin[g] = s + t, those of close[from][to] set
+ *     end[g] = s + t.  The last writer wins and nothing is reset between the copies of a repeat, so ((a)|b){2} on "ab"
+ *     keeps group 2 = "a", as Python does;
+ *   - group spans are HALF-OPEN [begin, end), because a group can be empty (unlike the library's inclusive match ends);
+ *     group 0 is [s, e + 1).
+ * Valid (bmx_regex_groups_valid): re is valid; 0 <= n_groups <= 16; every row p < m of pref lists exactly the positions of
+ * follow[p], each once, and row BMX_REGEX_START those of `first`, the rest of the row 0xFF; tag bits lie below n_groups
+ * and stand only on pairs (p, q) with q in follow[p], (START, q) with q in first and (p, END) with p in last. */
+#define BMX_MAX_REGEX_GROUPS 16
+#define BMX_REGEX_START 64   /* row: before the first byte of the match */
+#define BMX_REGEX_END   64   /* column: after its last byte             */
+typedef struct bmx_regex_groups {
+    int32_t  n_groups;        /* 0..16, numbered from 1 by their '(' left to right */
+    uint8_t  pref[65][64];    /* row p (row 64: START): the positions of follow[p] (row 64: of first), most preferred
+                                 first, the rest of the row 0xFF */
+    uint16_t open[65][65];    /* [from][to], bit g-1: group g begins at the boundary between `from` and `to` */
+    uint16_t close[65][65];   /*                      group g ends there */
+} bmx_regex_groups;
+/* Pure host code, no GPU.  bmx_compile_regex's grammar with two changes: ( ... ) captures and (?: ... ) groups without
+ * capturing ((?: stays an error in every other compile entry).  *re equals, byte for byte, what bmx_compile_regex gives for
+ * the same expression with every (?: written as (, so every search, starts, begins and ends entry works on it unchanged.
+ * The preference order and the tags come from the expression tree alone: counted repeats expand to a copies and b - a
+ * optional ones (all copies of a group share its bit); the epsilon moves are walked depth first in the order a
+ * backtracking matcher tries them (an alternation left to right, an optional copy before its skip), and the first epsilon
+ * path that reaches a consuming position, or END, gives that pair's rank and tags.  This is NOT the ascending position
+ * index: (a?|[bc])([bc]?)c on "bc" gives ((0,2),(0,0),(0,1)).
+ * BMX_ERR_ARG, outputs untouched, a text in bmx_last_error that begins "bmx_compile_regex_groups: ": every error of
+ * bmx_compile_regex; (? followed by anything but :; more than BMX_MAX_REGEX_GROUPS capturing groups; a repeat with b >= 2
+ * whose body can match the empty string and contains, or is, a capturing group ((a?){2}, ((a)|b?){1,3}, (){3}): engines
+ * disagree on such captures, so they are exact or refused, never approximated.  (a?)?, ((a?)b){2} and (a|b?)c are fine.
+ * Out of scope: back-references inside the expression; captures for the star, anchored and 128-position families; lazy
+ * quantifiers; named groups. */
+int bmx_compile_regex_groups(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *re, bmx_regex_groups *gr);
+/* 1 iff re and gr are valid by the rules above (NULL: 0).  Pure host code; the device entries below call it. */
+int bmx_regex_groups_valid(const bmx_regex *re, const bmx_regex_groups *gr);
+/* The groups of every span of a device-resident list: entry i is text[d_starts[i] - base_offset .. d_ends[i] - base_offset]
+ * (both inclusive, as bmx_regex_starts_device pairs them) and gets the (begin, end) pairs of groups 0..n_groups at
+ * d_groups[(i * (n_groups + 1) + g) * 2], each plus base_offset; an unset group gets UINT64_MAX twice.  One list entry per
+ * lane: a backward sweep over the span (the reversed-automaton recurrence of bmx_regex_starts_device) leaves for every
+ * byte the positions that consume it and can still reach `last` at e, a column of at most max_len <= 64 words per lane in
+ * LDS; one forward walk then takes the first entry of pref[cur] in the column's word and applies the two tag words.
+ * An entry whose start or end is UINT64_MAX, or whose end is below its start, is SKIPPED: all its outputs are UINT64_MAX
+ * and it is no error (the ends passes produce such entries).  An entry outside [base_offset, base_offset + n), longer than
+ * max_len, or whose span is not a match raises a status word: BMX_ERR_ARG, outputs unspecified.
+ * Errors, count == 0, the bytes read (none outside the aligned 16-byte lines of text[0..n)) and the stream rule as for
+ * bmx_regex_starts_device; a struct that is not valid is BMX_ERR_ARG before any HIP call.  The tables travel through a
+ * device block of the context, copied on `stream` in front of the launch. */
+int bmx_regex_groups_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                            const bmx_regex_groups *gr, const uint64_t *d_starts, const uint64_t *d_ends, uint64_t count,
+                            uint64_t *d_groups /* count * (n_groups + 1) * 2 */, void *stream);
+/* Host buffers in, host buffers out: upload, bmx_search_regex_device, bmx_regex_starts_device (flags: BMX_REGEX_LONGEST or
+ * 0), bmx_regex_groups_device, download.  starts[i], ends[i] and groups[i * (n_groups + 1) * 2 ..] belong together;
+ * capacity (entries) and *n_matches as for bmx_search_regex_spans.  ctx may be NULL. */
+int bmx_search_regex_groups(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const bmx_regex *re,
+                            const bmx_regex_groups *gr, uint32_t flags, uint64_t *starts, uint64_t *ends, uint64_t *groups,
+                            uint64_t capacity, uint64_t *n_matches);
+/* Device time (ms, HIP events around the kernel) of the last bmx_regex_groups_device on ctx; < 0 if none. */
+float bmx_last_regex_groups_ms(bmx_ctx *ctx);
+
+/* A replacement template, parsed: literal bytes, \1..\9, \g<0>..\g<16> and \\ (one backslash) -- the subset on which
+ * Python's `re` template syntax agrees byte for byte (\0 is a NUL there, hence \g<0>).  T = n_refs references cut the
+ * template into T + 1 literals: literal r stands in front of reference r, literal T behind the last one; any of them may
+ * be empty.  Their bytes go, unescaped and one after the other, to `lits` (room for `len` bytes; may be NULL when len is 0).
+ * BMX_ERR_ARG, outputs untouched, a text in bmx_last_error: NULL where a pointer is needed; anything else behind a
+ * backslash (a dangling one, \0, \n, \g without <digits>); a reference above n_groups; more than BMX_MAX_TEMPLATE_REFS
+ * references; len > BMX_MAX_REPLACEMENT; n_groups outside 0..BMX_MAX_REGEX_GROUPS.  Pure host code. */
+#define BMX_MAX_TEMPLATE_REFS 32
+typedef struct bmx_template {
+    int32_t  n_refs;                               /* T: 0..32 */
+    int32_t  ref[BMX_MAX_TEMPLATE_REFS];           /* the group of reference r, 0..n_groups */
+    uint32_t lit_off[BMX_MAX_TEMPLATE_REFS + 1];   /* literal r: lits[lit_off[r] .. lit_off[r] + lit_len[r]) */
+    uint32_t lit_len[BMX_MAX_TEMPLATE_REFS + 1];
+    uint32_t lit_bytes;                            /* all literals together */
+} bmx_template;
+int bmx_compile_template(const void *tmpl, uint64_t len, int32_t n_groups, bmx_template *out, void *lits);
+/* bmx_replace_device / bmx_extract_device with a template.  d_groups: what bmx_regex_groups_device wrote for `count`
+ * entries of n_groups + 1 pairs.  The matches are group 0 of every entry: ascending, pairwise disjoint, non-empty, inside
+ * [base_offset, base_offset + n), all set, and every other group unset or inside its entry's group 0; anything else raises
+ * a status word: BMX_ERR_ARG.  An unset group expands to nothing.
+ * flags 0: d_out receives the text with every match replaced by its expansion (re.sub).  BMX_EXPAND_EXTRACT: d_out
+ * receives the expansions one after the other and d_off the count + 1 offsets into them, always all of them
+ * (Match.expand; grep -o | sed; one group of re.findall with the template \1).  d_off is not read without the flag.
+ * Capacity and counting as for bmx_replace_device: the true size goes to *n_out, capacity 0 only counts, a smaller
+ * non-zero capacity stores the lowest `capacity` bytes and returns BMX_ERR_CAPACITY.  BMX_ERR_ARG before any HIP call, with
+ * ctx == NULL too: NULL where a pointer is needed, a bad template, unknown flags, n >= 2^40, count >= 2^32, an output
+ * that overlaps the text.  count == 0: flags 0 copies the text, EXTRACT writes the single offset 0.  Stream rule and the
+ * bytes read as for bmx_replace_device.
+ * Method: the output-driven copy of bmx_replace_device with T + 1 pieces per match; piece r opens with literal r (offset
+ * and length from a table in LDS, indexed by the piece's number modulo T + 1) and goes on with a run of text that may be
+ * empty: group ref[r], or behind literal T the text up to the next match (EXTRACT: nothing).  A template without a
+ * reference gives bmx_replace_device's bytes. */
+#define BMX_EXPAND_EXTRACT 1u
+int bmx_expand_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_groups,
+                      int32_t n_groups, uint64_t count, const void *tmpl /* host */, uint64_t tmpl_len, uint32_t flags,
+                      void *d_out, uint64_t capacity /* bytes */, uint64_t *d_off /* EXTRACT: count + 1 */, uint64_t *n_out,
+                      void *stream);
+/* Host buffers in, host buffers out, base_offset 0: upload, bmx_expand_device, download. */
+int bmx_expand(bmx_ctx *ctx /* NULL: device 0 */, const char *text, uint64_t n, const uint64_t *groups, int32_t n_groups,
+               uint64_t count, const void *tmpl, uint64_t tmpl_len, uint32_t flags, void *out, uint64_t capacity,
+               uint64_t *off /* EXTRACT: count + 1 */, uint64_t *n_out);
 
 #ifdef __cplusplus
 }

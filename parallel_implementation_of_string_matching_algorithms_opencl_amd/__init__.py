@@ -19,5 +19,7 @@ from .host import (BmxError, CLASS_ICASE, CLASS_IUPAC, Context, Dictionary, GAPS
 from .host import reverse_regex, search_regex_begins, search_regex_star_begins  # noqa: F401
 from .host import MAX_REGEX_LONG_POSITIONS, RegexLong, compile_regex_long, search_regex_long, widen_regex  # noqa: F401
 from .host import REGEX_LINE, REGEX_WORD, RegexAnchors, compile_regex_anchored, search_regex_anchored  # noqa: F401
+from .host import (EXPAND_EXTRACT, MAX_REGEX_GROUPS, MAX_TEMPLATE_REFS, RegexGroups, Template, compile_regex_groups,  # noqa: F401
+                   compile_template, search_regex_groups)
 
 __version__ = "0.1.0"

@@ -352,6 +352,48 @@ int bmx_extract(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint64_t *s
     return subst_copy_host("bmx_extract", ctx_in, text, n, starts, ends, len, count, nullptr, 0, blob, capacity, off, n_out);
 }
 
+// replace and extract with a template over host buffers: the device entry counts first, then fills what fits
+int bmx_expand(bmx_ctx *ctx_in, const char *text, uint64_t n, const uint64_t *groups, int32_t n_groups, uint64_t count, const void *tmpl,
+               uint64_t tmpl_len, uint32_t flags, void *out, uint64_t capacity, uint64_t *off, uint64_t *n_out)
+{
+    if (!bmx_expand_args_ok(text, n, groups, n_groups, count, flags, out, capacity, off, n_out)) return BMX_ERR_ARG;
+    bmx_template t;
+    std::vector<uint8_t> lits(tmpl_len <= BMX_MAX_REPLACEMENT ? (size_t)tmpl_len + 1 : 1);
+    if (bmx_compile_template(tmpl, tmpl_len, n_groups, &t, lits.data()) != BMX_OK) return BMX_ERR_ARG;
+    const bool extract = (flags & BMX_EXPAND_EXTRACT) != 0;
+    *n_out = 0;
+    if (count == 0) { // no match: the text itself, or the single offset 0; no device is touched
+        if (extract) {
+            off[0] = 0;
+            return BMX_OK;
+        }
+        *n_out = n;
+        if (capacity) memcpy(out, text, std::min(n, capacity));
+        return capacity && n > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+    }
+    HostCall c("bmx_expand", ctx_in);
+    const uint64_t words = count * ((uint64_t)n_groups + 1) * 2;
+    void *d_text = n ? c.upload(text, n) : nullptr;
+    const uint64_t *d_groups = c.upload<uint64_t>(groups, words * sizeof(uint64_t));
+    uint64_t *d_off = extract ? c.alloc<uint64_t>((count + 1) * sizeof(uint64_t)) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    uint64_t total = 0;
+    c.rc = bmx_expand_device(c.ctx(), d_text, n, 0, d_groups, n_groups, count, tmpl, tmpl_len, flags, nullptr, 0, d_off, &total, nullptr);
+    if (c.rc != BMX_OK) return c.rc;
+    const uint64_t dev_cap = std::min(capacity, total);
+    if (dev_cap) {
+        void *d_out = c.alloc(dev_cap);
+        if (c.rc != BMX_OK) return c.rc;
+        c.rc = bmx_expand_device(c.ctx(), d_text, n, 0, d_groups, n_groups, count, tmpl, tmpl_len, flags, d_out, dev_cap, d_off, &total, nullptr);
+        if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+        c.download(out, d_out, dev_cap, "the output");
+    }
+    if (extract) c.download(off, d_off, (count + 1) * sizeof(uint64_t), "the offsets");
+    *n_out = total;
+    if (c.rc == BMX_OK && capacity && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
 int bmx_lcp_array(bmx_ctx *ctx_in, const char *text, uint64_t n, int32_t *sa_out, int32_t *lcp_out)
 {
     if (!bmx_lcp_args_ok(text, n, lcp_out)) return BMX_ERR_ARG;
@@ -697,6 +739,36 @@ int bmx_search_regex_spans(bmx_ctx *ctx_in, const char *text, uint64_t n, const 
     if (src != BMX_OK) return src;
     c.download(ends, d_ends, stored * sizeof(uint64_t), "regex matches");
     c.download(starts, d_starts, stored * sizeof(uint64_t), "regex matches");
+    if (n_matches) *n_matches = total;
+    if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
+    return c.rc;
+}
+
+int bmx_search_regex_groups(bmx_ctx *ctx_in, const char *text, uint64_t n, const bmx_regex *re, const bmx_regex_groups *gr, uint32_t flags,
+                            uint64_t *starts, uint64_t *ends, uint64_t *groups, uint64_t capacity, uint64_t *n_matches)
+{
+    if (!bmx_regex_args_ok(n, 0, re, ends, capacity) || !bmx_regex_groups_valid(re, gr) || (capacity > 0 && (!starts || !groups)) ||
+        (n > 0 && !text) || (flags & ~BMX_REGEX_LONGEST))
+        return BMX_ERR_ARG;
+    if (n_matches) *n_matches = 0;
+    if (n == 0) return BMX_OK;
+    HostCall c("bmx_search_regex_groups", ctx_in);
+    const uint64_t dev_cap = std::min<uint64_t>(capacity, n), per_entry = ((uint64_t)gr->n_groups + 1) * 2 * sizeof(uint64_t);
+    uint64_t total = 0;
+    void *d_text = c.upload(text, n);
+    uint64_t *d_ends = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_starts = dev_cap ? c.alloc<uint64_t>(dev_cap * sizeof(uint64_t)) : nullptr;
+    uint64_t *d_groups = dev_cap ? c.alloc<uint64_t>(dev_cap * per_entry) : nullptr;
+    if (c.rc != BMX_OK) return c.rc;
+    c.rc = bmx_search_regex_device(c.ctx(), d_text, n, 0, 0, re, d_ends, dev_cap, &total, nullptr);
+    if (c.rc != BMX_OK && c.rc != BMX_ERR_CAPACITY) return c.rc;
+    const uint64_t stored = std::min(total, dev_cap);
+    int src = bmx_regex_starts_device(c.ctx(), d_text, n, 0, re, d_ends, stored, flags, d_starts, nullptr);
+    if (src == BMX_OK) src = bmx_regex_groups_device(c.ctx(), d_text, n, 0, re, gr, d_starts, d_ends, stored, d_groups, nullptr);
+    if (src != BMX_OK) return src;
+    c.download(ends, d_ends, stored * sizeof(uint64_t), "regex matches");
+    c.download(starts, d_starts, stored * sizeof(uint64_t), "regex matches");
+    c.download(groups, d_groups, stored * per_entry, "their groups");
     if (n_matches) *n_matches = total;
     if (c.rc == BMX_OK && total > capacity) c.rc = BMX_ERR_CAPACITY;
     return c.rc;

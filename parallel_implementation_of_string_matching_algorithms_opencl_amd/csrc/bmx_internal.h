@@ -124,6 +124,12 @@ int bmx_internal_regex_long_starts(void **state, const void *d_text, uint64_t n,
 void bmx_internal_regex_long_free(void *state);
 float bmx_internal_regex_long_ms(const void *state);
 constexpr uint64_t BMX_REGEX_STARTS_NO_MATCH = 2; // *bad_out: some end had no match (csrc/bmx_regex_kernel.h, REGEX_BAD_START)
+// bmx_regex_groups.hip: the capture groups of every span of a list (a state of its own: status word, the tables' block)
+int bmx_internal_regex_groups(void **state, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                              const bmx_regex_groups *gr, const uint64_t *d_starts, const uint64_t *d_ends, uint64_t count,
+                              uint64_t *d_groups, hipStream_t stream, char *err, size_t errlen);
+void bmx_internal_regex_groups_free(void *state);
+float bmx_internal_regex_groups_ms(const void *state);
 // ... its mirror image: every start (a state of its own; piece_shift: 0, or log2 of the starts per lane -- libbmx_exp.so's
 // knob) and the end of every start of a list (d_limit: NULL, or the last byte each entry may use)
 int bmx_internal_regex_begins(void **state, int num_cu, int piece_shift, const void *d_text, uint64_t n, uint64_t tail,
@@ -280,6 +286,10 @@ int bmx_internal_select(void **state, int tile_shift, const uint64_t *d_starts, 
 int bmx_internal_subst_copy(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_starts,
                             const uint64_t *d_ends, uint64_t len, uint64_t count, const void *repl, uint64_t repl_len, void *d_out,
                             uint64_t capacity, uint64_t *d_off, uint64_t *n_out, hipStream_t stream, char *err, size_t errlen);
+// ... the copy with a template (t, lits: bmx_compile_template's; d_off NULL = replace, else the offsets of the column)
+int bmx_internal_expand(void **state, int num_cu, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_groups,
+                        int32_t n_groups, uint64_t count, const bmx_template *t, const uint8_t *lits, void *d_out, uint64_t capacity,
+                        uint64_t *d_off, uint64_t *n_out, hipStream_t stream, char *err, size_t errlen);
 void bmx_internal_subst_free(void *state);
 float bmx_internal_subst_ms(const void *state);
 void bmx_internal_subst_last(const void *state, uint64_t out3[3]); // libbmx_exp.so only
@@ -304,6 +314,7 @@ struct bmx_ctx {
     void *gaps = nullptr; // gapped pattern search: the same again, and the status word of its starts pass (bmx_gaps.hip)
     void *regex = nullptr; // regular-expression search: the same as the gapped search's, its own (bmx_regex.hip)
     void *regex_long = nullptr; // ... for up to 128 positions: the same and the block of its tables (bmx_regex_long.hip)
+    void *regex_groups = nullptr; // ... its capture groups pass: status word, the block of its tables, events (bmx_regex_groups.hip)
     void *regex_begins = nullptr; // ... its begins search and ends pass: the same again, their own (bmx_regex.hip)
     int regex_begins_piece_shift = 0; // libbmx_exp.so: 0, or log2 of the starts per lane of the begins search (4..12)
     void *regex_anchored = nullptr; // ... anchored: the same and the gate tables (bmx_regex_anchored.hip)
@@ -405,6 +416,27 @@ inline bool bmx_regex_starts_args_ok(uint64_t n, const bmx_regex *re, const uint
 {
     if (!bmx_regex_ok(re) || n >= (1ull << 40) || (flags & ~BMX_REGEX_LONGEST)) return false;
     return count == 0 || (ends && starts);
+}
+
+// ... and their capture groups: a valid pair, the two lists and the output where there is an entry
+inline bool bmx_regex_groups_args_ok(uint64_t n, const bmx_regex *re, const bmx_regex_groups *gr, const uint64_t *starts,
+                                     const uint64_t *ends, uint64_t count, const uint64_t *groups)
+{
+    if (!bmx_regex_groups_valid(re, gr) || n >= (1ull << 40)) return false;
+    return count == 0 || (starts && ends && groups);
+}
+// ... the copy with a template (text and out: host or device; off: the offsets of the column with BMX_EXPAND_EXTRACT)
+inline bool bmx_expand_args_ok(const void *text, uint64_t n, const uint64_t *groups, int32_t n_groups, uint64_t count, uint32_t flags,
+                               const void *out, uint64_t capacity, const uint64_t *off, const uint64_t *n_out)
+{
+    if ((n > 0 && !text) || n >= (1ull << 40) || !n_out || (capacity > 0 && !out) || (flags & ~BMX_EXPAND_EXTRACT)) return false;
+    if (((flags & BMX_EXPAND_EXTRACT) && !off) || n_groups < 0 || n_groups > BMX_MAX_REGEX_GROUPS) return false;
+    if (count >= (1ull << 32) || (count > 0 && !groups)) return false;
+    if (n > 0 && capacity > 0) {
+        const uintptr_t t = reinterpret_cast<uintptr_t>(text), o = reinterpret_cast<uintptr_t>(out);
+        if (t < o + capacity && o < t + n) return false;
+    }
+    return true;
 }
 
 // ... for up to 128 positions: the same rules on struct bmx_regex_long

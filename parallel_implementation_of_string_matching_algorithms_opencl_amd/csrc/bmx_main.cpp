@@ -129,6 +129,14 @@
 //                             bmx_regex_ends_device with a limit), then the same selection.  With --regex-star it needs
 //                             --window N (bmx_search_regex_star_begins_spans, bmx_regex_star_ends_device) and fails, exit
 //                             status 1, if some match may be longer than N bytes: it never prints a shorter one
+//   bmx_cli --regex-groups EXPR (--spans | --replace TEMPLATE | --only-matching [--template T]) [--posix] [--lines] [--out F]
+//                             --regex where ( ... ) captures and (?: ... ) does not (bmx_compile_regex_groups).  --spans: every
+//                             match end with the start of its shortest (--posix: longest) match and the half-open span of
+//                             every group, "-" where unset (bmx_search_regex_groups).  --replace: the selection of --regex
+//                             (--posix, --lines as there), the groups of the matches taken (bmx_regex_groups_device) and the
+//                             text with every match replaced by the expansion of TEMPLATE: literal bytes, \1..\9,
+//                             \g<0>..\g<16>, \\ (bmx_expand: sed 's/\(..\)\(..\)/\2\1/g').  --only-matching: the expansion of
+//                             T (default \g<0>) for every match, one per line
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -136,6 +144,7 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -228,6 +237,8 @@ int main(int argc, char **argv)
     bool have_regex = false, regex_star = false, regex_both = false;
     bool regex_anchored = false; // --regex-anchored EXPR [--word] [--line]
     bool regex_long = false;     // --regex-long EXPR: up to 128 positions
+    bool regex_groups = false, have_template = false; // --regex-groups EXPR: ( captures, (?: does not; --template T with --only-matching
+    std::string template_str = "\\g<0>";
     uint32_t anchor_flags = 0;
     uint32_t star_window = 0;
     bool regex_begins = false, begins_spans = false, begins_longest = false, posix = false; // --begins [--spans [--longest]], --posix
@@ -280,6 +291,8 @@ int main(int argc, char **argv)
         else if (a == "--regex-long") regex_both = have_regex, regex_expr = need("--regex-long"), have_regex = regex_long = true;
         else if (a == "--regex-star") regex_both = have_regex, regex_expr = need("--regex-star"), have_regex = regex_star = true;
         else if (a == "--regex-anchored") regex_both = have_regex, regex_expr = need("--regex-anchored"), have_regex = regex_anchored = true;
+        else if (a == "--regex-groups") regex_both = have_regex, regex_expr = need("--regex-groups"), have_regex = regex_groups = true;
+        else if (a == "--template") have_template = true, template_str = need("--template");
         else if (a == "--word") anchor_flags |= BMX_REGEX_WORD;
         else if (a == "--line") anchor_flags |= BMX_REGEX_LINE;
         else if (a == "--begins") regex_begins = true;
@@ -317,11 +330,22 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (posix && (!have_regex || select_merge || !(have_replace || only_matching))) {
+    const bool groups_spans = regex_groups && spans; // --regex-groups EXPR --spans [--posix]: every match with its groups
+    if (regex_groups && (regex_both || regex_begins || gaps_starts || select_merge || positions || lines_invert ||
+                         (groups_spans ? (have_replace || only_matching || lines_mode) : !(have_replace || only_matching)))) {
+        fprintf(stderr, "--regex-groups EXPR goes with --spans [--posix], or with --replace TEMPLATE or --only-matching [--template T] and "
+                        "[--posix] [--lines] [--out F]\n");
+        return 2;
+    }
+    if (have_template && !(regex_groups && only_matching)) {
+        fprintf(stderr, "--template T goes with --regex-groups EXPR --only-matching\n");
+        return 2;
+    }
+    if (posix && !groups_spans && (!have_regex || select_merge || !(have_replace || only_matching))) {
         fprintf(stderr, "--posix needs --regex EXPR or --regex-star EXPR with --replace STR or --only-matching, without --merge\n");
         return 2;
     }
-    if ((spans && approx_k < 0) || (spans_best && !spans)) {
+    if ((spans && approx_k < 0 && !groups_spans) || (spans_best && !spans)) {
         fprintf(stderr, "--spans needs --approx K, --best needs --spans\n");
         return 2;
     }
@@ -695,6 +719,37 @@ int main(int argc, char **argv)
     // --lines: the rows of the text that hold a match (or, --invert, none): row<TAB>count, 0-based.  --replace STR and
     // --only-matching: the non-overlapping matches (--merge: the regions of their union, from the longest match of every end)
     // replaced by STR, or one per line; with --lines a match that crosses a line break is left alone.
+    // --regex-groups EXPR --spans: every end at which a match ends with the start of its shortest (--posix: longest) match and
+    // the half-open span of every group, "-" for a group that is unset
+    if (groups_spans) {
+        bmx_regex re;
+        std::unique_ptr<bmx_regex_groups> gr(new bmx_regex_groups);
+        if (bmx_compile_regex_groups(regex_expr.data(), regex_expr.size(), class_flags, &re, gr.get()) != BMX_OK) {
+            fprintf(stderr, "bad regular expression %s (%s)\n", regex_expr.c_str(), bmx_last_error());
+            return 1;
+        }
+        const uint64_t room = n ? n : 1, pairs = (uint64_t)gr->n_groups + 1;
+        std::vector<uint64_t> starts(room), ends(room), groups(room * pairs * 2);
+        uint64_t hits = 0;
+        const int rc = bmx_search_regex_groups(nullptr, text.data(), n, &re, gr.get(), posix ? BMX_REGEX_LONGEST : 0u, starts.data(), ends.data(),
+                                               groups.data(), room, &hits);
+        if (rc != BMX_OK) {
+            fprintf(stderr, "bmx_search_regex_groups failed: %d (%s)\n", rc, bmx_last_error());
+            return 1;
+        }
+        for (uint64_t i = 0; i < hits && i < max_print; ++i) {
+            printf("%llu\t%llu", (unsigned long long)starts[i], (unsigned long long)ends[i]);
+            for (uint64_t g = 1; g < pairs; ++g) {
+                const uint64_t b = groups[(i * pairs + g) * 2], e = groups[(i * pairs + g) * 2 + 1];
+                if (b == UINT64_MAX) printf("\t-");
+                else printf("\t%llu,%llu", (unsigned long long)b, (unsigned long long)e);
+            }
+            printf("\n");
+        }
+        printf("matches with groups: %llu (%d groups, %d positions, %d..%d bytes)\n", (unsigned long long)hits, gr->n_groups, re.m, re.min_len,
+               re.max_len);
+        return 0;
+    }
     if (lines_mode || subst_mode) {
         bmx_ctx *ctx = nullptr;
         int rc = bmx_ctx_create(device, &ctx);
@@ -717,11 +772,13 @@ int main(int argc, char **argv)
         std::vector<uint64_t> starts(room), ends(room);
         std::vector<uint8_t> dist(approx_k >= 0 ? room : 1);
         const char *what = "bmx_search";
+        bmx_regex re;
+        std::unique_ptr<bmx_regex_groups> gr(new bmx_regex_groups); // (--regex-groups: beside re)
         if (have_regex) {
-            bmx_regex re;
             bmx_regex_long rl; // (--regex-long: in place of re)
             bmx_regex_anchors an; // (full where the expression has no assertions: read by the anchored entries only)
             if ((regex_anchored ? bmx_compile_regex_anchored(regex_expr.data(), regex_expr.size(), class_flags | anchor_flags, &re, &an)
+                 : regex_groups ? bmx_compile_regex_groups(regex_expr.data(), regex_expr.size(), class_flags, &re, gr.get())
                  : regex_long   ? bmx_compile_regex_long(regex_expr.data(), regex_expr.size(), class_flags, &rl)
                  : regex_star   ? bmx_compile_regex_star(regex_expr.data(), regex_expr.size(), class_flags, &re)
                                 : bmx_compile_regex(regex_expr.data(), regex_expr.size(), class_flags, &re)) != BMX_OK) {
@@ -821,12 +878,47 @@ int main(int argc, char **argv)
                 return 1;
             }
             std::string result(have_replace ? n + taken * replace_str.size() + 1 : n + 1, '\0');
-            rc = have_replace ? bmx_replace(ctx, text.data(), n, sel_s.data(), sel_e.data(), 0, taken, replace_str.data(), replace_str.size(),
-                                            &result[0], result.size(), &n_new)
-                              : bmx_extract(ctx, text.data(), n, sel_s.data(), sel_e.data(), 0, taken, &result[0], result.size(),
-                                            blob_off.data(), &n_new);
+            if (regex_groups) { // the groups of the matches taken, then the copy with the template: counted first, then filled
+                const std::string &tmpl = have_replace ? replace_str : template_str;
+                const uint64_t words = taken * ((uint64_t)gr->n_groups + 1) * 2;
+                std::vector<uint64_t> groups(words ? words : 1);
+                void *d_text = nullptr, *d_s = nullptr, *d_e = nullptr;
+                uint64_t *d_groups = nullptr;
+                what = "bmx_regex_groups_device";
+                if (taken) {
+                    rc = bmx_text_upload(ctx, text.data(), n, &d_text);
+                    if (rc == BMX_OK) rc = bmx_text_upload(ctx, reinterpret_cast<const char *>(sel_s.data()), taken * sizeof(uint64_t), &d_s);
+                    if (rc == BMX_OK) rc = bmx_text_upload(ctx, reinterpret_cast<const char *>(sel_e.data()), taken * sizeof(uint64_t), &d_e);
+                    if (rc == BMX_OK) rc = bmx_device_alloc(ctx, words * sizeof(uint64_t), (void **)&d_groups);
+                    if (rc == BMX_OK)
+                        rc = bmx_regex_groups_device(ctx, d_text, n, 0, &re, gr.get(), static_cast<const uint64_t *>(d_s),
+                                                     static_cast<const uint64_t *>(d_e), taken, d_groups, nullptr);
+                    if (rc == BMX_OK) rc = bmx_device_download(ctx, groups.data(), d_groups, words * sizeof(uint64_t));
+                    bmx_device_free(ctx, d_groups);
+                    bmx_device_free(ctx, d_e);
+                    bmx_device_free(ctx, d_s);
+                    bmx_device_free(ctx, d_text);
+                }
+                const uint32_t flags = have_replace ? 0u : BMX_EXPAND_EXTRACT;
+                if (rc == BMX_OK) {
+                    what = "bmx_expand";
+                    rc = bmx_expand(ctx, text.data(), n, groups.data(), gr->n_groups, taken, tmpl.data(), tmpl.size(), flags, nullptr, 0,
+                                    blob_off.data(), &n_new);
+                }
+                if (rc == BMX_OK) {
+                    result.assign(n_new + 1, '\0');
+                    rc = bmx_expand(ctx, text.data(), n, groups.data(), gr->n_groups, taken, tmpl.data(), tmpl.size(), flags, &result[0],
+                                    result.size(), blob_off.data(), &n_new);
+                }
+            } else {
+                what = have_replace ? "bmx_replace" : "bmx_extract";
+                rc = have_replace ? bmx_replace(ctx, text.data(), n, sel_s.data(), sel_e.data(), 0, taken, replace_str.data(), replace_str.size(),
+                                                &result[0], result.size(), &n_new)
+                                  : bmx_extract(ctx, text.data(), n, sel_s.data(), sel_e.data(), 0, taken, &result[0], result.size(),
+                                                blob_off.data(), &n_new);
+            }
             if (rc != BMX_OK) {
-                fprintf(stderr, "%s failed: %d (%s)\n", have_replace ? "bmx_replace" : "bmx_extract", rc, bmx_last_error());
+                fprintf(stderr, "%s failed: %d (%s)\n", what, rc, bmx_last_error());
                 return 1;
             }
             FILE *dst = out_path.empty() ? stdout : fopen(out_path.c_str(), "wb");

@@ -126,12 +126,13 @@ struct AFrag {
     uint16_t first[BMX_MAX_REGEX_POSITIONS], last[BMX_MAX_REGEX_POSITIONS];
 };
 
-enum Kind { ELEM, CAT, ALT, REP, ASSERT };
+enum Kind { ELEM, CAT, ALT, REP, ASSERT, GROUP };
 struct Node {
     Kind kind;
-    int a = 1, b = 1;          // REP (b == UNBOUNDED: no upper count); ASSERT: a is its relation (below)
+    int a = 1, b = 1;          // REP (b == UNBOUNDED: no upper count); ASSERT: a is its relation (below); GROUP: a is its number
     bool has_element = false;  // some element stands below it
-    std::vector<int> kids;     // CAT, ALT: any number; REP: one
+    bool has_group = false;    // a capturing group stands below it, or it is one (bmx_compile_regex_groups)
+    std::vector<int> kids;     // CAT, ALT: any number; REP, GROUP: one
     uint8_t cls[BMX_CLASS_BYTES]; // ELEM
 };
 
@@ -154,6 +155,8 @@ struct Compiler {
     uint32_t flags;
     bool star = false; // the grammar of bmx_compile_regex_star
     bool anchored = false; // the grammar of bmx_compile_regex_anchored: ^ $ \b \B \< \> are zero-width atoms
+    bool groups = false; // the grammar of bmx_compile_regex_groups: ( captures, (?: does not
+    int n_groups = 0;
     uint64_t at = 0;
     const char *why = nullptr;
     bool has_assertion = false;
@@ -214,9 +217,27 @@ struct Compiler {
         if (c == '(') {
             if (depth + 1 > MAX_DEPTH) return fail("groups nested deeper than 32");
             ++at;
+            int number = 0; // of a capturing group, by its '(' (0: it does not capture)
+            if (groups) {
+                if (at < len && e[at] == '?') {
+                    if (at + 1 >= len || e[at + 1] != ':') return fail("(? followed by anything but : (only (?: is known)");
+                    at += 2;
+                } else {
+                    if (n_groups == BMX_MAX_REGEX_GROUPS) return fail("more than 16 capturing groups");
+                    number = ++n_groups;
+                }
+            }
             if (!parse_alt(depth + 1, atom)) return false;
             if (at >= len || e[at] != ')') return fail("an unbalanced (");
             ++at;
+            if (number) {
+                const int inner = atom;
+                atom = make(GROUP);
+                nodes[atom].a = number;
+                nodes[atom].has_element = nodes[inner].has_element;
+                nodes[atom].has_group = true;
+                nodes[atom].kids.push_back(inner);
+            }
         } else {
             const uint64_t end = element_end(e, len, at);
             uint8_t cls[BMX_MAX_CLASS_PATTERN * BMX_CLASS_BYTES];
@@ -251,6 +272,7 @@ struct Compiler {
         out = make(REP);
         nodes[out].a = a, nodes[out].b = b;
         nodes[out].has_element = nodes[atom].has_element;
+        nodes[out].has_group = nodes[atom].has_group;
         nodes[out].kids.push_back(atom);
         return true;
     }
@@ -265,9 +287,11 @@ struct Compiler {
                 if (!parse_repeat(depth, r)) return false;
                 nodes[cat].kids.push_back(r);
                 nodes[cat].has_element |= nodes[r].has_element;
+                nodes[cat].has_group |= nodes[r].has_group;
             }
             nodes[alt].kids.push_back(cat);
             nodes[alt].has_element |= nodes[cat].has_element;
+            nodes[alt].has_group |= nodes[cat].has_group;
             if (at >= len || e[at] != '|') break;
             ++at;
         }
@@ -292,6 +316,7 @@ struct Compiler {
         if (!nodes[id].has_element) return true; // the empty string, whatever its counts
         switch (nodes[id].kind) {
         case ASSERT: return true; // (has no element: not reached; the anchored grammar expands with aexpand)
+        case GROUP: return expand(nodes[id].kids[0], out); // (the automaton does not see it: bmx_compile_regex_groups' tables do)
         case ELEM: {
             if (re.m >= limit)
                 return fail(limit == BMX_MAX_REGEX_POSITIONS ? "more than 64 positions after expansion" : "more than 128 positions after expansion");
@@ -367,6 +392,7 @@ struct Compiler {
         std::memset(&out, 0, sizeof out);
         out.nullable = true, out.eps = REL_FULL;
         switch (nodes[id].kind) {
+        case GROUP: return false; // (bmx_compile_regex_groups only, which is not anchored)
         case ASSERT:
             out.eps = (uint16_t)nodes[id].a;
             return true;
@@ -409,6 +435,150 @@ struct Compiler {
         }
         }
         return false;
+    }
+
+    // ---- bmx_compile_regex_groups: the refusal rule, then pref / open / close from the expanded tree ----
+    bool can_be_empty(int id) const
+    {
+        const Node &n = nodes[id];
+        switch (n.kind) {
+        case ELEM: return false;
+        case ASSERT: return true;
+        case GROUP: return can_be_empty(n.kids[0]);
+        case REP: return n.a == 0 || can_be_empty(n.kids[0]);
+        case CAT:
+            for (int k : n.kids)
+                if (!can_be_empty(k)) return false;
+            return true;
+        case ALT:
+            for (int k : n.kids)
+                if (can_be_empty(k)) return true;
+            return false;
+        }
+        return false;
+    }
+
+    // No repeat with b >= 2 whose body can match the empty string and holds a capturing group: engines disagree there.
+    bool repeats_capture_exactly(int id)
+    {
+        const Node &n = nodes[id];
+        if (n.kind == REP && n.b >= 2 && n.has_group && can_be_empty(n.kids[0]))
+            return fail("a repeat of two or more whose body can match the empty string and holds a capturing group");
+        for (int k : n.kids)
+            if (!repeats_capture_exactly(k)) return false;
+        return true;
+    }
+
+    // The expanded tree as states with ordered epsilon moves: a state either consumes (pos >= 0, then `next`) or has moves
+    // in the order a backtracking matcher tries them.  A move may carry tags.
+    struct Move {
+        int to;
+        uint16_t open, close;
+    };
+    struct State {
+        int pos = -1, next = -1;
+        std::vector<Move> moves;
+    };
+    std::vector<State> states;
+    int n_pos = 0;
+
+    int state()
+    {
+        states.emplace_back();
+        return (int)states.size() - 1;
+    }
+    void move(int from, int to, uint16_t open = 0, uint16_t close = 0) { states[from].moves.push_back({to, open, close}); }
+
+    // Node id behind state `in`; returns the state behind it.  Positions are numbered as expand() numbers them: left to
+    // right, copy by copy.  A subtree without an element still threads its groups: () and (a|) fire their tags.
+    int thread(int id, int in)
+    {
+        const Node &n = nodes[id];
+        if (!n.has_element && !n.has_group) return in; // the empty string, and no tag
+        switch (n.kind) {
+        case ASSERT: return in;
+        case ELEM: {
+            const int c = state(), out = state();
+            states[c].pos = n_pos++;
+            states[c].next = out;
+            move(in, c);
+            return out;
+        }
+        case GROUP: {
+            const uint16_t bit = (uint16_t)(1u << (n.a - 1));
+            const int kin = state();
+            move(in, kin, bit, 0);
+            const int kout = thread(n.kids[0], kin), out = state();
+            move(kout, out, 0, bit);
+            return out;
+        }
+        case CAT:
+            for (int k : n.kids) in = thread(k, in);
+            return in;
+        case ALT: {
+            const int out = state();
+            for (int k : n.kids) { // left to right
+                const int kin = state();
+                move(in, kin);
+                move(thread(k, kin), out);
+            }
+            return out;
+        }
+        case REP: {
+            const int copies = n.has_element ? n.b : 1; // (without an element and with a group: b == 1, or it was refused)
+            for (int i = 0; i < copies; ++i) {
+                if (i < n.a) {
+                    in = thread(n.kids[0], in);
+                    continue;
+                }
+                const int kin = state(), after = state();
+                move(in, kin); // an optional copy before its skip
+                move(thread(n.kids[0], kin), after);
+                move(in, after);
+                in = after;
+            }
+            return in;
+        }
+        }
+        return in;
+    }
+
+    // depth first from the state behind `row`: the first path to a consuming position, or to the end, gives the pair's
+    // rank and tags.  All tags of one boundary fire at the same text offset, so their order among themselves is immaterial.
+    void walk(int s, uint16_t open, uint16_t close, int row, int final_state, std::vector<char> &seen, int &rank, bmx_regex_groups &g) const
+    {
+        if (seen[s]) return;
+        seen[s] = 1;
+        const int q = states[s].pos >= 0 ? states[s].pos : s == final_state ? BMX_REGEX_END : -1;
+        if (q >= 0) {
+            if (q != BMX_REGEX_END) g.pref[row][rank++] = (uint8_t)q;
+            g.open[row][q] = open;
+            g.close[row][q] = close;
+            return;
+        }
+        for (const Move &mv : states[s].moves) walk(mv.to, (uint16_t)(open | mv.open), (uint16_t)(close | mv.close), row, final_state, seen, rank, g);
+    }
+
+    void tables(int root, bmx_regex_groups &g)
+    {
+        states.clear();
+        n_pos = 0;
+        const int start = state();
+        const int final_state = thread(root, start);
+        std::memset(&g, 0, sizeof g);
+        std::memset(g.pref, 0xFF, sizeof g.pref);
+        g.n_groups = n_groups;
+        int behind[BMX_MAX_REGEX_POSITIONS + 1];
+        for (int &b : behind) b = -1;
+        behind[BMX_REGEX_START] = start;
+        for (const State &st : states)
+            if (st.pos >= 0) behind[st.pos] = st.next;
+        for (int row = 0; row <= BMX_MAX_REGEX_POSITIONS; ++row) {
+            if (behind[row] < 0) continue;
+            std::vector<char> seen(states.size(), 0);
+            int rank = 0;
+            walk(behind[row], 0, 0, row, final_state, seen, rank, g);
+        }
     }
 };
 
@@ -519,7 +689,7 @@ namespace {
 
 // The plain grammar (star: with * + {a,}) up to `limit` positions: c.re and f on BMX_OK, else the error text is set.
 int compile(const char *where, bool star, int limit, const char *expr, uint64_t expr_len, uint32_t flags, bool have_out, Compiler &c,
-            Frag &f)
+            Frag &f, bool groups = false, int *root_out = nullptr)
 {
     char text[160];
     if (!expr || !have_out) {
@@ -536,6 +706,7 @@ int compile(const char *where, bool star, int limit, const char *expr, uint64_t 
     c.len = expr_len;
     c.flags = flags;
     c.star = star;
+    c.groups = groups;
     c.limit = limit;
     std::memset(&c.re, 0, sizeof c.re);
     int root = 0;
@@ -545,6 +716,8 @@ int compile(const char *where, bool star, int limit, const char *expr, uint64_t 
     if (ok) ok = c.expand(root, f);
     if (ok && c.re.m == 0) ok = c.fail("zero positions");
     if (ok && f.nullable) ok = c.fail("the expression matches the empty string");
+    if (ok && groups) ok = c.repeats_capture_exactly(root);
+    if (root_out) *root_out = root;
     if (!ok) {
         snprintf(text, sizeof text, "%s: %s", where, c.why ? c.why : "a bad expression");
         bmx_internal_set_error(text);
@@ -553,13 +726,9 @@ int compile(const char *where, bool star, int limit, const char *expr, uint64_t 
     return BMX_OK;
 }
 
-// ... into struct bmx_regex (at most 64 positions: the low word of every set is the whole set)
-int compile(const char *where, bool star, const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+// the compiler's automaton of at most 64 positions as struct bmx_regex: the low word of every set is the whole set
+bmx_regex store(const Compiler &c, const Frag &f, bool star)
 {
-    Compiler c;
-    Frag f;
-    const int rc = compile(where, star, BMX_MAX_REGEX_POSITIONS, expr, expr_len, flags, out != nullptr, c, f);
-    if (rc != BMX_OK) return rc;
     bmx_regex re;
     std::memset(&re, 0, sizeof re);
     re.m = c.re.m;
@@ -569,11 +738,126 @@ int compile(const char *where, bool star, const char *expr, uint64_t expr_len, u
     std::memcpy(re.classes, c.re.classes, sizeof re.classes);
     if (star) bmx_regex_star_lengths(re.m, re.first, re.last, re.follow, &re.min_len, &re.max_len, nullptr);
     else bmx_regex_lengths(re.m, re.first, re.last, re.follow, &re.min_len, &re.max_len);
-    *out = re;
+    return re;
+}
+
+// ... into struct bmx_regex
+int compile(const char *where, bool star, const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
+{
+    Compiler c;
+    Frag f;
+    const int rc = compile(where, star, BMX_MAX_REGEX_POSITIONS, expr, expr_len, flags, out != nullptr, c, f);
+    if (rc != BMX_OK) return rc;
+    *out = store(c, f, star);
     return BMX_OK;
 }
 
 } // namespace
+
+// The star-free grammar with capturing groups: the same automaton, and the capture model from the tree beside it.
+extern "C" int bmx_compile_regex_groups(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *re, bmx_regex_groups *gr)
+{
+    Compiler c;
+    Frag f;
+    int root = 0;
+    const int rc = compile("bmx_compile_regex_groups", false, BMX_MAX_REGEX_POSITIONS, expr, expr_len, flags, re != nullptr && gr != nullptr,
+                           c, f, true, &root);
+    if (rc != BMX_OK) return rc;
+    bmx_regex_groups g;
+    c.tables(root, g);
+    *re = store(c, f, false);
+    *gr = g;
+    return BMX_OK;
+}
+
+extern "C" int bmx_regex_groups_valid(const bmx_regex *re, const bmx_regex_groups *gr)
+{
+    if (!re || !gr || !bmx_regex_sets_ok(re->m, re->first, re->last, re->follow)) return 0;
+    if (gr->n_groups < 0 || gr->n_groups > BMX_MAX_REGEX_GROUPS) return 0;
+    const uint32_t known = (1u << gr->n_groups) - 1u;
+    for (int row = 0; row <= BMX_MAX_REGEX_POSITIONS; ++row) {
+        const bool live = row == BMX_REGEX_START || row < re->m;
+        const uint64_t set = !live ? 0 : row == BMX_REGEX_START ? re->first : re->follow[row];
+        uint64_t seen = 0;
+        int k = 0;
+        for (; k < BMX_MAX_REGEX_POSITIONS && gr->pref[row][k] != 0xFF; ++k) { // a permutation of the set ...
+            const unsigned q = gr->pref[row][k];
+            if (q >= (unsigned)BMX_MAX_REGEX_POSITIONS || !((set >> q) & 1) || ((seen >> q) & 1)) return 0;
+            seen |= 1ull << q;
+        }
+        if (seen != set) return 0;
+        for (; k < BMX_MAX_REGEX_POSITIONS; ++k) // ... and nothing behind it
+            if (gr->pref[row][k] != 0xFF) return 0;
+        for (int col = 0; col <= BMX_MAX_REGEX_POSITIONS; ++col) {
+            const uint32_t tags = (uint32_t)gr->open[row][col] | gr->close[row][col];
+            if (tags == 0) continue;
+            const bool pair = col < BMX_MAX_REGEX_POSITIONS ? ((set >> col) & 1) != 0
+                                                            : row != BMX_REGEX_START && live && ((re->last >> row) & 1) != 0;
+            if (!pair || (tags & ~known)) return 0;
+        }
+    }
+    return 1;
+}
+
+// A replacement template into its references and the literals between them.
+extern "C" int bmx_compile_template(const void *tmpl, uint64_t len, int32_t n_groups, bmx_template *out, void *lits)
+{
+    const char *why = nullptr;
+    bmx_template t;
+    std::memset(&t, 0, sizeof t);
+    std::vector<uint8_t> bytes;
+    if (!out || (len > 0 && (!tmpl || !lits))) why = "a NULL argument";
+    else if (len > BMX_MAX_REPLACEMENT) why = "a template longer than 65536 bytes";
+    else if (n_groups < 0 || n_groups > BMX_MAX_REGEX_GROUPS) why = "n_groups outside 0..16";
+    const uint8_t *p = static_cast<const uint8_t *>(tmpl);
+    size_t lit0 = 0; // where the current literal begins in `bytes`
+    for (uint64_t i = 0; !why && i < len;) {
+        if (p[i] != '\\') {
+            bytes.push_back(p[i++]);
+            continue;
+        }
+        const unsigned c = i + 1 < len ? p[i + 1] : 0x100u;
+        int ref = -1;
+        if (c == '\\') {
+            bytes.push_back('\\');
+            i += 2;
+            continue;
+        } else if (c >= '1' && c <= '9') {
+            if (i + 2 < len && p[i + 2] >= '0' && p[i + 2] <= '9') why = "a digit right behind \\1..\\9 (engines read two digits there: write \\g<N>)";
+            ref = (int)(c - '0');
+            i += 2;
+        } else if (c == 'g' && i + 2 < len && p[i + 2] == '<') {
+            uint64_t j = i + 3;
+            int digits = 0;
+            for (ref = 0; j < len && p[j] >= '0' && p[j] <= '9' && digits < 3; ++j, ++digits) ref = 10 * ref + (int)(p[j] - '0');
+            if (digits < 1 || digits > 2 || j >= len || p[j] != '>') why = "\\g without <one or two digits>";
+            i = j + 1;
+        } else {
+            why = c == 0x100u ? "a dangling backslash" : "an escape that is none of \\1..\\9, \\g<N>, \\\\";
+        }
+        if (why) break;
+        if (ref > n_groups) why = "a reference to a group the expression does not have";
+        else if (t.n_refs == BMX_MAX_TEMPLATE_REFS) why = "more than 32 references";
+        if (why) break;
+        t.ref[t.n_refs] = ref;
+        t.lit_off[t.n_refs] = (uint32_t)lit0;
+        t.lit_len[t.n_refs] = (uint32_t)(bytes.size() - lit0);
+        lit0 = bytes.size();
+        ++t.n_refs;
+    }
+    if (why) {
+        char text[192];
+        snprintf(text, sizeof text, "bmx_compile_template: %s", why);
+        bmx_internal_set_error(text);
+        return BMX_ERR_ARG;
+    }
+    t.lit_off[t.n_refs] = (uint32_t)lit0;
+    t.lit_len[t.n_refs] = (uint32_t)(bytes.size() - lit0);
+    t.lit_bytes = (uint32_t)bytes.size();
+    *out = t;
+    if (!bytes.empty()) std::memcpy(lits, bytes.data(), bytes.size());
+    return BMX_OK;
+}
 
 extern "C" int bmx_compile_regex(const char *expr, uint64_t expr_len, uint32_t flags, bmx_regex *out)
 {

@@ -16,6 +16,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 #include "bmx_internal.h"
 #include "bmx_aux_kernels.h"
@@ -110,6 +111,7 @@ void bmx_ctx_destroy(bmx_ctx *ctx)
     bmx_internal_gaps_free(ctx->gaps);
     bmx_internal_regex_free(ctx->regex);
     bmx_internal_regex_long_free(ctx->regex_long);
+    bmx_internal_regex_groups_free(ctx->regex_groups);
     bmx_internal_regex_begins_free(ctx->regex_begins);
     bmx_internal_regex_anchored_free(ctx->regex_anchored);
     bmx_internal_regex_anchored_begins_free(ctx->regex_anchored_begins);
@@ -301,6 +303,33 @@ int bmx_extract_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t ba
                                    capacity, d_off, n_out, (hipStream_t)stream_v, g_err, sizeof g_err);
 }
 
+// ... with a template (bmx_compile_template is bmx_regex_compile.cpp); the template's errors come before any HIP call
+int bmx_expand_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_groups, int32_t n_groups,
+                      uint64_t count, const void *tmpl, uint64_t tmpl_len, uint32_t flags, void *d_out, uint64_t capacity,
+                      uint64_t *d_off, uint64_t *n_out, void *stream_v)
+{
+    if (!bmx_expand_args_ok(d_text, n, d_groups, n_groups, count, flags, d_out, capacity, d_off, n_out)) return BMX_ERR_ARG;
+    bmx_template t;
+    std::vector<uint8_t> lits(tmpl_len <= BMX_MAX_REPLACEMENT ? (size_t)tmpl_len + 1 : 1);
+    if (bmx_compile_template(tmpl, tmpl_len, n_groups, &t, lits.data()) != BMX_OK) return BMX_ERR_ARG;
+    const bool extract = (flags & BMX_EXPAND_EXTRACT) != 0;
+    if (!extract && count == 0 && (n == 0 || capacity == 0)) {
+        *n_out = n;
+        return BMX_OK;
+    }
+    if (!ctx) return BMX_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (count == 0) { // no match: the text itself, or the single offset 0
+        *n_out = extract ? 0 : n;
+        if (extract) HIPCHK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), (hipStream_t)stream_v));
+        else HIPCHK(hipMemcpyAsync(d_out, d_text, std::min(n, capacity), hipMemcpyDeviceToDevice, (hipStream_t)stream_v));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream_v));
+        return !extract && n > capacity ? BMX_ERR_CAPACITY : BMX_OK;
+    }
+    return bmx_internal_expand(&ctx->subst, ctx->num_cu, d_text, n, base_offset, d_groups, n_groups, count, &t, lits.data(), d_out,
+                               capacity, extract ? d_off : nullptr, n_out, (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
 float bmx_last_subst_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_subst_ms(ctx->subst) : -1.0f; }
 
 // ---- approximate search (bmx_approx.hip) -------------------------------------------------------
@@ -432,6 +461,21 @@ int bmx_regex_starts_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64
     return bmx_internal_regex_starts(&ctx->regex, d_text, n, base_offset, re, d_ends, count, 0, flags, d_starts, nullptr,
                                      (hipStream_t)stream_v, g_err, sizeof g_err);
 }
+
+// ... the capture groups of every span of a list (bmx_regex_groups.hip; bmx_compile_regex_groups is bmx_regex_compile.cpp)
+int bmx_regex_groups_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t base_offset, const bmx_regex *re,
+                            const bmx_regex_groups *gr, const uint64_t *d_starts, const uint64_t *d_ends, uint64_t count,
+                            uint64_t *d_groups, void *stream_v)
+{
+    if (!bmx_regex_groups_args_ok(n, re, gr, d_starts, d_ends, count, d_groups)) return BMX_ERR_ARG;
+    if (count == 0) return BMX_OK;
+    if (!ctx || !d_text) return BMX_ERR_ARG; // (a span needs a byte: n == 0 cannot have one)
+    HIPCHK(hipSetDevice(ctx->device));
+    return bmx_internal_regex_groups(&ctx->regex_groups, d_text, n, base_offset, re, gr, d_starts, d_ends, count, d_groups,
+                                     (hipStream_t)stream_v, g_err, sizeof g_err);
+}
+
+float bmx_last_regex_groups_ms(bmx_ctx *ctx) { return ctx ? bmx_internal_regex_groups_ms(ctx->regex_groups) : -1.0f; }
 
 // ... for automata of up to 128 positions (bmx_regex_long.hip; bmx_compile_regex_long is bmx_regex_compile.cpp)
 int bmx_search_regex_long_device(bmx_ctx *ctx, const void *d_text, uint64_t n, uint64_t lead, uint64_t base_offset,

@@ -1,5 +1,5 @@
 // bmx_subst.hip -- host side of the non-overlapping match selection, replace and extract (bmx_spans_select*, bmx_replace*,
-// bmx_extract*, include/bmx.h): per context four status words with their pinned copy, the workspace (keys,
+// bmx_extract*, include/bmx.h) and of the copy with a template (bmx_expand_device): per context four status words with their pinned copy, the workspace (keys,
 // prefix maxima, chain levels, flags, slots, pieces, rocPRIM's scratch), the device copy of the replacement and the events,
 // kept between calls as bmx_rows.hip keeps the rows'.  The kernels are in bmx_subst_kernel.h.  The argument checks and
 // the context are the shim's (bmx_shim.hip); everything here runs on valid arguments.
@@ -36,6 +36,7 @@ struct SubstHost {
     hipEvent_t ev[2] = {nullptr, nullptr};
     uint64_t last_shift = bmx::SUBST_TILE_SHIFT, last_levels = 0, last_tiles = 0; // the last select (bmx_exp_last_launch)
     bool lds_attr = false; // the copy kernel may take BMX_MAX_REPLACEMENT bytes of dynamic LDS
+    bool lds_attr_expand = false; // ... and the copy kernel of a template
     float last_ms = -1.0f;
 };
 
@@ -322,6 +323,104 @@ int bmx_internal_subst_copy(void **state_v, int num_cu, const void *d_text, uint
         const uint64_t per_cu = lds > 16384 ? 2 : 8; // (the replacement in LDS bounds the resident workgroups)
         const uint64_t grid = std::min<uint64_t>(g.n_tiles, (uint64_t)num_cu * per_cu);
         hipLaunchKernelGGL(bmx::subst_copy_kernel, dim3((uint32_t)grid), block, lds, stream, g);
+        rc = finish(st, nullptr, what, stream, err, errlen);
+        if (rc != BMX_OK) return rc;
+    }
+    work_release(st);
+    return (capacity && total > capacity) ? BMX_ERR_CAPACITY : BMX_OK;
+}
+
+// replace (d_off == NULL) and extract with a template; count >= 1, a template that bmx_compile_template accepted
+int bmx_internal_expand(void **state_v, int num_cu, const void *d_text, uint64_t n, uint64_t base_offset, const uint64_t *d_groups,
+                        int32_t n_groups, uint64_t count, const bmx_template *t, const uint8_t *lits, void *d_out, uint64_t capacity,
+                        uint64_t *d_off, uint64_t *n_out, hipStream_t stream, char *err, size_t errlen)
+{
+    const bool extract = d_off != nullptr;
+    const char *what = "bmx_expand_device";
+    SubstHost *st = nullptr;
+    int rc = state_ready(state_v, &st, what, err, errlen);
+    if (rc != BMX_OK) return rc;
+    if (t->lit_bytes) {
+        if (!st->d_repl) BMX_HIP(what, hipMalloc(&st->d_repl, MAX_REPL));
+        if (!st->h_repl) BMX_HIP(what, hipHostMalloc(&st->h_repl, MAX_REPL, hipHostMallocDefault));
+    }
+    bmx::ExpandList l{};
+    l.groups = d_groups;
+    l.count = count;
+    l.pairs = (uint32_t)n_groups + 1;
+    l.t1 = (uint32_t)t->n_refs + 1;
+    l.first = extract ? 0u : 1u;
+    bmx::SubstTemplate tp{};
+    tp.t1 = l.t1, tp.first = l.first;
+    for (int32_t r = 0; r < t->n_refs; ++r) l.ref[r] = t->ref[r];
+    for (uint32_t r = 0; r < l.t1; ++r) l.lit_len[r] = tp.len[r] = t->lit_len[r], tp.off[r] = t->lit_off[r];
+    const bmx::SubstView v{base_offset, n};
+    const dim3 block(bmx::SUBST_BLOCK);
+    const uint64_t pieces = count * l.t1 + l.first;
+
+    size_t scan_bytes = 0;
+    auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), bmx::ExpandPieceLen{l, v});
+    BMX_HIP(what, rocprim::exclusive_scan(nullptr, scan_bytes, lens, (uint64_t *)nullptr, uint64_t(0), (size_t)pieces + 1,
+                                          rocprim::plus<uint64_t>(), stream));
+    uint64_t *a = nullptr, *delta = nullptr;
+    void *scan_tmp = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver c{pass ? static_cast<char *>(st->d_work) : nullptr};
+        a = c.take<uint64_t>(pieces + 1);
+        delta = c.take<uint64_t>(pieces);
+        scan_tmp = c.take<char>(scan_bytes);
+        if (pass == 0) {
+            rc = work_ready(st, c.used, what, err, errlen);
+            if (rc != BMX_OK) return rc;
+        }
+    }
+
+    BMX_HIP(what, hipMemsetAsync(st->d_words, 0, bmx::SUBST_WORDS * sizeof(uint64_t), stream));
+    BMX_HIP(what, hipEventRecord(st->ev[0], stream));
+    hipLaunchKernelGGL(bmx::expand_check_kernel, dim3(grid_for(count)), block, 0, stream, l, v, st->d_words);
+    BMX_HIP(what, rocprim::exclusive_scan(scan_tmp, scan_bytes, lens, a, uint64_t(0), (size_t)pieces + 1, rocprim::plus<uint64_t>(), stream));
+    st->last_ms = 0.0f;
+    rc = finish(st, a + pieces, what, stream, err, errlen);
+    if (rc != BMX_OK) return rc;
+    if (st->h_words[0]) {
+        work_release(st);
+        snprintf(err, errlen, "%s: the matches (group 0) are not ascending, pairwise disjoint, non-empty and inside the view, or a group "
+                 "reaches outside its match", what);
+        return BMX_ERR_ARG;
+    }
+    const uint64_t total = st->h_words[1];
+    *n_out = total;
+    const uint64_t bytes = std::min(total, capacity);
+    if (bytes || extract) {
+        BMX_HIP(what, hipEventRecord(st->ev[0], stream));
+        hipLaunchKernelGGL(bmx::expand_delta_kernel, dim3(grid_for(pieces)), block, 0, stream, l, v, (const uint64_t *)a, pieces, delta, d_off);
+    }
+    if (bytes) {
+        if (t->lit_bytes) { // through pinned memory: the caller's buffer is free when the call returns, whatever the stream does
+            memcpy(st->h_repl, lits, t->lit_bytes);
+            BMX_HIP(what, hipMemcpyAsync(st->d_repl, st->h_repl, t->lit_bytes, hipMemcpyHostToDevice, stream));
+        }
+        bmx::SubstCopyArgs g{};
+        const uint64_t addr = reinterpret_cast<uint64_t>(d_out);
+        g.text = static_cast<const uint8_t *>(d_text);
+        g.a = a, g.delta = delta, g.pieces = pieces;
+        g.repl = st->d_repl;
+        g.lead = t->lit_bytes;
+        g.out16 = reinterpret_cast<uint8_t *>(addr & ~15ull);
+        g.own_lo = addr & 15ull;
+        g.own_hi = bytes + g.own_lo;
+        g.n_tiles = (g.own_hi + bmx::SUBST_TILE - 1) / bmx::SUBST_TILE;
+        const size_t lds = (g.lead + 15u) & ~(size_t)15;
+        if (lds && !st->lds_attr_expand) {
+            BMX_HIP(what, hipFuncSetAttribute(reinterpret_cast<const void *>(bmx::expand_copy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)MAX_REPL));
+            st->lds_attr_expand = true;
+        }
+        const uint64_t per_cu = lds > 16384 ? 2 : 8; // (the literals in LDS bound the resident workgroups)
+        const uint64_t grid = std::min<uint64_t>(g.n_tiles, (uint64_t)num_cu * per_cu);
+        hipLaunchKernelGGL(bmx::expand_copy_kernel, dim3((uint32_t)grid), block, lds, stream, g, tp);
+    }
+    if (bytes || extract) {
         rc = finish(st, nullptr, what, stream, err, errlen);
         if (rc != BMX_OK) return rc;
     }

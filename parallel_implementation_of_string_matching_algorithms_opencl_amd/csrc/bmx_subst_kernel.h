@@ -27,6 +27,11 @@
 // lies inside one piece's text is two aligned 16-byte loads, a funnel shift and one 16-byte store, the loads of the lane's
 // four lines issued before the first is used; any other line is put together byte by byte.  The replacement sits in LDS.
 // Only 16-byte lines that hold a byte of the text are loaded.
+//
+// Copy with a template (bmx_expand_device): the same body with a wider piece model.  T references make T + 1
+// pieces per match; piece r opens with literal r of the template (offset and length from a table in LDS, indexed by the
+// piece's number modulo T + 1) and goes on with a run of text that may be empty.  The piece starts are an exclusive sum over
+// lengths read from the group table of bmx_regex_groups_device.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -349,11 +354,32 @@ __device__ __forceinline__ subst_u32x4 subst_funnel(subst_u32x4 lo, subst_u32x4 
     return o;
 }
 
-__global__ __launch_bounds__(SUBST_BLOCK) void subst_copy_kernel(const SubstCopyArgs g)
+// The piece model of a template (bmx_expand_device): T references make t1 = T + 1 pieces per match.  Piece p >= first
+// opens with literal r = (p - first) % t1, len[r] bytes at off[r] of the literal bytes; the pieces below `first` (replace:
+// the text in front of the first match) have none.
+constexpr int SUBST_MAX_LITERALS = 33; // == BMX_MAX_TEMPLATE_REFS + 1
+struct SubstTemplate {
+    uint32_t t1, first;
+    uint32_t off[SUBST_MAX_LITERALS], len[SUBST_MAX_LITERALS];
+};
+
+// TMPL false: the literal replacement, every piece but the first opens with the g.lead bytes of it.  TMPL true: tab holds
+// the template's off[] and, SUBST_MAX_LITERALS words on, len[]; g.lead is the number of literal bytes in LDS.
+template <bool TMPL>
+__device__ __forceinline__ void subst_copy_body(const SubstCopyArgs &g, const uint8_t *sh_repl, const uint32_t *tab, uint32_t t1,
+                                                uint32_t first_piece)
 {
-    extern __shared__ uint8_t sh_repl[];
-    for (uint32_t i = threadIdx.x; i < g.lead; i += SUBST_BLOCK) sh_repl[i] = g.repl[i];
-    __syncthreads();
+    // the literal in front of piece p: its length, and (TMPL) where it begins in sh_repl
+    const auto lead_of = [&](uint64_t p, uint32_t &off) -> uint64_t {
+        if (TMPL) {
+            if (p < first_piece) return off = 0, 0;
+            const uint32_t r = (uint32_t)((p - first_piece) % t1);
+            off = tab[r];
+            return tab[SUBST_MAX_LITERALS + r];
+        }
+        off = 0;
+        return p ? g.lead : 0;
+    };
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint64_t t = blockIdx.x; t < g.n_tiles; t += gridDim.x) {
         const uint64_t wave0 = t * SUBST_TILE + (uint64_t)wave * SUBST_WAVE_BYTES; // aligned coordinate of the wave's first byte
@@ -378,8 +404,9 @@ __global__ __launch_bounds__(SUBST_BLOCK) void subst_copy_kernel(const SubstCopy
             uint64_t p = p_lo;
             if (c < g.own_hi && p_lo != p_hi) p = subst_upper(g.a, p_lo + 1, p_hi + 1, c >= g.own_lo ? x[i] : 0) - 1;
             piece[i] = p;
-            const uint64_t lead = p ? g.lead : 0;
-            fast[i] = whole && x[i] - g.a[p] >= lead && (p + 1 == g.pieces || x[i] + 16 <= g.a[p + 1]);
+            uint32_t lead_off = 0;
+            const uint64_t lead = TMPL ? lead_of(p, lead_off) : (p ? g.lead : 0);
+            fast[i] =whole && x[i] - g.a[p] >= lead && (p + 1 == g.pieces || x[i] + 16 <= g.a[p + 1]);
             src[i] = x[i] + g.delta[p];
         }
 #pragma unroll
@@ -405,11 +432,27 @@ __global__ __launch_bounds__(SUBST_BLOCK) void subst_copy_kernel(const SubstCopy
             uint8_t b[16];
             const uint32_t from = c >= g.own_lo ? 0u : (uint32_t)(g.own_lo - c);
             const uint32_t to = (uint32_t)min((uint64_t)16, g.own_hi - c);
-            for (uint32_t k = from; k < to; ++k) {
-                const uint64_t y = c + k - g.own_lo;
-                while (p + 1 < g.pieces && g.a[p + 1] <= y) ++p;
-                const uint64_t in = y - g.a[p];
-                b[k] = (p && in < g.lead) ? sh_repl[in] : g.text[y + g.delta[p]];
+            if (TMPL) {
+                uint32_t lit_off;
+                uint64_t lit_len = lead_of(p, lit_off);
+                for (uint32_t k = from; k < to; ++k) {
+                    const uint64_t y = c + k - g.own_lo;
+                    // the last piece with a[p] <= y: in a run of equal a[] (an empty group, an empty literal) the one that holds y
+                    if (p + 1 < g.pieces && g.a[p + 1] <= y) {
+                        do ++p;
+                        while (p + 1 < g.pieces && g.a[p + 1] <= y);
+                        lit_len = lead_of(p, lit_off);
+                    }
+                    const uint64_t in = y - g.a[p];
+                    b[k] = in < lit_len ? sh_repl[lit_off + in] : g.text[y + g.delta[p]];
+                }
+            } else {
+                for (uint32_t k = from; k < to; ++k) {
+                    const uint64_t y = c + k - g.own_lo;
+                    while (p + 1 < g.pieces && g.a[p + 1] <= y) ++p;
+                    const uint64_t in = y - g.a[p];
+                    b[k] = (p && in < g.lead) ? sh_repl[in] : g.text[y + g.delta[p]];
+                }
             }
             if (from == 0 && to == 16) {
                 subst_u32x4 o;
@@ -420,6 +463,108 @@ __global__ __launch_bounds__(SUBST_BLOCK) void subst_copy_kernel(const SubstCopy
                 for (uint32_t k = from; k < to; ++k) g.out16[c + k] = b[k];
             }
         }
+    }
+}
+
+__global__ __launch_bounds__(SUBST_BLOCK) void subst_copy_kernel(const SubstCopyArgs g)
+{
+    extern __shared__ uint8_t sh_repl[];
+    for (uint32_t i = threadIdx.x; i < g.lead; i += SUBST_BLOCK) sh_repl[i] = g.repl[i];
+    __syncthreads();
+    subst_copy_body<false>(g, sh_repl, nullptr, 1, 0);
+}
+
+// ... with a template: the literal bytes in the dynamic LDS, the table of the literals in front of them
+__global__ __launch_bounds__(SUBST_BLOCK) void expand_copy_kernel(const SubstCopyArgs g, const SubstTemplate tp)
+{
+    extern __shared__ uint8_t sh_repl[];
+    __shared__ uint32_t tab[2 * SUBST_MAX_LITERALS];
+    for (uint32_t i = threadIdx.x; i < g.lead; i += SUBST_BLOCK) sh_repl[i] = g.repl[i];
+    if (threadIdx.x < SUBST_MAX_LITERALS) {
+        tab[threadIdx.x] = tp.off[threadIdx.x];
+        tab[SUBST_MAX_LITERALS + threadIdx.x] = tp.len[threadIdx.x];
+    }
+    __syncthreads();
+    subst_copy_body<true>(g, sh_repl, tab, tp.t1, tp.first);
+}
+
+// ---- the pieces of a template expansion (bmx_expand_device) ----
+
+// d_groups of bmx_regex_groups_device: `pairs` = n_groups + 1 half-open (begin, end) pairs per entry
+struct ExpandList {
+    const uint64_t *groups;
+    uint64_t count;
+    uint32_t pairs, t1, first; // t1 = T + 1 pieces per match; first: 1 = replace (piece 0 is the text in front), 0 = extract
+    int32_t ref[SUBST_MAX_LITERALS - 1];
+    uint32_t lit_len[SUBST_MAX_LITERALS];
+};
+
+// group 0 of every entry: set, non-empty, inside the view, not below the entry in front; every other group unset or inside
+// its entry's group 0.  Anything else raises words[0].
+__global__ __launch_bounds__(SUBST_BLOCK) void expand_check_kernel(const ExpandList l, const SubstView v, unsigned long long *words)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * SUBST_BLOCK + threadIdx.x;
+    if (k >= l.count) return;
+    const uint64_t *g = l.groups + k * l.pairs * 2;
+    const uint64_t b0 = g[0], e0 = g[1];
+    bool ok = b0 != SUBST_NONE && e0 != SUBST_NONE && b0 >= v.base_offset && e0 > b0 && e0 - v.base_offset <= v.n;
+    if (ok && k > 0) {
+        const uint64_t pe = g[1 - (int64_t)l.pairs * 2]; // the end of the entry in front
+        ok = pe != SUBST_NONE && pe <= b0;
+    }
+    for (uint32_t q = 1; ok && q < l.pairs; ++q) {
+        const uint64_t gb = g[2 * q], ge = g[2 * q + 1];
+        if (gb == SUBST_NONE && ge == SUBST_NONE) continue;
+        ok = gb >= b0 && ge >= gb && ge <= e0;
+    }
+    if (!ok) words[0] = 1;
+}
+
+// the bytes of piece p (0 at p == pieces, which closes the exclusive sum), for rocPRIM's transform iterator
+struct ExpandPieceLen {
+    ExpandList l;
+    SubstView v;
+    __device__ uint64_t operator()(uint64_t p) const
+    {
+        if (p < l.first) return l.groups[0] - v.base_offset; // replace: the text in front of the first match
+        const uint64_t q = p - l.first, k = q / l.t1;
+        const uint32_t r = (uint32_t)(q % l.t1);
+        if (k >= l.count) return 0;
+        const uint64_t *g = l.groups + k * l.pairs * 2;
+        uint64_t len = l.lit_len[r];
+        if (r + 1 < l.t1) { // the group of reference r; nothing where it is unset
+            const uint64_t gb = g[2 * l.ref[r]], ge = g[2 * l.ref[r] + 1];
+            if (gb != SUBST_NONE) len += ge - gb;
+        } else if (l.first) { // replace: the text behind the match, up to the next one or the view's end
+            len += (k + 1 < l.count ? g[l.pairs * 2] : v.base_offset + v.n) - g[1];
+        }
+        return len;
+    }
+};
+
+// delta[p] from a = the exclusive sum of the piece lengths: the run of text behind piece p's literal begins at view byte
+// `src`, so text position = output position + (src - a[p] - literal length).  Extract: off[k] = a[k t1], off[count] = a[pieces].
+__global__ __launch_bounds__(SUBST_BLOCK) void expand_delta_kernel(const ExpandList l, const SubstView v, const uint64_t *a, uint64_t pieces,
+                                                                  uint64_t *delta, uint64_t *off)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * SUBST_BLOCK + threadIdx.x;
+    if (p >= pieces) return;
+    if (p < l.first) {
+        delta[p] = 0;
+        return;
+    }
+    const uint64_t q = p - l.first, k = q / l.t1;
+    const uint32_t r = (uint32_t)(q % l.t1);
+    const uint64_t *g = l.groups + k * l.pairs * 2;
+    uint64_t src = g[1]; // behind the match
+    if (r + 1 < l.t1) {
+        const uint64_t gb = g[2 * l.ref[r]];
+        src = gb != SUBST_NONE ? gb : g[0]; // (an unset group: an empty run, delta is never used)
+    }
+    delta[p] = src - v.base_offset - a[p] - l.lit_len[r];
+    if (off != nullptr) {
+        if (r == 0) off[k] = a[p];
+        if (p + 1 == pieces) off[l.count] = a[pieces];
     }
 }
 

@@ -77,6 +77,11 @@ ROW_NONE = 0xFFFFFFFFFFFFFFFF  # the row of a match that lies in no row (BMX_ROW
 ROWS_INVERT = 1  # Rows.matching: the rows without an entry (BMX_ROWS_INVERT)
 SELECT_MERGE = 1  # select_spans_device: the connected regions of the union of the spans (BMX_SELECT_MERGE)
 MAX_REPLACEMENT = 65536  # bytes of a replacement (BMX_MAX_REPLACEMENT)
+MAX_REGEX_GROUPS = 16  # capturing groups of compile_regex_groups
+REGEX_START = 64  # row of RegexGroups.pref / open / close: before the first byte of the match
+REGEX_END = 64  # column of open / close: after its last byte
+MAX_TEMPLATE_REFS = 32  # group references of a replacement template
+EXPAND_EXTRACT = 1  # expand_device: the column of expansions (BMX_EXPAND_EXTRACT)
 BAD_TABLE_SIZE = 128
 
 OK = 0
@@ -348,6 +353,18 @@ SYMBOLS = [
                               C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
     ("bmx_extract", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                               C.c_uint64, C.c_void_p, _u64p]),
+    ("bmx_compile_regex_groups", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("bmx_regex_groups_valid", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("bmx_regex_groups_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("bmx_search_regex_groups", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    ("bmx_last_regex_groups_ms", C.c_float, [C.c_void_p]),
+    ("bmx_compile_template", C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("bmx_expand_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64, C.c_char_p,
+                                    C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, _u64p, C.c_void_p]),
+    ("bmx_expand", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_uint64,
+                             C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
     ("bmx_gen_text_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     ("bmx_plant_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, _u64p,
                                    C.c_uint64, C.c_void_p]),
@@ -576,6 +593,61 @@ def compile_regex_star(expr, flags: int = 0) -> Regex:
     return out
 
 
+class RegexGroups(C.Structure):
+    """struct bmx_regex_groups (include/bmx.h): the capture model beside a Regex, plain data.  ``pref[p]`` (row 64: START)
+    lists the positions of follow[p] (of first), most preferred first, then 0xFF; bit g-1 of ``open[from][to]`` /
+    ``close[from][to]`` (column 64: END): group g begins / ends at the boundary between the two."""
+    _fields_ = [("n_groups", C.c_int32), ("pref", (C.c_uint8 * 64) * 65), ("open", (C.c_uint16 * 65) * 65),
+                ("close", (C.c_uint16 * 65) * 65)]
+
+    def pref_array(self) -> np.ndarray:
+        return np.frombuffer(bytes(self.pref), dtype=np.uint8).reshape(65, 64).copy()
+
+    def open_array(self) -> np.ndarray:
+        return np.frombuffer(bytes(self.open), dtype=np.uint16).reshape(65, 65).copy()
+
+    def close_array(self) -> np.ndarray:
+        return np.frombuffer(bytes(self.close), dtype=np.uint16).reshape(65, 65).copy()
+
+
+def compile_regex_groups(expr, flags: int = 0) -> Tuple[Regex, RegexGroups]:
+    """compile_regex's grammar where ``( )`` captures and ``(?: )`` does not (bmx_compile_regex_groups) -> (Regex,
+    RegexGroups).  The Regex is compile_regex's for the expression with every ``(?:`` written ``(``, so every search,
+    starts, begins and ends entry takes it.  Refused: more than 16 groups, ``(?`` + anything else, and a repeat of two or
+    more whose body can match the empty string and holds a capturing group (``(a?){2}``)."""
+    e = _pat_bytes(expr)
+    re_, gr = Regex(), RegexGroups()
+    _check(lib().bmx_compile_regex_groups(e, len(e), int(flags), C.byref(re_), C.byref(gr)), "bmx_compile_regex_groups")
+    return re_, gr
+
+
+def _regex_groups(expr_or_pair, flags: int = 0) -> Tuple[Regex, RegexGroups]:
+    if isinstance(expr_or_pair, tuple):
+        re_, gr = expr_or_pair
+        if not isinstance(re_, Regex) or not isinstance(gr, RegexGroups):
+            raise TypeError("a pair (Regex, RegexGroups), or an expression")
+        return re_, gr
+    return compile_regex_groups(expr_or_pair, flags)
+
+
+class Template(C.Structure):
+    """struct bmx_template (include/bmx.h): reference r names group ``ref[r]``; literal r (``lit_off``, ``lit_len`` into the
+    unescaped literal bytes) stands in front of it, literal ``n_refs`` behind the last one."""
+    _fields_ = [("n_refs", C.c_int32), ("ref", C.c_int32 * MAX_TEMPLATE_REFS), ("lit_off", C.c_uint32 * (MAX_TEMPLATE_REFS + 1)),
+                ("lit_len", C.c_uint32 * (MAX_TEMPLATE_REFS + 1)), ("lit_bytes", C.c_uint32)]
+
+
+def compile_template(template, n_groups: int) -> Tuple[Template, bytes]:
+    """A replacement template (bmx_compile_template: literal bytes, ``\\1``..``\\9``, ``\\g<0>``..``\\g<16>``, ``\\\\``) ->
+    (Template, the literal bytes).  Anything else behind a backslash, a digit right behind ``\\1``..``\\9``, a reference above
+    ``n_groups`` and more than 32 references are refused."""
+    t = _pat_bytes(template) if len(template) else b""
+    out = Template()
+    lits = C.create_string_buffer(max(len(t), 1))
+    _check(lib().bmx_compile_template(t, len(t), int(n_groups), C.byref(out), lits), "bmx_compile_template")
+    return out, lits.raw[: out.lit_bytes]
+
+
 def reverse_regex(expr_or_regex, flags: int = 0) -> Regex:
     """The reversed automaton (bmx_regex_reverse): position i becomes m - 1 - i, first and last swap, follow is transposed,
     the classes are mirrored; it matches the mirror image of what the input matches.  An expression is compiled with
@@ -678,8 +750,8 @@ def _regex_anchored(expr_or_pair, flags: int = 0) -> Tuple[Regex, RegexAnchors]:
 
 def _posix_args(kind="regex", merge=False, longest=None, **_):
     """What posix=True of sub / findall goes with (checked before any GPU work)."""
-    if kind not in ("regex", "regex_star", "regex_anchored") or merge or longest is not None:
-        raise ValueError("posix: kind 'regex', 'regex_star' or 'regex_anchored' only, without merge and without an explicit longest")
+    if kind not in ("regex", "regex_star", "regex_anchored", "regex_groups") or merge or longest is not None:
+        raise ValueError("posix: kind 'regex', 'regex_star', 'regex_anchored' or 'regex_groups' only, without merge and without an explicit longest")
 
 
 def _regex(expr_or_regex, flags: int = 0, star: bool = False) -> Regex:
@@ -1406,6 +1478,88 @@ class Context:
 
     def last_regex_ms(self) -> float:
         return float(self._L.bmx_last_regex_ms(self._h))
+
+    # -- ... capture groups ------------------------------------------------
+    def regex_groups_device(self, d_text, expr_or_pair, starts, ends, *, flags: int = 0, n: Optional[int] = None,
+                            base_offset: int = 0, stream=None):
+        """The capture groups of every span ``[starts[i], ends[i]]`` (ends inclusive, as the searches pair them; int64 /
+        uint64 CUDA tensors) of the resident text: an int64 tensor ``[count, G + 1, 2]`` of half-open ``(begin, end)``
+        pairs, group 0 the match itself, -1 twice for a group that is unset (bmx_regex_groups_device).  The groups are
+        those of Python's ``re.fullmatch`` on the span.  An entry whose start or end is -1, or whose end lies below its
+        start, is skipped (all -1); a span that is no match of the expression raises BmxError(ERR_ARG).
+        ``expr_or_pair``: an expression, or compile_regex_groups' pair."""
+        import torch
+
+        re_, gr = _regex_groups(expr_or_pair, flags)
+        count = starts.numel()
+        if n is None:
+            n = d_text.numel()
+        if starts.element_size() != 8 or ends.element_size() != 8 or ends.numel() != count:
+            raise ValueError("starts, ends: 8-byte entries, as many of one as of the other")
+        groups = torch.empty((max(count, 1), gr.n_groups + 1, 2), dtype=torch.int64, device=starts.device)
+        s = stream if stream is not None else torch.cuda.current_stream(starts.device)
+        rc = self._L.bmx_regex_groups_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset, C.byref(re_), C.byref(gr),
+                                             C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), count,
+                                             C.c_void_p(groups.data_ptr()), C.c_void_p(s.cuda_stream))
+        self._chk(rc, "bmx_regex_groups_device")
+        return groups[:count]
+
+    def search_regex_groups(self, text, expr_or_pair, flags: int = 0, posix: bool = False):
+        """Host buffers (bmx_search_regex_groups): (starts uint64, ends uint64, groups int64 [count, G + 1, 2]) of every
+        match END, ends ascending; each start the largest one for its end (the shortest match), or with ``posix`` the
+        smallest (the longest)."""
+        re_, gr = _regex_groups(expr_or_pair, flags)
+        tptr, n, keep = _host_text(text)
+        cap = max(1, min(n, 1 << 20))
+        while True:
+            starts = np.empty(cap, dtype=np.uint64)
+            ends = np.empty(cap, dtype=np.uint64)
+            groups = np.empty((cap, gr.n_groups + 1, 2), dtype=np.uint64)
+            total = C.c_uint64(0)
+            rc = self._L.bmx_search_regex_groups(self._h, tptr, n, C.byref(re_), C.byref(gr), REGEX_LONGEST if posix else 0,
+                                                 C.c_void_p(starts.ctypes.data), C.c_void_p(ends.ctypes.data),
+                                                 C.c_void_p(groups.ctypes.data), cap, C.byref(total))
+            if rc == ERR_CAPACITY:
+                cap = int(total.value)
+                continue
+            self._chk(rc, "bmx_search_regex_groups")
+            del keep
+            t = int(total.value)
+            return starts[:t].copy(), ends[:t].copy(), groups[:t].view(np.int64).copy()
+
+    def expand_device(self, d_text, groups, template, extract: bool = False, n: Optional[int] = None, base_offset: int = 0,
+                      out=None, stream=None):
+        """``groups``: what regex_groups_device returned, its matches (group 0) ascending and pairwise disjoint, as after
+        select_spans_device.  Default: (tensor, n_out), the view ``d_text[0:n)`` with every match replaced by the expansion
+        of ``template`` (re.sub with ``\\1``..``\\9``, ``\\g<N>``, ``\\\\``; an unset group expands to nothing).  ``extract``:
+        (blob, offsets), the expansions one after the other and count + 1 int64 offsets (Match.expand as a column)
+        (bmx_expand_device).  ``out``: a uint8 CUDA tensor that does not overlap the text."""
+        import torch
+
+        if groups.dim() != 3 or groups.shape[2] != 2 or groups.element_size() != 8:
+            raise ValueError("groups: an 8-byte tensor [count, G + 1, 2]")
+        groups = groups.contiguous()
+        count, n_groups = int(groups.shape[0]), int(groups.shape[1]) - 1
+        tmpl = _pat_bytes(template) if len(template) else b""
+        n = d_text.numel() if n is None else n
+        s = C.c_void_p((stream if stream is not None else torch.cuda.current_stream(d_text.device)).cuda_stream)
+        off = torch.empty(count + 1, dtype=torch.int64, device=d_text.device) if extract else None
+        total = C.c_uint64(0)
+
+        def call(buf, cap):
+            return self._L.bmx_expand_device(self._h, C.c_void_p(d_text.data_ptr()), n, base_offset,
+                                             C.c_void_p(groups.data_ptr()) if count else None, n_groups, count, tmpl, len(tmpl),
+                                             EXPAND_EXTRACT if extract else 0, C.c_void_p(buf.data_ptr()) if buf is not None else None,
+                                             cap, C.c_void_p(off.data_ptr()) if extract else None, C.byref(total), s)
+
+        if out is None:
+            self._chk(call(None, 0), "bmx_expand_device")
+            out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=d_text.device)
+        self._chk(call(out, out.numel()), "bmx_expand_device")
+        return (out[: int(total.value)], off) if extract else (out[: int(total.value)], int(total.value))
+
+    def last_regex_groups_ms(self) -> float:
+        return float(self._L.bmx_last_regex_groups_ms(self._h))
 
     # -- ... for expressions of up to 128 positions -------
     def search_regex_long_device(self, d_text, expr_or_regex, *, flags: int = 0, n: Optional[int] = None, lead: int = 0,
@@ -2511,14 +2665,35 @@ class Context:
         neither ``merge`` nor an explicit ``longest``: ValueError): the leftmost-longest matches, what grep -o, sed and awk
         take -- the begins search, the longest end of every start (with ``rows``: inside the start's row) and the same
         selection.  For "regex_star" the ends are looked for within ``window`` bytes (default: the longest row, else 4,096);
-        a match that may be longer than that raises ValueError, it is never returned shorter."""
+        a match that may be longer than that raises ValueError, it is never returned shorter.
+        kind "regex_groups" (with ``posix`` and ``rows`` only; ``merge`` or an explicit ``longest``: ValueError): ``expr`` is
+        compile_regex_groups' grammar and ``repl`` a TEMPLATE (``\\1``..``\\9``, ``\\g<N>``, ``\\\\``).  The matches are the
+        "regex" route's on the same automaton: leftmost-shortest, or leftmost-longest with ``posix``; the groups of each
+        are those of ``re.fullmatch`` on its span (regex_groups_device), the copy is expand_device."""
+        if kind == "regex_groups":
+            groups = self._selected_groups_device(d_text, expr, rows, merge, longest, flags, posix)
+            return self.expand_device(d_text, groups, repl)
         s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window, posix)
         return self.replace_device(d_text, s, e, repl)
+
+    def _selected_groups_device(self, d_text, expr, rows, merge, longest, flags, posix):
+        """kind "regex_groups": the selected matches of the "regex" route on the pair's automaton, and their groups."""
+        if merge or longest is not None:
+            raise ValueError("kind 'regex_groups': with posix and rows only, without merge and without an explicit longest")
+        pair = _regex_groups(expr, flags)
+        s, e = self._selected_spans_device(d_text, pair[0], "regex", rows, False, None, flags, 0, None, posix)
+        return self.regex_groups_device(d_text, pair, s, e)
 
     def findall_device(self, d_text, expr, kind: str = "regex", rows: Optional["Rows"] = None, merge: bool = False,
                        longest: Optional[bool] = None, flags: int = 0, k: int = 0, window: Optional[int] = None, posix: bool = False):
         """(blob, offsets): the non-overlapping matches of ``expr`` as a string column (re.findall, grep -o): the route of
-        sub_device into extract_device (``posix``: as there)."""
+        sub_device into extract_device (``posix``: as there).  kind "regex_groups": a list of one (blob, offsets) per group
+        1..G (for an expression without a group: of the whole match), an unset group an empty string -- the columns of
+        re.findall."""
+        if kind == "regex_groups":
+            groups = self._selected_groups_device(d_text, expr, rows, merge, longest, flags, posix)
+            n_groups = int(groups.shape[1]) - 1
+            return [self.expand_device(d_text, groups, "\\g<%d>" % g, extract=True) for g in (range(1, n_groups + 1) if n_groups else [0])]
         s, e = self._selected_spans_device(d_text, expr, kind, rows, merge, longest, flags, k, window, posix)
         return self.extract_device(d_text, s, e)
 
@@ -3129,6 +3304,15 @@ def search_regex_star(text, expr, flags: int = 0, spans: bool = False, longest: 
     return ctx.search_regex_star_spans(text, expr, flags, longest, window) if spans else ctx.search_regex_star(text, expr, flags)
 
 
+def search_regex_groups(text, expr, flags: int = 0, posix: bool = False):
+    """(text, star-free regular expression with capturing groups) -> (starts, ends, groups): every END at which a match
+    ends, ascending (ends inclusive), each with the start of its SHORTEST match -- the matches a leftmost-shortest selection
+    draws from -- or with ``posix`` of its LONGEST (what leftmost-longest draws from), and ``groups`` int64
+    [count, G + 1, 2]: the half-open (begin, end) of every group, -1 twice where unset, group 0 the match.  The groups are
+    those of Python's ``re.fullmatch`` on each span (bmx_search_regex_groups)."""
+    return default_context().search_regex_groups(text, expr, flags, posix)
+
+
 def rows_split(text, delim: int = 10) -> Tuple[np.ndarray, int]:
     """(text, delimiter byte) -> (offsets uint64, longest row): the rows of a host text (bmx_rows_split); offsets has
     rows + 1 entries."""
@@ -3191,9 +3375,14 @@ def findall(text, expr, **kw) -> list:
     d_text = _resident(text)
     if kw.get("rows") is True:
         kw["rows"] = ctx.rows_split_device(d_text)
-    blob, off = ctx.findall_device(d_text, expr, **kw)
-    blob, off = blob.cpu().numpy().tobytes(), off.cpu().numpy()
-    return [blob[off[i]:off[i + 1]] for i in range(off.size - 1)]
+    def column(blob, off):
+        blob, off = blob.cpu().numpy().tobytes(), off.cpu().numpy()
+        return [blob[off[i]:off[i + 1]] for i in range(off.size - 1)]
+
+    if kw.get("kind") == "regex_groups":  # what re.findall returns: strings for at most one group, tuples above
+        cols = [column(*c) for c in ctx.findall_device(d_text, expr, **kw)]
+        return cols[0] if len(cols) == 1 else list(zip(*cols))
+    return column(*ctx.findall_device(d_text, expr, **kw))
 
 
 def select_spans(starts=None, ends=None, length: int = 0, rows=None, merge: bool = False, index: bool = False):
